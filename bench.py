@@ -2,6 +2,8 @@
 """bench.py — atoms/s (fwd+bwd+Adam) of the nmrgnn message-passing hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--scaling weak|strong --total-graphs G]
+    python bench.py ... --dump-outputs DIR     also writes the last timed step's loss, updated parameters and
+                                               gradients as DIR/<name>.npy (same arguments -> same inputs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Without a torchrun environment `--gpus N` (N > 1) re-executes itself under torch.distributed.run on 127.0.0.1 with N
 ranks; a world size different from --gpus, or a backend other than nccl (= RCCL), is an error, not a warning.
@@ -436,7 +438,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the inference / fp32 / F=256 / configs[4] legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, updated parameters, gradients) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_under_torchrun(args.gpus))
@@ -518,6 +524,15 @@ def main():
         loss = step()
     barrier()
     elapsed_local = time.perf_counter() - t0
+    # --dump-outputs: what the LAST timed step handed its caller, copied before any later leg runs another step: the
+    # loss Trainer.step returns, the parameters Adam left and the gradient it applied
+    dumped = None
+    if args.dump_outputs:
+        dumped = {"loss": loss.detach().reshape(-1).cpu().numpy()}
+        for name, v in eng.params.views.items():
+            dumped["param." + name.replace("/", ".")] = v.detach().cpu().numpy()
+        for name, v in eng.params.grad_views.items():
+            dumped["grad." + name.replace("/", ".")] = v.detach().cpu().numpy()
     elapsed = elapsed_local
     rank_ms = [elapsed_local / args.steps * 1e3]
     if world > 1:
@@ -575,6 +590,14 @@ def main():
                         "range fall-backs: f32-input MFMA.  Error against float64 at or below the f32-input MFMA kernels' "
                         "(tests/test_gpu_edge_h2.py, test_gpu_fc_block.py, test_gpu_mp_w16.py)"),
     }
+    if dumped is not None and rank == 0:
+        assert sum(a.nbytes for a in dumped.values()) <= 64 << 20      # 23 + 23 arrays, ~0.9 MB at this architecture
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dumped.items():
+            assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+        out["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": len(dumped),
+                               "bytes": int(sum(a.nbytes for a in dumped.values()))}
 
     # ---- the reference sees a NEW graph tuple every step (nmrgnn/library.py:88-89): the same step with the batch
     # object rebuilt from the raw device tuple inside the timed region (compute-side lists + incoming-edge lists by

@@ -392,6 +392,39 @@ class TorchInterp(Interp):
         raise NotImplementedError(op)
 
 
+class ContractionInterp(Interp):
+    """Insurance for the Einsum / MatMul nodes (evaluated above with np.einsum / @): the same FunctionDef with those ops
+    evaluated by DIFFERENT code — tensordot with an explicit axis list, a hand-written loop over the edge-feature index, a
+    transposed product.  main() asserts it reproduces the inference peaks: a shared misreading of an equation string
+    would have to be made twice, in two notations."""
+
+    def eval(self, n, value):
+        op, a = n["op"], n["attr"]
+        if op == "Einsum":
+            x = [value(r) for r in n["input"] if not r.startswith("^")]
+            eq = a["equation"]["s"]
+            eq = eq.decode() if isinstance(eq, bytes) else eq
+            self.ops_seen[op] = self.ops_seen.get(op, 0) + 1
+            if eq == "lmn,ijl->mnij":       # w[l,m,n], gathered[i,j,l]
+                return np.tensordot(x[0], x[1], axes=([0], [2]))
+            if eq == "mnij,ijn->mi":        # t[m,n,i,j], edges[i,j,n]: loop over n, reduce j last
+                t, e = x
+                out = np.zeros((t.shape[0], t.shape[2]), t.dtype)
+                for nn in range(t.shape[1]):
+                    out += (t[:, nn, :, :] * e[None, :, :, nn]).sum(axis=2)
+                return out
+            if eq == "mi,i->im":
+                return (x[0] * x[1][None, :]).T.copy()
+            raise AssertionError(f"unexpected einsum {eq}")
+        if op == "MatMul":
+            x = [value(r) for r in n["input"] if not r.startswith("^")]
+            self.ops_seen[op] = self.ops_seen.get(op, 0) + 1
+            A = x[0].T if a.get("transpose_a", {}).get("b", False) else x[0]
+            B = x[1].T if a.get("transpose_b", {}).get("b", False) else x[1]
+            return np.dot(B.T, A.T).T
+        return super().eval(n, value)
+
+
 # resource argument (suffix after the function's name prefix) -> (state-dict key of this repo).
 # SURVEY App. A: edge-fc-block/dense..dense_3, mp-block/MPLayer w x4 (einsum, einsum_1..3),
 # fc-block/dense_4..7, out_layer = dense_8, embed_layer = dense_9.
@@ -568,6 +601,14 @@ def main():
         d_inf, d_tr = float(np.abs(q64 - p64).max()), float(np.abs(u64 - t64).max())
         assert d_inf <= 1e-12 * sc and d_tr <= 1e-12 * sc, (tag, d_inf, d_tr, sc)
         print("   torch-CPU float64 backend vs NumPy: inference %.2e, training %.2e (scale %.1f)" % (d_inf, d_tr, sc))
+        if tag == "padded":
+            # independent contractions (ContractionInterp): float64 to re-association noise, float32 to its rounding
+            for ft, tol in ((np.float64, 1e-9), (np.float32, 2e-4)):
+                pc, ops_c, _ = run_function(fd, top_consts, g, w, ft, backend=ContractionInterp)
+                assert ops_c.get("Einsum", 0) == 12 and ops_c.get("MatMul", 0) >= 9, ops_c
+                d_c = float(np.abs(np.asarray(pc, np.float64) - p64).max())
+                assert d_c < tol, (tag, ft, d_c)
+                print("   independent contractions (%s) vs NumPy einsum: %.2e" % (np.dtype(ft).name, d_c))
         el = np.argmax(g[0], axis=1).astype(np.int8)
         assert np.array_equal(np.eye(10, dtype=np.float32)[el], g[0])
         if graph_of is None:
