@@ -466,6 +466,18 @@ int ng_loss_l2(ng_ctx*, void* stream, int64_t N, int G, const int32_t* graph_ptr
 int ng_loss_name(ng_ctx*, void* stream, int64_t N, int G, const int32_t* graph_ptr, const float* y,
                  const float* w, const float* pred, float s, float* loss_out, float* dpred);
 
+/* Per-name shift metrics, nmrgnn/metrics.py:22-116 (NameRMSD 36-43, NameCount 64-70, NameCorr 91-116), for K <= 32 classes
+ * in one pass over the atoms.  Per class k the seven float64 sums
+ *   moments[K][7] = {S0 = sum m, Sd2 = sum m (y - p)^2, Sy = sum m y, Sp = sum m p, Syy = sum m y^2, Spp = sum m p^2,
+ *                    Syp = sum m y p},   m_i = w_i * [bit k of member[names_i]]
+ * (0 <= names_i < n_names, else the atom is in no class; w is used as given), from which the caller forms
+ *   RMSD = sqrt(divide_no_nan(Sd2, S0)),  count = S0,  r = cov / (S0 sqrt(var_y var_p))  (the host's few flops).
+ * accumulate = 0: moments are overwritten (the reference's assign); 1: the sums are added to them.  N = 0 writes zeros /
+ * adds nothing.  Two launches (per-workgroup partials in the context's scratch, then a fixed-order sum): asynchronous,
+ * bitwise deterministic, capturable in a graph. */
+int ng_name_metrics(ng_ctx*, void* stream, int64_t N, const float* y, const float* w, const int32_t* names, const float* pred,
+                    int n_names, const uint32_t* member, int K, int accumulate, double* moments);
+
 /* Keras Adam (nmrgnn/model.py:44-45): one fused pass over the flat parameter buffer.
  *   g is first multiplied by grad_scale (1/world_size after a summing all-reduce). */
 int ng_adam_step(ng_ctx*, void* stream, int64_t n, float* p, const float* g, float* m, float* v,

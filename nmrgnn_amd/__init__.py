@@ -2,7 +2,8 @@
 
 Drop-in surface of the reference package (nmrgnn/__init__.py:21-31):
 ``load_model``, ``universe2graph``, ``check_peaks``, ``MPLayer``, ``RBFExpansion``, ``EdgeFCBlock``,
-``MPBlock``, ``FCBlock``, ``GNNModel``, ``build_GNNModel``, ``NameLoss``.
+``MPBlock``, ``FCBlock``, ``GNNModel``, ``build_GNNModel``, ``NameLoss``, ``type_mask``, ``NameRMSD``, ``NameCorr``,
+``NameCount`` and ``custom_objects``; ``NameMetrics`` evaluates up to 32 metrics in one device pass.
 The compute path is libnmrgnn_hip.so (hand-written gfx950 HIP kernels) reached through ctypes;
 there is no CPU fallback.
 """
@@ -16,10 +17,16 @@ _LAZY = {
     "FCBlock": "layers", "GNNModel": "model", "build_GNNModel": "model",
     "load_model": "library", "universe2graph": "library", "check_peaks": "library",
     "save_model": "library", "NameLoss": "losses", "Trainer": "train",
+    "type_mask": "metrics", "NameRMSD": "metrics", "NameCorr": "metrics", "NameCount": "metrics", "NameMetrics": "metrics",
 }
+# nmrgnn/__init__.py:26-29: the reference's custom Keras objects, keyed by class name
+_CUSTOM_OBJECTS = ["NameRMSD", "NameCorr", "MPLayer", "NameLoss", "NameCount", "RBFExpansion", "EdgeFCBlock", "MPBlock",
+                   "FCBlock"]
 
 
 def __getattr__(name):
+    if name == "custom_objects":
+        return {n: __getattr__(n) for n in _CUSTOM_OBJECTS}
     mod = _LAZY.get(name)
     if mod is None:
         raise AttributeError(f"module 'nmrgnn_amd' has no attribute {name!r}")

@@ -43,6 +43,7 @@ class GNNModel:
         self._pending_state = None
         self._train_calls = 0         # training-mode calls so far: every one draws fresh noise / dropout
         self._flat_leaf = None        # torch.nn.Parameter over the flat weight buffer, created by parameters()
+        self.metrics = []             # Name* metrics (build_GNNModel with embeddings); reported by evaluate()
 
     # -- keras-like build: the number of elements comes from the first input (model.py:236-243)
     def build(self, num_elem):
@@ -107,6 +108,56 @@ class GNNModel:
 
     call = __call__
     predict = __call__
+
+    def evaluate(self, data, metrics=None):
+        """Validation pass (keras ``evaluate`` / the ``validation_data`` of nmrgnn/main.py:79-80).  ``data`` yields
+        ``(inputs, y_true[N, 3])`` or ``(inputs, y_true, graph_ptr)``; ``inputs`` is the model's input tuple.
+        Inference-mode forwards; the loss and the metric sums stay on the device until the end (no host read per batch).
+        Returns ``{'loss': mean over ALL graphs of the per-graph L2 NameLoss, <metric name>: value}`` for ``metrics``
+        (default ``self.metrics``).  The metrics are ACCUMULATED over the whole set (``NameMetrics(accumulate=True)``):
+        the reference's metrics keep only the last batch (``assign``), which says nothing about a validation set.
+        With one graph per batch the loss equals keras's mean over batches."""
+        from .losses import NameLoss
+        from .metrics import NameMetrics, _split_y_true
+        metrics = getattr(self, 'metrics', []) if metrics is None else metrics
+        nm = metrics if isinstance(metrics, NameMetrics) else (NameMetrics(metrics, accumulate=True) if metrics else None)
+        if nm is not None:
+            if not nm.accumulate:
+                raise ValueError("evaluate: a NameMetrics passed in must accumulate")
+            nm.reset_states()
+        loss_fn = getattr(self, 'loss', None)
+        label_idx = loss_fn.label_idx if isinstance(loss_fn, NameLoss) else None
+        loss_sum, graphs = None, 0
+        for item in data:
+            inputs, y_true = item[0], item[1]
+            graph_ptr = item[2] if len(item) > 2 else None
+            if isinstance(inputs, GraphBatch):
+                batch = inputs
+            else:
+                atoms, nlist, edges, inv_degree = inputs
+                self.build(int(atoms.shape[-1]))
+                batch = GraphBatch(atoms, nlist, edges, inv_degree, graph_ptr=graph_ptr, device=self.engine.device)
+            if self.engine is None:
+                self.build(batch.C)
+            eng = self.engine
+            peaks = eng.forward(batch, training=False)
+            y, w, names = _split_y_true(y_true, eng.device)
+            if y.shape[0] != batch.N:
+                raise ValueError(f"evaluate: y_true has {y.shape[0]} rows for {batch.N} atoms")
+            lw = w
+            if label_idx is not None:
+                ln = torch.as_tensor(np.atleast_1d(np.asarray(label_idx, np.int32)), device=eng.device)
+                lw = w * torch.isin(names, ln).to(torch.float32)
+            loss, _ = eng.loss_l2(batch, y, lw, peaks)
+            part = loss.to(torch.float64) * batch.G          # ng_loss_l2 is the mean over the batch's graphs
+            loss_sum = part if loss_sum is None else loss_sum + part
+            graphs += batch.G
+            if nm is not None:
+                nm.update(peaks, y, w, names)
+        out = {'loss': float(loss_sum.item()) / graphs if graphs else 0.0}
+        if nm is not None:
+            out.update(nm.results())
+        return out
 
     # -- torch.autograd surface (SURVEY 8b: the outer autograd shell)
     def parameters(self):
@@ -211,15 +262,20 @@ class GNNModel:
         self._restore_adam()
 
 
-def build_GNNModel(hp=None, metrics=True, loss_balance=1.0, device=None):
+def build_GNNModel(hp=None, metrics=True, loss_balance=1.0, device=None, embeddings=None):
     """nmrgnn/model.py:12-105.  Declares the hyper-parameter space on ``hp`` (same names/defaults),
     loads the peak standards and returns a GNNModel with ``optimizer`` / ``loss`` attributes set
-    (Adam at hp['learning_rate'], NameLoss(s=loss_balance)).  The 15 keras metrics of the
-    reference are training observability and are not part of the engine."""
+    (Adam at hp['learning_rate'], NameLoss(s=loss_balance)).
+    ``metrics=True`` with an ``embeddings`` dict that has ``'name'`` (nmrdata.load_embeddings(), not shipped here: the
+    package has no residue-name table) sets ``model.metrics`` to the reference's 15 metrics (model.py:56-103,
+    ``metrics.reference_metrics``; ``ValueError`` when a regular expression matches no name); otherwise
+    ``model.metrics = []``.  ``Trainer(..., metrics=model.metrics)`` and ``model.evaluate`` report them."""
     from .losses import NameLoss
+    from .metrics import reference_metrics
     hp = HyperParameters() if hp is None else hp
     declare_gnn_space(hp)
     model = GNNModel(hp, load_standards(), device=device)
+    model.metrics = reference_metrics(embeddings) if (metrics and embeddings is not None and 'name' in embeddings) else []
     model.loss = NameLoss(label_idx=None, s=loss_balance)
     model.optimizer = {"name": "Adam", "learning_rate": hp.get('learning_rate'),
                        "beta_1": 0.9, "beta_2": 0.999, "epsilon": 1e-7}

@@ -55,9 +55,12 @@ class TrainStepReplay:
     bit: same noise / dropout draws (the seed sequence of Trainer.step), same Adam step count.
 
     Single process (the gradient all-reduce of a data-parallel world is not captured).  The loss tensor returned by
-    ``step`` is a static buffer: read it before the next step."""
+    ``step`` is a static buffer: read it before the next step.
 
-    def __init__(self, trainer, example, y, w, graph_ptr=None):
+    ``names`` (int32 name ids [N]) captures the trainer's metric launch into the step (``Trainer(..., metrics=...)``);
+    the ids become one more staged buffer, and a ``step`` without ``names`` keeps the previous step's ids."""
+
+    def __init__(self, trainer, example, y, w, graph_ptr=None, names=None):
         eng = trainer.engine
         if trainer.buckets.world() != 1:
             raise ValueError("TrainStepReplay: single-process training only")
@@ -73,6 +76,9 @@ class TrainStepReplay:
         self.s_inv = as_t(inv, torch.float32).reshape(-1).clone()
         self.s_y = as_t(y, torch.float32).clone()
         self.s_w = as_t(w, torch.float32).clone()
+        if names is not None and trainer.metrics is None:
+            raise ValueError("TrainStepReplay: names given to a Trainer without metrics")
+        self.s_names = None if names is None else as_t(names, torch.int32).reshape(-1).clone()
         N = self.s_atoms.shape[0]
         self.graph_ptr = np.asarray([0, N] if graph_ptr is None else graph_ptr, dtype=np.int32)
         self.lr = trainer.lr if trainer.lr is not None else float(eng.hp.get('learning_rate'))
@@ -87,7 +93,7 @@ class TrainStepReplay:
         # the captured chain reads gb's device-side graph boundaries (and whatever else the batch allocated outside the
         # graph's pool) at every replay: the batch lives as long as the replay object, not as long as a cache entry
         self._gb = gb
-        return self.trainer.step(gb, self.s_y, self.s_w)
+        return self.trainer.step(gb, self.s_y, self.s_w, names=self.s_names)
 
     def _capture(self):
         eng, tr = self.eng, self.trainer
@@ -98,6 +104,8 @@ class TrainStepReplay:
         # warm-up does change, and the host-side step counters (the capture itself runs no kernel but counts steps) are
         # put back afterwards.
         keep = (eng.adam_m.clone(), eng.adam_v.clone(), eng.adam_t, tr.step_count)
+        nm = tr.metrics if self.s_names is not None else None
+        keep_nm = (nm.moments.clone() if nm.moments is not None else None, nm.updates) if nm is not None else None
         cur = torch.cuda.current_stream(eng.device)
         self._stream.wait_stream(cur)
         with torch.cuda.stream(self._stream):
@@ -116,9 +124,15 @@ class TrainStepReplay:
                 eng.lib.ng_replay_arm(eng.ctx.handle, 0)
             eng.adam_m.copy_(keep[0]); eng.adam_v.copy_(keep[1])
             eng.adam_t, tr.step_count = keep[2], keep[3]
+            if nm is not None:        # the warm-up steps' metric updates are not steps either
+                if keep_nm[0] is None:
+                    nm.moments.zero_()
+                else:
+                    nm.moments.copy_(keep_nm[0])
+                nm.updates = keep_nm[1]
         cur.wait_stream(self._stream)
 
-    def step(self, graph_tuple, y, w):
+    def step(self, graph_tuple, y, w, names=None):
         eng, tr = self.eng, self.trainer
         atoms, nlist, edges, inv = graph_tuple
         # the seed sequence of Trainer.step (rank 0)
@@ -126,6 +140,10 @@ class TrainStepReplay:
         pairs = [(_like(self.s_atoms, atoms), self.s_atoms), (_like(self.s_nlist, nlist), self.s_nlist),
                  (_like(self.s_edges, edges), self.s_edges), (_like(self.s_inv, inv), self.s_inv),
                  (_like(self.s_y, y), self.s_y), (_like(self.s_w, w), self.s_w)]
+        if names is not None:
+            if self.s_names is None:
+                raise ValueError("TrainStepReplay.step: names given, but the step was captured without them")
+            pairs.append((_like(self.s_names, names), self.s_names))
         eng._ck(eng.lib.ng_replay_arm(eng.ctx.handle, 1), "ng_replay_arm")
         try:
             _stage(eng, seed, self.lr, eng.adam_t + 1, pairs)
@@ -137,6 +155,8 @@ class TrainStepReplay:
             eng.lib.ng_replay_arm(eng.ctx.handle, 0)
         eng.adam_t += 1
         tr.step_count += 1
+        if self.s_names is not None:
+            tr.metrics.updates += 1
         return self.loss
 
 

@@ -19,10 +19,17 @@ class Trainer:
     writes into ``engine.params.flat`` in place between steps (weight surgery, finite-difference probes, a manual
     broadcast, clipping) must call ``engine.weights_changed()`` afterwards, or the next forward multiplies with the
     old images.  ``Trainer(..., cache_images=False)`` keeps per-call packing (always correct, one repack launch per
-    call slower); ``close()`` restores the engine's previous setting."""
+    call slower); ``close()`` restores the engine's previous setting.
 
-    def __init__(self, engine: Engine, lr=None, loss_balance=1.0, cache_images=True):
+    ``metrics``: a list of ``NameRMSD`` / ``NameCorr`` / ``NameCount`` (``model.metrics``) or a ``NameMetrics``.  A step
+    given ``names`` (int32 name ids [N], the int32 of y_true[:, 1]) queues ONE ``ng_name_metrics`` launch on the step's
+    training-mode peaks (what keras reports its training metrics on), with ``w`` as the weight column;
+    ``metric_results()`` reads them.  A step without ``names`` launches nothing more."""
+
+    def __init__(self, engine: Engine, lr=None, loss_balance=1.0, cache_images=True, metrics=None):
+        from .metrics import NameMetrics
         self.engine = engine
+        self.metrics = None if not metrics else (metrics if isinstance(metrics, NameMetrics) else NameMetrics(metrics))
         # the trainer owns the weight update: packed weight images are kept and refreshed in one launch behind Adam
         self._prev_cache_images = engine.cache_images
         engine.cache_images = bool(cache_images)
@@ -38,7 +45,7 @@ class Trainer:
         self.measure_comm = False
         self._comm_events = []
 
-    def step(self, batch: GraphBatch, y: torch.Tensor, w: torch.Tensor, seed=None, total_graphs=None):
+    def step(self, batch: GraphBatch, y: torch.Tensor, w: torch.Tensor, seed=None, total_graphs=None, names=None):
         """One optimiser step.  ``total_graphs``: number of graphs over ALL ranks this step (every rank can
         compute it from ``parallel.shard_range``); needed only when the shards are uneven — the loss is a mean
         over graphs, so a rank holding G_local of G_total graphs must weigh its gradient G_local/G_total, not
@@ -61,6 +68,8 @@ class Trainer:
             loss, dpred = eng.loss_name(batch, y, w, peaks, self.loss_balance)
             if wgt != 1.0:
                 dpred.mul_(wgt)
+        if names is not None and self.metrics is not None:
+            self.metrics.update(eng.tape.peaks, y, w, names)
         eng.backward(dpred, on_node_grads=self.buckets.launch_node)
         self.buckets.launch_edge()
         if self.measure_comm:
@@ -74,6 +83,12 @@ class Trainer:
         eng.adam_step(lr=self.lr, grad_scale=self.buckets.grad_scale())
         self.step_count += 1
         return loss
+
+    def metric_results(self):
+        """{metric name: value} of the last step that was given ``names`` (one device-to-host copy)"""
+        if self.metrics is None:
+            raise ValueError("Trainer was built without metrics")
+        return self.metrics.results()
 
     def comm_exposed_ms(self):
         """mean stall of the compute stream at the all-reduce wait over the steps measured so far (resets)"""
