@@ -432,18 +432,19 @@ int ng_head_loss_reduce(ng_ctx*, void* stream, const float* partial, int blocks,
  *   d_eff, pos     the distances fed to the RBF: slot order (pos == NULL) or compacted, slot i at d_eff[pos[i]]
  *                  (ng_build_live_edges / ng_add_noise_live)
  *   ng_edge_table_range    range[0..1] = min / max of d_eff over the live slots, widened by pad * (max - min) on both sides
- *                          (pad > 0: a table kept over calls), when d_eff != NULL; range[2] = max |de| over the live slots
- *                          when de != NULL.  range: 3 device floats.
+ *                          (pad > 0: a table kept over calls; equal distances: width max(1e-6, |lo| 2^-20)), when d_eff != NULL;
+ *                          range[2] = max |de| over the live slots (inf if one is not finite) when de != NULL.  range: 3 device floats.
  *   ng_edge_table_points   d_tab[t] = lo + (t - 1) h, h = (hi - lo) / (T - 3), t < T;  midpoints != 0: d_tab[T + t] =
  *                          lo + (t - 1/2) h too;  ones[.] = 1 (the table's d_src: all live);  perm[.] = identity (or NULL)
  *   ng_edge_table_check    e_all [2T,E] (or NULL: only the range is checked): err = max |interpolant - f_W| over the interior
  *                          midpoints, scale = max |f_W| over the table; bad = err > tol * scale, or a value not finite, or
  *                          cover != NULL and [cover[0], cover[1]] not inside [range[0], range[1]], or prev != NULL and
  *                          prev[0] != 0.  gate (8 device int32): {bad, bad ? *n_live : -1, bad ? 0 : rows, 0, err, scale (float
- *                          bits), -, -}.
+ *                          bits; e_all == NULL: prev's, or 0), -, -}.
  *   ng_edge_table_interp   e_out[i][c] = m_i sum_k w_k(d_i) e_tab[i0 + k][c]   (E <= 8, T * E <= 16384: T = 2048 for E > 4); skipped on gate[0]
  *   ng_edge_table_scatter  de_tab[t][c] = sum_i m_i w_k(d_i) de[i][c] over the stencils that contain t, rows T .. rows_out-1
- *                          of de_tab zeroed (the midpoint rows of the table's backward); writes range[2] */
+ *                          of de_tab zeroed (the midpoint rows of the table's backward); writes range[2].  Terms rounded to
+ *                          q = 2^(ex - sh), max|de| < 2^ex, sh = 38 - max(0, ceil(log2 n) - 24); a non-finite live de: NaN rows */
 int ng_edge_table_range(ng_ctx*, void* stream, int64_t n, int E, const float* d_src, const float* d_eff, const int32_t* pos,
                         const float* de, float pad, float* range);
 int ng_edge_table_points(ng_ctx*, void* stream, int T, int midpoints, const float* range, float* d_tab, float* ones, int32_t* perm);

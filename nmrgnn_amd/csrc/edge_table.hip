@@ -19,6 +19,13 @@
 //
 // Determinism: the scatter accumulates in 64-bit fixed point (LDS atomics per workgroup, integer sums over the workgroups) —
 // integer addition is associative, so the bits do not depend on the order the edges arrive in.
+//
+// Fixed point of the scatter: with M = max |de| over the live slots, 2^(ex-1) <= M < 2^ex (frexp), and n the slot count, every
+// term w_k de is rounded to a multiple of the quantum q = 2^(ex - sh), sh = 38 - max(0, ceil(log2 n) - 24).  A term is below
+// 1.5 * 2^sh quanta (|w_k| < 1.5), so any sum of n of them stays below 1.5 * 2^62 < 2^63: no wrap for any n the API accepts.
+// Up to n = 2^24 slots sh = 38, q < M * 2^-37.  The result for table entry j is within (count_j / 2) q of the sum of the fp32
+// terms fl(w_k * de) that land on it, before its one rounding to fp32.  A non-finite de in a live slot (the range pass records
+// it as max |de| = inf) makes every table entry NaN, as it makes every weight gradient NaN on the per-edge path.
 #include <algorithm>
 #include "ng_internal.h"
 
@@ -65,7 +72,10 @@ __global__ __launch_bounds__(ET_BLOCK) void et_range_kernel(int64_t n, int E, co
       if (live) {
         if (d_eff) { lo = fminf(lo, dv[u]); hi = fmaxf(hi, dv[u]); }
 #pragma unroll
-        for (int c = 0; c < ET_EMAX; ++c) mx = fmaxf(mx, fabsf(g[u][c]));
+        for (int c = 0; c < ET_EMAX; ++c) {
+          const float a = fabsf(g[u][c]);
+          mx = a <= 3.4028235e38f ? fmaxf(mx, a) : INFINITY;      // NaN / inf: recorded as inf (fmaxf would drop a NaN)
+        }
       }
     }
   }
@@ -96,7 +106,10 @@ __global__ __launch_bounds__(ET_BLOCK) void et_range_final_kernel(int nb, const 
     for (int w = 1; w < ET_BLOCK / 64; ++w) { lo = fminf(lo, s[0][w]); hi = fmaxf(hi, s[1][w]); mx = fmaxf(mx, s[2][w]); }
     if (write_range) {
       if (!(hi >= lo)) { lo = 0.f; hi = 1.f; }            // no live edge at all
-      if (!(hi - lo > 1e-6f)) hi = lo + 1e-6f;            // all distances equal: a table of (almost) one point
+      // all distances equal: a table of (almost) one point.  The width is relative to |lo| too: lo + 1e-6 rounds back to lo once
+      // ulp(lo) > 2e-6 (|lo| >= 32), and h = 0 would make every stencil weight NaN
+      const float wmin = fmaxf(1e-6f, fabsf(lo) * 0x1p-20f);
+      if (!(hi - lo >= wmin)) hi = lo + wmin;
       const float w = (hi - lo) * pad;                    // a table kept over calls covers more than the call that built it
       out[0] = lo - w; out[1] = hi + w;
     }
@@ -178,6 +191,7 @@ __global__ __launch_bounds__(ET_CHECK_THREADS) void et_check_kernel(int T, int E
     gate[2] = bad ? 0 : rows;
     gate[3] = 0;
     if (e_all) { gate[4] = __builtin_bit_cast(int32_t, err); gate[5] = __builtin_bit_cast(int32_t, sc); }
+    else { gate[4] = prev ? prev[4] : 0; gate[5] = prev ? prev[5] : 0; }      // only the range checked: the table's own err, scale
   }
 }
 
@@ -225,12 +239,12 @@ __global__ __launch_bounds__(ET_WIDE) void et_interp_kernel(int64_t n, int T, co
   }
 }
 
-// adjoint: table[i0 + k][c] += w_k * m_i * de[i][c], in 64-bit fixed point (scale 2^sh from max |de|: |sum| < 2^62 for up to
-// 2^21 terms of size <= 2^40 each), per workgroup in LDS, partial tables to memory
+// adjoint: table[i0 + k][c] += w_k * m_i * de[i][c], in 64-bit fixed point (quantum q = 2^(ex - sh), see the top of the file),
+// per workgroup in LDS, partial tables to memory.  Nothing to do when max |de| is not finite (the final pass writes NaN)
 template <int EC>
 __global__ __launch_bounds__(ET_WIDE) void et_scatter_kernel(int64_t n, int T, const float* __restrict__ d_src,
                                                             const float* __restrict__ d_eff, const int32_t* __restrict__ pos,
-                                                            const float* __restrict__ range, const float* __restrict__ de,
+                                                            const float* __restrict__ range, const float* __restrict__ de, int sh,
                                                             long long* __restrict__ part) {
   extern __shared__ long long et_q[];
   for (int t = threadIdx.x; t < T * EC; t += ET_WIDE) et_q[t] = 0;
@@ -238,9 +252,10 @@ __global__ __launch_bounds__(ET_WIDE) void et_scatter_kernel(int64_t n, int T, c
   float lo, inv_h, h;
   et_geom(range, T, lo, inv_h, h);
   const float mx = range[2];
+  if (!(mx <= 3.4028235e38f)) return;
   int ex = 0;
-  if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &ex);      // mx <= 2^ex
-  const float scale = ldexpf(1.0f, 38 - ex);                // |w de| * scale < 2^39 (|w| < 1.5)
+  if (mx > 0.f) (void)frexpf(mx, &ex);                      // mx < 2^ex
+  const float scale = ldexpf(1.0f, sh - ex);                // |w de| * scale < 1.5 * 2^sh (|w| < 1.5)
   for (int64_t i = (int64_t)blockIdx.x * ET_WIDE + threadIdx.x; i < n; i += (int64_t)gridDim.x * ET_WIDE) {
     if (d_src[i] > 0.f) {
       int i0;
@@ -267,12 +282,14 @@ __global__ __launch_bounds__(ET_WIDE) void et_scatter_kernel(int64_t n, int T, c
 // sums: any order gives the same bits.
 // entries [TE, TE_out): rows of the table's backward that carry no gradient (the midpoints of the guard): zeros
 __global__ __launch_bounds__(ET_BLOCK) void et_scatter_final_kernel(int nb, int TE, int TE_out, const long long* __restrict__ part,
-                                                                  const float* __restrict__ range, float* __restrict__ de_tab) {
+                                                                  const float* __restrict__ range, int sh, float* __restrict__ de_tab) {
   __shared__ long long red[ET_BLOCK];
   const int tt = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int t = blockIdx.x * 64 + tt;
+  const float mx = range[2];
+  const bool fin = mx <= 3.4028235e38f;      // a non-finite live de: every entry NaN (the partials were not written)
   long long s = 0;
-  if (t < TE) {
+  if (fin && t < TE) {
     int b = g;
     for (; b + 28 < nb; b += 32) {
       long long v[8];
@@ -287,10 +304,9 @@ __global__ __launch_bounds__(ET_BLOCK) void et_scatter_final_kernel(int nb, int 
   __syncthreads();
   if (g == 0 && t < TE) {
     s = red[tt] + red[64 + tt] + red[128 + tt] + red[192 + tt];
-    const float mx = range[2];
     int ex = 0;
-    if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &ex);
-    de_tab[t] = (float)((double)s * ldexp(1.0, ex - 38));
+    if (fin && mx > 0.f) (void)frexpf(mx, &ex);
+    de_tab[t] = fin ? (float)((double)s * ldexp(1.0, ex - sh)) : __builtin_nanf("");
   }
   if (g == 1 && t >= TE && t < TE_out) de_tab[t] = 0.f;
 }
@@ -367,17 +383,20 @@ extern "C" int ng_edge_table_scatter(ng_ctx* ctx, void* stream, int64_t n, int E
   // max |de| over the live slots -> range[2]
   if (int rc = ng_edge_table_range(ctx, stream, n, E, d_src, nullptr, nullptr, de, 0.f, range)) return rc;
   const int nb = std::max(1, (int)std::min<int64_t>(cdiv(n, (int64_t)ET_WIDE * 2), (int64_t)ctx->num_cu));
+  int lg = 0;                                 // ceil(log2 n): the fixed point gives up one bit per doubling of n beyond 2^24
+  while (lg < 62 && ((int64_t)1 << lg) < n) ++lg;
+  const int sh = 38 - std::max(0, lg - 24);
   long long* part = (long long*)workspace(ctx, (size_t)nb * T * E * 8);
   if (!part) return NG_ERR_NOMEM;
   const size_t lds = (size_t)T * E * 8;
   ProfScope ps(ctx, st, "edge_table_scatter");
   switch (E) {
-#define NG_ETS(EC) case EC: hipLaunchKernelGGL((et_scatter_kernel<EC>), dim3(nb), dim3(ET_WIDE), lds, st, n, T, d_src, d_eff, pos, range, de, part); break;
+#define NG_ETS(EC) case EC: hipLaunchKernelGGL((et_scatter_kernel<EC>), dim3(nb), dim3(ET_WIDE), lds, st, n, T, d_src, d_eff, pos, range, de, sh, part); break;
     NG_ETS(1) NG_ETS(2) NG_ETS(3) NG_ETS(4) NG_ETS(5) NG_ETS(6) NG_ETS(7) NG_ETS(8)
 #undef NG_ETS
   }
   hipLaunchKernelGGL(et_scatter_final_kernel, dim3((unsigned)cdiv(rows_out * E, 64)), dim3(ET_BLOCK), 0, st, nb, T * E, rows_out * E, part,
-                     range, de_tab);
+                     range, sh, de_tab);
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
 }

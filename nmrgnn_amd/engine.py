@@ -440,10 +440,11 @@ class Engine:
 
     def edge_table_report(self, table=None):
         """(guard up?, interpolation error at the midpoints, largest |e| of the table) of the last taped call's table (or of
-        ``table``).  Reads device words: synchronises; for tests and diagnostics."""
+        ``table``; a call that reused the table of frozen weights reports the error and scale measured when it was built).
+        Reads device words: synchronises; for tests and diagnostics.  Raises RuntimeError when there is no table to report on."""
         tb = table if table is not None else ((self.tape.table or self.tape.table_sync) if self.tape is not None else None)
         if tb is None:
-            return None
+            raise RuntimeError("edge_table_report: no edge-function table (no taped call, or the call went per edge)")
         g = tb["gate"].cpu().numpy()
         return bool(g[0]), float(g[4:6].view(np.float32)[0]), float(g[4:6].view(np.float32)[1])
 

@@ -228,3 +228,125 @@ def test_host_guarded_table_for_edge_shapes_without_the_fused_kernels(gpu_device
     for name in ea.params.offsets:
         x, z = ea.params.g(name), eb.params.g(name)
         assert float((x - z).abs().max()) <= 4e-5 * max(float(x.abs().max()), 1e-12), name
+
+
+def _degenerate_batch(kind, seed=31):
+    """a bench-like batch whose live distances are one value (0.3, or 40: lo + 1e-6 rounds back to lo there), one live edge
+    per graph, or the ordinary spread with one outlier that stretches the table's h towards the RBF width"""
+    from nmrgnn_amd import synth
+    b = synth.make_batch(8, 256, 16, 10, 0.05, seed=seed)
+    d = b["edges"]
+    live = d > 0
+    if kind in ("equal 0.3", "equal 40"):
+        d[live] = np.float32(kind.split()[1])
+    elif kind == "one per graph":
+        keep = np.zeros_like(live)
+        for g in range(len(b["graph_ptr"]) - 1):
+            a = int(b["graph_ptr"][g]) + 3
+            keep[a, int(np.argmax(live[a]))] = True
+        d[~keep] = 0.0
+    else:       # "outlier x": one live distance set to x
+        a, k = np.argwhere(live)[17]
+        d[a, k] = np.float32(kind.split()[1])
+    b["edges"] = d.astype(np.float32)
+    return b
+
+
+@pytest.mark.parametrize("kind", ["equal 0.3", "equal 40", "one per graph", "outlier 5", "outlier 100"])
+def test_degenerate_distance_sets(gpu_device, kind):
+    """the table path against the per-edge path where the table's range is degenerate or stretched: inference and a taped
+    inference-mode forward with its backward (distances exactly as given, no noise).  A guard that is up gives the per-edge
+    bits; a guard that is down, the tolerances of the ordinary case."""
+    from nmrgnn_amd.graph import GraphBatch
+    b = _degenerate_batch(kind)
+    gb = GraphBatch(b["atoms"], b["nlist"], b["edges"], b["inv_degree"], graph_ptr=b["graph_ptr"], device=gpu_device)
+    y = torch.from_numpy(b["y"]).to(gpu_device); w = torch.from_numpy(b["w"]).to(gpu_device)
+    ea, eb = _engines(64, gpu_device)
+    out = []
+    for eng in (ea, eb):
+        p_inf = eng.forward(gb).clone()
+        p = eng.forward(gb, keep_tape=True)
+        e = eng.tape.e.clone()
+        up = eng.edge_table_report()[0] if eng is eb else None
+        if eng is eb:
+            assert eng.tape.table is not None
+        loss, d = eng.loss_l2(gb, y, w, p)
+        eng.backward(d)
+        out.append((p_inf, p.clone(), e, eng.params.grad.clone(), up))
+    torch.cuda.synchronize()
+    (ia, pa, e_a, ga, _), (ib, pb, e_b, gb_, up) = out
+    assert torch.isfinite(ib).all() and torch.isfinite(pb).all() and torch.isfinite(e_b).all() and torch.isfinite(gb_).all()
+    if up:
+        assert torch.equal(ia, ib) and torch.equal(pa, pb) and torch.equal(e_a, e_b) and torch.equal(ga, gb_)
+        return
+    # a stretched range may pass the guard with an error up to its tolerance (3e-6 of max |e|): the tolerances of the sharp
+    # edge functions above; otherwise those of the ordinary case
+    tp, te, tg = (4e-6, 4e-6, 4e-5) if kind.startswith("outlier") else (2e-6, 1e-6, 2e-5)
+    scale = max(float(pa.abs().max()), 1.0)
+    assert float((pa - pb).abs().max()) <= tp * scale and float((ia - ib).abs().max()) <= tp * scale, kind
+    assert float((e_a - e_b).abs().max()) <= te * max(float(e_a.abs().max()), 1.0), kind
+    for name in ea.params.offsets:
+        x, z = ea.params.g(name), eb.params.g(name)
+        assert float((x - z).abs().max()) <= tg * max(float(x.abs().max()), 1e-12), (kind, name)
+
+
+@pytest.mark.parametrize("training", [False, True])
+def test_non_finite_upstream_gradient_reaches_the_edge_weights(gpu_device, training):
+    """dpeaks NaN for one atom: the per-edge backward gives NaN edge-weight gradients, and so must the table's (its scatter
+    turned a NaN de into a finite fixed-point word)"""
+    from nmrgnn_amd import synth
+    from nmrgnn_amd.graph import GraphBatch
+    b = synth.make_batch(8, 256, 16, 10, 0.05, seed=41)
+    gb = GraphBatch(b["atoms"], b["nlist"], b["edges"], b["inv_degree"], graph_ptr=b["graph_ptr"], device=gpu_device)
+    dp = np.random.default_rng(4).standard_normal(gb.N).astype(np.float32)
+    dp[300] = np.nan
+    ea, eb = _engines(64, gpu_device)
+    for eng in (ea, eb):
+        if training:
+            eng.forward(gb, training=True, seed=3)
+        else:
+            eng.forward(gb, keep_tape=True)
+        assert (eng.tape.table is not None) == (eng is eb)
+        if eng is eb:
+            assert not eng.edge_table_report()[0]
+        eng.backward(torch.from_numpy(dp).to(gpu_device))
+        torch.cuda.synchronize()
+        for t in range(4):
+            for k in ("kernel", "bias"):
+                g = eng.params.g(f"edge_fc/{t}/{k}")
+                assert not bool(torch.isfinite(g).all()), (eng is eb, t, k)
+
+
+def test_cached_table_report_and_no_table(gpu_device):
+    """frozen weights: a later call checks only its distance range against the kept table, and its guard words carry the err
+    and scale the table was built with (they were never written); with no table the report raises"""
+    from nmrgnn_amd import synth
+    from nmrgnn_amd.graph import GraphBatch
+    ea, eb = _engines(64, gpu_device)
+    with pytest.raises(RuntimeError):
+        eb.edge_table_report()
+    eb.freeze_weights(True)
+    batches = []
+    for s in (1, 2):
+        b = synth.make_batch(10, 256, 16, 10, 0.05, seed=50 + s)
+        batches.append(GraphBatch(b["atoms"], b["nlist"], b["edges"], b["inv_degree"], graph_ptr=b["graph_ptr"], device=gpu_device))
+    eb.forward(batches[0])
+    built = eb.edge_table_report(eb._table_cache)
+    assert not built[0] and np.isfinite(built[1:]).all() and built[2] > 0
+    # the words the second call's gate is allocated on held something else before (a freed block of the same size)
+    junk = torch.full((8,), 0x7FC00000, dtype=torch.int32, device=gpu_device)
+    del junk
+    gb2 = batches[1]
+    live = gb2.live_edges(force=True)
+    tb = eb._edge_table_build(gb2, live, live[2], False, False)
+    assert tb["e_all"] is eb._table_cache["e_all"]             # the kept table, range check only
+    rep = eb.edge_table_report(tb)
+    assert rep == built, (rep, built)
+    pa, pb = ea.forward(gb2), eb.forward(gb2)
+    assert float((pa - pb).abs().max()) <= 2e-6 * max(float(pa.abs().max()), 1.0)
+    # an untaped call leaves no table to report on; a per-edge engine never has one
+    with pytest.raises(RuntimeError):
+        eb.edge_table_report()
+    ea.forward(gb2, keep_tape=True)
+    with pytest.raises(RuntimeError):
+        ea.edge_table_report()
