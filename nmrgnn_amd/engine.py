@@ -33,10 +33,32 @@ def rbf_grid(low, high, count):
     return c, float(np.float32(c[1] - c[0]))
 
 
+def edge_path(edge_table, use_live_edges, live_kernels, E, n_edges, min_edges, is_csr, capturing):
+    """How the edge stage computes e for one call:
+    "table"      the edge-function table, its guard read on the device (fused live-edge kernels only);
+    "table_host" the same table, its guard read on the host (edge shapes without the fused kernels);
+    "live"       the per-edge MLP over the compacted live slots;
+    "slots"      the per-edge MLP over every slot.
+    ``live_kernels``: ng_edge_live_supported of the edge shape; ``capturing``: a stream capture is in progress.
+    The caller still falls back to "slots" where the batch has no live view ("table", "live") or the host-read guard
+    is up ("table_host")."""
+    # the live kernels and the table index e with 32 bits (check_live in edge_fwd_h2.hip)
+    fits = n_edges * E * 4 < (1 << 31)
+    sized = edge_table and E <= 8 and n_edges >= min_edges and fits
+    if live_kernels and fits:
+        return "table" if sized else ("live" if use_live_edges else "slots")
+    # is_csr and capturing gate only the host-guarded table: the device-guarded one also runs on CSR batches (through a
+    # forced live view) and under capture.  A host read cannot be captured, so a captured call goes per edge here even
+    # where its eager warm-up took the table (ADVICE.md, first finding).
+    if sized and not is_csr and not capturing:
+        return "table_host"
+    return "slots"
+
+
 class Tape:
     """activations kept between forward(training=True) and backward()"""
-    __slots__ = ("batch", "d_eff", "z_save", "z_layout", "e", "h", "A", "S", "fx", "fs", "g", "drop_mask",
-                 "peaks", "live", "table", "table_sync", "loss", "dpeaks", "dg", "head_partial")
+    __slots__ = ("batch", "d_eff", "z_save", "z_layout", "e", "h", "A", "S", "fx", "g", "drop_mask",
+                 "peaks", "edge_path", "live", "table", "loss", "dpeaks", "dg", "head_partial")
 
 
 class Engine:
@@ -90,21 +112,20 @@ class Engine:
         # per call, so code that writes into parameter views directly stays correct.
         self.cache_images = False
         self.defer_reductions = True      # backward(): queue the weight-gradient sums, one launch (ng_defer_reductions)
-        # edge shapes without the fused live-edge kernels (edge_hidden_size != 128, ...): the same table, its guard read on the
-        # HOST (one synchronisation per call: nothing on the device can gate the layered kernels) — False / NG_EDGE_TABLE_SYNC=0: per edge
-        self.edge_table_sync = os.environ.get("NG_EDGE_TABLE_SYNC", "1") != "0"
         # forward(loss=...): head + L2 loss + head backward as one launch where the shape allows (ng_head_loss_bwd)
         self.fuse_head_loss = os.environ.get("NG_HEAD_LOSS", "1") != "0"
         # padded slots (edges == 0) are skipped by the fused edge kernels (include/nmrgnn_hip.h: ng_edge_mlp_fwd_live);
         # NG_EDGE_LIVE=0 runs every slot as rounds 1-3 did (A/B measurements, tests)
         self.use_live_edges = os.environ.get("NG_EDGE_LIVE", "1") != "0"
         # DEFAULT since round 6 (round 5: opt-in; csrc/edge_table.hip): the edge MLP is a function of one scalar per edge —
-        # evaluate it with the fused kernels on EDGE_TABLE_POINTS equidistant distances and interpolate every edge (cubic, error
-        # < 1e-9 relative for weights of ordinary size); the backward scatters de onto the table (exact adjoint) and runs the
-        # fused backward on the table.  Guarded on the device: the same launch evaluates the function at the midpoints too,
-        # ng_edge_table_check compares, and above ``edge_table_tol`` x max |e| the SAME call is answered by the per-edge
-        # kernels (they run over a row count that is zero unless the guard is up).  NG_EDGE_TABLE=0 / edge_table = False: the
-        # per-edge kernels always — what the reference does and what bench.py's `value` is measured on.
+        # evaluate it on _table_points() equidistant distances and interpolate every edge (cubic); the backward scatters de
+        # onto the table (exact adjoint) and runs the MLP backward on the table.  The guard: the same launch evaluates the
+        # function at the midpoints too, ng_edge_table_check compares, and where the interpolation error there exceeds
+        # ``edge_table_tol`` x max |e| of the table (an absolute bound: a small component of e has no relative one) the SAME
+        # call is answered per edge.  With the fused live-edge kernels the guard is read on the device (the per-edge kernels
+        # run over a row count that is zero unless it is up); edge shapes without them read it on the host, one
+        # synchronisation per call (see edge_path).  NG_EDGE_TABLE=0 / edge_table = False: the per-edge kernels always —
+        # what the reference does and what bench.py's `value` is measured on.
         self.edge_table = os.environ.get("NG_EDGE_TABLE", "1") != "0"
         self.edge_table_tol = 3.0e-6          # bound on |interpolant - function| at the midpoints, relative to max |e| of the table
         self.edge_table_min_edges = 262144    # below, the table's extra launches (range, check, gated per-edge launch, interpolation:
@@ -112,6 +133,8 @@ class Engine:
         self.edge_table_force_fallback = False   # tests: raise the guard whatever the check finds (tol = -1)
         self._wgen = 0                        # bumped whenever the weights change: a table kept over calls (frozen weights)
         self._table_cache = None
+        # the row count of the table's own MLP launches (2T: the table and its midpoints), a device word the live kernels read
+        self._rows_2t = torch.full((1,), 2 * self._table_points(), dtype=torch.int32, device=self.device)
         Engine._ids += 1
         self._id = Engine._ids          # owner tag of the frozen-weight cache
 
@@ -187,14 +210,17 @@ class Engine:
         self._ck(lib.ng_ctx_set_graph_span(h, batch.max_graph_atoms), "ng_ctx_set_graph_span")
         d_src = batch.edges.reshape(-1)
         d_eff = d_src
-        # live-edge view: the fused edge kernels walk the compacted live slots only (same e bit for bit)
-        # (the live kernels index e with 32 bits: n_slots * E * 4 < 2^31, check_live in edge_fwd_h2.hip; larger batches take the
-        # every-slot kernels)
-        live_ok = ne * E * 4 < (1 << 31) and bool(lib.ng_edge_live_supported(H, E, self.Le, self.fc_act))
-        use_table = self.edge_table and E <= 8 and ne >= self.edge_table_min_edges and live_ok
-        live = batch.live_edges(force=use_table) if (live_ok and (use_table or self.use_live_edges)) else None
+        live_kernels = bool(lib.ng_edge_live_supported(H, E, self.Le, self.fc_act))
+        path = edge_path(self.edge_table, self.use_live_edges, live_kernels, E, ne, self.edge_table_min_edges, batch.is_csr,
+                         torch.cuda.is_current_stream_capturing())
+        # live-edge view: the fused edge kernels walk the compacted live slots only (same e bit for bit); the device-guarded
+        # table needs one even where no slot is dead
+        live = batch.live_edges(force=path == "table") if path in ("table", "live") else None
+        if live is None and path in ("table", "live"):
+            path = "slots"
+        perm = pos = rows = None
         if live is not None:
-            perm, pos, d_c, n_live = live
+            perm, pos, d_c, rows = live
             d_src = d_eff = d_c
             if training and self.sigma > 0:
                 d_eff = self._new(ne)       # compacted: the first n_live entries are used
@@ -208,43 +234,21 @@ class Engine:
                 noise = noise.reshape(-1)
                 self._ck(lib.ng_add_scaled(h, st, ne, ptr(d_src), ptr(noise), self.sigma, ptr(d_eff)),
                          "ng_add_scaled")
-        # the table of the edge function and the guard's verdict (device words) — before the per-edge launch, which runs over
-        # gate[1] rows: none unless the guard is up
-        table = self._edge_table_build(batch, live, d_eff, tape, training) if (use_table and live is not None) else None
-        table_sync = None
-        if (table is None and live is None and self.edge_table and self.edge_table_sync and not live_ok and not batch.is_csr
-                and E <= 8 and ne >= self.edge_table_min_edges and ne * E * 4 < (1 << 31)
-                and not torch.cuda.is_current_stream_capturing()):
-            table_sync = self._edge_table_build_sync(batch, d_src, d_eff, tape)      # None: the guard is up
-        if table_sync is not None:
-            z_save, z_layout = None, 0
-            e = self._new(ne, E)
-            self._ck(lib.ng_edge_table_interp(h, st, ne, E, table_sync["T"], ptr(batch.edges), ptr(d_eff), None,
-                                              ptr(table_sync["rng"]), ptr(table_sync["e_all"]), ptr(table_sync["gate"]), ptr(e)),
+        # the table of the edge function and the guard's verdict — before the per-edge launch, which on the "table" path runs
+        # over gate[1] rows: none unless the guard is up
+        table = self._edge_table_build(batch, live, d_eff, tape, training) if path in ("table", "table_host") else None
+        if path == "table_host" and table is None:      # the guard, read on the host, is up
+            path = "slots"
+        if path == "table":
+            rows = table["gate"][1:]
+        e = self._new(ne, E)
+        z_save, z_layout = None, 0
+        if path != "table_host":
+            z_save, z_layout = self._edge_mlp_fwd(ne, d_src, d_eff, e, tape, perm, rows)
+        if table is not None:       # every slot from the table — unless the device guard is up: then the launch returns at once
+            self._ck(lib.ng_edge_table_interp(h, st, ne, E, table["T"], ptr(batch.edges), ptr(d_eff), ptr(pos),
+                                              ptr(table["rng"]), ptr(table["e_all"]), ptr(table["gate"]), ptr(e)),
                      "ng_edge_table_interp")
-        z_save = self._new(self.Le - 1, ne, H) if (tape and table_sync is None) else None
-        # element order of the tape the edge forward is about to write (it depends on the NG_EDGE_* switches in force
-        # NOW; the backward is told, so a switch flipped in between cannot make it misread the tape)
-        z_layout = int(lib.ng_edge_tape_layout(H, E, self.Le, self.fc_act, ne)) if (tape and table_sync is None) else 0
-        W = [P[f"edge_fc/{t}/kernel"] for t in range(self.Le)]
-        B = [P[f"edge_fc/{t}/bias"] for t in range(self.Le)]
-        if table_sync is not None:
-            pass            # e came from the table
-        elif live is not None:
-            e = self._new(ne, E)
-            rows = table["gate"][1:] if table is not None else n_live
-            self._ck(lib.ng_edge_mlp_fwd_live(h, st, ne, H, E, self.Le, self.fc_act, ptr(d_src), ptr(d_eff), ptr(perm),
-                                              ptr(rows), ptr(self.centers), self.gap, ptr_array(W), ptr_array(B),
-                                              ptr(e), ptr(z_save)), "ng_edge_mlp_fwd_live")
-            if table is not None:       # every slot from the table — unless the guard is up: then the launch returns at once
-                self._ck(lib.ng_edge_table_interp(h, st, ne, E, table["T"], ptr(batch.edges), ptr(d_eff), ptr(pos),
-                                                  ptr(table["rng"]), ptr(table["e_all"]), ptr(table["gate"]), ptr(e)),
-                         "ng_edge_table_interp")
-        else:
-            e = self._new(ne, E)
-            self._ck(lib.ng_edge_mlp_fwd(h, st, ne, H, E, self.Le, self.fc_act, ptr(d_src), ptr(d_eff),
-                                         ptr(self.centers), self.gap, ptr_array(W), ptr_array(B),
-                                         ptr(e), ptr(z_save)), "ng_edge_mlp_fwd")
         h0 = self._new(N, F)
         self._ck(lib.ng_embed_fwd(h, st, N, self.C, F, ptr(batch.atoms), ptr(P["embed/kernel"]),
                                   ptr(h0)), "ng_embed_fwd")
@@ -289,7 +293,7 @@ class Engine:
                                         ptr(self.peak_avg), ptr(peaks)), "ng_fc_head_fwd")
             return peaks
         # FC block: every layer in one call; the tape keeps the layer inputs only (nmrgnn/model.py:191-196)
-        fx, fs = [hs[-1]], []
+        fx = [hs[-1]]
         for t in range(self.Lf - 1):
             fx.append(self._new(N, F))
         Fh = F // 2
@@ -334,150 +338,122 @@ class Engine:
             tp.loss, tp.dpeaks, tp.dg, tp.head_partial = loss_t, dpeaks, dg, head_partial
             tp.batch, tp.d_eff, tp.z_save, tp.e = batch, d_eff, z_save, e
             tp.z_layout = z_layout
-            tp.live = live
-            tp.table = table
-            tp.table_sync = table_sync
-            tp.h, tp.A, tp.S, tp.fx, tp.fs, tp.g, tp.drop_mask, tp.peaks = hs, As, Ss, fx, fs, g, mask, peaks
+            tp.edge_path, tp.live, tp.table = path, live, table
+            tp.h, tp.A, tp.S, tp.fx, tp.g, tp.drop_mask, tp.peaks = hs, As, Ss, fx, g, mask, peaks
             self.tape = tp
         return peaks
 
-    # ------------------------------------------------------------------ edge function table (opt-in)
+    # ------------------------------------------------------------------ edge MLP and edge function table
     EDGE_TABLE_POINTS = 4096      # E <= 4; 2048 for E = 5 .. 8 (the scatter's 64-bit table and the guard's staged copy share the LDS)
 
     def _table_points(self):
         return self.EDGE_TABLE_POINTS if self.E <= 4 else self.EDGE_TABLE_POINTS // 2
 
-    def _edge_table_build(self, batch, live, d_eff_c, tape, training):
-        """The table of the edge function for this call (csrc/edge_table.hip) and the guard's gate words.
-        ``d_eff_c``: the distances fed to the RBF in the COMPACTED row order of the live view (noise already added when
-        training).  With frozen weights and no tape the table of an earlier call is reused while the weights stay the same:
+    def _edge_weights(self):
+        P = self.params
+        return [P[f"edge_fc/{t}/kernel"] for t in range(self.Le)], [P[f"edge_fc/{t}/bias"] for t in range(self.Le)]
+
+    def _edge_grads(self, view=None):
+        """(dW, dB) of the edge MLP: views of params.grad, or ``view(name)`` of a buffer laid out like it"""
+        view = view or self.params.g
+        return [view(f"edge_fc/{t}/kernel") for t in range(self.Le)], [view(f"edge_fc/{t}/bias") for t in range(self.Le)]
+
+    def _edge_mlp_fwd(self, n, d_src, d_eff, e, tape, perm=None, rows=None):
+        """the per-edge MLP over n rows into e: with ``perm`` the live kernels over the rows it lists, as many as the device
+        word ``rows`` says; without (``rows`` unused), the every-slot kernels.  Returns the tape (z, its layout) when
+        ``tape``, else (None, 0)."""
+        lib, h, st = self.lib, self.ctx.handle, self._st()
+        z, z_layout = None, 0
+        if tape:
+            z = self._new(self.Le - 1, n, self.H)
+            # element order of the tape the launch is about to write (it depends on the NG_EDGE_* switches in force NOW; the
+            # backward is told, so a switch flipped in between cannot make it misread the tape)
+            z_layout = int(lib.ng_edge_tape_layout(self.H, self.E, self.Le, self.fc_act, n))
+        W, B = self._edge_weights()
+        if perm is None:
+            self._ck(lib.ng_edge_mlp_fwd(h, st, n, self.H, self.E, self.Le, self.fc_act, ptr(d_src), ptr(d_eff), ptr(self.centers),
+                                         self.gap, ptr_array(W), ptr_array(B), ptr(e), ptr(z)), "ng_edge_mlp_fwd")
+        else:
+            self._ck(lib.ng_edge_mlp_fwd_live(h, st, n, self.H, self.E, self.Le, self.fc_act, ptr(d_src), ptr(d_eff), ptr(perm),
+                                              ptr(rows), ptr(self.centers), self.gap, ptr_array(W), ptr_array(B), ptr(e), ptr(z)),
+                     "ng_edge_mlp_fwd_live")
+        return z, z_layout
+
+    def _edge_mlp_bwd(self, n, d_src, d_eff, z, z_layout, de, grads, perm=None, rows=None):
+        """the backward of _edge_mlp_fwd over the same rows: the weight gradients into ``grads`` = (dW, dB)"""
+        lib, h, st = self.lib, self.ctx.handle, self._st()
+        W, _ = self._edge_weights()
+        dW, dB = grads
+        if perm is None:
+            self._ck(lib.ng_edge_mlp_bwd_tape(h, st, n, self.H, self.E, self.Le, self.fc_act, ptr(d_src), ptr(d_eff),
+                                              ptr(self.centers), self.gap, ptr_array(W), ptr(z), ptr(de), ptr_array(dW),
+                                              ptr_array(dB), z_layout), "ng_edge_mlp_bwd")
+        else:
+            self._ck(lib.ng_edge_mlp_bwd_live(h, st, n, self.H, self.E, self.Le, self.fc_act, ptr(d_src), ptr(d_eff), ptr(perm),
+                                              ptr(rows), ptr(self.centers), self.gap, ptr_array(W), ptr(z), ptr(de),
+                                              ptr_array(dW), ptr_array(dB), z_layout), "ng_edge_mlp_bwd_live")
+
+    def _edge_table_build(self, batch, live, d_eff, tape, training):
+        """The table of the edge function for this call (csrc/edge_table.hip) and the guard's gate words: the distance range,
+        the T points and their T midpoints, the per-edge MLP on those 2T rows, the check.  ``d_eff``: the distances fed to the
+        RBF (noise already added when training), in the compacted row order of the live view ``live``.
+        ``live`` None: the host-guarded table of an edge shape without the fused kernels — the every-slot MLP on the 2T rows,
+        and the guard's verdict read on the host; None when the guard is up.
+        With a live view, frozen weights and no tape the table of an earlier call is reused while the weights stay the same:
         then only the call's distance range is checked against the table's."""
         lib, h, st = self.lib, self.ctx.handle, self._st()
-        P = self.params
-        perm, pos, d_c, n_live = live
-        ne, E, H, T = batch.n_edges, self.E, self.H, self._table_points()
+        pos, n_live = (None, None) if live is None else (live[1], live[3])
+        ne, E, T = batch.n_edges, self.E, self._table_points()
         d_src = batch.edges.reshape(-1)
         tol = -1.0 if self.edge_table_force_fallback else float(self.edge_table_tol)
-        reuse = self._frozen and not tape and not training and not self.edge_table_force_fallback
+        reuse = live is not None and self._frozen and not tape and not training and not self.edge_table_force_fallback
         gate = torch.empty(8, dtype=torch.int32, device=self.device)
-        if reuse and self._table_cache is not None and self._table_cache["key"] == (self._wgen, T, E):
+        kept = reuse and self._table_cache is not None and self._table_cache["key"] == (self._wgen, T, E)
+        # the call's distance range; a table kept over calls covers a quarter more on either side than the call that builds it
+        rng = self._new(4)
+        self._ck(lib.ng_edge_table_range(h, st, ne, E, ptr(d_src), ptr(d_eff), ptr(pos), None, 0.25 if reuse and not kept else 0.0,
+                                         ptr(rng)), "ng_edge_table_range")
+        if kept:        # the check's range-only form: the call's range against the kept table's, whose err and scale it copies
             c = self._table_cache
-            cover = self._new(4)
-            self._ck(lib.ng_edge_table_range(h, st, ne, E, ptr(d_src), ptr(d_eff_c), ptr(pos), None, 0.0, ptr(cover)),
-                     "ng_edge_table_range")
-            self._ck(lib.ng_edge_table_check(h, st, T, E, None, 0.0, ptr(c["rng"]), ptr(cover), ptr(n_live), 2 * T,
+            self._ck(lib.ng_edge_table_check(h, st, T, E, None, 0.0, ptr(c["rng"]), ptr(rng), ptr(n_live), 2 * T,
                                              ptr(c["gate"]), ptr(gate)), "ng_edge_table_check")
             return {"e_all": c["e_all"], "rng": c["rng"], "gate": gate, "T": T}
-        rng = self._new(4)
-        # a table kept over calls covers a quarter more on either side than the call that builds it
-        self._ck(lib.ng_edge_table_range(h, st, ne, E, ptr(d_src), ptr(d_eff_c), ptr(pos), None, 0.25 if reuse else 0.0, ptr(rng)),
-                 "ng_edge_table_range")
         d_tab, ones = self._new(2 * T), self._new(2 * T)
-        perm_tab = torch.empty(2 * T, dtype=torch.int32, device=self.device)
+        perm_tab = None if live is None else torch.empty(2 * T, dtype=torch.int32, device=self.device)
         self._ck(lib.ng_edge_table_points(h, st, T, 1, ptr(rng), ptr(d_tab), ptr(ones), ptr(perm_tab)), "ng_edge_table_points")
-        if getattr(self, "_rows_2t", None) is None or int(self._rows_2t_value) != 2 * T:
-            self._rows_2t = torch.full((1,), 2 * T, dtype=torch.int32, device=self.device)
-            self._rows_2t_value = 2 * T
         e_all = self._new(2 * T, E)
-        z_tab = self._new(self.Le - 1, 2 * T, H) if tape else None
-        z_layout = int(lib.ng_edge_tape_layout(H, E, self.Le, self.fc_act, 2 * T)) if tape else 0
-        W = [P[f"edge_fc/{t}/kernel"] for t in range(self.Le)]
-        B = [P[f"edge_fc/{t}/bias"] for t in range(self.Le)]
         # rows 0 .. T-1: the table; rows T .. 2T-1: the midpoints the guard compares at (same launch: the 32 tiles run side by side)
-        self._ck(lib.ng_edge_mlp_fwd_live(h, st, 2 * T, H, E, self.Le, self.fc_act, ptr(ones), ptr(d_tab), ptr(perm_tab),
-                                          ptr(self._rows_2t), ptr(self.centers), self.gap, ptr_array(W), ptr_array(B),
-                                          ptr(e_all), ptr(z_tab)), "ng_edge_mlp_fwd_live")
+        z_tab, z_layout = self._edge_mlp_fwd(2 * T, ones, d_tab, e_all, tape, perm_tab, self._rows_2t)
         self._ck(lib.ng_edge_table_check(h, st, T, E, ptr(e_all), tol, ptr(rng), None, ptr(n_live), 2 * T, None, ptr(gate)),
                  "ng_edge_table_check")
-        tb = {"e_all": e_all, "rng": rng, "gate": gate, "T": T, "d_tab": d_tab, "ones": ones, "perm_tab": perm_tab, "z_tab": z_tab,
-              "z_layout": z_layout}
+        if live is None and int(gate[0].item()) != 0:      # the host read of the guard: the one synchronisation of "table_host"
+            return None
         if reuse:
             self._table_cache = {"key": (self._wgen, T, E), "e_all": e_all, "rng": rng, "gate": gate}
-        return tb
+        return {"e_all": e_all, "rng": rng, "gate": gate, "T": T, "d_tab": d_tab, "ones": ones, "perm_tab": perm_tab,
+                "z_tab": z_tab, "z_layout": z_layout}
 
-    def _edge_table_build_sync(self, batch, d_src, d_eff, tape):
-        """The table for an edge shape WITHOUT the fused live-edge kernels (layered edge MLP: any hidden size / depth): the same
-        passes on the every-slot entry points, and the guard's verdict read on the host — one synchronisation per call instead
-        of the device-side gate (nothing on the device can make the layered kernels skip themselves).  None: the guard is up,
-        the caller evaluates the MLP per edge as before."""
-        lib, h, st = self.lib, self.ctx.handle, self._st()
-        P = self.params
-        ne, E, H, T = batch.n_edges, self.E, self.H, self._table_points()
-        tol = -1.0 if self.edge_table_force_fallback else float(self.edge_table_tol)
-        rng = self._new(4)
-        self._ck(lib.ng_edge_table_range(h, st, ne, E, ptr(d_src), ptr(d_eff), None, None, 0.0, ptr(rng)), "ng_edge_table_range")
-        d_tab, ones = self._new(2 * T), self._new(2 * T)
-        self._ck(lib.ng_edge_table_points(h, st, T, 1, ptr(rng), ptr(d_tab), ptr(ones), None), "ng_edge_table_points")
-        e_all = self._new(2 * T, E)
-        z_tab = self._new(self.Le - 1, 2 * T, H) if tape else None
-        z_layout = int(lib.ng_edge_tape_layout(H, E, self.Le, self.fc_act, 2 * T)) if tape else 0
-        W = [P[f"edge_fc/{t}/kernel"] for t in range(self.Le)]
-        B = [P[f"edge_fc/{t}/bias"] for t in range(self.Le)]
-        self._ck(lib.ng_edge_mlp_fwd(h, st, 2 * T, H, E, self.Le, self.fc_act, ptr(ones), ptr(d_tab), ptr(self.centers), self.gap,
-                                     ptr_array(W), ptr_array(B), ptr(e_all), ptr(z_tab)), "ng_edge_mlp_fwd")
-        gate = torch.empty(8, dtype=torch.int32, device=self.device)
-        self._ck(lib.ng_edge_table_check(h, st, T, E, ptr(e_all), tol, ptr(rng), None, None, 2 * T, None, ptr(gate)),
-                 "ng_edge_table_check")
-        if int(gate[0].item()) != 0:          # the one host round trip of this path
-            return None
-        return {"e_all": e_all, "rng": rng, "gate": gate, "T": T, "d_tab": d_tab, "ones": ones, "z_tab": z_tab, "z_layout": z_layout}
-
-    def _edge_table_backward_sync(self, tp, de):
-        """edge-weight gradients of a call answered by the host-guarded table: scatter de onto the table, the layered backward on
-        its 2T rows"""
-        lib, h, st = self.lib, self.ctx.handle, self._st()
-        P, tb, b = self.params, tp.table_sync, tp.batch
-        ne, E, H, T = b.n_edges, self.E, self.H, tb["T"]
-        W = [P[f"edge_fc/{t}/kernel"] for t in range(self.Le)]
-        dW = [P.g(f"edge_fc/{t}/kernel") for t in range(self.Le)]
-        dB = [P.g(f"edge_fc/{t}/bias") for t in range(self.Le)]
-        de_tab = self._new(2 * T, E)
-        self._ck(lib.ng_edge_table_scatter(h, st, ne, E, T, 2 * T, ptr(b.edges), ptr(tp.d_eff), None, ptr(tb["rng"]), ptr(de),
-                                           ptr(de_tab)), "ng_edge_table_scatter")
-        self._ck(lib.ng_edge_mlp_bwd_tape(h, st, 2 * T, H, E, self.Le, self.fc_act, ptr(tb["ones"]), ptr(tb["d_tab"]),
-                                          ptr(self.centers), self.gap, ptr_array(W), ptr(tb["z_tab"]), ptr(de_tab),
-                                          ptr_array(dW), ptr_array(dB), tb["z_layout"]), "ng_edge_mlp_bwd")
+    def _edge_table_backward(self, tp, de, grads):
+        """the table's share of the edge-weight gradients, into ``grads``: de scattered onto the table's points (the exact
+        adjoint of the interpolation), then the MLP backward on its 2T rows — with the device guard over gate[2] rows, zero
+        when the guard was up"""
+        tb, b = tp.table, tp.batch
+        T = tb["T"]
+        pos = None if tp.live is None else tp.live[1]
+        de_tab = self._new(2 * T, self.E)
+        self._ck(self.lib.ng_edge_table_scatter(self.ctx.handle, self._st(), b.n_edges, self.E, T, 2 * T, ptr(b.edges), ptr(tp.d_eff),
+                                                ptr(pos), ptr(tb["rng"]), ptr(de), ptr(de_tab)), "ng_edge_table_scatter")
+        self._edge_mlp_bwd(2 * T, tb["ones"], tb["d_tab"], tb["z_tab"], tb["z_layout"], de_tab, grads, tb["perm_tab"], tb["gate"][2:])
 
     def edge_table_report(self, table=None):
         """(guard up?, interpolation error at the midpoints, largest |e| of the table) of the last taped call's table (or of
         ``table``; a call that reused the table of frozen weights reports the error and scale measured when it was built).
         Reads device words: synchronises; for tests and diagnostics.  Raises RuntimeError when there is no table to report on."""
-        tb = table if table is not None else ((self.tape.table or self.tape.table_sync) if self.tape is not None else None)
+        tb = table if table is not None else (self.tape.table if self.tape is not None else None)
         if tb is None:
             raise RuntimeError("edge_table_report: no edge-function table (no taped call, or the call went per edge)")
         g = tb["gate"].cpu().numpy()
         return bool(g[0]), float(g[4:6].view(np.float32)[0]), float(g[4:6].view(np.float32)[1])
-
-    def _edge_table_backward(self, tp, de):
-        """edge-weight gradients of a call that went through the table: the per-edge backward over gate[1] rows (zero unless the
-        guard was up) into temporaries, the table's backward over gate[2] rows (zero when it was) into the gradients, and the
-        sum of the two — one of which is exactly zero."""
-        lib, h, st = self.lib, self.ctx.handle, self._st()
-        P, tb, b = self.params, tp.table, tp.batch
-        ne, E, H, T = b.n_edges, self.E, self.H, tb["T"]
-        perm, pos, d_c, n_live = tp.live
-        names = [f"edge_fc/{t}/{k}" for t in range(self.Le) for k in ("kernel", "bias")]
-        o0 = min(P.offsets[n] for n in names)
-        o1 = max(P.offsets[n] + int(np.prod(P.shapes[n])) for n in names)
-        tmp = self._new(o1 - o0)
-        tv = lambda n: tmp[P.offsets[n] - o0:P.offsets[n] - o0 + int(np.prod(P.shapes[n]))]
-        W = [P[f"edge_fc/{t}/kernel"] for t in range(self.Le)]
-        dW = [P.g(f"edge_fc/{t}/kernel") for t in range(self.Le)]
-        dB = [P.g(f"edge_fc/{t}/bias") for t in range(self.Le)]
-        dWt = [tv(f"edge_fc/{t}/kernel") for t in range(self.Le)]
-        dBt = [tv(f"edge_fc/{t}/bias") for t in range(self.Le)]
-        self._ck(lib.ng_edge_mlp_bwd_live(h, st, ne, H, E, self.Le, self.fc_act, ptr(d_c), ptr(tp.d_eff), ptr(perm),
-                                          ptr(tb["gate"][1:]), ptr(self.centers), self.gap, ptr_array(W), ptr(tp.z_save),
-                                          ptr(de), ptr_array(dWt), ptr_array(dBt), tp.z_layout), "ng_edge_mlp_bwd_live")
-        de_tab = self._new(2 * T, E)
-        self._ck(lib.ng_edge_table_scatter(h, st, ne, E, T, 2 * T, ptr(b.edges), ptr(tp.d_eff), ptr(pos), ptr(tb["rng"]), ptr(de),
-                                           ptr(de_tab)), "ng_edge_table_scatter")
-        self._ck(lib.ng_edge_mlp_bwd_live(h, st, 2 * T, H, E, self.Le, self.fc_act, ptr(tb["ones"]), ptr(tb["d_tab"]),
-                                          ptr(tb["perm_tab"]), ptr(tb["gate"][2:]), ptr(self.centers), self.gap, ptr_array(W),
-                                          ptr(tb["z_tab"]), ptr(de_tab), ptr_array(dW), ptr_array(dB), tb["z_layout"]),
-                 "ng_edge_mlp_bwd_live")
-        blk = P.grad[o0:o1]
-        self._ck(lib.ng_add_scaled(h, st, o1 - o0, ptr(blk), ptr(tmp), 1.0, ptr(blk)), "ng_add_scaled")
 
     # ------------------------------------------------------------------ backward
     def backward(self, dpeaks, on_node_grads=None):
@@ -504,7 +480,7 @@ class Engine:
     def _backward(self, tp, dpeaks, on_node_grads, lib, h, st):
         P = self.params
         b = tp.batch
-        N, K, F, E, H = b.N, b.K, self.F, self.E, self.H
+        N, K, F, E = b.N, b.K, self.F, self.E
         Fh = F // 2
         ne = b.n_edges
         self._ck(lib.ng_ctx_set_graph_span(h, b.max_graph_atoms), "ng_ctx_set_graph_span")
@@ -568,22 +544,26 @@ class Engine:
         self._ck(lib.ng_flush_reductions(h, st), "ng_flush_reductions")
         if on_node_grads is not None:
             on_node_grads()
-        W = [P[f"edge_fc/{t}/kernel"] for t in range(self.Le)]
-        dW = [P.g(f"edge_fc/{t}/kernel") for t in range(self.Le)]
-        dB = [P.g(f"edge_fc/{t}/bias") for t in range(self.Le)]
-        if getattr(tp, "table", None) is not None:
-            self._edge_table_backward(tp, de)
-        elif tp.table_sync is not None:
-            self._edge_table_backward_sync(tp, de)
-        elif tp.live is not None:
+        if tp.edge_path == "slots":
+            self._edge_mlp_bwd(ne, b.edges, tp.d_eff, tp.z_save, tp.z_layout, de, self._edge_grads())
+        elif tp.edge_path == "live":
             perm, _, d_c, n_live = tp.live
-            self._ck(lib.ng_edge_mlp_bwd_live(h, st, ne, H, E, self.Le, self.fc_act, ptr(d_c), ptr(tp.d_eff), ptr(perm),
-                                              ptr(n_live), ptr(self.centers), self.gap, ptr_array(W), ptr(tp.z_save),
-                                              ptr(de), ptr_array(dW), ptr_array(dB), tp.z_layout), "ng_edge_mlp_bwd_live")
+            self._edge_mlp_bwd(ne, d_c, tp.d_eff, tp.z_save, tp.z_layout, de, self._edge_grads(), perm, n_live)
+        elif tp.edge_path == "table_host":
+            self._edge_table_backward(tp, de, self._edge_grads())
         else:
-            self._ck(lib.ng_edge_mlp_bwd_tape(h, st, ne, H, E, self.Le, self.fc_act, ptr(b.edges), ptr(tp.d_eff),
-                                              ptr(self.centers), self.gap, ptr_array(W), ptr(tp.z_save),
-                                              ptr(de), ptr_array(dW), ptr_array(dB), tp.z_layout), "ng_edge_mlp_bwd")
+            # "table": the per-edge backward over gate[1] rows (none unless the guard was up) into temporaries, the table's
+            # over gate[2] rows (none when it was) into the gradients, and the sum of the two — one of which is exactly zero
+            names = [f"edge_fc/{t}/{k}" for t in range(self.Le) for k in ("kernel", "bias")]
+            o0 = min(P.offsets[n] for n in names)
+            o1 = max(P.offsets[n] + int(np.prod(P.shapes[n])) for n in names)
+            tmp = self._new(o1 - o0)
+            tv = lambda n: tmp[P.offsets[n] - o0:P.offsets[n] - o0 + int(np.prod(P.shapes[n]))]
+            perm, _, d_c, _ = tp.live
+            self._edge_mlp_bwd(ne, d_c, tp.d_eff, tp.z_save, tp.z_layout, de, self._edge_grads(tv), perm, tp.table["gate"][1:])
+            self._edge_table_backward(tp, de, self._edge_grads())
+            blk = P.grad[o0:o1]
+            self._ck(lib.ng_add_scaled(h, st, o1 - o0, ptr(blk), ptr(tmp), 1.0, ptr(blk)), "ng_add_scaled")
         self.tape = None
 
     # ------------------------------------------------------------------ loss / optimiser

@@ -36,7 +36,7 @@ def test_table_path_matches_the_per_edge_path(gpu_device, F, graphs, E):
         scale = float(pa.abs().max())
         assert float((pa - pb).abs().max()) <= 2e-6 * max(scale, 1.0), (training, float((pa - pb).abs().max()), scale)
     # edge features themselves: interpolation error far below fp32 resolution of the values
-    assert eb.tape.table is not None and not eb.edge_table_report()[0]
+    assert eb.tape.edge_path == "table" and not eb.edge_table_report()[0]
     assert float((ea.tape.e - eb.tape.e).abs().max()) <= 1e-6 * max(float(ea.tape.e.abs().max()), 1.0)
     la, da = ea.loss_l2(gb, y, w, pa); lb, db = eb.loss_l2(gb, y, w, pb)
     ea.backward(da); eb.backward(db)
@@ -80,7 +80,7 @@ def test_table_path_against_the_oracle(gpu_device, ci):
     xi = eng.randn(N * K, seed=123)
     mask = eng.dropout_mask(N * Fh, seed=321)
     peaks = eng.forward(gb, training=True, noise=xi, dropout_mask=mask)
-    assert eng.tape.table is not None and not eng.edge_table_report()[0]
+    assert eng.tape.edge_path == "table" and not eng.edge_table_report()[0]
     dpeaks = np.random.default_rng(9).standard_normal(N).astype(np.float32)
     eng.backward(torch.from_numpy(dpeaks).to(gpu_device))
     grads = eng.params.grads_dict()
@@ -192,7 +192,7 @@ def test_table_is_kept_over_calls_while_the_weights_are_frozen(gpu_device):
                                  dict(atom_feature_size=64, edge_feature_size=3, edge_hidden_size=256, mp_layers=1, fc_layers=2, edge_fc_layers=2)])
 def test_host_guarded_table_for_edge_shapes_without_the_fused_kernels(gpu_device, cfg):
     """edge_hidden_size != 128 / other depths: the layered edge MLP has no device-gated form, so the table's guard is read on the host
-    (Engine.edge_table_sync): outputs and gradients against the per-edge engine; a forced guard gives the per-edge bits"""
+    (edge path "table_host"): outputs and gradients against the per-edge engine; a forced guard gives the per-edge bits"""
     from nmrgnn_amd import synth
     from nmrgnn_amd.engine import Engine
     from nmrgnn_amd.graph import GraphBatch
@@ -213,7 +213,7 @@ def test_host_guarded_table_for_edge_shapes_without_the_fused_kernels(gpu_device
     for e in (ea, eb, ec):
         p_inf = e.forward(gb).clone()
         p = e.forward(gb, training=True, seed=5)
-        used = e.tape.table_sync is not None
+        used = e.tape.edge_path == "table_host"
         ee = e.tape.e.clone()
         l, d = e.loss_l2(gb, y, w, p)
         e.backward(d)
@@ -269,7 +269,7 @@ def test_degenerate_distance_sets(gpu_device, kind):
         e = eng.tape.e.clone()
         up = eng.edge_table_report()[0] if eng is eb else None
         if eng is eb:
-            assert eng.tape.table is not None
+            assert eng.tape.edge_path == "table"
         loss, d = eng.loss_l2(gb, y, w, p)
         eng.backward(d)
         out.append((p_inf, p.clone(), e, eng.params.grad.clone(), up))
@@ -306,7 +306,7 @@ def test_non_finite_upstream_gradient_reaches_the_edge_weights(gpu_device, train
             eng.forward(gb, training=True, seed=3)
         else:
             eng.forward(gb, keep_tape=True)
-        assert (eng.tape.table is not None) == (eng is eb)
+        assert (eng.tape.edge_path == "table") == (eng is eb)
         if eng is eb:
             assert not eng.edge_table_report()[0]
         eng.backward(torch.from_numpy(dp).to(gpu_device))

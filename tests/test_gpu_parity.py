@@ -342,7 +342,7 @@ def test_full_size_gradients_match_oracle(gpu_device, edge_table):
     mask = eng.dropout_mask(N * 32, seed=8)
     # the loss gradient of the bench step: NameLoss s=1 on the batch's labels (1/G per graph)
     peaks = eng.forward(gb, training=True, noise=xi, dropout_mask=mask)
-    assert (eng.tape.table is not None) == edge_table
+    assert (eng.tape.edge_path == "table") == edge_table
     loss, dpe = eng.loss_l2(gb, torch.from_numpy(b["y"]).to(gpu_device), torch.from_numpy(b["w"]).to(gpu_device),
                             peaks)
     eng.backward(dpe)

@@ -100,7 +100,7 @@ def test_hip_equals_reference_graph_training(gpu_device, tag, edge_table):
     mask = torch.from_numpy((c["train_keep"].astype(np.float32) * np.float32(1.25))).to(gpu_device)
     peaks = eng.forward(gb, training=True, noise=xi, dropout_mask=mask).cpu().numpy()
     if edge_table:
-        assert eng.tape.table is not None and not eng.edge_table_report()[0]
+        assert eng.tape.edge_path == "table" and not eng.edge_table_report()[0]
     _check(tag, c, peaks, c["train_peaks64"], c["train_peaks32"], "training" + ("/table" if edge_table else ""))
 
 

@@ -137,3 +137,48 @@ def test_batch_prefetcher_on_a_host_device_builds_each_batch_when_asked():
         ref = GraphBatch(b["atoms"], b["nlist"], b["edges"], b["inv_degree"], graph_ptr=b["graph_ptr"], device="cpu")
         assert g.G == 2 and torch.equal(g.csc()[0], ref.csc()[0]) and torch.equal(g.csc()[1], ref.csc()[1])
     assert list(BatchPrefetcher([], device="cpu")) == []
+
+
+MIN_EDGES = 262144      # Engine.edge_table_min_edges
+_EDGE_PATH_CASES = [
+    # (edge_table, use_live_edges, live_kernels, E, n_edges, is_csr, capturing) -> path
+    # fused live-edge kernels: the table from min_edges on, else the live slots
+    ((True, True, True, 3, MIN_EDGES, False, False), "table"),
+    ((True, True, True, 3, MIN_EDGES - 1, False, False), "live"),
+    ((True, True, True, 3, 4 * MIN_EDGES, False, False), "table"),
+    ((True, False, True, 3, MIN_EDGES - 1, False, False), "slots"),
+    ((False, True, True, 3, 4 * MIN_EDGES, False, False), "live"),
+    ((False, False, True, 3, 4 * MIN_EDGES, False, False), "slots"),
+    # n_edges * E * 4 reaching 2^31: neither the live kernels nor the table
+    ((True, True, True, 8, (1 << 26) - 1, False, False), "table"),
+    ((True, True, True, 8, 1 << 26, False, False), "slots"),
+    # E up to 8 takes the table
+    ((True, True, True, 8, MIN_EDGES, False, False), "table"),
+    ((True, True, True, 9, MIN_EDGES, False, False), "live"),
+    ((True, True, True, 64, MIN_EDGES, False, False), "live"),
+    # CSR and capture do not gate the device-guarded table
+    ((True, True, True, 3, MIN_EDGES, True, True), "table"),
+    ((True, True, True, 3, MIN_EDGES - 1, True, False), "live"),
+    # no fused kernels: the host-guarded table, except for CSR batches and under capture
+    ((True, True, False, 3, MIN_EDGES, False, False), "table_host"),
+    ((True, False, False, 3, MIN_EDGES, False, False), "table_host"),
+    ((True, True, False, 3, MIN_EDGES, True, False), "slots"),
+    ((True, True, False, 3, MIN_EDGES, False, True), "slots"),
+    ((True, True, False, 3, MIN_EDGES, True, True), "slots"),
+    ((True, True, False, 3, MIN_EDGES - 1, False, False), "slots"),
+    ((False, True, False, 3, MIN_EDGES, False, False), "slots"),
+    ((True, True, False, 8, MIN_EDGES, False, False), "table_host"),
+    ((True, True, False, 9, MIN_EDGES, False, False), "slots"),
+    ((True, True, False, 64, MIN_EDGES, False, False), "slots"),
+    ((True, True, False, 8, (1 << 26) - 1, False, False), "table_host"),
+    ((True, True, False, 8, 1 << 26, False, False), "slots"),
+]
+
+
+@pytest.mark.parametrize("args,path", _EDGE_PATH_CASES)
+def test_edge_path_decision(args, path):
+    """Engine's choice of how the edge stage computes e (before the fallbacks to "slots" that need the batch or the
+    guard's verdict)"""
+    from nmrgnn_amd.engine import edge_path
+    edge_table, use_live_edges, live_kernels, E, n_edges, is_csr, capturing = args
+    assert edge_path(edge_table, use_live_edges, live_kernels, E, n_edges, MIN_EDGES, is_csr, capturing) == path

@@ -35,7 +35,7 @@ for s in range(steps):
     lb = tb.step(GraphBatch(*raw, graph_ptr=b["graph_ptr"], device=dev), t(y), t(b["w"]), seed=s)
     if s % max(1, steps // 10) == 0 or s == steps - 1:
         eb.forward(GraphBatch(*raw, graph_ptr=b["graph_ptr"], device=dev), training=True, seed=s)      # (a taped forward only to read the guard's words)
-        rep = eb.edge_table_report() if eb.tape is not None and eb.tape.table is not None else None
+        rep = eb.edge_table_report() if eb.tape is not None and eb.tape.edge_path == "table" else None
         eb.tape = None
         print("%4d   %.6f        %.6f        %.2e   %s" % (s, float(la), float(lb), abs(float(la) - float(lb)),
                                                            "" if rep is None else "guard %s err/scale %.2e" % ("UP" if rep[0] else "down", rep[1] / max(rep[2], 1e-30))))
