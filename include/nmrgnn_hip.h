@@ -211,6 +211,27 @@ int ng_edge_mlp_bwd_live(ng_ctx*, void* stream, int64_t n_slots, int H, int E, i
                          const float* centers, float gap, const float* const* W, const float* z_save,
                          const float* de, float* const* dW, float* const* db, int tape_layout);
 
+/* Gradients with respect to the inputs (csrc/input_grad.hip).
+ * ng_edge_mlp_dinput: dd_out[slot] = sum_c de[slot][c] * J[slot][c], J = d e / d d_eff, the derivative of the edge function of
+ *   ng_edge_mlp_fwd with respect to its input distance, in forward mode (value and tangent through the hidden layers, f32 MFMA,
+ *   recomputed from d_eff: no tape).  perm == n_live == NULL: every slot in slot order, d_src / d_eff [n_slots]; otherwise the
+ *   live view of ng_edge_mlp_fwd_live (d_src / d_eff compacted, slot of row r = perm[r], rows >= *n_live dead).  de, J_out
+ *   [n_slots][E] and dd_out [n_slots] in slot layout; dead slots (d_src <= 0) get exactly 0.  J_out may be NULL.  No atomics:
+ *   bitwise deterministic.  H % 16 == 0, H <= 512, 1 <= E <= 256, 2 <= Le <= 6, any activation code.
+ * ng_positions_grad / _csr: dpos [N][3] (N = G*n, batch-global rows) = sum over the live slots (i -> j) of
+ *   dd * scale * (r_i - r_j) / |r_i - r_j| on atom i and its negative on atom j, the gradient of a function of the edges
+ *   (edges = |r_i - r_j| * scale, ng_knn_graph / ng_cutoff_fill) with respect to the positions pos [N][3] at fixed lists.
+ *   Padded form: nlist / edges / dd [N][K] (a slot is live when edges > 0); CSR form: row_ptr [N+1], col / row_of / dd [nnz].
+ *   csc_ptr / csc_edge: the incoming-edge lists (ng_build_incoming_lists).  A gather, no atomics: bitwise deterministic. */
+int ng_edge_mlp_dinput(ng_ctx*, void* stream, int64_t n_slots, int H, int E, int Le, int act, const float* d_src,
+                       const float* d_eff, const int32_t* perm, const int32_t* n_live, const float* centers, float gap,
+                       const float* const* W, const float* const* b, const float* de, float* J_out, float* dd_out);
+int ng_positions_grad(ng_ctx*, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist, const float* edges,
+                      const float* dd, float scale, const int32_t* csc_ptr, const int32_t* csc_edge, float* dpos);
+int ng_positions_grad_csr(ng_ctx*, void* stream, int64_t N, int64_t nnz, const float* pos, const int32_t* row_ptr,
+                          const int32_t* col, const int32_t* row_of, const float* dd, float scale, const int32_t* csc_ptr,
+                          const int32_t* csc_edge, float* dpos);
+
 /* ---- node path ----------------------------------------------------------------------------- */
 /* embed_layer, nmrgnn/model.py:241,262: h0 = atoms[N,C] @ Wemb[C,F] */
 int ng_embed_fwd(ng_ctx*, void* stream, int64_t N, int C, int F, const float* atoms,

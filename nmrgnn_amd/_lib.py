@@ -70,6 +70,10 @@ SIGNATURES = {
                                     C.POINTER(_vp), C.POINTER(_vp), _vp, _vp]),
     "ng_edge_mlp_bwd_live": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _f,
                                     C.POINTER(_vp), _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _int]),
+    "ng_edge_mlp_dinput": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _f,
+                                  C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp]),
+    "ng_positions_grad": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    "ng_positions_grad_csr": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "ng_embed_fwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "ng_embed_bwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "ng_mp_aggregate": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp]),

@@ -17,8 +17,8 @@ import torch
 class GNNModelFunction(torch.autograd.Function):
     """peaks[N] = GNNModel.call((atoms, nlist, edges, inv_degree)) as an autograd node over the flat parameter leaf.
 
-    Inputs of the graph tuple receive no gradient (the reference's inputs are constants of the traced graph:
-    nlist / mask / inv_degree have none).  ``backward`` may run once per forward (the tape is
+    Inputs of the graph tuple receive no gradient here (nlist / mask / inv_degree have none); a call
+    whose ``edges`` require grad goes through GNNModelInputFunction instead.  ``backward`` may run once per forward (the tape is
     released, like ``retain_graph=False``)."""
 
     @staticmethod
@@ -48,6 +48,46 @@ class GNNModelFunction(torch.autograd.Function):
 
 def model_forward(engine, flat_leaf, batch, training=False, seed=0, noise=None, dropout_mask=None):
     return GNNModelFunction.apply(flat_leaf, engine, batch, bool(training), int(seed), noise, dropout_mask)
+
+
+class GNNModelInputFunction(torch.autograd.Function):
+    """``GNNModelFunction`` with the graph's ``edges`` as a differentiable input too: the backward returns the gradient
+    of the flat parameter buffer (when it requires grad) and of ``batch.edges`` — dL/d(edges) from
+    ``Engine.backward(edge_grad=...)`` (ng_edge_mlp_dinput), the derivative the reference's ``tf.GradientTape`` gives
+    for a watched ``edges``.  ``edges`` must be ``batch.edges`` itself (the tensor the kernels read).  Through
+    ``frames_to_batch`` the edges carry a grad_fn back to the positions, so the chain continues to ``frames.grad``.
+    The parameter gradient is the same bits as GNNModelFunction's; backward may run once per forward."""
+
+    @staticmethod
+    def forward(ctx, flat, edges, engine, batch, training, seed, noise, dropout_mask):
+        if flat.data_ptr() != engine.params.flat.data_ptr():
+            raise ValueError("GNNModelInputFunction: the parameter tensor is not this engine's flat buffer")
+        if edges.data_ptr() != batch.edges.data_ptr():
+            raise ValueError("GNNModelInputFunction: edges is not the batch's edges tensor")
+        engine.weights_changed()
+        peaks = engine.forward(batch, training=training, noise=noise, dropout_mask=dropout_mask, seed=seed,
+                               keep_tape=True)
+        ctx.engine = engine
+        ctx.tape = engine.tape
+        engine.tape = None
+        return peaks
+
+    @staticmethod
+    def backward(ctx, dpeaks):
+        engine, tape = ctx.engine, ctx.tape
+        if tape is None:
+            raise RuntimeError("GNNModelInputFunction.backward: the tape was already consumed (backward twice)")
+        ctx.tape = None
+        engine.tape = tape
+        edges = tape.batch.edges
+        edge_grad = torch.empty(edges.shape, dtype=torch.float32, device=edges.device)
+        engine.backward(dpeaks.contiguous().to(torch.float32), edge_grad=edge_grad)
+        dflat = engine.params.grad.clone() if ctx.needs_input_grad[0] else None
+        return dflat, edge_grad, None, None, None, None, None, None
+
+
+def model_forward_inputs(engine, flat, batch, training=False, seed=0, noise=None, dropout_mask=None):
+    return GNNModelInputFunction.apply(flat, batch.edges, engine, batch, bool(training), int(seed), noise, dropout_mask)
 
 
 class KerasAdam(torch.optim.Optimizer):

@@ -456,11 +456,21 @@ class Engine:
         return bool(g[0]), float(g[4:6].view(np.float32)[0]), float(g[4:6].view(np.float32)[1])
 
     # ------------------------------------------------------------------ backward
-    def backward(self, dpeaks, on_node_grads=None):
+    def backward(self, dpeaks, on_node_grads=None, edge_grad=None):
         """fills params.grad (overwrite) from the upstream gradient dpeaks[N] (None: the gradient of the loss
         taken inside ``forward(loss=...)``).
         ``on_node_grads`` is called once every non-edge gradient has been enqueued (the data-parallel
-        trainer launches the node-side all-reduce there, overlapping the edge-MLP backward)."""
+        trainer launches the node-side all-reduce there, overlapping the edge-MLP backward).
+        ``edge_grad``: a float32 device tensor shaped like ``batch.edges``, OVERWRITTEN with dL/d(edges) — one
+        ng_edge_mlp_dinput launch behind the rest, from the tape's distances, de and the current weights; exact on every
+        edge path (the table's included: the derivative is of the edge function itself).  In training mode it is the
+        gradient with respect to the un-noised input (d d_eff / d edges = 1).  params.grad is the same bits either way."""
+        if edge_grad is not None:
+            b = self.tape.batch if self.tape is not None else None
+            if b is not None and (edge_grad.dtype != torch.float32 or edge_grad.device != self.device
+                                  or not edge_grad.is_contiguous() or tuple(edge_grad.shape) != tuple(b.edges.shape)):
+                raise ValueError("backward: edge_grad must be a contiguous float32 tensor on the engine's device, "
+                                 "shaped like batch.edges")
         tp = self.tape
         if tp is None:
             raise RuntimeError("backward() without forward(training=True)")
@@ -471,13 +481,13 @@ class Engine:
         if self.cache_images:
             self._ck(lib.ng_weights_frozen(h, self._id), "ng_weights_frozen")
         try:
-            self._backward(tp, dpeaks, on_node_grads, lib, h, st)
+            self._backward(tp, dpeaks, on_node_grads, lib, h, st, edge_grad)
         finally:
             if self.cache_images:
                 lib.ng_weights_frozen(h, 0)
             self._ck(lib.ng_defer_reductions(h, st, 0), "ng_defer_reductions")
 
-    def _backward(self, tp, dpeaks, on_node_grads, lib, h, st):
+    def _backward(self, tp, dpeaks, on_node_grads, lib, h, st, edge_grad=None):
         P = self.params
         b = tp.batch
         N, K, F, E = b.N, b.K, self.F, self.E
@@ -564,7 +574,23 @@ class Engine:
             self._edge_table_backward(tp, de, self._edge_grads())
             blk = P.grad[o0:o1]
             self._ck(lib.ng_add_scaled(h, st, o1 - o0, ptr(blk), ptr(tmp), 1.0, ptr(blk)), "ng_add_scaled")
+        if edge_grad is not None:
+            self._edge_dinput(tp, de, edge_grad)
         self.tape = None
+
+    def _edge_dinput(self, tp, de, out):
+        """dL/d(edges) into ``out`` (slot layout): de . de/dd per edge (ng_edge_mlp_dinput), over the live view where the
+        forward had one (the per-edge "live" path and the device-guarded table), over every slot otherwise"""
+        b = tp.batch
+        W, B = self._edge_weights()
+        if tp.live is not None:
+            perm, _, d_src, n_live = tp.live
+        else:
+            perm = n_live = None
+            d_src = b.edges.reshape(-1)
+        self._ck(self.lib.ng_edge_mlp_dinput(self.ctx.handle, self._st(), b.n_edges, self.H, self.E, self.Le, self.fc_act,
+                                             ptr(d_src), ptr(tp.d_eff), ptr(perm), ptr(n_live), ptr(self.centers), self.gap,
+                                             ptr_array(W), ptr_array(B), ptr(de), None, ptr(out)), "ng_edge_mlp_dinput")
 
     # ------------------------------------------------------------------ loss / optimiser
     def loss_l2(self, batch, y, w, peaks):

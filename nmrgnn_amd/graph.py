@@ -65,6 +65,8 @@ def _to_dev(x, dtype, device):
 class GraphBatch:
     is_csr = False
     row_ptr = None
+    positions = None   # [G, n, 3] Angstrom, and the distance scale: set by frames_to_batch / frames_to_batch_cutoff
+    scale = None
 
     _ctx = None        # library context for the list builders; None = the device's shared one (BatchPrefetcher sets its own)
 
@@ -267,6 +269,21 @@ class GraphBatch:
             self._build_lists(None)
         return self._csc
 
+    def positions_grad(self, dedges):
+        """dL/d(positions) [G, n, 3] from dL/d(edges) ``dedges`` (shaped like ``edges``), at fixed neighbour lists: the
+        chain rule through edges = |r_i - r_j| * scale (include/nmrgnn_hip.h: ng_positions_grad).  Needs the positions the
+        lists were built from (frames_to_batch / frames_to_batch_cutoff)."""
+        if self.positions is None:
+            raise ValueError("positions_grad: this batch was not built from positions (frames_to_batch / frames_to_batch_cutoff)")
+        return _positions_grad(self._positions_state(), dedges)
+
+    def _positions_state(self):
+        """what positions_grad reads, without the batch itself (an autograd node keeps this, not the batch whose edges are
+        its output: no reference cycle)"""
+        csc_ptr, csc_edge = self.csc()
+        return (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
+                self.edges.detach(), self.row_ptr, getattr(self, "row_of", None), csc_ptr, csc_edge)
+
     def as_tuple(self):
         if self.is_csr:
             raise ValueError("a CSR batch has no (atoms, nlist, edges, inv_degree) tuple; see row_ptr / nlist / edges")
@@ -367,10 +384,72 @@ class BatchPrefetcher:
             yield self._hand_over(*cur)
 
 
+def _positions_grad(state, dedges):
+    import ctypes as C
+    from . import _lib
+    from ._lib import ptr
+    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, row_of, csc_ptr, csc_edge = state
+    ctx = ctx or _lib.get_context(device.index)
+    dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
+    if dd.numel() != edges.numel():
+        raise ValueError(f"positions_grad: dedges has {dd.numel()} entries for {edges.numel()} edges")
+    dpos = torch.empty_like(pos)
+    with torch.cuda.device(device):
+        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        if is_csr:
+            ctx.check(ctx.lib.ng_positions_grad_csr(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist),
+                                                    ptr(row_of), ptr(dd), scale, ptr(csc_ptr), ptr(csc_edge), ptr(dpos)),
+                      "ng_positions_grad_csr")
+        else:
+            ctx.check(ctx.lib.ng_positions_grad(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale,
+                                                ptr(csc_ptr), ptr(csc_edge), ptr(dpos)), "ng_positions_grad")
+    return dpos
+
+
+class _EdgesOfPositions(torch.autograd.Function):
+    """edges = |r_i - r_j| * scale of a batch built from ``frames`` (the batch's own edges tensor, not a copy); the
+    backward is ng_positions_grad at fixed neighbour lists"""
+
+    @staticmethod
+    def forward(ctx, frames, build):
+        # a copy of the positions: an in-place update of ``frames`` before the backward must not move the lists' atoms
+        batch = build(frames.detach().clone())
+        ctx.state = batch._positions_state()
+        ctx.frames_shape, ctx.frames_device = frames.shape, frames.device
+        return batch.edges
+
+    @staticmethod
+    def backward(ctx, dedges):
+        dpos = _positions_grad(ctx.state, dedges)
+        return dpos.reshape(ctx.frames_shape).to(ctx.frames_device), None
+
+
+def _positions_batch(frames, build):
+    """``build(frames)`` with edges that carry a grad_fn back to ``frames`` when they require grad"""
+    if not (isinstance(frames, torch.Tensor) and frames.requires_grad and torch.is_grad_enabled()):
+        return build(frames)
+    holder = {}
+
+    def make(f):
+        holder["batch"] = build(f)
+        return holder["batch"]
+    edges = _EdgesOfPositions.apply(frames, make)
+    batch = holder.pop("batch")
+    batch.edges = edges         # the same storage the kernels read, now with a grad_fn
+    return batch
+
+
 def frames_to_batch(atoms, frames, neighbor_number=16, scale=0.1, device=None):
     """Build the graphs of ``G`` trajectory frames on the GPU (ng_knn_graph) and return them as one
     device-resident GraphBatch: ``atoms`` [n,C] one-hot (shared by all frames), ``frames`` [G,n,3]
-    positions in Angstrom.  Same conventions as :func:`nmrgnn_amd.structure.knn_graph`."""
+    positions in Angstrom.  Same conventions as :func:`nmrgnn_amd.structure.knn_graph`.
+    The batch keeps the positions and ``scale`` (``GraphBatch.positions_grad``); with ``frames.requires_grad`` (and
+    grad mode on) its ``edges`` carry a grad_fn back to ``frames``, so a loss of ``model(batch)`` differentiates to
+    ``frames.grad`` — at fixed neighbour lists, as TensorFlow's tape does through the reference's graph."""
+    return _positions_batch(frames, lambda f: _frames_to_batch(atoms, f, neighbor_number, scale, device))
+
+
+def _frames_to_batch(atoms, frames, neighbor_number, scale, device):
     import ctypes as C
     from . import _lib
     from ._lib import ptr
@@ -393,15 +472,22 @@ def frames_to_batch(atoms, frames, neighbor_number=16, scale=0.1, device=None):
                                    ptr(inv)), "ng_knn_graph")
     ptrs = np.arange(G + 1, dtype=np.int64) * n
     # n > K: every atom has K real neighbours, no padded slot -> the compute-side list IS the list
-    return GraphBatch(at.repeat(G, 1) if G > 1 else at, nlist, edges, inv, graph_ptr=ptrs, device=device, validate=False,
-                      nlist_c=nlist if n > K else None)
+    b = GraphBatch(at.repeat(G, 1) if G > 1 else at, nlist, edges, inv, graph_ptr=ptrs, device=device, validate=False,
+                   nlist_c=nlist if n > K else None)
+    b.positions, b.scale = pos, float(scale)
+    return b
 
 
 def frames_to_batch_cutoff(atoms, frames, cutoff=4.0, scale=0.1, device=None):
     """Distance-cutoff graphs of ``G`` trajectory frames, built on the GPU (ng_cutoff_count / ng_cutoff_fill) and
     returned as one device-resident CSR GraphBatch: every other atom of the same frame closer than ``cutoff``
     (Angstrom) is a neighbour, rows in ascending neighbour index, distances x ``scale`` (nm), inv_degree by the
-    reference's rule (library.py:115-116).  Variable degree: BASELINE configs[4]."""
+    reference's rule (library.py:115-116).  Variable degree: BASELINE configs[4].
+    Positions and gradients as in :func:`frames_to_batch`."""
+    return _positions_batch(frames, lambda f: _frames_to_batch_cutoff(atoms, f, cutoff, scale, device))
+
+
+def _frames_to_batch_cutoff(atoms, frames, cutoff, scale, device):
     import ctypes as C
     from . import _lib
     from ._lib import ptr
@@ -433,5 +519,7 @@ def frames_to_batch_cutoff(atoms, frames, cutoff=4.0, scale=0.1, device=None):
         ctx.check(ctx.lib.ng_cutoff_fill_rows(ctx.handle, st, G, n, float(cutoff), float(scale), ptr(pos), ptr(row_ptr),
                                               ptr(col), ptr(dist), ptr(inv), ptr(row_of)), "ng_cutoff_fill_rows")
     ptrs = np.arange(G + 1, dtype=np.int64) * n
-    return GraphBatch.from_csr(at.repeat(G, 1) if G > 1 else at, row_ptr, col, dist, inv, graph_ptr=ptrs, device=device,
-                               validate=False, row_of=row_of)
+    b = GraphBatch.from_csr(at.repeat(G, 1) if G > 1 else at, row_ptr, col, dist, inv, graph_ptr=ptrs, device=device,
+                            validate=False, row_of=row_of)
+    b.positions, b.scale = pos, float(scale)
+    return b

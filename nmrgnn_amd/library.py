@@ -1,5 +1,6 @@
 """Library surface of the reference (nmrgnn/library.py): ``load_model``, ``universe2graph``,
-``check_peaks`` (+ ``save_model``), same names, argument order and return order."""
+``check_peaks`` (+ ``save_model``), same names, argument order and return order; and ``shift_restraint``, the
+chemical-shift restraint energy and forces of a structure."""
 from __future__ import annotations
 
 import json
@@ -121,3 +122,44 @@ def check_peaks(atoms, peaks, cutoff_sigma=4, warn_sigma=2.5):
         raise Warning('Your peaks look awful. Likely solvent or missing hydrogens or bad units. '
                       'Check README for suggestions')
     return confident
+
+
+def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_number=16):
+    """Chemical-shift restraint of one structure: ``(energy, forces)`` with
+
+        energy = sum_i w_i (delta_pred_i - delta_exp_i)^2          ppm^2, a 0-d device tensor
+        forces = -d energy / d positions                           ppm^2 / Angstrom, [n, 3] on the device
+
+    ``atoms`` [n, C] one-hot, ``positions`` [n, 3] in Angstrom, ``targets`` [n] measured shifts in ppm, ``weights`` [n]
+    (default 1; put 0 where no shift was measured).  The graph is the kNN graph of ``frames_to_batch`` with
+    ``neighbor_number`` neighbours; the model runs in inference mode.  One forward with a tape, one backward with the
+    edge gradient (``Engine.backward(edge_grad=...)``) and one positions kernel (``GraphBatch.positions_grad``), no torch
+    autograd; the forces are bitwise those of ``energy.backward()`` through ``model(frames_to_batch(atoms, pos))``.
+
+    The forces are the gradient at FIXED neighbour lists: where an atom's K nearest neighbours change between two
+    structures the energy and the forces jump (the model itself is discontinuous there, as the reference is).  The call
+    overwrites the engine's parameter gradient buffer (``engine.params.grad``) as a side effect."""
+    import torch
+    from .graph import frames_to_batch
+    if model.engine is None:
+        model.build(int(np.asarray(atoms).shape[-1]) if not isinstance(atoms, torch.Tensor) else int(atoms.shape[-1]))
+    eng = model.engine
+    pos = positions.detach() if isinstance(positions, torch.Tensor) else positions
+    batch = frames_to_batch(atoms, pos, neighbor_number=neighbor_number, device=eng.device)
+    if batch.G != 1:
+        raise ValueError("shift_restraint: one structure [n, 3] at a time")
+    y = torch.as_tensor(np.asarray(targets, np.float32) if not isinstance(targets, torch.Tensor) else targets,
+                        dtype=torch.float32, device=eng.device).reshape(-1)
+    w = torch.ones_like(y) if weights is None else torch.as_tensor(
+        np.asarray(weights, np.float32) if not isinstance(weights, torch.Tensor) else weights,
+        dtype=torch.float32, device=eng.device).reshape(-1)
+    if y.shape[0] != batch.N or w.shape[0] != batch.N:
+        raise ValueError(f"shift_restraint: targets / weights need {batch.N} entries")
+    peaks = eng.forward(batch, training=False, keep_tape=True)
+    diff = peaks - y
+    energy = (diff * diff * w).sum()
+    dpeaks = w * (2.0 * diff)              # d energy / d peaks, the bits torch autograd gives for the same expression
+    dedges = torch.empty(batch.edges.shape, dtype=torch.float32, device=eng.device)
+    eng.backward(dpeaks, edge_grad=dedges)
+    forces = -batch.positions_grad(dedges)[0]
+    return energy, forces

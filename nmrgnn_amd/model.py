@@ -96,6 +96,12 @@ class GNNModel:
             seed = ((int(self._seed) * 0x9E3779B97F4A7C15) ^ (self._train_calls * 1000003 + 0x632BE5AB)) & ((1 << 63) - 1)
             self._train_calls += 1
         leaf = self._flat_leaf
+        if torch.is_grad_enabled() and batch.edges.requires_grad:
+            # gradients with respect to the inputs (a watched ``edges``, or positions through frames_to_batch): the edges
+            # are an input of the autograd node too, whether or not the parameters require grad
+            from .autograd import model_forward_inputs
+            flat = leaf if leaf is not None else self.engine.params.flat
+            return model_forward_inputs(self.engine, flat, batch, training=training, seed=seed or 0)
         if leaf is not None and leaf.requires_grad and torch.is_grad_enabled():
             # differentiable call (nmrgnn/main.py:74-80 trains by autodiff through model(x)): the result is a device
             # tensor with a grad_fn whatever the input container was — a numpy array could not carry one
