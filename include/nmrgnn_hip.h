@@ -231,6 +231,17 @@ int ng_positions_grad(ng_ctx*, void* stream, int64_t N, int K, const float* pos,
 int ng_positions_grad_csr(ng_ctx*, void* stream, int64_t N, int64_t nnz, const float* pos, const int32_t* row_ptr,
                           const int32_t* col, const int32_t* row_of, const float* dd, float scale, const int32_t* csc_ptr,
                           const int32_t* csc_edge, float* dpos);
+/* ng_positions_grad_pbc / _csr_pbc: the same gradient for lists built in periodic boxes (ng_knn_graph_pbc,
+ *   ng_cutoff_fill_rows_pbc): along each edge the minimum-image vector, recomputed from the raw positions by the function
+ *   that built the edge.  n = atoms per frame (frame of row i = i / n, N % n == 0), box / triclinic as ng_knn_graph_pbc.
+ *   No gradient with respect to the box. */
+int ng_positions_grad_pbc(ng_ctx*, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist,
+                          const float* edges, const float* dd, float scale, const int32_t* csc_ptr, const int32_t* csc_edge,
+                          int n, const float* box, int triclinic, float* dpos);
+int ng_positions_grad_csr_pbc(ng_ctx*, void* stream, int64_t N, int64_t nnz, const float* pos, const int32_t* row_ptr,
+                              const int32_t* col, const int32_t* row_of, const float* dd, float scale,
+                              const int32_t* csc_ptr, const int32_t* csc_edge, int n, const float* box, int triclinic,
+                              float* dpos);
 
 /* ---- node path ----------------------------------------------------------------------------- */
 /* embed_layer, nmrgnn/model.py:241,262: h0 = atoms[N,C] @ Wemb[C,F] */
@@ -349,6 +360,13 @@ int ng_cutoff_fill(ng_ctx*, void* stream, int G, int n, float cutoff, float scal
 /* ng_cutoff_fill that also writes row_of[nnz], the row of every entry (NULL: not written) */
 int ng_cutoff_fill_rows(ng_ctx*, void* stream, int G, int n, float cutoff, float scale, const float* pos,
                         const int32_t* row_ptr, int32_t* col, float* dist, float* inv_degree, int32_t* row_of);
+/* ng_cutoff_count_pbc / ng_cutoff_fill_rows_pbc: the same lists in periodic boxes, by minimum-image distance (box /
+ *   triclinic as ng_knn_graph_pbc).  The caller keeps cutoff below half the smallest perpendicular width of every box. */
+int ng_cutoff_count_pbc(ng_ctx*, void* stream, int G, int n, float cutoff, const float* pos, const float* box, int triclinic,
+                        int32_t* deg);
+int ng_cutoff_fill_rows_pbc(ng_ctx*, void* stream, int G, int n, float cutoff, float scale, const float* pos,
+                            const float* box, int triclinic, const int32_t* row_ptr, int32_t* col, float* dist,
+                            float* inv_degree, int32_t* row_of);
 /* out[0..n] = exclusive prefix sums of in[0..n-1], out[n] = total (row_ptr from ng_cutoff_count's degrees) */
 int ng_exclusive_scan_i32(ng_ctx*, void* stream, int64_t n, const int32_t* in, int32_t* out);
 
@@ -360,6 +378,14 @@ int ng_exclusive_scan_i32(ng_ctx*, void* stream, int64_t n, const int32_t* in, i
  *   inv_degree [G*n] = 1/#(local neighbour index > 0), 0 when none (library.py:115-116).  K <= 64. */
 int ng_knn_graph(ng_ctx*, void* stream, int G, int n, int K, float scale, const float* pos,
                  int32_t* nlist, float* edges, float* inv_degree);
+/* ng_knn_graph in periodic boxes (minimum-image convention): box [G][9] on the device, one box per frame as lower-triangular
+ *   lattice vectors, row-major a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz) (GROMACS / MDAnalysis triclinic_vectors).
+ *   triclinic = 0: orthorhombic (bx = cx = cy = 0); 1: reduced triclinic, |bx| <= ax/2, |cx| <= ax/2, |cy| <= by/2 (the
+ *   host validates; other boxes are not supported).  Distances are min over lattice vectors L of |r_j - r_i + L|, from the
+ *   raw positions (anywhere, not wrapped); an atom's own images are never neighbours, each atom appears at most once in a
+ *   list.  Conventions, path choice (brute force / cell grid) and NG_KNN as ng_knn_graph. */
+int ng_knn_graph_pbc(ng_ctx*, void* stream, int G, int n, int K, float scale, const float* pos, const float* box,
+                     int triclinic, int32_t* nlist, float* edges, float* inv_degree);
 
 /* AMPLayer attention aggregation, nmrgnn/layers.py:89-96 (the layer is exported by the reference package but not
  * used by its model):

@@ -74,6 +74,8 @@ SIGNATURES = {
                                   C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp]),
     "ng_positions_grad": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
     "ng_positions_grad_csr": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp]),
+    "ng_positions_grad_pbc": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _vp, _vp, _int, _vp, _int, _vp]),
+    "ng_positions_grad_csr_pbc": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _int, _vp, _int, _vp]),
     "ng_embed_fwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "ng_embed_bwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "ng_mp_aggregate": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp]),
@@ -94,6 +96,8 @@ SIGNATURES = {
     "ng_cutoff_count": (_int, [_vp, _vp, _int, _int, _f, _vp, _vp]),
     "ng_cutoff_fill": (_int, [_vp, _vp, _int, _int, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "ng_cutoff_fill_rows": (_int, [_vp, _vp, _int, _int, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ng_cutoff_count_pbc": (_int, [_vp, _vp, _int, _int, _f, _vp, _vp, _int, _vp]),
+    "ng_cutoff_fill_rows_pbc": (_int, [_vp, _vp, _int, _int, _f, _f, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "ng_exclusive_scan_i32": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "ng_dense_fwd": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "ng_dense_bwd": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -116,6 +120,7 @@ SIGNATURES = {
     "ng_fc_head_fwd": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _vp,
                               _vp, _vp, _vp]),
     "ng_knn_graph": (_int, [_vp, _vp, _int, _int, _int, _f, _vp, _vp, _vp, _vp]),
+    "ng_knn_graph_pbc": (_int, [_vp, _vp, _int, _int, _int, _f, _vp, _vp, _int, _vp, _vp, _vp]),
     "ng_amp_attend": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ng_amp_attend_bwd": (_int, [_vp, _vp, _i64, _int, _int, _int] + [_vp] * 13),
     "ng_loss_l2": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),

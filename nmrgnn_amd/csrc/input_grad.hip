@@ -20,6 +20,7 @@
 
 #include "mfma_gemm.cuh"
 #include "ng_common.h"
+#include "pbc.cuh"
 
 namespace ng {
 
@@ -202,30 +203,40 @@ __global__ __launch_bounds__(DI_THREADS) void edge_dinput_kernel(
   }
 }
 
-// the term of slot (i -> j): f * (r_i - r_j), f = g * scale / |r_i - r_j|; both ends call it with (i, j) in this order
-__device__ __forceinline__ float3 pg_term(const float* __restrict__ pos, int64_t i, int64_t j, float g, float scale) {
-  const float vx = pos[3 * i] - pos[3 * j], vy = pos[3 * i + 1] - pos[3 * j + 1], vz = pos[3 * i + 2] - pos[3 * j + 2];
+// the term of slot (i -> j): f * (r_i - r_j), f = g * scale / |r_i - r_j|; both ends call it with (i, j) in this order.
+// r_i - r_j is minus the displacement D(r_i, r_j) the list builders computed for the edge (pbc.cuh; for DispOpen the same
+// bits as r_i - r_j: a negated difference is exact)
+template <class Disp>
+__device__ __forceinline__ float3 pg_term(const Disp& D, const float* __restrict__ pos, int64_t i, int64_t j, float g, float scale) {
+  float ux, uy, uz;
+  D(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], ux, uy, uz);
+  const float vx = -ux, vy = -uy, vz = -uz;
   const float f = g * scale / sqrtf(vx * vx + vy * vy + vz * vz);
   return make_float3(f * vx, f * vy, f * vz);
 }
 
 // row_ptr == NULL: padded lists (slots i*K .. i*K+K-1, a slot is live when edges > 0, source of slot s = s / K);
-// otherwise CSR (entries row_ptr[i] .. row_ptr[i+1], all live, source of entry s = row_of[s])
+// otherwise CSR (entries row_ptr[i] .. row_ptr[i+1], all live, source of entry s = row_of[s]).
+// Periodic policies: atom i belongs to frame i / n and both ends of its edges to the same frame.
+template <class Disp>
 __global__ __launch_bounds__(256) void positions_grad_kernel(int64_t N, int K, const float* __restrict__ pos,
                                                              const int32_t* __restrict__ row_ptr,
                                                              const int32_t* __restrict__ col,
                                                              const int32_t* __restrict__ row_of,
                                                              const float* __restrict__ edges, const float* __restrict__ dd,
                                                              float scale, const int32_t* __restrict__ csc_ptr,
-                                                             const int32_t* __restrict__ csc_edge, float* __restrict__ dpos) {
+                                                             const int32_t* __restrict__ csc_edge, int n,
+                                                             const float* __restrict__ box, float* __restrict__ dpos) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
+  Disp D;
+  if (Disp::periodic) D.load(box, (int)(i / n));
   const int64_t s0 = row_ptr ? row_ptr[i] : i * K, s1 = row_ptr ? row_ptr[i + 1] : i * K + K;
   float ax = 0.f, ay = 0.f, az = 0.f;
   for (int64_t s = s0; s < s1; ++s) {
     const float g = dd[s];
     if (g == 0.f || (edges && !(edges[s] > 0.f))) continue;
-    const float3 w = pg_term(pos, i, col[s], g, scale);
+    const float3 w = pg_term(D, pos, i, col[s], g, scale);
     ax += w.x;
     ay += w.y;
     az += w.z;
@@ -235,7 +246,7 @@ __global__ __launch_bounds__(256) void positions_grad_kernel(int64_t N, int K, c
     const float g = dd[s];
     if (g == 0.f) continue;
     const int64_t src = row_ptr ? (int64_t)row_of[s] : s / K;
-    const float3 w = pg_term(pos, src, i, g, scale);
+    const float3 w = pg_term(D, pos, src, i, g, scale);
     ax -= w.x;
     ay -= w.y;
     az -= w.z;
@@ -299,15 +310,29 @@ extern "C" int ng_edge_mlp_dinput(ng_ctx* ctx, void* stream, int64_t n_slots, in
 
 static int positions_grad_common(ng_ctx* ctx, void* stream, int64_t N, int K, const float* pos, const int32_t* row_ptr,
                                  const int32_t* col, const int32_t* row_of, const float* edges, const float* dd, float scale,
-                                 const int32_t* csc_ptr, const int32_t* csc_edge, float* dpos) {
+                                 const int32_t* csc_ptr, const int32_t* csc_edge, float* dpos, int n = 0,
+                                 const float* box = nullptr, int triclinic = -1) {
   NG_REQUIRE(ctx, N >= 0 && N < ((int64_t)1 << 31), "positions_grad: atom count below 2^31");
+  if (triclinic >= 0) {
+    NG_REQUIRE(ctx, triclinic <= 1, "positions_grad (pbc): triclinic flag 0 or 1");
+    NG_REQUIRE(ctx, n >= 1 && N % n == 0, "positions_grad (pbc): atoms per frame n >= 1 dividing N");
+  }
   if (N == 0) return NG_OK;
   NG_REQUIRE(ctx, pos && col && dd && csc_ptr && csc_edge && dpos, "positions_grad: arguments");
+  NG_REQUIRE(ctx, triclinic < 0 || box, "positions_grad (pbc): box required");
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard dg(ctx->device);
   ProfScope ps(ctx, st, "positions_grad");
-  hipLaunchKernelGGL(positions_grad_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, N, K, pos, row_ptr, col, row_of,
-                     edges, dd, scale, csc_ptr, csc_edge, dpos);
+  const dim3 grid((unsigned)cdiv(N, 256)), block(256);
+  if (triclinic < 0)
+    hipLaunchKernelGGL(positions_grad_kernel<DispOpen>, grid, block, 0, st, N, K, pos, row_ptr, col, row_of, edges, dd, scale,
+                       csc_ptr, csc_edge, 1, nullptr, dpos);
+  else if (triclinic)
+    hipLaunchKernelGGL(positions_grad_kernel<DispTric>, grid, block, 0, st, N, K, pos, row_ptr, col, row_of, edges, dd, scale,
+                       csc_ptr, csc_edge, n, box, dpos);
+  else
+    hipLaunchKernelGGL(positions_grad_kernel<DispOrtho>, grid, block, 0, st, N, K, pos, row_ptr, col, row_of, edges, dd, scale,
+                       csc_ptr, csc_edge, n, box, dpos);
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
 }
@@ -328,4 +353,28 @@ extern "C" int ng_positions_grad_csr(ng_ctx* ctx, void* stream, int64_t N, int64
   NG_REQUIRE(ctx, nnz >= 0 && nnz < ((int64_t)1 << 31), "positions_grad_csr: nnz below 2^31");
   NG_REQUIRE(ctx, N == 0 || (row_ptr && row_of), "positions_grad_csr: row_ptr and row_of required");
   return positions_grad_common(ctx, stream, N, 0, pos, row_ptr, col, row_of, nullptr, dd, scale, csc_ptr, csc_edge, dpos);
+}
+
+// periodic boxes: box [G][9] (G = N / n) lower-triangular lattice vectors on the device, triclinic = 0 / 1 (pbc.cuh)
+extern "C" int ng_positions_grad_pbc(ng_ctx* ctx, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist,
+                                     const float* edges, const float* dd, float scale, const int32_t* csc_ptr,
+                                     const int32_t* csc_edge, int n, const float* box, int triclinic, float* dpos) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, K >= 1 && N * K < ((int64_t)1 << 31), "positions_grad: K >= 1, N * K below 2^31");
+  NG_REQUIRE(ctx, N == 0 || edges, "positions_grad: edges required (dead slots)");
+  NG_REQUIRE(ctx, triclinic == 0 || triclinic == 1, "positions_grad (pbc): triclinic flag 0 or 1");
+  return positions_grad_common(ctx, stream, N, K, pos, nullptr, nlist, nullptr, edges, dd, scale, csc_ptr, csc_edge, dpos, n, box,
+                               triclinic);
+}
+
+extern "C" int ng_positions_grad_csr_pbc(ng_ctx* ctx, void* stream, int64_t N, int64_t nnz, const float* pos,
+                                         const int32_t* row_ptr, const int32_t* col, const int32_t* row_of, const float* dd,
+                                         float scale, const int32_t* csc_ptr, const int32_t* csc_edge, int n, const float* box,
+                                         int triclinic, float* dpos) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, nnz >= 0 && nnz < ((int64_t)1 << 31), "positions_grad_csr: nnz below 2^31");
+  NG_REQUIRE(ctx, N == 0 || (row_ptr && row_of), "positions_grad_csr: row_ptr and row_of required");
+  NG_REQUIRE(ctx, triclinic == 0 || triclinic == 1, "positions_grad (pbc): triclinic flag 0 or 1");
+  return positions_grad_common(ctx, stream, N, 0, pos, row_ptr, col, row_of, nullptr, dd, scale, csc_ptr, csc_edge, dpos, n, box,
+                               triclinic);
 }

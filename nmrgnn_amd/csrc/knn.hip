@@ -16,6 +16,7 @@
 
 #include "ng_common.h"
 #include "ng_internal.h"
+#include "pbc.cuh"
 
 namespace ng {
 
@@ -24,14 +25,18 @@ constexpr int KNN_TILE = 1024;
 // the distance expression of every kNN kernel (knn_cells.hip has the same one): identical lists need identical rounding
 __device__ __forceinline__ float knn_dist2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
-template <int KMAX>
+// Disp: the displacement policy of pbc.cuh (DispOpen: open boundaries, box unused)
+template <int KMAX, class Disp>
 __global__ __launch_bounds__(256) void knn_kernel(int n, int K, float scale,
                                                   const float* __restrict__ pos,      // [G][n][3]
+                                                  const float* __restrict__ box,      // [G][9] or unused
                                                   int32_t* __restrict__ nlist,        // [G*n][K]
                                                   float* __restrict__ edges,          // [G*n][K]
                                                   float* __restrict__ inv_degree) {   // [G*n]
   __shared__ float sx[KNN_TILE], sy[KNN_TILE], sz[KNN_TILE];
   const int frame = blockIdx.y;
+  Disp D;
+  D.load(box, frame);
   const int i = blockIdx.x * 256 + threadIdx.x;
   const float* fp = pos + (int64_t)frame * n * 3;
   float qx = 0.f, qy = 0.f, qz = 0.f;
@@ -50,7 +55,8 @@ __global__ __launch_bounds__(256) void knn_kernel(int n, int K, float scale,
     __syncthreads();
     if (i < n) {
       for (int t = 0; t < cnt; ++t) {
-        const float dx = sx[t] - qx, dy = sy[t] - qy, dz = sz[t] - qz;
+        float dx, dy, dz;
+        D(qx, qy, qz, sx[t], sy[t], sz[t], dx, dy, dz);
         const float d2 = knn_dist2(dx, dy, dz);
         const int j = t0 + t;
         if (d2 < bd[KMAX - 1] && j != i) {
@@ -87,12 +93,14 @@ __global__ __launch_bounds__(256) void knn_kernel(int n, int K, float scale,
 // what a single molecule-sized frame needs (2770 atoms: 0.47 ms -> see tools/knn_time.py).  Order and ties are
 // those of the one-lane kernel: (distance, index) ascending.
 // S = 8 or 16 lanes per query (one DPP row at most): a single molecule-sized frame (2770 queries) fills 87 / 173 workgroups
-template <int KMAX, int S>
+template <int KMAX, int S, class Disp>
 __global__ __launch_bounds__(256) void knn_kernel_s8(int n, int K, float scale, const float* __restrict__ pos,
-                                                     int32_t* __restrict__ nlist, float* __restrict__ edges,
-                                                     float* __restrict__ inv_degree) {
+                                                     const float* __restrict__ box, int32_t* __restrict__ nlist,
+                                                     float* __restrict__ edges, float* __restrict__ inv_degree) {
   __shared__ float sx[KNN_TILE], sy[KNN_TILE], sz[KNN_TILE];
   const int frame = blockIdx.y;
+  Disp D;
+  D.load(box, frame);
   const int sl = threadIdx.x & (S - 1);
   const int i = blockIdx.x * (256 / S) + threadIdx.x / S;
   const float* fp = pos + (int64_t)frame * n * 3;
@@ -112,7 +120,8 @@ __global__ __launch_bounds__(256) void knn_kernel_s8(int n, int K, float scale, 
     __syncthreads();
     if (i < n) {
       for (int t = sl; t < cnt; t += S) {
-        const float dx = sx[t] - qx, dy = sy[t] - qy, dz = sz[t] - qz;
+        float dx, dy, dz;
+        D(qx, qy, qz, sx[t], sy[t], sz[t], dx, dy, dz);
         const float d2 = knn_dist2(dx, dy, dz);
         const int j = t0 + t;
         if (d2 < bd[KMAX - 1] && j != i) {
@@ -198,10 +207,10 @@ __device__ __forceinline__ knn_u64 knn_shr1(knn_u64 v) {
 }
 constexpr int KNN_WAVE_MAXN = 4096;
 
-template <int STEPS>
+template <int STEPS, class Disp>
 __global__ __launch_bounds__(256) void knn_wave_kernel(int n, int K, float scale, const float* __restrict__ pos,
-                                                       int32_t* __restrict__ nlist, float* __restrict__ edges,
-                                                       float* __restrict__ inv_degree) {
+                                                       const float* __restrict__ box, int32_t* __restrict__ nlist,
+                                                       float* __restrict__ edges, float* __restrict__ inv_degree) {
   extern __shared__ float spos[];                 // [3][64 * STEPS]
   constexpr int NP = 64 * STEPS;
   float* sx = spos; float* sy = spos + NP; float* sz = spos + 2 * NP;
@@ -214,6 +223,8 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int n, int K, float scale
   const int i = blockIdx.x * 4 + wave;
   if (i >= n) return;                             // uniform over the wave
   const float qx = sx[i], qy = sy[i], qz = sz[i];
+  Disp D;
+  D.load(box, frame);
   // A: keys of this lane's candidates t = 64 s + lane, and their minimum
   knn_u64 key[STEPS];
   knn_u64 mn = ~0ull;
@@ -221,7 +232,9 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int n, int K, float scale
   for (int s = 0; s < STEPS; ++s) {
     const int t = 64 * s + lane;
     const int tc = min(t, n - 1);
-    const float d2 = knn_dist2(sx[tc] - qx, sy[tc] - qy, sz[tc] - qz);
+    float dx, dy, dz;
+    D(qx, qy, qz, sx[tc], sy[tc], sz[tc], dx, dy, dz);
+    const float d2 = knn_dist2(dx, dy, dz);
     knn_u64 k = ((knn_u64)__builtin_bit_cast(unsigned, d2) << 32) | (unsigned)t;
     if (t >= n || t == i) k = ~0ull;
     key[s] = k;
@@ -263,46 +276,71 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int n, int K, float scale
   if (lane == 0) inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
 }
 
-}  // namespace ng
-
-extern "C" int ng_knn_graph(ng_ctx* ctx, void* stream, int G, int n, int K, float scale,
-                            const float* pos, int32_t* nlist, float* edges, float* inv_degree) {
-  using namespace ng;
-  if (!ctx) return NG_ERR_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn: neighbour count must be in [1,64]");
-  NG_REQUIRE(ctx, G >= 0 && n >= 0, "knn: negative size");
-  NG_REQUIRE(ctx, (int64_t)G * n < (int64_t)1 << 31, "knn: batch exceeds int32 indices");
-  NG_REQUIRE(ctx, G <= 65535, "knn: at most 65535 frames per call");
-  if (G == 0 || n == 0) return NG_OK;
+// the launch of every brute-force kernel for one displacement policy; the cell grid for large frames
+template <class Disp>
+static int knn_graph_impl(ng_ctx* ctx, hipStream_t st, int G, int n, int K, float scale, const float* pos, const float* box,
+                          int triclinic, int32_t* nlist, float* edges, float* inv_degree) {
   // large frames: cell grid (knn_cells.hip), the same lists in O(n) instead of O(n^2); NG_KNN=cells / brute force the choice
   if (!sw().knn_brute && !sw().knn_serial && knn_cells_supported(G, n, K) && (n >= 16384 || sw().knn_cells))
-    return knn_cells(ctx, st, G, n, K, scale, pos, nlist, edges, inv_degree);
+    return knn_cells(ctx, st, G, n, K, scale, pos, nlist, edges, inv_degree, Disp::periodic ? box : nullptr, triclinic);
   ProfScope ps(ctx, st, "knn_graph");
   const dim3 grid((unsigned)cdiv(n, 256), (unsigned)G), block(256);
   // molecule-sized calls: one wave per query (NG_KNN=serial / lanes: the earlier kernels for every size)
   if (!sw().knn_serial && !sw().knn_lanes && n <= KNN_WAVE_MAXN && (int64_t)G * n <= 16384) {
     const dim3 gw((unsigned)cdiv(n, 4), (unsigned)G);
-    if (n <= 1024) hipLaunchKernelGGL((knn_wave_kernel<16>), gw, block, 3 * 64 * 16 * 4, st, n, K, scale, pos, nlist, edges, inv_degree);
-    else if (n <= 2048) hipLaunchKernelGGL((knn_wave_kernel<32>), gw, block, 3 * 64 * 32 * 4, st, n, K, scale, pos, nlist, edges, inv_degree);
-    else if (n <= 3072) hipLaunchKernelGGL((knn_wave_kernel<48>), gw, block, 3 * 64 * 48 * 4, st, n, K, scale, pos, nlist, edges, inv_degree);
-    else hipLaunchKernelGGL((knn_wave_kernel<64>), gw, block, 3 * 64 * 64 * 4, st, n, K, scale, pos, nlist, edges, inv_degree);
+    if (n <= 1024) hipLaunchKernelGGL((knn_wave_kernel<16, Disp>), gw, block, 3 * 64 * 16 * 4, st, n, K, scale, pos, box, nlist, edges, inv_degree);
+    else if (n <= 2048) hipLaunchKernelGGL((knn_wave_kernel<32, Disp>), gw, block, 3 * 64 * 32 * 4, st, n, K, scale, pos, box, nlist, edges, inv_degree);
+    else if (n <= 3072) hipLaunchKernelGGL((knn_wave_kernel<48, Disp>), gw, block, 3 * 64 * 48 * 4, st, n, K, scale, pos, box, nlist, edges, inv_degree);
+    else hipLaunchKernelGGL((knn_wave_kernel<64, Disp>), gw, block, 3 * 64 * 64 * 4, st, n, K, scale, pos, box, nlist, edges, inv_degree);
   } else if (K <= 16 && !sw().knn_serial)      // 8 / 16 lanes per query
   {
     const int64_t nq = (int64_t)G * n;          // few queries: more lanes per query, so that the launch still fills the chip
     if (nq <= 16384)
-      hipLaunchKernelGGL((knn_kernel_s8<16, 16>), dim3((unsigned)cdiv(n, 16), (unsigned)G), block, 0, st, n, K, scale, pos,
-                         nlist, edges, inv_degree);
+      hipLaunchKernelGGL((knn_kernel_s8<16, 16, Disp>), dim3((unsigned)cdiv(n, 16), (unsigned)G), block, 0, st, n, K, scale, pos,
+                         box, nlist, edges, inv_degree);
     else
-      hipLaunchKernelGGL((knn_kernel_s8<16, 8>), dim3((unsigned)cdiv(n, 32), (unsigned)G), block, 0, st, n, K, scale, pos,
-                         nlist, edges, inv_degree);
+      hipLaunchKernelGGL((knn_kernel_s8<16, 8, Disp>), dim3((unsigned)cdiv(n, 32), (unsigned)G), block, 0, st, n, K, scale, pos,
+                         box, nlist, edges, inv_degree);
   }
   else if (K <= 16)
-    hipLaunchKernelGGL(knn_kernel<16>, grid, block, 0, st, n, K, scale, pos, nlist, edges, inv_degree);
+    hipLaunchKernelGGL((knn_kernel<16, Disp>), grid, block, 0, st, n, K, scale, pos, box, nlist, edges, inv_degree);
   else if (K <= 32)
-    hipLaunchKernelGGL(knn_kernel<32>, grid, block, 0, st, n, K, scale, pos, nlist, edges, inv_degree);
+    hipLaunchKernelGGL((knn_kernel<32, Disp>), grid, block, 0, st, n, K, scale, pos, box, nlist, edges, inv_degree);
   else
-    hipLaunchKernelGGL(knn_kernel<64>, grid, block, 0, st, n, K, scale, pos, nlist, edges, inv_degree);
+    hipLaunchKernelGGL((knn_kernel<64, Disp>), grid, block, 0, st, n, K, scale, pos, box, nlist, edges, inv_degree);
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
+}
+
+}  // namespace ng
+
+static int knn_check(ng_ctx* ctx, int G, int n, int K) {
+  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn: neighbour count must be in [1,64]");
+  NG_REQUIRE(ctx, G >= 0 && n >= 0, "knn: negative size");
+  NG_REQUIRE(ctx, (int64_t)G * n < (int64_t)1 << 31, "knn: batch exceeds int32 indices");
+  NG_REQUIRE(ctx, G <= 65535, "knn: at most 65535 frames per call");
+  return NG_OK;
+}
+
+extern "C" int ng_knn_graph(ng_ctx* ctx, void* stream, int G, int n, int K, float scale,
+                            const float* pos, int32_t* nlist, float* edges, float* inv_degree) {
+  using namespace ng;
+  if (!ctx) return NG_ERR_INVALID;
+  if (const int rc = knn_check(ctx, G, n, K)) return rc;
+  if (G == 0 || n == 0) return NG_OK;
+  return knn_graph_impl<DispOpen>(ctx, (hipStream_t)stream, G, n, K, scale, pos, nullptr, 0, nlist, edges, inv_degree);
+}
+
+// periodic boxes: box [G][9] lower-triangular lattice vectors on the device (pbc.cuh); triclinic = 0 orthorhombic, 1 reduced
+extern "C" int ng_knn_graph_pbc(ng_ctx* ctx, void* stream, int G, int n, int K, float scale, const float* pos,
+                                const float* box, int triclinic, int32_t* nlist, float* edges, float* inv_degree) {
+  using namespace ng;
+  if (!ctx) return NG_ERR_INVALID;
+  if (const int rc = knn_check(ctx, G, n, K)) return rc;
+  NG_REQUIRE(ctx, triclinic == 0 || triclinic == 1, "knn_pbc: triclinic flag 0 or 1");
+  if (G == 0 || n == 0) return NG_OK;
+  NG_REQUIRE(ctx, box != nullptr, "knn_pbc: box required");
+  hipStream_t st = (hipStream_t)stream;
+  return triclinic ? knn_graph_impl<DispTric>(ctx, st, G, n, K, scale, pos, box, 1, nlist, edges, inv_degree)
+                   : knn_graph_impl<DispOrtho>(ctx, st, G, n, K, scale, pos, box, 0, nlist, edges, inv_degree);
 }

@@ -14,6 +14,7 @@
 
 #include "ng_common.h"
 #include "ng_internal.h"
+#include "pbc.cuh"
 
 extern "C" int ng_exclusive_scan_i32(ng_ctx*, void*, int64_t, const int32_t*, int32_t*);
 
@@ -127,6 +128,30 @@ __global__ __launch_bounds__(256) void kc_fill_kernel(int n, int cap, const floa
 // whose bit patterns order like the values, so key order IS (distance, index) order — one compare per slot instead of
 // three.  The insertion appears once in the kernel (one loop over the one or two record ranges of a row of cells): with
 // a copy per call site, and four more for a four-deep prefetch, the kernel was instruction-fetch bound (6 us per ROW).
+// the candidates of one row of cells — the record ranges [a0, b0) and [a1, b1) — into the query's list, distances through the
+// displacement policy D (pbc.cuh); the one call site of each query kernel
+template <int KMAX, class Disp>
+__device__ __forceinline__ void kc_scan(const Disp& D, float4 q, int i, const float4* __restrict__ rec, int a0, int b0, int a1,
+                                        int b1, uint64_t (&key)[KMAX]) {
+  const int len0 = b0 - a0, total = len0 + (b1 - a1);
+  for (int u = 0; u < total; ++u) {
+    const float4 c = rec[u < len0 ? a0 + u : a1 + (u - len0)];
+    float dx, dy, dz;
+    D(q.x, q.y, q.z, c.x, c.y, c.z, dx, dy, dz);
+    const float d2 = knn_dist2(dx, dy, dz);
+    const unsigned j = __builtin_bit_cast(unsigned, c.w);
+    const uint64_t kk = ((uint64_t)__builtin_bit_cast(unsigned, d2) << 32) | j;
+    if (kk < key[KMAX - 1] && (int)j != i) {
+#pragma unroll
+      for (int k = KMAX - 1; k >= 1; --k) {
+        const bool shift = kk < key[k - 1];                 // old element k-1 moves up
+        key[k] = shift ? key[k - 1] : (kk < key[k] ? kk : key[k]);
+      }
+      key[0] = kk < key[0] ? kk : key[0];
+    }
+  }
+}
+
 template <int KMAX>
 __global__ __launch_bounds__(256) void kc_query_kernel(int n, int K, int cap, float scale, const KcGrid* __restrict__ grids,
                                                        const int32_t* __restrict__ start, const float4* __restrict__ rec,
@@ -164,21 +189,7 @@ __global__ __launch_bounds__(256) void kc_query_kernel(int n, int K, int cap, fl
           a0 = xl >= 0 ? st[rowc + xl] : 0; b0 = xl >= 0 ? st[rowc + xl + 1] : 0;
           a1 = xr < g.nx ? st[rowc + xr] : 0; b1 = xr < g.nx ? st[rowc + xr + 1] : 0;
         }
-        const int len0 = b0 - a0, total = len0 + (b1 - a1);
-        for (int u = 0; u < total; ++u) {
-          const float4 c = rec[u < len0 ? a0 + u : a1 + (u - len0)];
-          const float d2 = knn_dist2(c.x - q.x, c.y - q.y, c.z - q.z);
-          const unsigned j = __builtin_bit_cast(unsigned, c.w);
-          const uint64_t kk = ((uint64_t)__builtin_bit_cast(unsigned, d2) << 32) | j;
-          if (kk < key[KMAX - 1] && (int)j != i) {
-#pragma unroll
-            for (int k = KMAX - 1; k >= 1; --k) {
-              const bool shift = kk < key[k - 1];                 // old element k-1 moves up
-              key[k] = shift ? key[k - 1] : (kk < key[k] ? kk : key[k]);
-            }
-            key[0] = kk < key[0] ? kk : key[0];
-          }
-        }
+        kc_scan<KMAX>(DispOpen(), q, i, rec, a0, b0, a1, b1, key);
       }
     }
     // every atom outside the cube of shells 0..r is at least r L from the query (it is at least r whole cells away along
@@ -187,6 +198,149 @@ __global__ __launch_bounds__(256) void kc_query_kernel(int n, int K, int cap, fl
     uint64_t kth = EMPTY;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) kth = k == K - 1 ? key[k] : kth;      // (a run-time index would put the list on the stack)
+    if (__builtin_bit_cast(float, (unsigned)(kth >> 32)) <= reach * reach) break;
+  }
+
+  const int64_t row = (int64_t)frame * n + i;
+  int deg = 0;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    if (k < K) {
+      const float d2 = __builtin_bit_cast(float, (unsigned)(key[k] >> 32));
+      const int j = (int)(unsigned)key[k];
+      const bool ok = d2 < INFINITY;
+      nlist[row * K + k] = ok ? frame * n + j : 0;
+      edges[row * K + k] = ok ? sqrtf(d2) * scale : 0.f;
+      deg += (ok && j > 0) ? 1 : 0;
+    }
+  }
+  inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+}
+
+// ---- periodic boxes: the grid lives in fractional coordinates ----------------------------------------------------------
+// Box (pbc.cuh) a = (ax, 0, 0), b = (bx, by, 0), c = (cx, cy, cz); an atom's cell is floor(n_axis * frac(f_axis)) of its
+// fractional coordinates, whatever image the raw position is in.  Per-axis cell counts follow the perpendicular widths
+// w_axis of the box (n_axis = w_axis / L, at least 1), so a cell is at least L thick along every axis.  Shells of cells wrap
+// modulo the grid; along an axis of n cells a shell reaches at most lo = (n - 1) / 2 cells down and hi = n - 1 - lo up, so
+// each cell is visited once even where 2r + 1 exceeds n.  An atom none of whose images lies in shells 0..r is more than
+// r cells away along some axis that shell r does not yet cover: at least r * (w_axis / n_axis) away in the minimum image.
+struct KpGrid {
+  float ax, bx, by, cx, cy, cz;
+  float iax, iby, icz;
+  float wx, wy, wz;      // perpendicular thickness of one cell along a, b, c
+  int nx, ny, nz;
+};
+
+__device__ __forceinline__ int kp_axis(float f, int n) {
+  f -= floorf(f);
+  return min(max((int)(f * (float)n), 0), n - 1);
+}
+
+__global__ __launch_bounds__(64) void kp_grid_kernel(int G, int n, int K, int cap, const float* __restrict__ box,
+                                                     KpGrid* __restrict__ grids) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= G) return;
+  const float* b = box + (int64_t)f * 9;
+  KpGrid g;
+  g.ax = b[0]; g.bx = b[3]; g.by = b[4]; g.cx = b[6]; g.cy = b[7]; g.cz = b[8];
+  g.iax = 1.0f / g.ax; g.iby = 1.0f / g.by; g.icz = 1.0f / g.cz;
+  const float v = g.ax * g.by * g.cz;
+  const float bcx = g.by * g.cz, bcy = -g.bx * g.cz, bcz = g.bx * g.cy - g.by * g.cx;
+  const float wa = v / sqrtf(bcx * bcx + bcy * bcy + bcz * bcz), wb = g.by * g.cz / sqrtf(g.cy * g.cy + g.cz * g.cz), wc = g.cz;
+  // the cell edge of the open grid at the box's density (a filled box: the density is the true one)
+  float l = KC_EDGE * cbrtf((float)K * v / (float)n);
+  int nx = 1, ny = 1, nz = 1;
+  for (int it = 0; it < 256; ++it) {      // bounded: a box the host would refuse (NaN widths) ends as one cell
+    nx = max((int)fminf(wa / l, 4.0e6f), 1); ny = max((int)fminf(wb / l, 4.0e6f), 1); nz = max((int)fminf(wc / l, 4.0e6f), 1);
+    if ((int64_t)nx * ny * nz <= cap) break;
+    nx = ny = nz = 1;
+    l *= 1.26f;
+  }
+  g.nx = nx; g.ny = ny; g.nz = nz;
+  g.wx = wa / (float)nx; g.wy = wb / (float)ny; g.wz = wc / (float)nz;
+  grids[f] = g;
+}
+
+__global__ __launch_bounds__(256) void kp_count_kernel(int n, int cap, const float* __restrict__ pos, const KpGrid* __restrict__ grids,
+                                                       int32_t* __restrict__ cell_of, int32_t* __restrict__ count) {
+  const int frame = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const KpGrid g = grids[frame];
+  const float* p = pos + ((int64_t)frame * n + i) * 3;
+  const float fc = p[2] * g.icz;
+  const float fb = fmaf(-fc, g.cy, p[1]) * g.iby;
+  const float fa = fmaf(-fc, g.cx, fmaf(-fb, g.bx, p[0])) * g.iax;
+  const int c = (kp_axis(fc, g.nz) * g.ny + kp_axis(fb, g.ny)) * g.nx + kp_axis(fa, g.nx);
+  cell_of[(int64_t)frame * n + i] = c;
+  atomicAdd(count + (int64_t)frame * cap + c, 1);
+}
+
+__device__ __forceinline__ int kp_wrap(int x, int n) { return x < 0 ? x + n : (x >= n ? x - n : x); }
+
+template <int KMAX, class Disp>
+__global__ __launch_bounds__(256) void kp_query_kernel(int n, int K, int cap, float scale, const KpGrid* __restrict__ grids,
+                                                       const float* __restrict__ box, const int32_t* __restrict__ cell_of,
+                                                       const int32_t* __restrict__ start, const float4* __restrict__ rec,
+                                                       int32_t* __restrict__ nlist, float* __restrict__ edges,
+                                                       float* __restrict__ inv_degree) {
+  const int frame = blockIdx.y;
+  const int p = blockIdx.x * 256 + threadIdx.x;      // sorted slot inside the frame
+  if (p >= n) return;
+  const KpGrid g = grids[frame];
+  Disp D;
+  D.load(box, frame);
+  const float4 q = rec[(int64_t)frame * n + p];
+  const int i = __builtin_bit_cast(int, q.w);
+  const int c = cell_of[(int64_t)frame * n + i];      // the cell the count pass gave the query
+  const int cx = c % g.nx, cy = (c / g.nx) % g.ny, cz = c / (g.nx * g.ny);
+  const int lox = (g.nx - 1) / 2, hix = g.nx - 1 - lox;
+  const int loy = (g.ny - 1) / 2, hiy = g.ny - 1 - loy;
+  const int loz = (g.nz - 1) / 2, hiz = g.nz - 1 - loz;
+  const int32_t* st = start + (int64_t)frame * cap;
+  constexpr uint64_t EMPTY = ((uint64_t)0x7f800000u << 32) | 0x7fffffffu;      // (inf, no index)
+  uint64_t key[KMAX];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) key[k] = EMPTY;
+
+  const int rmax = max(max(hix, hiy), hiz);
+  for (int r = 0; r <= rmax; ++r) {
+    const int xl = min(r, lox), xh = min(r, hix);
+    for (int dz = -min(r, loz); dz <= min(r, hiz); ++dz) {
+      const int z = kp_wrap(cz + dz, g.nz);
+      const bool bz = dz == -r || dz == r;
+      for (int dy = -min(r, loy); dy <= min(r, hiy); ++dy) {
+        const int y = kp_wrap(cy + dy, g.ny);
+        const int rowc = (z * g.ny + y) * g.nx;
+        int a0 = 0, b0 = 0, a1 = 0, b1 = 0;
+        if (bz || dy == -r || dy == r) {
+          // a whole row of the shell: cells cx - xl .. cx + xh, one range of records or — wrapped — two
+          const int x0 = cx - xl, x1 = cx + xh;
+          if (x0 < 0) {
+            a0 = st[rowc + x0 + g.nx]; b0 = st[rowc + g.nx]; a1 = st[rowc]; b1 = st[rowc + x1 + 1];
+          } else if (x1 >= g.nx) {
+            a0 = st[rowc + x0]; b0 = st[rowc + g.nx]; a1 = st[rowc]; b1 = st[rowc + x1 - g.nx + 1];
+          } else {
+            a0 = st[rowc + x0]; b0 = st[rowc + x1 + 1];
+          }
+        } else {
+          // an interior row: its end cells, on the sides where the axis is not yet exhausted (r >= 1 here: distinct cells)
+          if (r <= lox) { const int x = kp_wrap(cx - r, g.nx); a0 = st[rowc + x]; b0 = st[rowc + x + 1]; }
+          if (r <= hix) { const int x = kp_wrap(cx + r, g.nx); a1 = st[rowc + x]; b1 = st[rowc + x + 1]; }
+        }
+        kc_scan<KMAX>(D, q, i, rec, a0, b0, a1, b1, key);
+      }
+    }
+    // the thinnest cell along the axes shell r does not cover yet (0.1 % off for the rounding of the cell assignment)
+    float w = INFINITY;
+    if (r < hix) w = fminf(w, g.wx);
+    if (r < hiy) w = fminf(w, g.wy);
+    if (r < hiz) w = fminf(w, g.wz);
+    if (w == INFINITY) break;                          // every cell visited
+    const float reach = (float)r * w * 0.999f;
+    uint64_t kth = EMPTY;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) kth = k == K - 1 ? key[k] : kth;
     if (__builtin_bit_cast(float, (unsigned)(kth >> 32)) <= reach * reach) break;
   }
 
@@ -218,11 +372,12 @@ bool knn_cells_supported(int G, int n, int K) {
 }
 
 int knn_cells(ng_ctx* ctx, hipStream_t st, int G, int n, int K, float scale, const float* pos, int32_t* nlist, float* edges,
-              float* inv_degree) {
+              float* inv_degree, const float* box, int triclinic) {
   const int cap = kc_cell_cap(n);
   const int64_t rows = (int64_t)G * n, cells = (int64_t)G * cap;
   // scratch: records [rows] float4 | cell_of [rows] | count [cells] | start [cells + 1] | grids [G] | partial boxes [G][64][6]
-  const size_t bytes = (size_t)rows * 16 + (size_t)rows * 4 + (size_t)cells * 4 + (size_t)(cells + 1) * 4 + (size_t)G * (sizeof(KcGrid) + KC_BOX_BLOCKS * 6 * 4) + 256;
+  // (periodic boxes: grids [G] KpGrid, no partial boxes)
+  const size_t bytes = (size_t)rows * 16 + (size_t)rows * 4 + (size_t)cells * 4 + (size_t)(cells + 1) * 4 + (size_t)G * (sizeof(KpGrid) + KC_BOX_BLOCKS * 6 * 4) + 256;
   char* ws = (char*)workspace(ctx, bytes);
   if (!ws) return NG_ERR_NOMEM;
   float4* rec = reinterpret_cast<float4*>(ws);
@@ -231,13 +386,19 @@ int knn_cells(ng_ctx* ctx, hipStream_t st, int G, int n, int K, float scale, con
   int32_t* start = count + cells;
   KcGrid* grids = reinterpret_cast<KcGrid*>(start + cells + 1 + ((cells + 1) & 1));
   float* boxes = reinterpret_cast<float*>(grids + G);
+  KpGrid* pgrids = reinterpret_cast<KpGrid*>(grids);
   const dim3 grid((unsigned)cdiv(n, 256), (unsigned)G), block(256);
   {
     ProfScope ps(ctx, st, "knn_cells_sort");
     NG_HIP(ctx, hipMemsetAsync(count, 0, (size_t)cells * 4, st));
-    hipLaunchKernelGGL(kc_box_kernel, dim3(KC_BOX_BLOCKS, (unsigned)G), dim3(256), 0, st, n, pos, boxes);
-    hipLaunchKernelGGL(kc_grid_kernel, dim3((unsigned)G), dim3(64), 0, st, n, K, cap, boxes, grids);
-    hipLaunchKernelGGL(kc_count_kernel, grid, block, 0, st, n, cap, pos, grids, cell_of, count);
+    if (box) {
+      hipLaunchKernelGGL(kp_grid_kernel, dim3((unsigned)cdiv(G, 64)), dim3(64), 0, st, G, n, K, cap, box, pgrids);
+      hipLaunchKernelGGL(kp_count_kernel, grid, block, 0, st, n, cap, pos, pgrids, cell_of, count);
+    } else {
+      hipLaunchKernelGGL(kc_box_kernel, dim3(KC_BOX_BLOCKS, (unsigned)G), dim3(256), 0, st, n, pos, boxes);
+      hipLaunchKernelGGL(kc_grid_kernel, dim3((unsigned)G), dim3(64), 0, st, n, K, cap, boxes, grids);
+      hipLaunchKernelGGL(kc_count_kernel, grid, block, 0, st, n, cap, pos, grids, cell_of, count);
+    }
     NG_HIP(ctx, hipGetLastError());
     const int rc = ng_exclusive_scan_i32(ctx, st, cells, count, start);
     if (rc) return rc;
@@ -246,6 +407,19 @@ int knn_cells(ng_ctx* ctx, hipStream_t st, int G, int n, int K, float scale, con
     NG_HIP(ctx, hipGetLastError());
   }
   ProfScope ps(ctx, st, "knn_cells_query");
+#define NG_KP(KM, DISP)                                                                                                \
+  hipLaunchKernelGGL((kp_query_kernel<KM, DISP>), grid, block, 0, st, n, K, cap, scale, pgrids, box, cell_of, start, rec, nlist, \
+                     edges, inv_degree)
+  if (box) {
+    if (triclinic) {
+      if (K <= 16) NG_KP(16, DispTric); else if (K <= 32) NG_KP(32, DispTric); else NG_KP(64, DispTric);
+    } else {
+      if (K <= 16) NG_KP(16, DispOrtho); else if (K <= 32) NG_KP(32, DispOrtho); else NG_KP(64, DispOrtho);
+    }
+    NG_HIP(ctx, hipGetLastError());
+    return NG_OK;
+  }
+#undef NG_KP
   if (K <= 16)
     hipLaunchKernelGGL(kc_query_kernel<16>, grid, block, 0, st, n, K, cap, scale, grids, start, rec, nlist, edges, inv_degree);
   else if (K <= 32)

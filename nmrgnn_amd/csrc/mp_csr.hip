@@ -22,6 +22,8 @@
 #include "ng_internal.h"
 #include "reduce.cuh"
 
+#include "pbc.cuh"
+
 namespace ng {
 
 namespace {
@@ -687,13 +689,16 @@ constexpr int CUT_TILE = 1024;
 // by the count and then filled; left to -ffp-contract two instantiations may round differently by an ulp.
 __device__ __forceinline__ float cut_dist2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
-template <bool FILL>
+template <bool FILL, class Disp>
 __global__ __launch_bounds__(256) void cutoff_kernel(int n, float cutoff2, float scale, const float* __restrict__ pos,
                                                      int32_t* __restrict__ deg, const int32_t* __restrict__ row_ptr,
                                                      int32_t* __restrict__ col, float* __restrict__ dist,
-                                                     float* __restrict__ inv_degree, int32_t* __restrict__ row_of) {
+                                                     float* __restrict__ inv_degree, int32_t* __restrict__ row_of,
+    const float* __restrict__ box) {
   __shared__ float sx[CUT_TILE], sy[CUT_TILE], sz[CUT_TILE];
   const int frame = blockIdx.y;
+  Disp D;
+  D.load(box, frame);
   const int i = blockIdx.x * 256 + threadIdx.x;
   const float* fp = pos + (int64_t)frame * n * 3;
   float qx = 0.f, qy = 0.f, qz = 0.f;
@@ -711,7 +716,8 @@ __global__ __launch_bounds__(256) void cutoff_kernel(int n, float cutoff2, float
     __syncthreads();
     if (i < n) {
       for (int t = 0; t < m; ++t) {
-        const float dx = sx[t] - qx, dy = sy[t] - qy, dz = sz[t] - qz;
+        float dx, dy, dz;
+        D(qx, qy, qz, sx[t], sy[t], sz[t], dx, dy, dz);
         const float d2 = cut_dist2(dx, dy, dz);
         const int j = t0 + t;
         if (d2 < cutoff2 && j != i) {
@@ -735,13 +741,16 @@ __global__ __launch_bounds__(256) void cutoff_kernel(int n, float cutoff2, float
 // ballot per 16-candidate chunk gives the hits in ascending candidate order, so rows come out exactly as the
 // one-thread-per-atom kernel writes them.  One thread per atom left a 2770-atom frame with 11 workgroups walking 2770
 // candidates each, its hits stored one by one: 80 us (count) + 295 us (fill) per frame; this form: 256 threads = 16 atoms.
-template <bool FILL>
+template <bool FILL, class Disp>
 __global__ __launch_bounds__(256) void cutoff_s16_kernel(int n, float cutoff2, float scale, const float* __restrict__ pos,
                                                          int32_t* __restrict__ deg, const int32_t* __restrict__ row_ptr,
                                                          int32_t* __restrict__ col, float* __restrict__ dist,
-                                                         float* __restrict__ inv_degree, int32_t* __restrict__ row_of) {
+                                                         float* __restrict__ inv_degree, int32_t* __restrict__ row_of,
+    const float* __restrict__ box) {
   __shared__ float sx[CUT_TILE], sy[CUT_TILE], sz[CUT_TILE];
   const int frame = blockIdx.y;
+  Disp D;
+  D.load(box, frame);
   const int s = threadIdx.x & 15, grp = (threadIdx.x & 63) >> 4;
   const int i = blockIdx.x * 16 + (threadIdx.x >> 4);
   const float* fp = pos + (int64_t)frame * n * 3;
@@ -769,7 +778,8 @@ __global__ __launch_bounds__(256) void cutoff_s16_kernel(int n, float cutoff2, f
         hit[u] = false;
         d2[u] = 0.f;
         if (t < m && i < n) {
-          const float dx = sx[t] - qx, dy = sy[t] - qy, dz = sz[t] - qz;
+          float dx, dy, dz;
+          D(qx, qy, qz, sx[t], sy[t], sz[t], dx, dy, dz);
           d2[u] = cut_dist2(dx, dy, dz);
           hit[u] = d2[u] < cutoff2 && t0 + t != i;
         }
@@ -809,14 +819,17 @@ __global__ __launch_bounds__(256) void cutoff_s16_kernel(int n, float cutoff2, f
 // distance expression, so the rows are the same bit for bit — and the frame's positions are staged in LDS once per workgroup
 // (n <= 4096).  A 2770-atom frame: count 27-38 us + fill 36 us (16 lanes per atom) -> a few us each.
 constexpr int CUT_WAVE_MAXN = 4096;
-template <bool FILL>
+template <bool FILL, class Disp>
 __global__ __launch_bounds__(256) void cutoff_wave_kernel(int n, float cutoff2, float scale, const float* __restrict__ pos,
                                                           int32_t* __restrict__ deg, const int32_t* __restrict__ row_ptr,
                                                           int32_t* __restrict__ col, float* __restrict__ dist,
-                                                          float* __restrict__ inv_degree, int32_t* __restrict__ row_of) {
+                                                          float* __restrict__ inv_degree, int32_t* __restrict__ row_of,
+    const float* __restrict__ box) {
   extern __shared__ float cw_pos[];               // [3][n]
   float* sx = cw_pos; float* sy = cw_pos + n; float* sz = cw_pos + 2 * n;
   const int frame = blockIdx.y;
+  Disp D;
+  D.load(box, frame);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const float* fp = pos + (int64_t)frame * n * 3;
@@ -832,7 +845,9 @@ __global__ __launch_bounds__(256) void cutoff_wave_kernel(int n, float cutoff2, 
   for (int tb = 0; tb < n; tb += 64) {
     const int t = tb + lane;
     const int tc = min(t, n - 1);
-    const float d2 = cut_dist2(sx[tc] - qx, sy[tc] - qy, sz[tc] - qz);
+    float dx, dy, dz;
+    D(qx, qy, qz, sx[tc], sy[tc], sz[tc], dx, dy, dz);
+    const float d2 = cut_dist2(dx, dy, dz);
     const bool hit = t < n && t != i && d2 < cutoff2;
     const unsigned long long m = __ballot(hit);
     if (FILL && hit) {
@@ -888,24 +903,34 @@ extern "C" int ng_mp_layer_bwd_csr(ng_ctx* ctx, void* stream, int64_t N, int64_t
                         s_save, csc_ptr, csc_edge, dh_out, dh_in, de, de_accum, dw, nullptr, nnz);
 }
 
-extern "C" int ng_cutoff_count(ng_ctx* ctx, void* stream, int G, int n, float cutoff, const float* pos,
-                               int32_t* deg) {
-  if (!ctx) return NG_ERR_INVALID;
+// count (FILL = false) or fill pass of one displacement policy; the kernel choice of both passes is the same, so that they
+// agree on every `d2 < cutoff2`
+template <bool FILL, class Disp>
+static int cutoff_launch(ng_ctx* ctx, hipStream_t st, int G, int n, float cutoff, float scale, const float* pos, const float* box,
+                         int32_t* deg, const int32_t* row_ptr, int32_t* col, float* dist, float* inv_degree, int32_t* row_of) {
   NG_REQUIRE(ctx, G >= 0 && n >= 0 && cutoff > 0.f, "cutoff graph: sizes >= 0, cutoff > 0");
   NG_REQUIRE(ctx, (int64_t)G * n < (int64_t)1 << 31 && G <= 65535, "cutoff graph: batch too large");
   if (G == 0 || n == 0) return NG_OK;
-  ProfScope ps(ctx, (hipStream_t)stream, "cutoff_count");
+  NG_REQUIRE(ctx, !Disp::periodic || box, "cutoff graph (pbc): box required");
+  ProfScope ps(ctx, st, FILL ? "cutoff_fill" : "cutoff_count");
   if (!sw().knn_serial && !sw().knn_lanes && n <= CUT_WAVE_MAXN && (int64_t)G * n <= 16384)      // molecule-sized: one wave per atom
-    hipLaunchKernelGGL((cutoff_wave_kernel<false>), dim3((unsigned)cdiv(n, 4), (unsigned)G), dim3(256), (size_t)3 * n * 4,
-                       (hipStream_t)stream, n, cutoff * cutoff, 1.0f, pos, deg, nullptr, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((cutoff_wave_kernel<FILL, Disp>), dim3((unsigned)cdiv(n, 4), (unsigned)G), dim3(256), (size_t)3 * n * 4,
+                       st, n, cutoff * cutoff, scale, pos, deg, row_ptr, col, dist, inv_degree, row_of, box);
   else if (sw().knn_serial)
-    hipLaunchKernelGGL((cutoff_kernel<false>), dim3((unsigned)cdiv(n, 256), (unsigned)G), dim3(256), 0,
-                       (hipStream_t)stream, n, cutoff * cutoff, 1.0f, pos, deg, nullptr, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((cutoff_kernel<FILL, Disp>), dim3((unsigned)cdiv(n, 256), (unsigned)G), dim3(256), 0,
+                       st, n, cutoff * cutoff, scale, pos, deg, row_ptr, col, dist, inv_degree, row_of, box);
   else
-    hipLaunchKernelGGL((cutoff_s16_kernel<false>), dim3((unsigned)cdiv(n, 16), (unsigned)G), dim3(256), 0,
-                       (hipStream_t)stream, n, cutoff * cutoff, 1.0f, pos, deg, nullptr, nullptr, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL((cutoff_s16_kernel<FILL, Disp>), dim3((unsigned)cdiv(n, 16), (unsigned)G), dim3(256), 0,
+                       st, n, cutoff * cutoff, scale, pos, deg, row_ptr, col, dist, inv_degree, row_of, box);
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
+}
+
+extern "C" int ng_cutoff_count(ng_ctx* ctx, void* stream, int G, int n, float cutoff, const float* pos,
+                               int32_t* deg) {
+  if (!ctx) return NG_ERR_INVALID;
+  return cutoff_launch<false, DispOpen>(ctx, (hipStream_t)stream, G, n, cutoff, 1.0f, pos, nullptr, deg, nullptr, nullptr,
+                                        nullptr, nullptr, nullptr);
 }
 
 extern "C" int ng_cutoff_fill_rows(ng_ctx* ctx, void* stream, int G, int n, float cutoff, float scale, const float* pos,
@@ -919,19 +944,27 @@ extern "C" int ng_cutoff_fill(ng_ctx* ctx, void* stream, int G, int n, float cut
 extern "C" int ng_cutoff_fill_rows(ng_ctx* ctx, void* stream, int G, int n, float cutoff, float scale, const float* pos,
                                    const int32_t* row_ptr, int32_t* col, float* dist, float* inv_degree, int32_t* row_of) {
   if (!ctx) return NG_ERR_INVALID;
-  NG_REQUIRE(ctx, G >= 0 && n >= 0 && cutoff > 0.f, "cutoff graph: sizes >= 0, cutoff > 0");
-  NG_REQUIRE(ctx, (int64_t)G * n < (int64_t)1 << 31 && G <= 65535, "cutoff graph: batch too large");
-  if (G == 0 || n == 0) return NG_OK;
-  ProfScope ps(ctx, (hipStream_t)stream, "cutoff_fill");
-  if (!sw().knn_serial && !sw().knn_lanes && n <= CUT_WAVE_MAXN && (int64_t)G * n <= 16384)
-    hipLaunchKernelGGL((cutoff_wave_kernel<true>), dim3((unsigned)cdiv(n, 4), (unsigned)G), dim3(256), (size_t)3 * n * 4,
-                       (hipStream_t)stream, n, cutoff * cutoff, scale, pos, nullptr, row_ptr, col, dist, inv_degree, row_of);
-  else if (sw().knn_serial)
-    hipLaunchKernelGGL((cutoff_kernel<true>), dim3((unsigned)cdiv(n, 256), (unsigned)G), dim3(256), 0,
-                       (hipStream_t)stream, n, cutoff * cutoff, scale, pos, nullptr, row_ptr, col, dist, inv_degree, row_of);
-  else
-    hipLaunchKernelGGL((cutoff_s16_kernel<true>), dim3((unsigned)cdiv(n, 16), (unsigned)G), dim3(256), 0,
-                       (hipStream_t)stream, n, cutoff * cutoff, scale, pos, nullptr, row_ptr, col, dist, inv_degree, row_of);
-  NG_HIP(ctx, hipGetLastError());
-  return NG_OK;
+  return cutoff_launch<true, DispOpen>(ctx, (hipStream_t)stream, G, n, cutoff, scale, pos, nullptr, nullptr, row_ptr, col, dist,
+                                       inv_degree, row_of);
+}
+
+// periodic boxes: box [G][9] lower-triangular lattice vectors on the device (pbc.cuh), triclinic = 0 orthorhombic / 1 reduced;
+// the caller keeps cutoff below half the smallest perpendicular width of every box
+extern "C" int ng_cutoff_count_pbc(ng_ctx* ctx, void* stream, int G, int n, float cutoff, const float* pos, const float* box,
+                                   int triclinic, int32_t* deg) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, triclinic == 0 || triclinic == 1, "cutoff graph (pbc): triclinic flag 0 or 1");
+  hipStream_t st = (hipStream_t)stream;
+  return triclinic ? cutoff_launch<false, DispTric>(ctx, st, G, n, cutoff, 1.0f, pos, box, deg, nullptr, nullptr, nullptr, nullptr, nullptr)
+                   : cutoff_launch<false, DispOrtho>(ctx, st, G, n, cutoff, 1.0f, pos, box, deg, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int ng_cutoff_fill_rows_pbc(ng_ctx* ctx, void* stream, int G, int n, float cutoff, float scale, const float* pos,
+                                       const float* box, int triclinic, const int32_t* row_ptr, int32_t* col, float* dist,
+                                       float* inv_degree, int32_t* row_of) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, triclinic == 0 || triclinic == 1, "cutoff graph (pbc): triclinic flag 0 or 1");
+  hipStream_t st = (hipStream_t)stream;
+  return triclinic ? cutoff_launch<true, DispTric>(ctx, st, G, n, cutoff, scale, pos, box, nullptr, row_ptr, col, dist, inv_degree, row_of)
+                   : cutoff_launch<true, DispOrtho>(ctx, st, G, n, cutoff, scale, pos, box, nullptr, row_ptr, col, dist, inv_degree, row_of);
 }

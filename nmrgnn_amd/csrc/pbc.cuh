@@ -1,0 +1,92 @@
+// Periodic boxes under the minimum-image convention: the displacement policies of the neighbour-list builders (knn.hip,
+// knn_cells.hip, mp_csr.hip's cutoff kernels) and of the position gradient (input_grad.hip).
+//
+// A box is three lattice vectors in lower-triangular form, [9] floats per frame, row-major: a = (ax, 0, 0),
+// b = (bx, by, 0), c = (cx, cy, cz) — the GROMACS / MDAnalysis triclinic_vectors convention.  The host converts
+// (a, b, c, alpha, beta, gamma) to that form and accepts only orthorhombic and reduced triclinic boxes
+// (|bx| <= ax/2, |cx| <= ax/2, |cy| <= by/2).
+//
+// A policy D is called as D(q, c, d): d = the displacement from q to c, from the two RAW positions.  Every kernel that
+// builds or differentiates a periodic edge calls the same policy with (query, candidate) in that order, so the cell grid
+// and brute force see the same bits and the gradient uses exactly the vector behind each edge.
+//   DispOpen   c - q: today's arithmetic, bit for bit (the open-boundary instantiations stay what they were)
+//   DispOrtho  c - q, then rint per axis
+//   DispTric   c - q, sequential z / y / x wrap; when the wrapped vector is not shorter than w_min / 2 (w_min: the smallest
+//              perpendicular width) the nearest of its 27 neighbouring images.  Below w_min / 2 it is provably the minimum
+//              image: every other image is at least w_min - |d| away.
+// Which policy runs is chosen on the host from the box values: a template argument, not a user switch.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace ng {
+
+// the squared-distance expression of every builder (knn.hip: knn_dist2, mp_csr.hip: cut_dist2)
+__device__ __forceinline__ float pbc_dist2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
+
+struct DispOpen {
+  static constexpr bool periodic = false;
+  __device__ __forceinline__ void load(const float*, int) {}
+  __device__ __forceinline__ void operator()(float qx, float qy, float qz, float cx, float cy, float cz, float& dx, float& dy,
+                                             float& dz) const {
+    dx = cx - qx; dy = cy - qy; dz = cz - qz;
+  }
+};
+
+struct DispOrtho {
+  static constexpr bool periodic = true;
+  float lx, ly, lz, ix, iy, iz;
+  __device__ __forceinline__ void load(const float* box, int frame) {
+    const float* b = box + (int64_t)frame * 9;
+    lx = b[0]; ly = b[4]; lz = b[8];
+    ix = 1.0f / lx; iy = 1.0f / ly; iz = 1.0f / lz;
+  }
+  __device__ __forceinline__ void operator()(float qx, float qy, float qz, float cx, float cy, float cz, float& dx, float& dy,
+                                             float& dz) const {
+    dx = cx - qx; dy = cy - qy; dz = cz - qz;
+    dx = fmaf(-lx, rintf(dx * ix), dx);
+    dy = fmaf(-ly, rintf(dy * iy), dy);
+    dz = fmaf(-lz, rintf(dz * iz), dz);
+  }
+};
+
+struct DispTric {
+  static constexpr bool periodic = true;
+  float ax, bx, by, cx, cy, cz, iax, iby, icz, h2;
+  __device__ __forceinline__ void load(const float* box, int frame) {
+    const float* b = box + (int64_t)frame * 9;
+    ax = b[0]; bx = b[3]; by = b[4]; cx = b[6]; cy = b[7]; cz = b[8];
+    iax = 1.0f / ax; iby = 1.0f / by; icz = 1.0f / cz;
+    // perpendicular widths: V / |b x c|, V / |c x a| = by cz / |(cy, cz)|, V / |a x b| = cz
+    const float v = ax * by * cz;
+    const float bcx = by * cz, bcy = -bx * cz, bcz = bx * cy - by * cx;
+    const float wa = v / sqrtf(bcx * bcx + bcy * bcy + bcz * bcz);
+    const float wb = by * cz / sqrtf(cy * cy + cz * cz);
+    const float w = fminf(fminf(wa, wb), cz);
+    h2 = 0.25f * w * w;
+  }
+  __device__ __forceinline__ void operator()(float qx, float qy, float qz, float px, float py, float pz, float& dx, float& dy,
+                                             float& dz) const {
+    dx = px - qx; dy = py - qy; dz = pz - qz;
+    float s = rintf(dz * icz);
+    dx = fmaf(-s, cx, dx); dy = fmaf(-s, cy, dy); dz = fmaf(-s, cz, dz);
+    s = rintf(dy * iby);
+    dx = fmaf(-s, bx, dx); dy = fmaf(-s, by, dy);
+    s = rintf(dx * iax);
+    dx = fmaf(-s, ax, dx);
+    float best = pbc_dist2(dx, dy, dz);
+    if (best >= h2) {
+      const float ox = dx, oy = dy, oz = dz;
+      for (int k = -1; k <= 1; ++k)
+        for (int j = -1; j <= 1; ++j)
+          for (int i = -1; i <= 1; ++i) {
+            const float ex = fmaf((float)k, cx, fmaf((float)j, bx, fmaf((float)i, ax, ox)));
+            const float ey = fmaf((float)k, cy, fmaf((float)j, by, oy));
+            const float ez = fmaf((float)k, cz, oz);
+            const float e2 = pbc_dist2(ex, ey, ez);
+            if (e2 < best) { best = e2; dx = ex; dy = ey; dz = ez; }
+          }
+    }
+  }
+};
+
+}  // namespace ng

@@ -67,6 +67,8 @@ class GraphBatch:
     row_ptr = None
     positions = None   # [G, n, 3] Angstrom, and the distance scale: set by frames_to_batch / frames_to_batch_cutoff
     scale = None
+    box = None         # [G, 9] lattice vectors on the device (nmrgnn_amd.pbc) when the lists were built in periodic boxes
+    box_triclinic = False
 
     _ctx = None        # library context for the list builders; None = the device's shared one (BatchPrefetcher sets its own)
 
@@ -282,7 +284,8 @@ class GraphBatch:
         its output: no reference cycle)"""
         csc_ptr, csc_edge = self.csc()
         return (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
-                self.edges.detach(), self.row_ptr, getattr(self, "row_of", None), csc_ptr, csc_edge)
+                self.edges.detach(), self.row_ptr, getattr(self, "row_of", None), csc_ptr, csc_edge, self.box,
+                int(self.box_triclinic))
 
     def as_tuple(self):
         if self.is_csr:
@@ -388,7 +391,7 @@ def _positions_grad(state, dedges):
     import ctypes as C
     from . import _lib
     from ._lib import ptr
-    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, row_of, csc_ptr, csc_edge = state
+    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, row_of, csc_ptr, csc_edge, box, tric = state
     ctx = ctx or _lib.get_context(device.index)
     dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
     if dd.numel() != edges.numel():
@@ -396,7 +399,17 @@ def _positions_grad(state, dedges):
     dpos = torch.empty_like(pos)
     with torch.cuda.device(device):
         st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        if is_csr:
+        if box is not None:             # minimum-image vectors along the edges (csrc/pbc.cuh)
+            n = pos.shape[-2]
+            if is_csr:
+                ctx.check(ctx.lib.ng_positions_grad_csr_pbc(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist),
+                                                            ptr(row_of), ptr(dd), scale, ptr(csc_ptr), ptr(csc_edge), n,
+                                                            ptr(box), tric, ptr(dpos)), "ng_positions_grad_csr_pbc")
+            else:
+                ctx.check(ctx.lib.ng_positions_grad_pbc(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale,
+                                                        ptr(csc_ptr), ptr(csc_edge), n, ptr(box), tric, ptr(dpos)),
+                          "ng_positions_grad_pbc")
+        elif is_csr:
             ctx.check(ctx.lib.ng_positions_grad_csr(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist),
                                                     ptr(row_of), ptr(dd), scale, ptr(csc_ptr), ptr(csc_edge), ptr(dpos)),
                       "ng_positions_grad_csr")
@@ -439,17 +452,40 @@ def _positions_batch(frames, build):
     return batch
 
 
-def frames_to_batch(atoms, frames, neighbor_number=16, scale=0.1, device=None):
+def _frame_count(frames):
+    shape = tuple(frames.shape) if hasattr(frames, "shape") else np.shape(frames)
+    return 1 if len(shape) == 2 else int(shape[0])
+
+
+def _host_box(box, frames):
+    """None, or (vectors [G, 9] float32, triclinic flag, smallest perpendicular widths [G]): validated on the host"""
+    if box is None:
+        return None
+    from .pbc import prepare
+    return prepare(box, _frame_count(frames))
+
+
+def _device_box(pbc, device):
+    return torch.from_numpy(pbc[0]).to(device) if pbc is not None else None
+
+
+def frames_to_batch(atoms, frames, neighbor_number=16, scale=0.1, device=None, box=None):
     """Build the graphs of ``G`` trajectory frames on the GPU (ng_knn_graph) and return them as one
     device-resident GraphBatch: ``atoms`` [n,C] one-hot (shared by all frames), ``frames`` [G,n,3]
     positions in Angstrom.  Same conventions as :func:`nmrgnn_amd.structure.knn_graph`.
     The batch keeps the positions and ``scale`` (``GraphBatch.positions_grad``); with ``frames.requires_grad`` (and
     grad mode on) its ``edges`` carry a grad_fn back to ``frames``, so a loss of ``model(batch)`` differentiates to
-    ``frames.grad`` — at fixed neighbour lists, as TensorFlow's tape does through the reference's graph."""
-    return _positions_batch(frames, lambda f: _frames_to_batch(atoms, f, neighbor_number, scale, device))
+    ``frames.grad`` — at fixed neighbour lists, as TensorFlow's tape does through the reference's graph.
+
+    ``box``: periodic boxes under the minimum-image convention (csrc/pbc.cuh), ``(a, b, c, alpha, beta, gamma)`` in
+    Angstrom and degrees, [6] for every frame or [G, 6] one per frame (nmrgnn_amd.pbc: orthorhombic and reduced triclinic
+    boxes).  Positions may lie anywhere; nothing is wrapped.  The batch keeps the box (``GraphBatch.box``) and its
+    gradient uses the minimum-image vector of each edge.  None: open boundaries, as before."""
+    pbc = _host_box(box, frames)
+    return _positions_batch(frames, lambda f: _frames_to_batch(atoms, f, neighbor_number, scale, device, pbc))
 
 
-def _frames_to_batch(atoms, frames, neighbor_number, scale, device):
+def _frames_to_batch(atoms, frames, neighbor_number, scale, device, pbc=None):
     import ctypes as C
     from . import _lib
     from ._lib import ptr
@@ -468,26 +504,37 @@ def _frames_to_batch(atoms, frames, neighbor_number, scale, device):
     inv = torch.empty(G * n, dtype=torch.float32, device=device)
     ctx = _lib.get_context(device.index)
     st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    ctx.check(ctx.lib.ng_knn_graph(ctx.handle, st, G, n, K, float(scale), ptr(pos), ptr(nlist), ptr(edges),
-                                   ptr(inv)), "ng_knn_graph")
+    box = _device_box(pbc, device)
+    if box is None:
+        ctx.check(ctx.lib.ng_knn_graph(ctx.handle, st, G, n, K, float(scale), ptr(pos), ptr(nlist), ptr(edges),
+                                       ptr(inv)), "ng_knn_graph")
+    else:
+        ctx.check(ctx.lib.ng_knn_graph_pbc(ctx.handle, st, G, n, K, float(scale), ptr(pos), ptr(box), int(pbc[1]),
+                                           ptr(nlist), ptr(edges), ptr(inv)), "ng_knn_graph_pbc")
     ptrs = np.arange(G + 1, dtype=np.int64) * n
     # n > K: every atom has K real neighbours, no padded slot -> the compute-side list IS the list
     b = GraphBatch(at.repeat(G, 1) if G > 1 else at, nlist, edges, inv, graph_ptr=ptrs, device=device, validate=False,
                    nlist_c=nlist if n > K else None)
     b.positions, b.scale = pos, float(scale)
+    if box is not None:
+        b.box, b.box_triclinic = box, bool(pbc[1])
     return b
 
 
-def frames_to_batch_cutoff(atoms, frames, cutoff=4.0, scale=0.1, device=None):
+def frames_to_batch_cutoff(atoms, frames, cutoff=4.0, scale=0.1, device=None, box=None):
     """Distance-cutoff graphs of ``G`` trajectory frames, built on the GPU (ng_cutoff_count / ng_cutoff_fill) and
     returned as one device-resident CSR GraphBatch: every other atom of the same frame closer than ``cutoff``
     (Angstrom) is a neighbour, rows in ascending neighbour index, distances x ``scale`` (nm), inv_degree by the
     reference's rule (library.py:115-116).  Variable degree: BASELINE configs[4].
-    Positions and gradients as in :func:`frames_to_batch`."""
-    return _positions_batch(frames, lambda f: _frames_to_batch_cutoff(atoms, f, cutoff, scale, device))
+    Positions, gradients and ``box`` as in :func:`frames_to_batch`; with a box, ``cutoff`` must stay below half the
+    smallest perpendicular width of every frame's box (one image per neighbour)."""
+    pbc = _host_box(box, frames)
+    if pbc is not None and len(pbc[2]) and not float(cutoff) < 0.5 * float(pbc[2].min()):
+        raise ValueError(f"cutoff {cutoff} must be below half the smallest box width ({0.5 * float(pbc[2].min()):.6g})")
+    return _positions_batch(frames, lambda f: _frames_to_batch_cutoff(atoms, f, cutoff, scale, device, pbc))
 
 
-def _frames_to_batch_cutoff(atoms, frames, cutoff, scale, device):
+def _frames_to_batch_cutoff(atoms, frames, cutoff, scale, device, pbc=None):
     import ctypes as C
     from . import _lib
     from ._lib import ptr
@@ -504,7 +551,12 @@ def _frames_to_batch_cutoff(atoms, frames, cutoff, scale, device):
     with torch.cuda.device(device):
         st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         deg = torch.empty(G * n, dtype=torch.int32, device=device)
-        ctx.check(ctx.lib.ng_cutoff_count(ctx.handle, st, G, n, float(cutoff), ptr(pos), ptr(deg)), "ng_cutoff_count")
+        box = _device_box(pbc, device)
+        if box is None:
+            ctx.check(ctx.lib.ng_cutoff_count(ctx.handle, st, G, n, float(cutoff), ptr(pos), ptr(deg)), "ng_cutoff_count")
+        else:
+            ctx.check(ctx.lib.ng_cutoff_count_pbc(ctx.handle, st, G, n, float(cutoff), ptr(pos), ptr(box), int(pbc[1]),
+                                                  ptr(deg)), "ng_cutoff_count_pbc")
         row_ptr = torch.empty(G * n + 1, dtype=torch.int32, device=device)
         ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, G * n, ptr(deg), ptr(row_ptr)), "ng_exclusive_scan_i32")
         # the one host synchronisation: the list length sizes the buffers.  Summed in int64 — the device scan is int32
@@ -516,10 +568,17 @@ def _frames_to_batch_cutoff(atoms, frames, cutoff, scale, device):
         dist = torch.empty(nnz, dtype=torch.float32, device=device)
         row_of = torch.empty(nnz, dtype=torch.int32, device=device)
         inv = torch.empty(G * n, dtype=torch.float32, device=device)
-        ctx.check(ctx.lib.ng_cutoff_fill_rows(ctx.handle, st, G, n, float(cutoff), float(scale), ptr(pos), ptr(row_ptr),
-                                              ptr(col), ptr(dist), ptr(inv), ptr(row_of)), "ng_cutoff_fill_rows")
+        if box is None:
+            ctx.check(ctx.lib.ng_cutoff_fill_rows(ctx.handle, st, G, n, float(cutoff), float(scale), ptr(pos), ptr(row_ptr),
+                                                  ptr(col), ptr(dist), ptr(inv), ptr(row_of)), "ng_cutoff_fill_rows")
+        else:
+            ctx.check(ctx.lib.ng_cutoff_fill_rows_pbc(ctx.handle, st, G, n, float(cutoff), float(scale), ptr(pos), ptr(box),
+                                                      int(pbc[1]), ptr(row_ptr), ptr(col), ptr(dist), ptr(inv), ptr(row_of)),
+                      "ng_cutoff_fill_rows_pbc")
     ptrs = np.arange(G + 1, dtype=np.int64) * n
     b = GraphBatch.from_csr(at.repeat(G, 1) if G > 1 else at, row_ptr, col, dist, inv, graph_ptr=ptrs, device=device,
                             validate=False, row_of=row_of)
     b.positions, b.scale = pos, float(scale)
+    if box is not None:
+        b.box, b.box_triclinic = box, bool(pbc[1])
     return b

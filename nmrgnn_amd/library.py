@@ -124,7 +124,7 @@ def check_peaks(atoms, peaks, cutoff_sigma=4, warn_sigma=2.5):
     return confident
 
 
-def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_number=16):
+def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_number=16, box=None):
     """Chemical-shift restraint of one structure: ``(energy, forces)`` with
 
         energy = sum_i w_i (delta_pred_i - delta_exp_i)^2          ppm^2, a 0-d device tensor
@@ -138,14 +138,17 @@ def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_num
 
     The forces are the gradient at FIXED neighbour lists: where an atom's K nearest neighbours change between two
     structures the energy and the forces jump (the model itself is discontinuous there, as the reference is).  The call
-    overwrites the engine's parameter gradient buffer (``engine.params.grad``) as a side effect."""
+    overwrites the engine's parameter gradient buffer (``engine.params.grad``) as a side effect.
+
+    ``box`` ``(a, b, c, alpha, beta, gamma)``: a periodic box under the minimum-image convention, as ``frames_to_batch``
+    takes it; the forces are then those of ``model(frames_to_batch(atoms, pos, box=box))``."""
     import torch
     from .graph import frames_to_batch
     if model.engine is None:
         model.build(int(np.asarray(atoms).shape[-1]) if not isinstance(atoms, torch.Tensor) else int(atoms.shape[-1]))
     eng = model.engine
     pos = positions.detach() if isinstance(positions, torch.Tensor) else positions
-    batch = frames_to_batch(atoms, pos, neighbor_number=neighbor_number, device=eng.device)
+    batch = frames_to_batch(atoms, pos, neighbor_number=neighbor_number, device=eng.device, box=box)
     if batch.G != 1:
         raise ValueError("shift_restraint: one structure [n, 3] at a time")
     y = torch.as_tensor(np.asarray(targets, np.float32) if not isinstance(targets, torch.Tensor) else targets,

@@ -24,19 +24,21 @@ def main():
 def _open_structure(struct_files):
     from .structure import Structure, read_pdb
     first = read_pdb(struct_files[0])
-    frames = list(first.frames)
+    frames, dims = list(first.frames), list(first.dimensions)
     for extra in struct_files[1:]:                  # md.Universe(topology, *trajectory pieces)
         s = read_pdb(extra)
         if s.n_atoms != first.n_atoms:
             raise ValueError(f"{extra}: {s.n_atoms} atoms, but {struct_files[0]} has {first.n_atoms}")
         frames.extend(s.frames)
-    return Structure(first.names, first.resnames, first.resids, first.elements, frames)
+        dims.extend(s.dimensions)
+    return Structure(first.names, first.resnames, first.resids, first.elements, frames, dims)
 
 
 def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16, stride=1,
-                   frames_per_batch=32, keep_going=False, device=None, echo=print):
+                   frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False):
     """Predict shifts for every ``stride``-th frame and write the reference's CSV.  Returns the timing
-    buckets in seconds."""
+    buckets in seconds.  ``pbc``: neighbour lists under the minimum-image convention in each frame's box (its CRYST1
+    record); a frame without one is an error."""
     if len(struct_files) == 0:
         raise ValueError('Must pass at least on structure file')
     import torch
@@ -47,6 +49,10 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     model = load_model(model_file, device=device)
     u = _open_structure(struct_files)
     frame_ids = list(range(0, len(u), stride))
+    if pbc:
+        missing = [fr for fr in frame_ids if u.dimensions[fr] is None]
+        if missing:
+            raise ValueError(f"--pbc: frame {missing[0]} has no box (no CRYST1 record, or the 1 Angstrom placeholder)")
     atoms = atoms_onehot(u.elements)
     n = atoms.shape[0]
     model.build(atoms.shape[1])
@@ -58,7 +64,8 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         t = time.perf_counter()
         model.build(atoms.shape[1])
         dev = model.engine.device
-        batch = frames_to_batch(atoms, np.stack([u.frames[fr] for fr in chunk]), neighbor_number, device=dev)
+        box = np.stack([u.dimensions[fr] for fr in chunk]) if pbc else None
+        batch = frames_to_batch(atoms, np.stack([u.frames[fr] for fr in chunk]), neighbor_number, device=dev, box=box)
         torch.cuda.synchronize(dev)
         timing['Structure'] += time.perf_counter() - t
         t = time.perf_counter()
@@ -100,10 +107,11 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
 @click.option('--stride', default=1, help='Stride for reading trajectory, if multiple frames are present')
 @click.option('--frames-per-batch', default=32, help='Frames evaluated per device batch')
 @click.option('--keep-going', is_flag=True, help='Report implausible-shift warnings instead of aborting')
-def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going):
+@click.option('--pbc', is_flag=True, help='Minimum-image neighbour lists in each frame\'s periodic box (CRYST1)')
+def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, pbc):
     '''Predict NMR chemical shifts with specific file'''
     eval_structure(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch,
-                   keep_going, echo=click.echo)
+                   keep_going, echo=click.echo, pbc=pbc)
 
 
 if __name__ == '__main__':

@@ -20,12 +20,16 @@ from .standards import ELEMENTS, load_embeddings
 class Structure:
     """minimal stand-in for the attributes of an MDAnalysis Universe that the path reads"""
 
-    def __init__(self, names, resnames, resids, elements, frames):
+    def __init__(self, names, resnames, resids, elements, frames, dimensions=None):
         self.names = np.asarray(names)
         self.resnames = np.asarray(resnames)
         self.resids = np.asarray(resids)
         self.elements = np.asarray(elements)
         self.frames = [np.asarray(f, dtype=np.float32) for f in frames]   # list of [N,3] Angstrom
+        # per frame: the box (a, b, c, alpha, beta, gamma) of its CRYST1 record as float64 [6], or None (no box)
+        self.dimensions = list(dimensions) if dimensions is not None else [None] * len(self.frames)
+        if len(self.dimensions) != len(self.frames):
+            raise ValueError(f"{len(self.dimensions)} boxes for {len(self.frames)} frames")
         self.frame = 0
 
     @property
@@ -53,16 +57,32 @@ def _element_from(line, name):
     return el
 
 
+def _cryst1(line):
+    """the box of a CRYST1 record, or None for the 1 Angstrom cube that NMR and other box-less entries carry (as
+    MDAnalysis reads it)"""
+    dims = np.array([float(line[6:15]), float(line[15:24]), float(line[24:33]), float(line[33:40]), float(line[40:47]),
+                     float(line[47:54])])
+    if np.array_equal(dims, [1.0, 1.0, 1.0, 90.0, 90.0, 90.0]):
+        return None
+    return dims
+
+
 def read_pdb(path):
-    """ATOM/HETATM records; every MODEL becomes a frame (atom order/identity taken from the first)."""
+    """ATOM/HETATM records; every MODEL becomes a frame (atom order/identity taken from the first).  A CRYST1 record
+    gives the box of the frames that follow it until the next CRYST1 (``Structure.dimensions``)."""
     opener = gzip.open if str(path).endswith(".gz") else open
     names, resnames, resids, elements = [], [], [], []
-    frames, cur = [], []
+    frames, cur, dims = [], [], []
+    box = None
     first_done = False
     with opener(path, "rt") as f:
         for line in f:
             rec = line[:6]
-            if rec in ("ATOM  ", "HETATM"):
+            if rec == "CRYST1":
+                box = _cryst1(line)
+            elif rec in ("ATOM  ", "HETATM"):
+                if not cur:
+                    dims.append(box)
                 cur.append((float(line[30:38]), float(line[38:46]), float(line[46:54])))
                 if not first_done:
                     name = line[12:16].strip()
@@ -81,10 +101,11 @@ def read_pdb(path):
     if cur:
         frames.append(cur)
     n = len(names)
-    frames = [np.asarray(fr, np.float32) for fr in frames if len(fr) == n]
-    if not frames:
+    keep = [k for k, fr in enumerate(frames) if len(fr) == n]
+    if not keep:
         raise ValueError(f"no atoms found in {path}")
-    return Structure(names, resnames, resids, elements, frames)
+    return Structure(names, resnames, resids, elements, [np.asarray(frames[k], np.float32) for k in keep],
+                     [dims[k] for k in keep])
 
 
 def knn_graph(positions, K=16, scale=0.1):
