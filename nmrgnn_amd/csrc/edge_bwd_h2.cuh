@@ -31,11 +31,7 @@ constexpr int HX_IMG_Z = 2 * HX_PIECE_Z;     // 33,792 B
 constexpr int HX_STG = 132;                  // fp32 staging row stride (floats)
 constexpr int HX_MISC_FLOATS = FH * 4 + FTM * 4 + FH;   // sWo4 | sdE | sCen
 constexpr int HX_IMGS = 2 * HX_IMG_Z + 2 * HX_IMG_G;     // two Z-type images (the fp16 pieces freed the room)
-#ifdef HX_STAMP
-constexpr int HX_LDS_BYTES = HX_IMGS + HX_MISC_FLOATS * 4 + 1024;
-#else
-constexpr int HX_LDS_BYTES = HX_IMGS + HX_MISC_FLOATS * 4;
-#endif             // 140,544 of 163,840
+constexpr int HX_LDS_BYTES = HX_IMGS + HX_MISC_FLOATS * 4;   // 140,544 of 163,840
 constexpr int HX_WS = 8;                     // log2 of the W^T scale
 constexpr float HX_WSCALE = (float)(1 << HX_WS), HX_WINV = 1.0f / (float)(1 << HX_WS);
 
@@ -66,7 +62,6 @@ struct EdgeBwdH2Args {
   int part_stride;
   int E;
   int tape_blocked;     // z_save layout: 1 = blocked inside full 32-edge groups (edge_fused.h), 0 = row-major
-  unsigned long long* stamps;
   RangeGuard guard;     // raised when a partial comes out non-finite (an operand left the fp16 range)
   // live-edge view (ng_internal.h: LiveEdges; kernel template LIVE): the rows of this launch are the compacted live
   // slots [row_base, row_base + n_edges) clipped to *n_live; d_eff and the tape are compacted (this segment's part), `de`

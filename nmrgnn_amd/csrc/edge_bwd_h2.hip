@@ -34,17 +34,6 @@
 
 namespace ng {
 
-
-#ifdef HX_STAMP
-#define HX_T(k)                                                                              \
-  do {                                                                                       \
-    if (lane == 0 && (wave & 3) == 0 && titer >= 2 && titer < 6)                             \
-      sStamp[((wave >> 2) * 4 + (titer - 2)) * 16 + (k)] = __builtin_readcyclecounter();     \
-  } while (0)
-#else
-#define HX_T(k)
-#endif
-
 template <bool LIVE>
 __global__ __launch_bounds__(HX_THREADS, 1) void edge_bwd_h2_kernel(EdgeBwdH2Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem_hx[];
@@ -52,10 +41,6 @@ __global__ __launch_bounds__(HX_THREADS, 1) void edge_bwd_h2_kernel(EdgeBwdH2Arg
   float* sWo4 = reinterpret_cast<float*>(smem_hx + HX_IMGS);      // [128][4]
   float* sdE = sWo4 + FH * 4;         // [64][4]
   float* sCen = sdE + FTM * 4;        // [128]
-#ifdef HX_STAMP
-  unsigned long long* sStamp = reinterpret_cast<unsigned long long*>(sCen + FH);   // [2][4][16]
-  int titer = -1;
-#endif
 
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -268,10 +253,6 @@ __global__ __launch_bounds__(HX_THREADS, 1) void edge_bwd_h2_kernel(EdgeBwdH2Arg
   // address VGPR per access site: 21 spills in a kernel that has no register to spare).
   auto tile_body = [&](int64_t tile, auto parity) {
     constexpr int gp = decltype(parity)::value, zp = gp;
-#ifdef HX_STAMP
-    ++titer;
-#endif
-    HX_T(0);
     const bool has_next = tile + gridDim.x < ntiles;
     const int64_t row0n = std::min<int64_t>(tile + gridDim.x, ntiles - 1) * FTM;
     char* IZ = smem_hx + zp * HX_IMG_Z;                             // Z2 -> R
@@ -282,7 +263,6 @@ __global__ __launch_bounds__(HX_THREADS, 1) void edge_bwd_h2_kernel(EdgeBwdH2Arg
     // the two waves of a SIMD (zrt = 0 / 1) take the two independent GEMMs of the phase in opposite order, so that
     // one wave's epilogue (VALU: s', split) runs beside the other's MFMAs
     if (zrt == 0) hx_dw_gemm(accW[2], accB, 4, IZ, GA, kslab, nsl0, lane);
-    HX_T(1);
     {
       float g[16];
       // the wave whose epilogue comes NEXT gets the matrix pipe first (the arbiter otherwise favours the partner,
@@ -296,20 +276,15 @@ __global__ __launch_bounds__(HX_THREADS, 1) void edge_bwd_h2_kernel(EdgeBwdH2Arg
         }
       });
       if (zrt != 0) __builtin_amdgcn_s_setprio(0);
-      HX_T(2);
 #pragma unroll
       for (int r = 0; r < 16; r += 2) hx_sprime2(g[r], g[r + 1], z2r[r], z2r[r + 1]);
       hx_img_write<HX_ROWG>(GB, prg, col0, g);       // G2
     }
     hx_wload(w0, wrs, lane * 16, ((0 * 4 + zk) * 8) * 2 * 1024, 0);
-    HX_T(3);
     if (zrt != 0) hx_dw_gemm(accW[2], accB, 4, IZ, GA, kslab, nsl0, lane);
-    HX_T(4);
     NG_LDS_BARRIER();      // G2, Z1 images complete; every reader of G3 (GA) and Z2 (IZ) is done
-    HX_T(5);
     // ------------------------------------------------------------------ phase C (layer 2)
     if (zrt == 0) hx_dw_gemm(accW[1], accB, 2, IZb, GB, kslab, nsl0, lane);
-    HX_T(6);
     {
       float g[16];
       if (zrt != 0) __builtin_amdgcn_s_setprio(2);
@@ -331,33 +306,24 @@ __global__ __launch_bounds__(HX_THREADS, 1) void edge_bwd_h2_kernel(EdgeBwdH2Arg
       // next tile's Z3 / d / dE (registers dead since the head).  Issued BEHIND the last W^T fragment loads of the tile:
       // memory returns in order, a fragment load queued behind these HBM loads would wait for all of them.
       prefetch(row0n, row0_of(tile, 2));
-      HX_T(7);
 #pragma unroll
       for (int r = 0; r < 16; r += 2) hx_sprime2(g[r], g[r + 1], z1r[r], z1r[r + 1]);
       hx_img_write<HX_ROWG>(GA, prg, col0, g);       // G1
     }
-    HX_T(8);
     if (zrt != 0) hx_dw_gemm(accW[1], accB, 2, IZb, GB, kslab, nsl0, lane);
-    HX_T(9);
     NG_LDS_BARRIER();      // G1, R images complete; every reader of G2 (GB) and Z1 (IZb) is done
-    HX_T(10);
     // ------------------------------------------------------------------ phase D (layer 1) with the NEXT tile's head
     prefetch_z2(row0n);    // unconditional (clamped): no branch around the loads
     head1(row0n, has_next, IZb, on, dn);     // the loop-carried mask / distance now belong to the next tile (R is built)
-    HX_T(11);
     NG_LDS_BARRIER();      // staging complete
-    HX_T(12);
     if (zrt == 0) hx_dw_gemm(accW[0], accB, 0, IZ, GA, kslab, nsl0, lane);
     head2(GB, IZb);
     load_z1(row0n);
-    HX_T(13);
     if (zrt != 0) hx_dw_gemm(accW[0], accB, 0, IZ, GA, kslab, nsl0, lane);
-    HX_T(14);
     NG_LDS_BARRIER();      // every reader of the staging is done; every reader of G1 / R too
     hx_img_write<HX_ROWZ>(IZb, prz, col0, z2r);      // next tile's Z2 pieces over the staging
     hx_wload(w0, wrs, lane * 16, ((1 * 4 + zk) * 8) * 2 * 1024, 0);
     NG_LDS_BARRIER();
-    HX_T(15);
   };
 #pragma unroll 1
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += 2 * (int64_t)gridDim.x) {
@@ -366,11 +332,6 @@ __global__ __launch_bounds__(HX_THREADS, 1) void edge_bwd_h2_kernel(EdgeBwdH2Arg
     tile_body(tile + gridDim.x, std::integral_constant<int, 1>());
   }
 
-#ifdef HX_STAMP
-  __syncthreads();
-  if (blockIdx.x == 3 && tid < 128) a.stamps[tid] = sStamp[tid];
-  __syncthreads();
-#endif
   __syncthreads();
   // ---------------------------------------------------------------------- write this workgroup's partial
   float* part = a.partial + (int64_t)blockIdx.x * a.part_stride;
@@ -513,13 +474,7 @@ int edge_bwd_h2_launch(ng_ctx* ctx, hipStream_t st, int64_t n_edges, int E, cons
     a.de = live.perm ? de : de + e0 * E;
     a.perm = live.perm ? live.perm + e0 : nullptr; a.n_live = live.n_live; a.row_base = e0;
     a.partial = partial + (size_t)sg * grid * part_stride; a.part_stride = part_stride; a.E = E; a.tape_blocked = tape_blocked;
-    a.stamps = nullptr;
     a.guard = guard;
-#ifdef HX_STAMP
-    static unsigned long long* dbg = nullptr;
-    if (!dbg) { hipMalloc(&dbg, 4096); hipMemset(dbg, 0, 4096); }
-    a.stamps = dbg;
-#endif
     ProfScope ps(ctx, st, "edge_bwd_h2");
     if (live.perm)
       hipLaunchKernelGGL(edge_bwd_h2_kernel<true>, dim3(grid), dim3(HX_THREADS), HX_LDS_BYTES, st, a);
@@ -527,24 +482,6 @@ int edge_bwd_h2_launch(ng_ctx* ctx, hipStream_t st, int64_t n_edges, int E, cons
       hipLaunchKernelGGL(edge_bwd_h2_kernel<false>, dim3(grid), dim3(HX_THREADS), HX_LDS_BYTES, st, a);
     NG_HIP(ctx, hipGetLastError());
     if (sg + 1 < nseg) continue;
-#ifdef HX_STAMP
-    {
-      static int calls = 0;
-      if (++calls == 3) {
-        unsigned long long h[256];
-        hipStreamSynchronize(st);
-        hipMemcpy(h, a.stamps, 2048, hipMemcpyDeviceToHost);
-        const int ngrp = 2;      // stamped waves: 0, 4
-        for (int w = 0; w < ngrp; ++w)
-          for (int t = 0; t < 4; ++t) {
-            printf("wave %d tile %d:", 4 * w, t);
-            for (int k = 1; k < 16; ++k) printf(" %5lld", (long long)(h[(w * 4 + t) * 16 + k] - h[(w * 4 + t) * 16 + k - 1]));
-            if (t < 3) printf(" | next %5lld", (long long)(h[(w * 4 + t + 1) * 16] - h[(w * 4 + t) * 16 + 15]));
-            printf("  t0 %lld\n", (long long)(h[(w * 4 + t) * 16] - h[0]));
-          }
-      }
-    }
-#endif
   }
   return NG_OK;
 }

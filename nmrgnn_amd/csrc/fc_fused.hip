@@ -59,9 +59,6 @@ struct FcFwdArgs {
 
 __device__ __forceinline__ float4 act4(int act, const f32x4& a) {
   float4 v = make_float4(a[0], a[1], a[2], a[3]);
-#ifdef FC_ABL_NOACT      // timing experiment: what the activation costs
-  return v;
-#endif
   if (act == NG_ACT_SOFTPLUS) {
     v.x = softplus_f(v.x); v.y = softplus_f(v.y); v.z = softplus_f(v.z); v.w = softplus_f(v.w);
   } else if (act != NG_ACT_NONE) {
@@ -83,10 +80,6 @@ __device__ __forceinline__ void fc_unit2(const float* wf, const float* __restric
   }
   acc0 = f32x4{bias.x, bias.y, bias.z, bias.w};
   acc1 = acc0;
-#ifdef FC_ABL_NOMFMA     // timing experiment: the matrix products removed (operands still read)
-  acc0[0] += xa[0].x + xa[1].y + xa[2].z + xa[3].w + wf[0]; acc1[0] += xb[0].x + xb[1].y + xb[2].z + xb[3].w;
-  return;
-#endif
 #pragma unroll
   for (int T = 0; T < 4; ++T) {
     acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[4 * T + 0], xa[T].x, acc0, 0, 0, 0);
@@ -131,11 +124,7 @@ __device__ __forceinline__ void fc_fwd_tile_f32(const FcFwdArgs& a, int64_t row0
         const float4 xo = *reinterpret_cast<const float4*>(Xin + r * FC_LD + col);
         const float4 y = make_float4(s.x + xo.x, s.y + xo.y, s.z + xo.z, s.w + xo.w);
         *reinterpret_cast<float4*>(Xout + r * FC_LD + col) = y;
-#ifndef FC_ABL_NOSTORE
         if (a.p.y[l])
-#else
-        if (a.p.y[l] && a.N < 0)
-#endif
         {
           const int64_t row = row0 + r;
           *reinterpret_cast<float4*>(row < a.N ? a.p.y[l] + row * FC_F + col : a.dummy + col) = y;
@@ -240,10 +229,10 @@ __device__ __forceinline__ void fc_fwd_repair(const FcFwdArgs& a, int64_t tile, 
 }
 
 // ---- the piece body (round 4): every product as three v_mfma_f32_16x16x32_f16 on two-fp16-piece operands -----------
-// The f32-input MFMAs were 24 us of the forward's 71 and 44 of the backward's 112 (-DFC_ABL_NOMFMA*): 64 instructions
-// of 32 cycles per layer, tile and wave, and an f32-input MFMA stream blocks the SIMD's issue.  Here a layer is 24
-// instructions of 16 cycles.  Operands: weights as pieces of 2^8 W (PK_FC image, fc_h2; out of range -> flag word ->
-// the fp32 body for the whole launch), activations UNSCALED (h2_common.cuh: absolute piece error max(2^-25, 2^-22 |x|))
+// The f32-input MFMAs were 24 us of the forward's 71 and 44 of the backward's 112 (ablation builds, since removed):
+// 64 instructions of 32 cycles per layer, tile and wave, and an f32-input MFMA stream blocks the SIMD's issue.  Here a
+// layer is 24 instructions of 16 cycles.  Operands: weights as pieces of 2^8 W (PK_FC image, fc_h2; out of range ->
+// flag word -> the fp32 body for the whole launch), activations UNSCALED (h2_common.cuh: absolute piece error max(2^-25, 2^-22 |x|))
 // in two row-major planes [64][64 + 8] fp16 that ping-pong between layers.  The lane that produces y[row][4 columns] in
 // layer l produces the same rows and columns in layer l + 1, so the residual input stays in registers (layer 0 reads
 // it from the staged fp32 tile).  An activation at or beyond 65504 (or non-finite) flags the TILE; after its last layer
@@ -587,11 +576,7 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
             s.x -= x.x; s.y -= x.y; s.z -= x.z; s.w -= x.w;
           }
           p = d;
-#ifdef FC_ABL_NOACT_BWD
-          if (act_ != NG_ACT_NONE && a.N < 0) {
-#else
           if (act_ != NG_ACT_NONE) {
-#endif
             p.x *= act_grad_from_out(act_, s.x); p.y *= act_grad_from_out(act_, s.y);
             p.z *= act_grad_from_out(act_, s.z); p.w *= act_grad_from_out(act_, s.w);
           }
@@ -604,11 +589,7 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
         } else {
           accb[H2 ? 0 : l].x += p.x; accb[H2 ? 0 : l].y += p.y; accb[H2 ? 0 : l].z += p.z; accb[H2 ? 0 : l].w += p.w;
         }
-#ifdef FC_ABL_H2_NOP
-        if (H2 && a.N < 0) {
-#else
         if (H2) {
-#endif
           float m = fmaxf(fmaxf(fabsf(p.x), fabsf(p.y)), fmaxf(fabsf(p.z), fabsf(p.w)));
           m = fmaxf(m, fc_ror<8>(m)); m = fmaxf(m, fc_ror<4>(m)); m = fmaxf(m, fc_ror<2>(m)); m = fmaxf(m, fc_ror<1>(m));
           const int ef = (__builtin_bit_cast(int, m) >> 23) & 255;
@@ -637,11 +618,7 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
         // steps.  The P rows carry different scales S_r, so the x operand takes the inverse: x'[r] = x[r] * S_ref / S_r with
         // S_ref the smallest S of the tile (its largest row; ratio <= 1), the step's product goes into a fresh accumulator and
         // is added to the running sums times 1 / S_ref (mp_win_bwd.hip, node kernel: the same scheme).
-#ifdef FC_ABL_H2_NODW
-        if (a.N < 0) {
-#else
         if (!last || pr == 0) {
-#endif
           int sbref = s_wmin[0];
 #pragma unroll
           for (int i = 1; i < 8; ++i) sbref = min(sbref, s_wmin[i]);
@@ -708,10 +685,6 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
           const float bv = xb[ro];
           const float a0 = p0[ro];
           const float a1 = p0[ro + 16];
-#ifdef FC_ABL_NOMFMA_BWD
-          accW[l][0][0] += a0 * bv; accW[l][1][0] += a1 * bv;
-          continue;
-#endif
           accW[l][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, accW[l][0], 0, 0, 0);
           accW[l][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bv, accW[l][1], 0, 0, 0);
         }
@@ -724,9 +697,6 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
         if (H2) {
           // piece body: per row tile three MFMAs per 32-wide step (the last layer's dP has 32 columns: one step); the small
           // products and the leading one in separate accumulators, the row's 2^-8 / S at the end
-#ifdef FC_ABL_H2_NODX
-          if (a.N < 0)
-#endif
 #pragma unroll
           for (int h = 0; h < 2; ++h) {      // one row tile after the other: eight operand registers live, not sixteen
             const char* xr = planes + (16 * (2 * pr + h) + a16) * FC_ROWB + 16 * g4;
@@ -751,10 +721,6 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
           if (T < nT) {
             const float4 xa = *reinterpret_cast<const float4*>(q0 + 16 * T);
             const float4 xb4 = *reinterpret_cast<const float4*>(q1 + 16 * T);
-#ifdef FC_ABL_NOMFMA_BWD
-            c0[0] += xa.x + xa.y + xa.z + xa.w + wb[H2 ? 0 : l][4 * T]; c1[0] += xb4.x + xb4.y + xb4.z + xb4.w;
-            continue;
-#endif
             c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[H2 ? 0 : l][4 * T + 0], xa.x, c0, 0, 0, 0);
             c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[H2 ? 0 : l][4 * T + 0], xb4.x, c1, 0, 0, 0);
             c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wb[H2 ? 0 : l][4 * T + 1], xa.y, c0, 0, 0, 0);

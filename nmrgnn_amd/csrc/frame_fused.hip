@@ -32,19 +32,10 @@ constexpr int FF_XPLANE = FF_ROWS * FF_XROW;   // 16,896
 constexpr int FF_WCHUNK = 2 * 4 * 2 * 2 * 1024; // gx_wchunk(4): [n-block 8][k-step of 16: 2][piece 2][1 KB]
 constexpr float FF_WSCALE = 256.0f, FF_WINV = 1.0f / 256.0f;
 constexpr int FF_GLD = FFW / 2 + 4;            // row stride (floats) of the g tile [32][128]
-constexpr int FF_MAXC = 16;
-#ifndef FF_MAX_TILES
-#define FF_MAX_TILES 512          // batches up to 16384 atoms (above: the per-layer GEMMs have enough rows to fill the chip)
-#endif
-#ifndef FF_RING
-#define FF_RING 16
-#endif
-#ifndef FF_NO_SPLIT
-#define FF_NO_SPLIT 0
-#endif
-#ifndef FF_NB
-#define FF_NB 8
-#endif                    // element columns the head handles
+constexpr int FF_MAXC = 16;                    // element columns the head handles
+constexpr int FF_MAXT = 512;   // tiles: batches up to 16384 atoms (above: the per-layer GEMMs have enough rows to fill the chip)
+constexpr int FF_WRING = 16;                   // weight-fragment ring depth in k-halves (ff_gemm_n)
+constexpr int FF_INFLIGHT = 8;                 // neighbour rows requested ahead (mp_layer_short_kernel)
 
 // image of a [K][n_valid] weight matrix in the layout of pk::gx_img (pack_bodies.cuh) for 256-column tiles, columns
 // n_valid .. 255 zero:  lane (row n = 32 nb + (l&31), k-slot t) = piece_p(2^8 W[k = 32 kt + 16 ks + 8 (l>>5) + t][n])
@@ -102,19 +93,19 @@ __device__ __forceinline__ void ff_gemm_n(f32x16 (&acc)[NJ], const char* __restr
   };
   // One wave per SIMD and one workgroup per CU: nothing covers the L2 round trip of a fragment (~0.6-1 us = 3-5 k-halves
   // of MFMAs) but the wave's own requests in flight.  The kernel has 512 registers per lane to itself, so the ring is
-  // FF_RING k-halves deep (64 registers per 4): with 16, a 256-deep contraction has every fragment requested up front.
-  u32x4 w[FF_RING][NJ][2];
+  // FF_WRING k-halves deep (64 registers per 4): with 16, a 256-deep contraction has every fragment requested up front.
+  u32x4 w[FF_WRING][NJ][2];
 #pragma unroll
-  for (int q = 0; q < FF_RING - 1; ++q) w_request(w[q], q);
+  for (int q = 0; q < FF_WRING - 1; ++q) w_request(w[q], q);
 #pragma unroll
   for (int q = 0; q < 2 * KT; ++q) {
-    if (q + FF_RING - 1 < 2 * KT) w_request(w[(q + FF_RING - 1) % FF_RING], q + FF_RING - 1);
+    if (q + FF_WRING - 1 < 2 * KT) w_request(w[(q + FF_WRING - 1) % FF_WRING], q + FF_WRING - 1);
     u32x4 xb[2];
 #pragma unroll
     for (int p = 0; p < 2; ++p)
       xb[p] = *reinterpret_cast<const u32x4*>(sX + p * XPLANE + l31 * XROW + (16 * q + 8 * half) * 2);
-    if (NJ == 2) mma3_2a(w[q % FF_RING][0], w[q % FF_RING][NJ - 1], xb, acc[0], acc[NJ - 1]);
-    else acc[0] = mma3(w[q % FF_RING][0], xb, acc[0]);
+    if (NJ == 2) mma3_2a(w[q % FF_WRING][0], w[q % FF_WRING][NJ - 1], xb, acc[0], acc[NJ - 1]);
+    else acc[0] = mma3(w[q % FF_WRING][0], xb, acc[0]);
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -239,9 +230,7 @@ __global__ __launch_bounds__(256, 1) void fc_head_short_kernel(FcHeadArgs a) {
         for (int q = 0; q < 4; ++q)
           bias[j][q] = *reinterpret_cast<const float4*>(a.b[l] + std::min(64 * nq + 32 * j + 8 * q + 4 * half, ncol - 4));
     }
-#ifndef FF_SKIP_GEMM
     ff_gemm<FFW / 32>(acc, sX, a.img[l], nq, lane);
-#endif
     ff_repair_rows(acc, xr, a.W[l], l < 3 ? FFW : FFW / 2, sRow, sMask, tid);     // (also the barrier behind the X reads)
     if (l < 3) {
       // x <- softplus(x W + b) + x, kept in registers and re-split into the planes for the next layer
@@ -252,11 +241,7 @@ __global__ __launch_bounds__(256, 1) void fc_head_short_kernel(FcHeadArgs a) {
           const float4 bv = bias[j][q];
           const float bb[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
-#ifdef FF_SKIP_ACT
-          for (int r = 0; r < 4; ++r) xr[j][4 * q + r] += fmaf(acc[j][4 * q + r], FF_WINV, bb[r]);
-#else
           for (int r = 0; r < 4; ++r) xr[j][4 * q + r] += softplus_f(fmaf(acc[j][4 * q + r], FF_WINV, bb[r]));
-#endif
         }
       ff_store_x(sX, xr, nq, lane);
       NG_LDS_BARRIER();
@@ -398,16 +383,12 @@ __global__ __launch_bounds__(256, 1) void mp_layer_short_kernel(MpShortArgs a) {
     }
     const int32_t* nl = CSR ? a.nlist : s_nl;
     const float* ee = CSR ? a.e : s_e;
-    // FF_NB neighbour rows (8 x 16 B each) requested before the first is consumed: the phase is a chain of L2 round trips
+    // FF_INFLIGHT neighbour rows (8 x 16 B each) requested before the first is consumed: the phase is a chain of L2 round trips
     // with one wave per SIMD, and the kernel has the registers (512 per lane) to keep 56-64 loads in flight
-#ifdef FF_SKIP_AGG
-    for (int j0 = p0; j0 < p0; j0 += FF_NB) {
-#else
-    for (int j0 = p0; j0 < p1; j0 += FF_NB) {
-#endif
-      float4 hv[FF_NB][8];
+    for (int j0 = p0; j0 < p1; j0 += FF_INFLIGHT) {
+      float4 hv[FF_INFLIGHT][8];
 #pragma unroll
-      for (int u = 0; u < FF_NB; ++u) {
+      for (int u = 0; u < FF_INFLIGHT; ++u) {
         const int j = j0 + u < p1 ? j0 + u : p1 - 1;
         // lane cc takes the float4 columns cc, cc + 8, ..: the eight lanes of a row read 128 contiguous bytes per load
         // instruction (contiguous 32-column slices per lane made every instruction touch 64 different cache lines)
@@ -416,7 +397,7 @@ __global__ __launch_bounds__(256, 1) void mp_layer_short_kernel(MpShortArgs a) {
         for (int v = 0; v < 8; ++v) hv[u][v] = h4[base + 8 * v];
       }
 #pragma unroll
-      for (int u = 0; u < FF_NB; ++u) {
+      for (int u = 0; u < FF_INFLIGHT; ++u) {
         if (j0 + u < p1) {
 #pragma unroll
           for (int n = 0; n < E; ++n) {
@@ -452,9 +433,7 @@ __global__ __launch_bounds__(256, 1) void mp_layer_short_kernel(MpShortArgs a) {
   for (int j = 0; j < NJ; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-#ifndef FF_SKIP_GEMM
   ff_gemm_n<KF / 32, XROW, NJ>(acc, sX, a.img, cb0, lane);
-#endif
 
   // ---- range repair (file header): rows with non-finite accumulators, recomputed by the whole workgroup in fp32
   {
@@ -517,12 +496,12 @@ __global__ __launch_bounds__(256, 1) void mp_layer_short_kernel(MpShortArgs a) {
 
 bool mp_layer_short_supported(int64_t N, int K, int F, int E) {
   if (sw().mp_layered || sw().gemm_math_fp32) return false;       // the any-shape / strict-fp32 paths were asked for
-  return F == FFW && E >= 1 && E <= 3 && K >= 1 && K <= 32 && N > 0 && N <= (int64_t)FF_ROWS * FF_MAX_TILES;
+  return F == FFW && E >= 1 && E <= 3 && K >= 1 && K <= 32 && N > 0 && N <= (int64_t)FF_ROWS * FF_MAXT;
 }
 
 bool fc_head_short_supported(int64_t N, int F, int L, int C, int act) {
   if (sw().fc_layered || sw().gemm_math_fp32 || sw().head_generic) return false;
-  return F == FFW && L == 4 && C <= FF_MAXC && act == NG_ACT_SOFTPLUS && N > 0 && N <= (int64_t)FF_ROWS * FF_MAX_TILES;
+  return F == FFW && L == 4 && C <= FF_MAXC && act == NG_ACT_SOFTPLUS && N > 0 && N <= (int64_t)FF_ROWS * FF_MAXT;
 }
 
 }  // namespace ng
@@ -588,7 +567,7 @@ static int mp_layer_short_launch(ng_ctx* ctx, void* stream, int64_t N, int K, in
   ProfScope ps(ctx, st, "mp_layer_short");
   // two workgroups per tile (128 output columns each) while that still fits the chip in one round
   const int64_t tiles = cdiv(N, FF_ROWS);
-  const bool split = 2 * tiles <= ctx->num_cu && !FF_NO_SPLIT;
+  const bool split = 2 * tiles <= ctx->num_cu;
   const dim3 grid((unsigned)tiles, split ? 2u : 1u);
 #define NG_MPS(EE, CC)                                                                                               \
   if (split) hipLaunchKernelGGL((mp_layer_short_kernel<EE, CC, 2>), grid, dim3(256), lds, st, a);                     \

@@ -387,11 +387,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_fwdr_kernel(GxArgs a) {
 
   // this thread's slice of an X tile: row tid >> 1, 16 floats at column 16 (tid & 1) of the k-step
   const int xr = tid >> 1, xh = tid & 1;
-#ifdef GX_ABL_XL2      // ablation: every workgroup reads the same 1024 rows of X (L2 hits instead of HBM) — results are wrong
-  const int64_t xrow = std::min<int64_t>(m0 + xr, a.M - 1) & 1023;
-#else
   const int64_t xrow = std::min<int64_t>(m0 + xr, a.M - 1);
-#endif
   const float* xp = a.X + xrow * a.K + 16 * xh;
   const float* sp = GRAD && a.Sin ? a.Sin + xrow * a.K + 16 * xh : nullptr;
   const float gS = GRAD && a.gscale ? a.gscale[0] : 1.0f;          // power of two (gemm_grad_scale)
@@ -435,12 +431,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_fwdr_kernel(GxArgs a) {
   };
   // W^T fragments of the k-half (kt, ks) for this wave's two 32-column blocks
   auto w_request = [&](u32x4 (&wa)[2][2], int i, int ks) {
-#ifdef GX_ABL_WL1      // ablation: every request reads the fragments of k-tile 0 (L1 hits instead of L2) — results are wrong
-    const int ktc = 0;
-    (void)i;
-#else
     const int ktc = kstep(i);
-#endif
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -490,15 +481,6 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_fwdr_kernel(GxArgs a) {
     NG_LDS_BARRIER();
   }
 
-#ifdef GX_ABL_NOEPI    // ablation: the products are formed, nothing is written
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) asm volatile("" ::"v"(acc[j][i][r]));
-  return;
-#endif
   // epilogue: lane holds, for row m = m0 + 32 i + l31, columns n = 256 ct + 32 (2 nq + j) + 8 q + 4 half + (0..3)
   float rsv[4];
 #pragma unroll
@@ -1188,17 +1170,6 @@ static int gg_launch(ng_ctx* ctx, hipStream_t st, GgArgs& a, int E, const char* 
       hipLaunchKernelGGL((mp_gw_kernel<LK, 3, GRAD, 6>), dim3(wgrid), dim3(GW_THREADS), GW_LDS, st, a);
     else
       hipLaunchKernelGGL((mp_gw_kernel<LK, 3, GRAD, 8>), dim3(wgrid), dim3(GW_THREADS), GW_LDS, st, a);
-#ifdef GW_STAMP
-    if (getenv("NG_GW_STAMP")) {
-      unsigned long long h[64];
-      (void)hipStreamSynchronize(st);
-      (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(gw_stamps), sizeof(h));
-      fprintf(stderr, "gw %s: stage %llu setup %llu dma0 %llu gather0 %llu loop %llu epi %llu | steps", tag, h[1] - h[0], h[2] - h[1], h[3] - h[2],
-              h[4] - h[3], h[5] - h[4], h[6] - h[5]);
-      for (int i = 8; i < 23; ++i) fprintf(stderr, " %llu", h[i + 1] - h[i]);
-      fprintf(stderr, "\n");
-    }
-#endif
     NG_HIP(ctx, hipGetLastError());
   }
   ProfScope ps(ctx, st, "mp_gg_range_fallback");

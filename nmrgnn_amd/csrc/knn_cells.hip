@@ -35,9 +35,7 @@ __device__ __forceinline__ int kc_coord(float x, float o, float inv_l, int n) {
 
 // ---- 1. bounding box (KC_BOX_BLOCKS partial boxes per frame), then the grid of every frame -----------------------------
 constexpr int KC_BOX_BLOCKS = 64;
-#ifndef KC_EDGE
-#define KC_EDGE 0.50f
-#endif
+constexpr float KC_CELL = 0.50f;
 
 __device__ __forceinline__ void kc_box_reduce(float (&lo)[3], float (&hi)[3], float (*red)[16]) {
 #pragma unroll
@@ -76,10 +74,10 @@ __global__ __launch_bounds__(64) void kc_grid_kernel(int n, int K, int cap, cons
     // mean density of the box (a protein does not fill its box: the true local density is higher, the cells then hold more
     // atoms than aimed for — slower, never wrong)
     const float rho = (float)n / (ex * ey * ez);
-    // cell edge = KC_EDGE (K / rho)^(1/3) = 0.8 x the radius of the sphere that holds K atoms at that density: most queries
+    // cell edge = KC_CELL (K / rho)^(1/3) = 0.8 x the radius of the sphere that holds K atoms at that density: most queries
     // settle after the second shell (125 cells, ~8 K candidates).  Measured per 110,800-atom frame: 0.40 -> 235 us, 0.50 ->
     // 202, 0.60 -> 232, 0.72 (one shell for an interior atom, but a wave of 64 queries always has one that needs two) -> 320
-    float l = KC_EDGE * cbrtf((float)K / rho);
+    float l = KC_CELL * cbrtf((float)K / rho);
     int nx, ny, nz;
     for (;;) {
       nx = (int)fminf(ex / l, 4.0e6f) + 1; ny = (int)fminf(ey / l, 4.0e6f) + 1; nz = (int)fminf(ez / l, 4.0e6f) + 1;
@@ -248,7 +246,7 @@ __global__ __launch_bounds__(64) void kp_grid_kernel(int G, int n, int K, int ca
   const float bcx = g.by * g.cz, bcy = -g.bx * g.cz, bcz = g.bx * g.cy - g.by * g.cx;
   const float wa = v / sqrtf(bcx * bcx + bcy * bcy + bcz * bcz), wb = g.by * g.cz / sqrtf(g.cy * g.cy + g.cz * g.cz), wc = g.cz;
   // the cell edge of the open grid at the box's density (a filled box: the density is the true one)
-  float l = KC_EDGE * cbrtf((float)K * v / (float)n);
+  float l = KC_CELL * cbrtf((float)K * v / (float)n);
   int nx = 1, ny = 1, nz = 1;
   for (int it = 0; it < 256; ++it) {      // bounded: a box the host would refuse (NaN widths) ends as one cell
     nx = max((int)fminf(wa / l, 4.0e6f), 1); ny = max((int)fminf(wb / l, 4.0e6f), 1); nz = max((int)fminf(wc / l, 4.0e6f), 1);

@@ -30,13 +30,6 @@ typedef dma_i4 gw_i4;
 __device__ __forceinline__ gw_i4 gw_rsrc(const void* p, unsigned bytes) { return dma_rsrc(p, bytes); }
 __device__ __forceinline__ void gw_dma(gw_i4 rs, const void* lds_dst, int voff, int soff) { lds_dma16(rs, lds_dst, voff, soff); }
 
-#ifdef GW_STAMP
-__device__ unsigned long long gw_stamps[64];
-#define GW_T(i) do { if (blockIdx.x == 300 && threadIdx.x == 0) gw_stamps[i] = __builtin_readcyclecounter(); } while (0)
-#else
-#define GW_T(i) do { } while (0)
-#endif
-typedef float gw_f2 __attribute__((ext_vector_type(2)));
 typedef float gw_f4 __attribute__((ext_vector_type(4)));
 constexpr int GW_THREADS = 256, GW_BM = 256, GW_WROWS = 320;
 constexpr int GW_WINB = (GW_WROWS + 1) * 64;                             // one window buffer: 16 columns of 320 rows + one row of zeros
@@ -65,7 +58,6 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
   const int F = a.F, NK = F / 16;
   const int64_t m0 = (int64_t)blockIdx.x * GW_BM;
 
-  GW_T(0);
   // ---- the tile's entries into LDS: thread r stages row m0 + r (raw source index first), lowest / highest source on the way
   const int64_t srow = m0 + tid;
   const bool sval = srow < a.M;
@@ -146,7 +138,6 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
       srec[q].x = __builtin_bit_cast(float, winok ? ((sidx - wlo) * 64) | ((((sidx - wlo) >> 2) & 3) << 4) : sidx * (F * 4));
     }
   }
-  GW_T(1);
   // ---- this lane's two rows (row b was staged by the lane pair's half b)
   int64_t mrow[2];
   bool valid[2];
@@ -199,15 +190,11 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
 
   const __amdgpu_buffer_rsrc_t rsG =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.G), 0, (unsigned)(a.M * a.F * 4), 0x00020000);
-  GW_T(2);
   const gw_i4 dmaG = gw_rsrc(a.G, (unsigned)(a.M * a.F * 4));
   const gw_i4 dmaW = gw_rsrc(a.Wimg, (unsigned)((int64_t)(F / 32) * E * WCHUNK));
 
   // W fragments of step (kk, n) -> ring slot n: 16 instructions of 1 KB, 4 per wave
   auto req_w = [&](int kk, int n) __attribute__((always_inline)) {
-#ifdef GW_ABL_NOWDMA
-    if (kk > 0) return;
-#endif
     const int u = kk >> 1, ks = kk & 1;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -219,9 +206,6 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
   // window of k-step kk -> win[kk & 1]: rows wlo .. wlo + 319, 64 bytes each; 20 instructions of 1 KB (16 rows), 5 per wave.
   // The row is part of the LANE offset, which the buffer bounds check covers: rows past the end of the array read as zeros.
   auto req_win = [&](int kk) __attribute__((always_inline)) {
-#ifdef GW_ABL_NOWINDMA
-    if (kk > 1) return;
-#endif
     char* dst = win + (kk & 1) * GW_WINB;
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
@@ -300,23 +284,11 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
       constexpr int T = decltype(Tc)::value;
       const float4& rc = rec[(T + 1) % 3][b];
       const float w1 = n == 0 ? rc.y : (n == 1 ? rc.z : rc.w);
-#ifdef GW_PK
-      const gw_f2 ww = {w1, w1};
-#pragma unroll
-      for (int hq = 0; hq < 2; ++hq)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          gw_f2 p = {s[b][n][4 * hq + 2 * u], s[b][n][4 * hq + 2 * u + 1]};
-          p = __builtin_elementwise_fma(ww, gw_f2{val[(T + 1) % 2][b][hq][2 * u], val[(T + 1) % 2][b][hq][2 * u + 1]}, p);
-          s[b][n][4 * hq + 2 * u] = p[0]; s[b][n][4 * hq + 2 * u + 1] = p[1];
-        }
-#else
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         s[b][n][t] = fmaf(w1, val[(T + 1) % 2][b][0][t], s[b][n][t]);
         s[b][n][4 + t] = fmaf(w1, val[(T + 1) % 2][b][1][t], s[b][n][4 + t]);
       }
-#endif
     };
     auto slot = [&](auto Tc, int t, int kk, float (&s)[2][E][8], bool on = true) __attribute__((always_inline)) {
       slot_loads(Tc, t, kk, on);
@@ -406,7 +378,6 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
     if (WIN) { req_win(0); if (NK > 1) req_win(1); }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     NG_LDS_BARRIER();
-    GW_T(3);
     zero(sums);
     const int nslots = wdmax + 2;            // slots a gather needs (the stream is three stages deep)
     stream_reset();
@@ -414,10 +385,8 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
     spill_entries(0, 0, wdmax, sums);
     split(sums, X);
     NG_LDS_BARRIER();      // window(2) goes where window(0) is: not before every wave has finished the gather above
-    GW_T(4);
 #pragma unroll 1
     for (int kk = 0; kk < NK; ++kk) {
-      if (kk < 4) GW_T(8 + 4 * kk);
       // top: X = operand of k-step kk, its sums still in `sums`; W(kk, 0) landed, W(kk, 1) requested; window(kk + 1) landed
       store_a(kk, sums);
       zero(sums);
@@ -442,10 +411,8 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
         };
         // MFMA i of a group: pieces (l h, h l, h h) on the accumulators of row blocks 0 and 1 alternately
         auto mma1 = [&](const u32x4 (&w)[2], int j, int i) __attribute__((always_inline)) {
-#ifndef GW_ABL_NOMFMA
           const int b = i & 1, pw = i < 2 ? 1 : 0, px = (i >> 1) == 1 ? 1 : 0;
           acc[b][j] = mfma_f16(w[pw], X[b][n][px], acc[b][j]);
-#endif
         };
         wread(0, wa[0]);
 #pragma unroll
@@ -453,12 +420,7 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
           __builtin_amdgcn_sched_barrier(0);
           if (j + 1 < 8) wread(j + 1, wa[(j + 1) & 1]);
           const int t = SL * n + j;
-#ifdef GW_ABL_NOGATHER
-          constexpr bool gather_on = false;
-#else
-          constexpr bool gather_on = true;
-#endif
-          if (gather_on && j < SL) {
+          if (j < SL) {
             // this slot's requests, then six times (one MFMA, eight FMAs of entry t - 2), each pinned: left to itself the
             // scheduler pulls several slots' worth of loads to the front and spills ~1 KB per lane
             const int T6 = t % 6;       // a constant after unrolling: the rotation index folds
@@ -490,9 +452,7 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
           __builtin_amdgcn_sched_barrier(0);
         }
         if (n == E - 1) {
-#ifndef GW_ABL_NOGATHER
           if (more && nslots > 3 * SL) stream_plain(3 * SL, nslots, kk + 1, sums);
-#endif
           if (kk + 1 < NK) spill_entries(kk + 1, 0, wdmax, sums);
         }
         if (n == E - 1 && kk + 1 < NK) split(sums, X);
@@ -506,7 +466,6 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         NG_LDS_BARRIER();
-        if (kk < 4) GW_T(9 + 4 * kk + n);
       }
     }
   };
@@ -517,7 +476,6 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
   // range check happen in that layout; the 64-column chunk of the wave's 32 rows then turns through a wave-private piece of
   // LDS (the loop's last barrier has released all of it) so that 16 lanes read / write 256 contiguous bytes of one row
   // (row-per-lane 16-byte accesses made the residual loads and the stores 56-78k of a tile's 390k cycles: store-issue-bound)
-  GW_T(5);
   constexpr int EPROW = 272;                                  // 64 columns + 16 B: b128 rows conflict-free
   char* const ep = smem_gw + wave * (32 * EPROW);
   const int rr = lane >> 4, cc = lane & 15;
@@ -571,5 +529,4 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
       }
     }
   }
-  GW_T(6);
 }

@@ -20,7 +20,6 @@
 // lie inside takes them from memory instead (same sums, same order).  Only the window change is a workgroup event.
 // Per atom the entries are added in list order and the k-steps in order: results agree with mp_win16.hip to rounding.
 #include <algorithm>
-#include <cstdio>
 
 #include "mfma_gemm.cuh"
 #include "ng_internal.h"
@@ -52,20 +51,7 @@ struct Args {
   RangeGuard guard;
   const unsigned* wflag;
   unsigned wflag_ver;
-#ifdef WV_STAMP
-  unsigned long long* stamps;
-#endif
 };
-#ifdef WV_STAMP
-// [group 0..1][micro-tile 0..1][wave][slot]
-#define WV_T(k) do { if (a.stamps && blockIdx.x == 3 && lane == 0) a.stamps[(((int)((g0 - A0) / GROUP) * 2 + i) * NWV + wave) * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
-#define WV_G(k) do { if (a.stamps && blockIdx.x == 3 && lane == 0) a.stamps[4 * NWV * 8 + ((int)((g0 - A0) / GROUP) * NWV + wave) * 4 + (k)] = __builtin_readcyclecounter(); } while (0)
-#define WV_GN(k) do { if (a.stamps && blockIdx.x == 3 && lane == 0 && g0 == A0) a.stamps[4 * NWV * 8 + (NWV + wave) * 4 + (k)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define WV_T(k) do {} while (0)
-#define WV_G(k) do {} while (0)
-#define WV_GN(k) do {} while (0)
-#endif
 
 // the lists of micro-tile row0 .. row0+15 into the wave's strip; rows past N and pieces past K read as zeros
 __device__ __forceinline__ void lists_dma(const Args& a, char* strip, int64_t row0, int lane) {
@@ -105,11 +91,7 @@ __device__ __forceinline__ void gather(const char* __restrict__ strip, const cha
     for (int s = 0; s < 4; ++s) {
       float4 hr[4];
       if (!GLOBAL) {
-#ifdef WV_ABL_SAMEROW      // timing experiment (wrong results): the sixteen lanes of a read group take sixteen consecutive rows — no bank conflicts
-        const int R = (at + 16 * s + (ci[s] & 0)) & 255;
-#else
         const int R = min(max(ci[s] - wlo, 0), WROWS - 1);
-#endif
         const int sw = (R & 15) << 4;
         const char* row = win + (R << 8);
         hr[0] = *reinterpret_cast<const float4*>(row + (kc0 ^ sw));
@@ -156,9 +138,6 @@ __device__ __forceinline__ void body(const Args& a) {
   const int64_t A1 = std::min<int64_t>(A0 + a.atoms_per_wg, a.N);
   if (A0 >= A1) return;
   const float resf = a.residual ? 1.f : 0.f;
-#ifdef WV_STAMP
-  if (a.stamps && tid == 0) a.stamps[1024 + blockIdx.x] = wall_clock64();
-#endif
 
   if (H2) wimg_dma(wimg, a.Wfrag, wave, lane);
   int64_t have = A0 + (int64_t)wave * MT;          // the micro-tile whose lists the strip holds (or is receiving)
@@ -208,7 +187,6 @@ __device__ __forceinline__ void body(const Args& a) {
             split2_pair(acc[n][8 * u + 2 * j], acc[n][8 * u + 2 * j + 1], hp, lp);
             xh[2 * n + u][j] = hp; xl[2 * n + u][j] = lp;
           }
-      WV_T(3);
       // matrix interval: weights as the A operand out of LDS; per k-step the products of the four column tiles interleaved
       // (consecutive MFMAs on different accumulators)
       f32x4 acc0[4], acc1[4];
@@ -254,7 +232,6 @@ __device__ __forceinline__ void body(const Args& a) {
         }
       rsx = rs;
     }
-    WV_T(4);
     // epilogue: lane (atom, kg) holds out[atom][16 ct + 4 kg .. + 3]
     f32x4 re[4];
     if (a.residual && !fromwin) {
@@ -275,11 +252,9 @@ __device__ __forceinline__ void body(const Args& a) {
         v[ct].z = act_apply(a.act, v[ct].z); v[ct].w = act_apply(a.act, v[ct].w);
       }
     }
-    WV_T(5);
     // the prefetched lists have landed long ago; waiting for them HERE (in front of the stores) keeps the stores' own
     // completion out of the next micro-tile's first wait.  (Not for the micro-tile finished beside a window in flight.)
     if (wait_lists) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WV_T(6);
     if (live) {
       typedef float nt4 __attribute__((ext_vector_type(4)));
       float* po = a.out + row * WF + 4 * kg;
@@ -295,7 +270,6 @@ __device__ __forceinline__ void body(const Args& a) {
           __builtin_nontemporal_store(nt4{v[ct].x, v[ct].y, v[ct].z, v[ct].w}, reinterpret_cast<nt4*>(ps + 16 * ct));
       }
     }
-    WV_T(7);
   };
 
 #pragma unroll 1
@@ -305,12 +279,9 @@ __device__ __forceinline__ void body(const Args& a) {
     const int wlo = (int)wlo64;      // (window kernels are dispatched for N < 2^31)
     const bool more = g0 + GROUP < A1;
     if (g0 == A0) {
-      WV_G(0); WV_G(1);
       win_dma(win, a.h, wlo64, a.N, wave, lane);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      WV_G(2);
       NG_LDS_BARRIER();
-      WV_G(3);
     }
     int64_t drow0 = -1;              // the micro-tile finished behind the group's barrier
     bool dwin = false;
@@ -321,28 +292,23 @@ __device__ __forceinline__ void body(const Args& a) {
     for (int i = 0; i < 2; ++i) {
       const int64_t row0 = g0 + (int64_t)(wave + NWV * i) * MT;
       if (row0 >= A1) break;
-#ifndef WV_NOPRIO
       // the two waves of a SIMD: the older one wins the issue arbitration; in its second micro-tile the younger one is given
       // priority, so that both reach the group's barrier together
       if (i == 1 && wave >= NWV / 2) __builtin_amdgcn_s_setprio(1);
       else __builtin_amdgcn_s_setprio(0);
-#endif
       if (have != row0) {            // (not reached with the prefetch below; kept so that the strip is right by construction)
         lists_dma(a, strip, row0, lane);
         have = row0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      WV_T(0);
       // ---- do the micro-tile's sources lie in the window?
       const bool inwin = sources_in_window(strip, lane, nq, row0, a.N, wlo);
 #pragma unroll
       for (int n = 0; n < E; ++n)
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[n][j] = 0.f;
-      WV_T(1);
       if (inwin) gather<false>(strip, win, a.h, nq, at, kg, wlo, acc);
       else gather<true>(strip, win, a.h, nq, at, kg, wlo, acc);
-      WV_T(2);
       // ---- the strip is free: the lists of this wave's next micro-tile travel beside the matrix interval
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       {
@@ -370,9 +336,7 @@ __device__ __forceinline__ void body(const Args& a) {
       // every wave is through with this window; the next one is requested, and the last micro-tile's matrix interval,
       // activation and stores run while it travels
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      WV_GN(0);
       NG_LDS_BARRIER();
-      WV_GN(1);
       const int64_t g1 = g0 + GROUP;
       const int64_t nlo = std::max<int64_t>(0, std::min<int64_t>(g1 - (WROWS - GROUP) / 2, a.N - WROWS));
       win_dma(win, a.h, nlo, a.N, wave, lane);
@@ -382,14 +346,9 @@ __device__ __forceinline__ void body(const Args& a) {
         finish(drow0, dwin, false, 1, g0);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      WV_GN(2);
       NG_LDS_BARRIER();
-      WV_GN(3);
     }
   }
-#ifdef WV_STAMP
-  if (a.stamps && lane == 0) a.stamps[2048 + blockIdx.x * NWV + wave] = wall_clock64();
-#endif
 }
 
 __global__ __launch_bounds__(WTHREADS) void mp_wave_fwd_kernel(Args a) {
@@ -424,53 +383,9 @@ int mp_wave_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int act, int r
   a.out = h_out; a.S_save = s_save; a.act = act;
   a.guard = guard; a.wflag = wflag; a.wflag_ver = pack_flag_version(ctx);
   const int grid = (int)cdiv(N, a.atoms_per_wg);
-#ifdef WV_STAMP
-  static unsigned long long* dbg = nullptr;
-  static int calls = 0;
-  constexpr int NST = 4 * NWV * 8 + 2 * NWV * 4;
-  if (!dbg) { (void)hipMalloc(&dbg, 8192 * 8); (void)hipMemset(dbg, 0, 8192 * 8); }
-  a.stamps = dbg;
-#endif
   ProfScope ps(ctx, st, "mp_win_fwd");
   hipLaunchKernelGGL(mp_wave_fwd_kernel, dim3(grid), dim3(WTHREADS), LDS_BYTES, st, a);
   NG_HIP(ctx, hipGetLastError());
-#ifdef WV_STAMP
-  if (++calls == 40) {
-    {
-      static unsigned long long wb[8192];
-      (void)hipStreamSynchronize(st);
-      (void)hipMemcpy(wb, dbg, sizeof(wb), hipMemcpyDeviceToHost);
-      unsigned long long s0 = ~0ull, s1 = 0, e0 = ~0ull, e1 = 0;
-      for (int b = 0; b < grid && b < 512; ++b) {
-        s0 = std::min(s0, wb[1024 + b]); s1 = std::max(s1, wb[1024 + b]);
-        for (int w = 0; w < NWV; ++w) { e0 = std::min(e0, wb[2048 + b * NWV + w]); e1 = std::max(e1, wb[2048 + b * NWV + w]); }
-      }
-      fprintf(stderr, "WV wall (100 MHz ticks): first start 0, last start %llu, first end %llu, last end %llu; block 3: start %llu end %llu\n",
-              s1 - s0, e0 - s0, e1 - s0, wb[1024 + 3] - s0, wb[2048 + 3 * NWV] - s0);
-      int hist[16] = {0};
-      for (int b = 0; b < grid && b < 512; ++b) { unsigned long long m = 0; for (int w = 0; w < NWV; ++w) m = std::max(m, wb[2048 + b * NWV + w]); const int k = (int)((m - s0) / 500); hist[k < 15 ? k : 15]++; }
-      fprintf(stderr, "WV end-time histogram (5 us bins):");
-      for (int k = 0; k < 16; ++k) fprintf(stderr, " %d", hist[k]);
-      fprintf(stderr, "\n");
-    }
-    unsigned long long hb[NST];
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(hb, dbg, sizeof(hb), hipMemcpyDeviceToHost);
-    const unsigned long long t0 = hb[4 * NWV * 8 + 0];
-    for (int g = 0; g < 2; ++g)
-      for (int w = 0; w < NWV; ++w) {
-        const unsigned long long* q = hb + 4 * NWV * 8 + (g * NWV + w) * 4;
-        fprintf(stderr, "WV group %d wave %d: arrive %6lld  bar %5lld  window %5lld  bar %5lld\n", g, w, (long long)(q[0] - t0),
-                (long long)(q[1] - q[0]), (long long)(q[2] - q[1]), (long long)(q[3] - q[2]));
-        for (int i = 0; i < 2; ++i) {
-          const unsigned long long* p = hb + ((g * 2 + i) * NWV + w) * 8;
-          fprintf(stderr, "   mt %d: start %6lld  range %4lld  gather %5lld  dma+scale %4lld  split %4lld  mfma %5lld  act %5lld  wait %4lld  stores %4lld | %6lld\n",
-                  i, (long long)(p[0] - t0), (long long)(p[1] - p[0]), (long long)(p[2] - p[1]), (long long)(p[3] - p[2]), 0LL,
-                  (long long)(p[4] - p[3]), (long long)(p[5] - p[4]), (long long)(p[6] - p[5]), (long long)(p[7] - p[6]), (long long)(p[7] - p[0]));
-        }
-      }
-  }
-#endif
   return NG_OK;
 }
 

@@ -17,7 +17,6 @@
 // LDS: window 72 KB + two piece planes 50 KB + exchange tile 16 KB.  Per atom the gather sums in the order of the eight-wave
 // kernel; the matrix sums meet as (k-half 0) + (k-half 1), so results agree with it to rounding, not bit for bit.
 #include <algorithm>
-#include <cstdio>
 
 #include "mfma_gemm.cuh"
 #include "ng_internal.h"
@@ -49,15 +48,7 @@ struct Args {
   RangeGuard guard;
   const unsigned* wflag;
   unsigned wflag_ver;
-#ifdef W16_STAMP
-  unsigned long long* stamps;
-#endif
 };
-#ifdef W16_STAMP
-#define W16_T(k) do { if (a.stamps && blockIdx.x == 3 && lane == 0 && t - T0 >= 2 && t - T0 < 6) a.stamps[((t - T0 - 2) * 16 + wave) * 8 + (k)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define W16_T(k) do {} while (0)
-#endif
 
 template <int E>
 struct Tile {
@@ -178,11 +169,7 @@ __device__ __forceinline__ void gather(int lane, int al, int wlo, int idx, const
   __builtin_amdgcn_sched_barrier(0);                                         \
   rot_fma4<E, S0>(ha, w, lo, hi);                                            \
   __builtin_amdgcn_sched_barrier(0);
-#ifdef W16_ABL_NOGATHER      // timing experiment: one rotation group instead of four
-  NG_W16_STEP(0)
-#else
   NG_W16_STEP(0) NG_W16_STEP(4) NG_W16_STEP(8) NG_W16_STEP(12)
-#endif
 #undef NG_W16_STEP
   tile_put<E, H2>(tb, al, c, lo, hi, rs);
 }
@@ -261,7 +248,6 @@ __device__ __forceinline__ void body(const Args& a) {
   for (int64_t t = T0; t < T1; ++t) {
     // ---- lists of t+2 requested, range of t+1 published, epilogue operands requested, tile t gathered
     const int64_t tn = t + 1 < T1 ? t + 1 : t, tnn = t + 2 < T1 ? t + 2 : t;
-    W16_T(0);
     Slot<E> nn = slot_load<E>(a.nlist, a.e, tnn * WTA + al, K, c, a.N);
     slot_mask(nxt, c < K && tn * WTA + al < a.N);
     if (t + 1 < T1) range_of(nxt, t + 1, ctl + ((t + 1) & 1) * (2 * NW));
@@ -270,12 +256,9 @@ __device__ __forceinline__ void body(const Args& a) {
     const int64_t rowc = live ? row : a.N - 1;
     const float rs = a.rowscale[rowc];
     const float4 re = *reinterpret_cast<const float4*>(a.h + rowc * WF + col);
-    W16_T(1);
     if (mode == 0) gather<E, H2, false>(lane, al, wlo, cur.idx, cur.w, tile, win4, src4, s_rs);
     else gather_global<E, H2>(lane, al, cur.idx, cur.w[0], cur.w[E > 1 ? 1 : 0], cur.w[E > 2 ? 2 : 0], tile, src4, s_rs);
-    W16_T(2);
     NG_LDS_BARRIER();
-    W16_T(3);
     // the next tile's window, when it needs one: requested NOW (every gather of this tile is done, its range was published
     // before the barrier) as LDS-DMA and awaited in front of the tile's last barrier: the HBM / L2 round trip runs beside
     // the matrix interval and the epilogue.
@@ -328,11 +311,7 @@ __device__ __forceinline__ void body(const Args& a) {
       const f32x4 o = kh ? part[0] : part[1];      // the block the partner finishes: row tile 2 rp + (1 - kh)
       xch[((2 * rp + (1 - kh)) * 4 + ct) * 64 + lane] = make_float4(o[0], o[1], o[2], o[3]);
     }
-    W16_T(4);
-#ifndef W16_ABL_NOXBAR       // timing experiment: without the exchange barrier (wrong results)
     NG_LDS_BARRIER();
-#endif
-    W16_T(5);
     {
       const float4 q = xch[(rt_own * 4 + ct) * 64 + lane];
       const f32x4 mine = kh ? part[1] : part[0];
@@ -340,11 +319,7 @@ __device__ __forceinline__ void body(const Args& a) {
       const f32x4 k0 = kh ? f32x4{q.x, q.y, q.z, q.w} : mine, k1 = kh ? mine : f32x4{q.x, q.y, q.z, q.w};
       const float rsx = H2 ? rs * (1.0f / 256.0f) * s_rs[16 * rt_own + a16] : rs;
       float4 v = make_float4((k0[0] + k1[0]) * rsx, (k0[1] + k1[1]) * rsx, (k0[2] + k1[2]) * rsx, (k0[3] + k1[3]) * rsx);
-#ifdef W16_ABL_NOACT
-      if (a.N < 0) {
-#else
       if (a.act == NG_ACT_SOFTPLUS) {
-#endif
         v.x = softplus_f(v.x); v.y = softplus_f(v.y); v.z = softplus_f(v.z); v.w = softplus_f(v.w);
       } else if (a.act != NG_ACT_NONE) {
         v.x = act_apply(a.act, v.x); v.y = act_apply(a.act, v.y);
@@ -358,12 +333,10 @@ __device__ __forceinline__ void body(const Args& a) {
     }
     cur = nxt;
     nxt = nn;
-    W16_T(6);
     if (restage) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // the next gather writes the tile planes and s_rs, which this tile's matrix interval and epilogue read; a restaged
     // window must be complete: one barrier for both
     NG_LDS_BARRIER();
-    W16_T(7);
   }
 }
 
@@ -397,12 +370,6 @@ int mp_win16_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int ac
   a.guard = guard; a.wflag = wflag; a.wflag_ver = pack_flag_version(ctx);
   const int grid = (int)cdiv(a.ntiles, per);
   const size_t lds = mp_win16_lds_bytes(E);
-#ifdef W16_STAMP
-  static unsigned long long* dbg = nullptr;
-  static int calls = 0;
-  if (!dbg) { (void)hipMalloc(&dbg, 4 * 16 * 8 * 8); (void)hipMemset(dbg, 0, 4 * 16 * 8 * 8); }
-  a.stamps = dbg;
-#endif
   ProfScope ps(ctx, st, "mp_win_fwd");
   switch (E) {
     case 1: hipLaunchKernelGGL((mp_win16_fwd_kernel<1>), dim3(grid), dim3(WTHREADS), lds, st, a); break;
@@ -410,20 +377,6 @@ int mp_win16_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int ac
     case 3: hipLaunchKernelGGL((mp_win16_fwd_kernel<3>), dim3(grid), dim3(WTHREADS), lds, st, a); break;
   }
   NG_HIP(ctx, hipGetLastError());
-#ifdef W16_STAMP
-  if (++calls == 40) {
-    unsigned long long hbuf[4 * 16 * 8];
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(hbuf, dbg, sizeof(hbuf), hipMemcpyDeviceToHost);
-    for (int tt = 0; tt < 4; ++tt)
-      for (int w = 0; w < 16; w += (tt == 0 ? 1 : 4)) {
-        const unsigned long long* p = hbuf + (tt * 16 + w) * 8;
-        fprintf(stderr, "W16 tile %d wave %2d: loads %5lld  gather %5lld  bar1 %5lld  mfma %5lld  bar1b %5lld  epilogue %5lld  end-bar %5lld | total %6lld\n",
-                tt, w, (long long)(p[1] - p[0]), (long long)(p[2] - p[1]), (long long)(p[3] - p[2]), (long long)(p[4] - p[3]),
-                (long long)(p[5] - p[4]), (long long)(p[6] - p[5]), (long long)(p[7] - p[6]), (long long)(p[7] - p[0]));
-      }
-  }
-#endif
   return NG_OK;
 }
 

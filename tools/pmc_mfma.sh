@@ -8,8 +8,9 @@ P=0
 for SET in "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_COEXEC_CYCLES" \
            "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS"; do
   P=$((P+1)); OUT=gpurun_out/pmc_mfma_$P; rm -rf "$OUT"
-  rocprofv3 --pmc $SET --output-format csv -d "$OUT" -o t -- \
-      python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-extras > gpurun_out/pmc_mfma_$P.log 2>&1
+  timeout -k 10 600 rocprofv3 --pmc $SET --output-format csv -d "$OUT" -o t -- \
+      python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-extras > "$OUT.log" 2>&1 \
+    || { rc=$?; echo "pmc pass $P failed (exit $rc): $OUT.log" >&2; exit $rc; }
 done
 python - <<'PY'
 import csv, glob, json, collections

@@ -4,8 +4,9 @@
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 for C in FETCH_SIZE WRITE_SIZE; do
   OUT=gpurun_out/pmc_${C}; rm -rf "$OUT"
-  rocprofv3 --pmc $C --output-format csv -d "$OUT" -o t -- \
-      python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-extras > gpurun_out/pmc_${C}.log 2>&1
+  timeout -k 10 600 rocprofv3 --pmc $C --output-format csv -d "$OUT" -o t -- \
+      python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-profile --no-extras > "$OUT.log" 2>&1 \
+    || { rc=$?; echo "pmc pass $C failed (exit $rc): $OUT.log" >&2; exit $rc; }
 done
 python - <<'PY'
 import csv, glob, json, collections
