@@ -386,6 +386,22 @@ int ng_knn_graph(ng_ctx*, void* stream, int G, int n, int K, float scale, const 
  *   list.  Conventions, path choice (brute force / cell grid) and NG_KNN as ng_knn_graph. */
 int ng_knn_graph_pbc(ng_ctx*, void* stream, int G, int n, int K, float scale, const float* pos, const float* box,
                      int triclinic, int32_t* nlist, float* edges, float* inv_degree);
+/* Ragged batches: G structures of different sizes, rows concatenated, graph_ptr [G+1] on the device (gp[0] = 0, non-decreasing,
+ *   gp[G] = N); max_n = the largest structure.  Only atoms of the same structure are neighbours.  Each structure's rows are
+ *   bit for bit what ng_knn_graph / ng_cutoff_count / ng_cutoff_fill_rows give for that structure alone (G = 1), with the
+ *   indices shifted by gp[g]: batch-global nlist / col, inv_degree = 1/#(structure-local neighbour index > 0).  One launch
+ *   per pass, no host synchronisation, G bounded only by N < 2^31.
+ *   ng_knn_graph_ragged: structures of >= 16384 atoms take the cell grid (as ng_knn_graph does) one call each, found from
+ *   graph_ptr_host, the same [G+1] array in host memory (required when max_n >= 16384, else may be NULL).  NG_KNN as ng_knn_graph.
+ *   ng_cutoff_count_ragged / ng_cutoff_fill_rows_ragged: brute force at every size; the caller's exclusive scan of deg [N]
+ *   is row_ptr [N+1]; row_of may be NULL.  No periodic boxes. */
+int ng_knn_graph_ragged(ng_ctx*, void* stream, int G, int64_t N, int K, float scale, const float* pos, const int32_t* graph_ptr,
+                        const int32_t* graph_ptr_host, int max_n, int32_t* nlist, float* edges, float* inv_degree);
+int ng_cutoff_count_ragged(ng_ctx*, void* stream, int G, int64_t N, float cutoff, const float* pos, const int32_t* graph_ptr,
+                           int max_n, int32_t* deg);
+int ng_cutoff_fill_rows_ragged(ng_ctx*, void* stream, int G, int64_t N, float cutoff, float scale, const float* pos,
+                               const int32_t* graph_ptr, int max_n, const int32_t* row_ptr, int32_t* col, float* dist,
+                               float* inv_degree, int32_t* row_of);
 
 /* AMPLayer attention aggregation, nmrgnn/layers.py:89-96 (the layer is exported by the reference package but not
  * used by its model):

@@ -121,6 +121,9 @@ SIGNATURES = {
                               _vp, _vp, _vp]),
     "ng_knn_graph": (_int, [_vp, _vp, _int, _int, _int, _f, _vp, _vp, _vp, _vp]),
     "ng_knn_graph_pbc": (_int, [_vp, _vp, _int, _int, _int, _f, _vp, _vp, _int, _vp, _vp, _vp]),
+    "ng_knn_graph_ragged": (_int, [_vp, _vp, _int, _i64, _int, _f, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "ng_cutoff_count_ragged": (_int, [_vp, _vp, _int, _i64, _f, _vp, _vp, _int, _vp]),
+    "ng_cutoff_fill_rows_ragged": (_int, [_vp, _vp, _int, _i64, _f, _f, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "ng_amp_attend": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ng_amp_attend_bwd": (_int, [_vp, _vp, _i64, _int, _int, _int] + [_vp] * 13),
     "ng_loss_l2": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,372 @@
+// Neighbour lists of a RAGGED batch: G structures of different sizes, concatenated along the rows (graph_ptr [G+1] on the
+// device), built in one launch per pass.  The uniform builders (knn.hip, mp_csr.hip's cutoff kernels) take G frames of one
+// topology with the frames on gridDim.y (G <= 65535); here a library of small molecules or a few proteins of different sizes
+// is one call, G limited only by int32 rows.
+//
+// One thread per query row, 256 consecutive rows per workgroup.  A thread finds its row's structure by a binary search of
+// graph_ptr; the rows of a workgroup belong to a run of consecutive structures, so the candidates the workgroup needs are one
+// contiguous span of rows, [gp[first], gp[last + 1]).  That span streams through LDS tiles of float4 positions (one
+// ds_read_b128 per candidate; lanes of different structures read different slots) and every thread walks only the part of a
+// tile that lies inside its own structure.  A 24-atom molecule therefore costs its thread 23 candidate steps, not a wave of 64
+// lanes with 40 idle (knn_wave_kernel) or a 256-thread workgroup of its own (knn_kernel).  For a structure of a few thousand
+// atoms one thread per query is a serial chain of thousands of steps in too few waves, so the kNN rows of structures of
+// 257..4096 atoms take a second launch, one wave per query (knn_ragged_wave_kernel), and the first launch skips them.
+//
+// Every convention is the uniform builders', so that each structure's rows are, bit for bit, what ng_knn_graph /
+// ng_cutoff_fill_rows give for that structure alone, indices shifted by gp[g]: the same squared-distance expression
+// (pbc.cuh: pbc_dist2, with DispOpen's c - q), candidates visited in ascending index with strict comparisons (ties -> lower
+// index), distances sqrt(d2) * scale, unused kNN slots (0, 0.0), batch-global indices, inv_degree = 1/#(structure-local
+// neighbour index > 0) (library.py:115-116), cutoff rows in ascending neighbour index.
+//
+// kNN structures of >= 16384 atoms (the uniform path's switch point) take the cell grid of knn_cells.hip, one call per such
+// structure on its own rows: the ragged launch skips their rows, and a fix-up launch adds gp[g] to the frame-local indices the
+// grid writes.  The cutoff builder is brute force at every size, as the uniform one is.
+#include <algorithm>
+#include <climits>
+
+#include "ng_common.h"
+#include "ng_internal.h"
+#include "pbc.cuh"
+
+namespace ng {
+
+constexpr int RG_TILE = 1024;        // candidates per LDS tile: 16 KiB of float4
+constexpr int RG_CELLS_MIN = 16384;  // kNN structures from this size on take the cell grid (knn.hip: knn_graph_impl)
+constexpr int RG_WAVE_MIN = 256;     // kNN structures of more atoms, up to 4096, take one wave per query row
+typedef unsigned long long knn_u64;
+
+// the structure of row i: the g with gp[g] <= i < gp[g + 1] (gp non-decreasing, gp[0] = 0, gp[G] = N > i; empty structures
+// are skipped over), and its row range clamped to [0, N) around i, so that a malformed graph_ptr cannot send a read out of
+// the batch
+struct RgRange {
+  int lo, hi;
+};
+__device__ __forceinline__ RgRange rg_range(const int32_t* __restrict__ gp, int G, int N, int i) {
+  int a = 0, b = G;
+  while (b - a > 1) {
+    const int m = (a + b) >> 1;
+    if (gp[m] <= i) a = m; else b = m;
+  }
+  return {max(0, min(gp[a], i)), min(N, max(gp[a + 1], i + 1))};
+}
+
+// the candidate span of a workgroup: the union of the ranges of its active rows (block-wide min / max through LDS);
+// returns false when no row of the workgroup is active
+__device__ __forceinline__ bool rg_span(bool active, RgRange r, int& s0, int& s1) {
+  __shared__ int lo_s, hi_s;
+  if (threadIdx.x == 0) { lo_s = INT_MAX; hi_s = INT_MIN; }
+  __syncthreads();
+  if (active) { atomicMin(&lo_s, r.lo); atomicMax(&hi_s, r.hi); }
+  __syncthreads();
+  s0 = lo_s; s1 = hi_s;
+  return s0 < s1;
+}
+
+// rows [t0, t0 + cnt) of pos -> LDS
+__device__ __forceinline__ void rg_stage(float4* sp, const float* __restrict__ pos, int t0, int cnt) {
+  __syncthreads();
+  for (int t = threadIdx.x; t < cnt; t += 256) {
+    const float* p = pos + 3 * (int64_t)(t0 + t);
+    sp[t] = make_float4(p[0], p[1], p[2], 0.f);
+  }
+  __syncthreads();
+}
+
+// kNN: the search of knn_kernel (knn.hip) over the row's own structure.  Rows of structures of (wlo, whi] atoms are left to
+// knn_ragged_wave_kernel, rows of structures of `big` atoms or more to the cell grid (neither is written here).
+template <int KMAX>
+__global__ __launch_bounds__(256) void knn_ragged_kernel(int G, int N, int K, float scale, int wlo, int whi, int big,
+                                                         const float* __restrict__ pos,       // [N][3]
+                                                         const int32_t* __restrict__ gp,      // [G+1]
+                                                         int32_t* __restrict__ nlist,         // [N][K]
+                                                         float* __restrict__ edges,           // [N][K]
+                                                         float* __restrict__ inv_degree) {    // [N]
+  __shared__ float4 sp[RG_TILE];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  RgRange r{0, 0};
+  if (i < N) r = rg_range(gp, G, N, i);
+  const int n = r.hi - r.lo;
+  const bool active = i < N && n < big && !(n > wlo && n <= whi);
+  int s0, s1;
+  if (!rg_span(active, r, s0, s1)) return;          // uniform over the workgroup
+  DispOpen D;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (active) { qx = pos[3 * (int64_t)i]; qy = pos[3 * (int64_t)i + 1]; qz = pos[3 * (int64_t)i + 2]; }
+  float bd[KMAX];
+  int bi[KMAX];
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) { bd[k] = INFINITY; bi[k] = 0; }
+
+  for (int t0 = s0; t0 < s1; t0 += RG_TILE) {
+    const int cnt = min(RG_TILE, s1 - t0);
+    rg_stage(sp, pos, t0, cnt);
+    if (active) {
+      const int ta = max(r.lo, t0) - t0, tb = min(r.hi, t0 + cnt) - t0;
+      for (int t = ta; t < tb; ++t) {
+        const float4 c = sp[t];
+        float dx, dy, dz;
+        D(qx, qy, qz, c.x, c.y, c.z, dx, dy, dz);
+        const float d2 = pbc_dist2(dx, dy, dz);
+        const int j = t0 + t;
+        if (d2 < bd[KMAX - 1] && j != i) {
+#pragma unroll
+          for (int k = KMAX - 1; k >= 1; --k) {
+            const bool shift = bd[k - 1] > d2;          // old element k-1 moves up
+            const bool here = !shift && bd[k] > d2;     // candidate lands in slot k
+            bi[k] = shift ? bi[k - 1] : (here ? j : bi[k]);
+            bd[k] = shift ? bd[k - 1] : (here ? d2 : bd[k]);
+          }
+          if (bd[0] > d2) { bd[0] = d2; bi[0] = j; }
+        }
+      }
+    }
+  }
+  if (!active) return;
+  const int64_t row = i;
+  int deg = 0;
+#pragma unroll
+  for (int k = 0; k < KMAX; ++k) {
+    if (k < K) {
+      const bool ok = bd[k] < INFINITY;
+      nlist[row * K + k] = ok ? bi[k] : 0;
+      edges[row * K + k] = ok ? sqrtf(bd[k]) * scale : 0.f;
+      deg += (ok && bi[k] > r.lo) ? 1 : 0;        // structure-local index > 0
+    }
+  }
+  inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+}
+
+// One WAVE per query row for the rows of mid-sized structures (wlo, 64 * STEPS] atoms: the algorithm of knn_wave_kernel
+// (knn.hip) on the row's own structure, keys (bits(d2) << 32 | structure-local index), so the lists are the other kernels'
+// bit for bit.  One thread per query leaves a 2770-atom structure with 44 waves that each walk all 2770 candidates (0.44 ms);
+// here it is 2770 waves of 44 steps.  Candidates are read from global memory (a structure of <= 4096 atoms is <= 48 KiB, held
+// by the caches); the waves of rows outside (wlo, 64 * STEPS] leave after the search of graph_ptr.
+__device__ __forceinline__ knn_u64 rg_readlane64(knn_u64 v, int l) {            // knn.hip: knn_readlane64
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
+  return ((knn_u64)hi << 32) | lo;
+}
+__device__ __forceinline__ knn_u64 rg_shr1(knn_u64 v) {                         // knn.hip: knn_shr1 (DPP wave_shr:1)
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, 0x138, 0xf, 0xf, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), 0x138, 0xf, 0xf, false);
+  return ((knn_u64)hi << 32) | lo;
+}
+
+template <int STEPS>
+__global__ __launch_bounds__(256) void knn_ragged_wave_kernel(int G, int N, int K, float scale, int wlo,
+                                                              const float* __restrict__ pos, const int32_t* __restrict__ gp,
+                                                              int32_t* __restrict__ nlist, float* __restrict__ edges,
+                                                              float* __restrict__ inv_degree) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int i = blockIdx.x * 4 + wave;
+  if (i >= N) return;                             // uniform over the wave
+  const RgRange r = rg_range(gp, G, N, i);
+  const int lo = __builtin_amdgcn_readfirstlane(r.lo), n = __builtin_amdgcn_readfirstlane(r.hi) - lo;
+  if (n <= wlo || n > 64 * STEPS) return;
+  const float qx = pos[3 * (int64_t)i], qy = pos[3 * (int64_t)i + 1], qz = pos[3 * (int64_t)i + 2];
+  const float* sp = pos + 3 * (int64_t)lo;
+  DispOpen D;
+  // A: keys of this lane's candidates t = 64 s + lane, and their minimum
+  knn_u64 key[STEPS];
+  knn_u64 mn = ~0ull;
+#pragma unroll
+  for (int s = 0; s < STEPS; ++s) {
+    const int t = 64 * s + lane;
+    const int tc = min(t, n - 1);
+    float dx, dy, dz;
+    D(qx, qy, qz, sp[3 * tc], sp[3 * tc + 1], sp[3 * tc + 2], dx, dy, dz);
+    const float d2 = pbc_dist2(dx, dy, dz);
+    knn_u64 k = ((knn_u64)__builtin_bit_cast(unsigned, d2) << 32) | (unsigned)t;
+    if (t >= n || lo + t == i) k = ~0ull;
+    key[s] = k;
+    mn = k < mn ? k : mn;
+  }
+  // B: the K-th smallest lane minimum bounds the K-th smallest key
+  knn_u64 tau = ~0ull;
+  {
+    int rank = 0;
+    for (int b = 0; b < 64; ++b) rank += rg_readlane64(mn, b) < mn ? 1 : 0;
+    const unsigned long long hit = __ballot(rank == K - 1 && mn != ~0ull);
+    if (hit) tau = rg_readlane64(mn, __builtin_ctzll(hit));
+  }
+  // C: insert what lies at or below the bound into the list held across the lanes
+  knn_u64 list = ~0ull, kth = ~0ull;
+#pragma unroll
+  for (int s = 0; s < STEPS; ++s) {
+    unsigned long long m = __ballot(key[s] <= tau && key[s] != ~0ull);
+    while (m) {
+      const int b = __builtin_ctzll(m);
+      m &= m - 1;
+      const knn_u64 c = rg_readlane64(key[s], b);
+      if (c < kth) {
+        const knn_u64 prev = rg_shr1(list);
+        list = c < prev ? prev : (c < list ? c : list);
+        kth = rg_readlane64(list, K - 1);
+      }
+    }
+  }
+  const int64_t row = i;
+  const bool ok = lane < K && list != ~0ull;
+  const int idx = (int)(unsigned)list;
+  const float d2 = __builtin_bit_cast(float, (unsigned)(list >> 32));
+  if (lane < K) {
+    nlist[row * K + lane] = ok ? lo + idx : 0;
+    edges[row * K + lane] = ok ? sqrtf(d2) * scale : 0.f;
+  }
+  const int deg = __popcll(__ballot(ok && idx > 0));
+  if (lane == 0) inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+}
+
+// frame-local -> batch-global indices of one structure's rows from the cell grid (n >= 16384 > K: every slot is real)
+__global__ __launch_bounds__(256) void knn_ragged_offset_kernel(int64_t count, int off, int32_t* __restrict__ nlist) {
+  const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (s < count) nlist[s] += off;
+}
+
+// cutoff: count (FILL = false: deg[N]) or fill pass (col / dist / row_of at row_ptr, inv_degree) of cutoff_kernel
+// (mp_csr.hip) over the row's own structure
+template <bool FILL>
+__global__ __launch_bounds__(256) void cutoff_ragged_kernel(int G, int N, float cutoff2, float scale,
+                                                            const float* __restrict__ pos, const int32_t* __restrict__ gp,
+                                                            int32_t* __restrict__ deg, const int32_t* __restrict__ row_ptr,
+                                                            int32_t* __restrict__ col, float* __restrict__ dist,
+                                                            float* __restrict__ inv_degree, int32_t* __restrict__ row_of) {
+  __shared__ float4 sp[RG_TILE];
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  RgRange r{0, 0};
+  if (i < N) r = rg_range(gp, G, N, i);
+  const bool active = i < N;
+  int s0, s1;
+  if (!rg_span(active, r, s0, s1)) return;
+  DispOpen D;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (active) { qx = pos[3 * (int64_t)i]; qy = pos[3 * (int64_t)i + 1]; qz = pos[3 * (int64_t)i + 2]; }
+  int cnt = 0, cnt_pos = 0;
+  int64_t out = 0, lim = 0;          // a row never writes past its own extent, whatever the count pass saw
+  if (FILL && active) { out = row_ptr[i]; lim = row_ptr[i + 1]; }
+  for (int t0 = s0; t0 < s1; t0 += RG_TILE) {
+    const int m = min(RG_TILE, s1 - t0);
+    rg_stage(sp, pos, t0, m);
+    if (active) {
+      const int ta = max(r.lo, t0) - t0, tb = min(r.hi, t0 + m) - t0;
+      for (int t = ta; t < tb; ++t) {
+        const float4 c = sp[t];
+        float dx, dy, dz;
+        D(qx, qy, qz, c.x, c.y, c.z, dx, dy, dz);
+        const float d2 = pbc_dist2(dx, dy, dz);
+        const int j = t0 + t;
+        if (d2 < cutoff2 && j != i) {
+          if (FILL && out + cnt < lim) {
+            col[out + cnt] = j;
+            dist[out + cnt] = sqrtf(d2) * scale;
+            if (row_of) row_of[out + cnt] = i;
+          }
+          ++cnt;
+          cnt_pos += j > r.lo ? 1 : 0;
+        }
+      }
+    }
+  }
+  if (!active) return;
+  if (FILL) inv_degree[i] = cnt_pos > 0 ? 1.0f / (float)cnt_pos : 0.f;
+  else deg[i] = cnt;
+}
+
+static int ragged_check(ng_ctx* ctx, int G, int64_t N, int max_n, const float* pos, const int32_t* graph_ptr) {
+  NG_REQUIRE(ctx, G >= 0 && N >= 0 && max_n >= 0, "ragged graph: negative size");
+  NG_REQUIRE(ctx, N < ((int64_t)1 << 31), "ragged graph: batch exceeds int32 rows");
+  NG_REQUIRE(ctx, max_n <= N, "ragged graph: max_n exceeds the batch");
+  NG_REQUIRE(ctx, N == 0 || (G >= 1 && pos && graph_ptr), "ragged graph: positions and graph_ptr required");
+  return NG_OK;
+}
+
+}  // namespace ng
+
+using namespace ng;
+
+extern "C" int ng_knn_graph_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, int K, float scale, const float* pos,
+                                   const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, int32_t* nlist,
+                                   float* edges, float* inv_degree) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn (ragged): neighbour count must be in [1,64]");
+  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  NG_REQUIRE(ctx, N * K < ((int64_t)1 << 31), "knn (ragged): N * K exceeds int32 slots");
+  if (N == 0) return NG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  // structures of the cell grid: only when one may be that large, from the host copy of graph_ptr
+  const bool cells = !sw().knn_brute && !sw().knn_serial && max_n >= RG_CELLS_MIN;
+  NG_REQUIRE(ctx, !cells || graph_ptr_host, "knn (ragged): graph_ptr_host required when max_n >= 16384");
+  const int big = cells ? RG_CELLS_MIN : INT_MAX;
+  // one wave per query for structures of (256, 4096] atoms, sized by the largest of them (NG_KNN=serial / lanes: off, as the
+  // uniform path's wave kernel)
+  const int wmax = std::min(max_n, 4096);
+  const int steps = (sw().knn_serial || sw().knn_lanes || max_n <= RG_WAVE_MIN) ? 0 : wmax <= 1024 ? 16 : wmax <= 2048 ? 32
+                    : wmax <= 3072 ? 48 : 64;
+  const int whi = 64 * steps;
+  {
+    ProfScope ps(ctx, st, "knn_graph_ragged");
+    const dim3 grid((unsigned)cdiv(N, 256)), block(256);
+#define NG_RG(KM) hipLaunchKernelGGL(knn_ragged_kernel<KM>, grid, block, 0, st, G, (int)N, K, scale, RG_WAVE_MIN, whi, big, pos, \
+                                     graph_ptr, nlist, edges, inv_degree)
+    if (K <= 16) NG_RG(16); else if (K <= 32) NG_RG(32); else NG_RG(64);
+#undef NG_RG
+    NG_HIP(ctx, hipGetLastError());
+    if (steps) {
+      const dim3 gw((unsigned)cdiv(N, 4));
+#define NG_RGW(S) hipLaunchKernelGGL(knn_ragged_wave_kernel<S>, gw, block, 0, st, G, (int)N, K, scale, RG_WAVE_MIN, pos, graph_ptr, \
+                                     nlist, edges, inv_degree)
+      if (steps == 16) NG_RGW(16); else if (steps == 32) NG_RGW(32); else if (steps == 48) NG_RGW(48); else NG_RGW(64);
+#undef NG_RGW
+      NG_HIP(ctx, hipGetLastError());
+    }
+  }
+  if (!cells) return NG_OK;
+  for (int g = 0; g < G; ++g) {
+    const int lo = graph_ptr_host[g], n = graph_ptr_host[g + 1] - lo;
+    NG_REQUIRE(ctx, lo >= 0 && n >= 0 && (int64_t)lo + n <= N, "knn (ragged): graph_ptr_host outside the batch");
+    if (n < big) continue;
+    // the rows the ragged launch skipped; the brute-force kernel cannot take them back, so a size the grid refuses is an error
+    NG_REQUIRE(ctx, knn_cells_supported(1, n, K), "knn (ragged): structure too large for the cell grid");
+    const int64_t s0 = (int64_t)lo * K;
+    if (const int rc = knn_cells(ctx, st, 1, n, K, scale, pos + 3 * (int64_t)lo, nlist + s0, edges + s0, inv_degree + lo,
+                                 nullptr, 0))
+      return rc;
+    if (lo > 0) {
+      hipLaunchKernelGGL(knn_ragged_offset_kernel, dim3((unsigned)cdiv((int64_t)n * K, 256)), dim3(256), 0, st,
+                         (int64_t)n * K, lo, nlist + s0);
+      NG_HIP(ctx, hipGetLastError());
+    }
+  }
+  return NG_OK;
+}
+
+extern "C" int ng_cutoff_count_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, const float* pos,
+                                      const int32_t* graph_ptr, int max_n, int32_t* deg) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
+  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  if (N == 0) return NG_OK;
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(ctx, st, "cutoff_count_ragged");
+  hipLaunchKernelGGL(cutoff_ragged_kernel<false>, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, G, (int)N, cutoff * cutoff,
+                     1.0f, pos, graph_ptr, deg, nullptr, nullptr, nullptr, nullptr, nullptr);
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}
+
+extern "C" int ng_cutoff_fill_rows_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, float scale,
+                                          const float* pos, const int32_t* graph_ptr, int max_n, const int32_t* row_ptr,
+                                          int32_t* col, float* dist, float* inv_degree, int32_t* row_of) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
+  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  if (N == 0) return NG_OK;
+  NG_REQUIRE(ctx, row_ptr && inv_degree, "cutoff graph (ragged): row_ptr and inv_degree required");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(ctx, st, "cutoff_fill_ragged");
+  hipLaunchKernelGGL(cutoff_ragged_kernel<true>, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, G, (int)N, cutoff * cutoff,
+                     scale, pos, graph_ptr, nullptr, row_ptr, col, dist, inv_degree, row_of);
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}

@@ -582,3 +582,135 @@ def _frames_to_batch_cutoff(atoms, frames, cutoff, scale, device, pbc=None):
     if box is not None:
         b.box, b.box_triclinic = box, bool(pbc[1])
     return b
+
+
+def _cat_rows(parts, device):
+    """one [N, ...] array from per-structure parts: a torch tensor (on ``device``, grad kept) when any part is one"""
+    if any(isinstance(p, torch.Tensor) for p in parts):
+        return torch.cat([torch.as_tensor(p).to(device=device, dtype=torch.float32) for p in parts])
+    return np.concatenate([np.asarray(p, dtype=np.float32) for p in parts])
+
+
+def _ragged_inputs(atoms, positions, sizes, graph_ptr, device):
+    """(atoms [N, C], positions [N, 3], graph_ptr [G+1] int64 on the host), validated before any device work"""
+    if isinstance(atoms, (list, tuple)) or isinstance(positions, (list, tuple)):
+        if not (isinstance(atoms, (list, tuple)) and isinstance(positions, (list, tuple))):
+            raise ValueError("structures_to_batch: atoms and positions must both be lists, or both concatenated arrays")
+        if sizes is not None or graph_ptr is not None:
+            raise ValueError("structures_to_batch: sizes= / graph_ptr= go with concatenated arrays, not with lists")
+        if len(atoms) != len(positions):
+            raise ValueError(f"structures_to_batch: {len(atoms)} atom arrays but {len(positions)} position arrays")
+        n = []
+        for g, (a, p) in enumerate(zip(atoms, positions)):
+            sa, sp = tuple(np.shape(a)), tuple(np.shape(p))
+            if len(sa) != 2 or len(sp) != 2 or sp[1] != 3:
+                raise ValueError(f"structures_to_batch: structure {g}: atoms must be [n, C] and positions [n, 3]")
+            if sa[0] != sp[0]:
+                raise ValueError(f"structures_to_batch: structure {g}: {sa[0]} atom rows but {sp[0]} positions")
+            n.append(sa[0])
+        sizes = np.asarray(n, dtype=np.int64)
+        if len(sizes) == 0:
+            raise ValueError("structures_to_batch: no structures")
+        if (sizes == 0).any():
+            raise ValueError(f"structures_to_batch: structure {int(np.argmax(sizes == 0))} has no atoms")
+        atoms, positions = _cat_rows(atoms, device), _cat_rows(positions, device)
+    else:
+        sa, sp = tuple(np.shape(atoms)), tuple(np.shape(positions))
+        if len(sa) != 2 or len(sp) != 2 or sp[1] != 3:
+            raise ValueError("structures_to_batch: atoms must be [N, C] and positions [N, 3]")
+        if sa[0] != sp[0]:
+            raise ValueError(f"structures_to_batch: {sa[0]} atom rows but {sp[0]} positions")
+        if (sizes is None) == (graph_ptr is None):
+            raise ValueError("structures_to_batch: concatenated arrays need exactly one of sizes= or graph_ptr=")
+        if sizes is not None:
+            sizes = np.asarray(sizes, dtype=np.int64).reshape(-1)
+        else:
+            gp = np.asarray(graph_ptr, dtype=np.int64).reshape(-1)
+            if len(gp) < 1 or gp[0] != 0:
+                raise ValueError("structures_to_batch: graph_ptr must start at 0")
+            sizes = np.diff(gp)
+        if len(sizes) == 0:
+            raise ValueError("structures_to_batch: no structures")
+        if (sizes <= 0).any():
+            raise ValueError(f"structures_to_batch: structure {int(np.argmax(sizes <= 0))} has no atoms")
+        if int(sizes.sum()) != sa[0]:
+            raise ValueError(f"structures_to_batch: the structures hold {int(sizes.sum())} atoms, the arrays {sa[0]}")
+    gp = np.zeros(len(sizes) + 1, dtype=np.int64)
+    gp[1:] = np.cumsum(sizes)
+    if gp[-1] >= 2 ** 31:
+        raise ValueError("structures_to_batch: more than 2^31 - 1 atoms in one batch")
+    return atoms, positions, gp
+
+
+def structures_to_batch(atoms, positions, neighbor_number=16, cutoff=None, scale=0.1, device=None, sizes=None,
+                        graph_ptr=None, box=None):
+    """Build the graphs of G DIFFERENT structures on the GPU in one launch per pass and return them as one device-resident
+    GraphBatch with ``graph_ptr`` set: a library of small molecules, several proteins, a training set given as coordinates.
+
+    ``atoms`` / ``positions``: lists of per-structure ``[n_g, C]`` one-hot and ``[n_g, 3]`` Angstrom arrays, or the
+    concatenated ``[N, C]`` / ``[N, 3]`` with ``sizes=`` [G] or ``graph_ptr=`` [G+1].  Only atoms of the same structure are
+    neighbours.  ``cutoff=None``: the padded kNN lists of :func:`frames_to_batch` (ng_knn_graph_ragged) with
+    ``neighbor_number`` neighbours; a cutoff in Angstrom: the CSR lists of :func:`frames_to_batch_cutoff`
+    (ng_cutoff_count_ragged / ng_cutoff_fill_rows_ragged).  Each structure's rows are bit for bit that builder's lists for
+    the structure alone, with indices shifted to the batch; a one-atom structure has only padded slots and inv_degree 0.
+
+    The batch keeps the concatenated positions [N, 3] and ``scale``; with a ``positions`` tensor (or list of tensors) that
+    requires grad its ``edges`` carry a grad_fn back to them, as in :func:`frames_to_batch`.  Periodic boxes are not
+    supported on ragged batches (``box=`` raises ValueError)."""
+    if box is not None:
+        raise ValueError("structures_to_batch: periodic boxes are not supported on ragged batches; use frames_to_batch")
+    K = int(neighbor_number)
+    if not 1 <= K <= 64:
+        raise ValueError(f"structures_to_batch: neighbor_number must be in [1, 64], got {neighbor_number}")
+    if cutoff is not None and not float(cutoff) > 0:
+        raise ValueError(f"structures_to_batch: cutoff must be > 0, got {cutoff}")
+    device = _norm_device(device)
+    atoms, pos, gp = _ragged_inputs(atoms, positions, sizes, graph_ptr, device)
+    if cutoff is None and int(gp[-1]) * K >= 2 ** 31:
+        raise ValueError("structures_to_batch: N * neighbor_number exceeds 2^31 - 1 slots")
+    return _positions_batch(pos, lambda f: _structures_to_batch(atoms, f, gp, K, cutoff, scale, device))
+
+
+def _structures_to_batch(atoms, positions, gp, K, cutoff, scale, device):
+    import ctypes as C
+    from . import _lib
+    from ._lib import ptr
+    pos = _to_dev(positions, torch.float32, device).reshape(-1, 3)
+    at = _to_dev(atoms, torch.float32, device)
+    N, G = int(gp[-1]), len(gp) - 1
+    max_n = int(np.max(np.diff(gp)))
+    gp_host = gp.astype(np.int32)
+    gp_dev = _graph_ptr_dev(gp_host, device)
+    ctx = _lib.get_context(device.index)
+    with torch.cuda.device(device):
+        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        if cutoff is None:
+            nlist = torch.empty(N, K, dtype=torch.int32, device=device)
+            edges = torch.empty(N, K, dtype=torch.float32, device=device)
+            inv = torch.empty(N, dtype=torch.float32, device=device)
+            ctx.check(ctx.lib.ng_knn_graph_ragged(ctx.handle, st, G, N, K, float(scale), ptr(pos), ptr(gp_dev),
+                                                  C.c_void_p(gp_host.ctypes.data), max_n, ptr(nlist), ptr(edges), ptr(inv)),
+                      "ng_knn_graph_ragged")
+            # every structure larger than K: no padded slot, the compute-side list IS the list (as _frames_to_batch)
+            b = GraphBatch(at, nlist, edges, inv, graph_ptr=gp_host, device=device, validate=False,
+                           nlist_c=nlist if int(np.min(np.diff(gp))) > K else None)
+        else:
+            deg = torch.empty(N, dtype=torch.int32, device=device)
+            ctx.check(ctx.lib.ng_cutoff_count_ragged(ctx.handle, st, G, N, float(cutoff), ptr(pos), ptr(gp_dev), max_n,
+                                                     ptr(deg)), "ng_cutoff_count_ragged")
+            row_ptr = torch.empty(N + 1, dtype=torch.int32, device=device)
+            ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, N, ptr(deg), ptr(row_ptr)), "ng_exclusive_scan_i32")
+            nnz = int(deg.sum(dtype=torch.int64))      # the one host synchronisation, as in _frames_to_batch_cutoff
+            if nnz >= 2 ** 31:
+                raise ValueError("cutoff graph: more than 2^31 edges in one batch")
+            col = torch.empty(nnz, dtype=torch.int32, device=device)
+            dist = torch.empty(nnz, dtype=torch.float32, device=device)
+            row_of = torch.empty(nnz, dtype=torch.int32, device=device)
+            inv = torch.empty(N, dtype=torch.float32, device=device)
+            ctx.check(ctx.lib.ng_cutoff_fill_rows_ragged(ctx.handle, st, G, N, float(cutoff), float(scale), ptr(pos),
+                                                         ptr(gp_dev), max_n, ptr(row_ptr), ptr(col), ptr(dist), ptr(inv),
+                                                         ptr(row_of)), "ng_cutoff_fill_rows_ragged")
+            b = GraphBatch.from_csr(at, row_ptr, col, dist, inv, graph_ptr=gp_host, device=device, validate=False,
+                                    row_of=row_of)
+    b.positions, b.scale = pos, float(scale)
+    return b

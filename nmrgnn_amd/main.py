@@ -3,7 +3,8 @@
 Same arguments, options, CSV columns and per-phase timing line as the reference command.  Frames
 of a trajectory are independent graphs, so they are concatenated ``--frames-per-batch`` at a time into
 one device batch (one launch sequence per batch instead of one per frame) and their neighbour lists
-are built on the GPU (ng_knn_graph); the reference evaluates frame by frame with a CPU neighbour search.  The training / hyper-parameter-search commands of the reference are out of scope
+are built on the GPU (ng_knn_graph); the reference evaluates frame by frame with a CPU neighbour search.  With
+``--separate`` every file is a structure of its own, batched as a ragged batch (graph.structures_to_batch).  The training / hyper-parameter-search commands of the reference are out of scope
 (control plane)."""
 from __future__ import annotations
 
@@ -35,12 +36,18 @@ def _open_structure(struct_files):
 
 
 def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16, stride=1,
-                   frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False):
+                   frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False, separate=False):
     """Predict shifts for every ``stride``-th frame and write the reference's CSV.  Returns the timing
     buckets in seconds.  ``pbc``: neighbour lists under the minimum-image convention in each frame's box (its CRYST1
-    record); a frame without one is an error."""
+    record); a frame without one is an error.  ``separate``: every file is a structure of its own (see
+    :func:`_eval_separate`)."""
     if len(struct_files) == 0:
         raise ValueError('Must pass at least on structure file')
+    if separate and pbc:
+        raise ValueError('--separate and --pbc cannot be combined: periodic boxes are not supported on ragged batches')
+    if separate:
+        return _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going,
+                              device, echo)
     import torch
     from .graph import frames_to_batch
     from .library import check_peaks, load_model
@@ -98,6 +105,64 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     return timing
 
 
+def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, device, echo):
+    """``eval-struct --separate``: every file is a structure of its own, with all of its MODEL frames (every ``stride``-th,
+    counted per file).  The structure-frames of all files go ``frames_per_batch`` at a time into one ragged device batch
+    (graph.structures_to_batch); the CSV has a leading ``file`` column (the path as given), then the reference's."""
+    import torch
+    from .graph import structures_to_batch
+    from .library import check_peaks, load_model
+    from .structure import atoms_onehot, read_pdb
+
+    model = load_model(model_file, device=device)
+    timing = {'Structure': 0.0, 'Model Inference (MI355X)': 0.0, 'Parsing': 0.0}
+    t = time.perf_counter()
+    structs = [read_pdb(f) for f in struct_files]
+    atoms = [atoms_onehot(s.elements) for s in structs]
+    items = [(k, fr) for k, s in enumerate(structs) for fr in range(0, len(s), stride)]     # (file, frame)
+    timing['Structure'] += time.perf_counter() - t
+    model.build(atoms[0].shape[1])
+    model.freeze()
+    rows = []
+    for b0 in range(0, len(items), max(1, frames_per_batch)):
+        chunk = items[b0:b0 + max(1, frames_per_batch)]
+        t = time.perf_counter()
+        dev = model.engine.device
+        batch = structures_to_batch([atoms[k] for k, _ in chunk], [structs[k].frames[fr] for k, fr in chunk],
+                                    neighbor_number, device=dev)
+        torch.cuda.synchronize(dev)
+        timing['Structure'] += time.perf_counter() - t
+        t = time.perf_counter()
+        peaks = model(batch).cpu().numpy().reshape(-1)
+        gp = batch.graph_ptr_host
+        conf = []
+        for m, (k, fr) in enumerate(chunk):
+            try:
+                conf.append(check_peaks(atoms[k], peaks[gp[m]:gp[m + 1]]))
+            except Warning as w:
+                if not keep_going:
+                    raise
+                echo(f'{struct_files[k]} frame {fr}: {w}')
+                conf.append(np.zeros(gp[m + 1] - gp[m], dtype=bool))
+        timing['Model Inference (MI355X)'] += time.perf_counter() - t
+        t = time.perf_counter()
+        for m, (k, fr) in enumerate(chunk):
+            s = structs[k]
+            pk = np.round(peaks[gp[m]:gp[m + 1]].astype(np.float64), 2)
+            for i in range(s.n_atoms):
+                rows.append((struct_files[k], i, s.resnames[i], int(s.resids[i]), s.names[i], pk[i], bool(conf[m][i]),
+                             float(fr), fr))
+        timing['Parsing'] += time.perf_counter() - t
+        echo('|'.join(f'{k}:{v:5.2f}s' for k, v in timing.items()))
+    os.makedirs(os.path.dirname(os.path.abspath(output_csv)), exist_ok=True)
+    with open(output_csv, 'w', newline='') as f:
+        wr = csv.writer(f)
+        wr.writerow(['file', 'index', 'residues', 'resids', 'names', 'peaks', 'confident', 'time', 'frame'])
+        wr.writerows(rows)
+    echo(f'You can now find your result in {output_csv}')
+    return timing
+
+
 @main.command(name='eval-struct')
 @click.argument('struct-files', nargs=-1, type=click.Path(exists=True))
 @click.argument('output-csv')
@@ -108,10 +173,14 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
 @click.option('--frames-per-batch', default=32, help='Frames evaluated per device batch')
 @click.option('--keep-going', is_flag=True, help='Report implausible-shift warnings instead of aborting')
 @click.option('--pbc', is_flag=True, help='Minimum-image neighbour lists in each frame\'s periodic box (CRYST1)')
-def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, pbc):
+@click.option('--separate', is_flag=True,
+              help='Treat every struct file as a structure of its own (CSV gains a leading file column)')
+def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, pbc, separate):
     '''Predict NMR chemical shifts with specific file'''
+    if separate and pbc:
+        raise click.UsageError('--separate and --pbc cannot be combined')
     eval_structure(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch,
-                   keep_going, echo=click.echo, pbc=pbc)
+                   keep_going, echo=click.echo, pbc=pbc, separate=separate)
 
 
 if __name__ == '__main__':
