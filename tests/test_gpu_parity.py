@@ -27,6 +27,9 @@ CONFIGS = [
          edge_fc_layers=3),
     dict(atom_feature_size=256, edge_feature_size=64, edge_hidden_size=128, mp_layers=1, fc_layers=2,
          edge_fc_layers=2, fc_activation='relu'),
+    # F = 128 with E <= 3: the generic MPLayer's wide-lane backward at 8 lanes per atom (csrc/mp_csr.hip)
+    dict(atom_feature_size=128, edge_feature_size=3, edge_hidden_size=128),
+    dict(atom_feature_size=128, edge_feature_size=1, edge_hidden_size=16, mp_activation='tanh', edge_fc_layers=6),
 ]
 
 
@@ -355,6 +358,38 @@ def test_full_size_gradients_match_oracle(gpu_device, edge_table):
     assert np.max(np.abs(pk - ref_pk)) < PEAK_ATOL
     errs = {k: rel_err(grads[k], g) for k, g in ref_g.items()}
     print("full-size gradient rel. errors:", {k: f"{v:.1e}" for k, v in errs.items()})
+    assert max(errs.values()) < GRAD_RTOL, errs
+
+
+@pytest.mark.parametrize("F,fc_activation", [(128, "softplus"), (64, "relu")])
+def test_split_gemm_sized_step_matches_oracle(gpu_device, F, fc_activation):
+    """one training step at 24 graphs x 200 atoms (N = 4800 >= 4096 rows, graph span 200): at F = 128 the generic MPLayer
+    with its slab-window aggregate / edge gradient and the split-operand dense GEMMs; at F = 64 with fc_activation = relu the
+    layered edge MLP at split-GEMM size.  Peaks and every gradient tensor against the float64 oracle over all 24 graphs."""
+    from nmrgnn_amd import synth
+    from nmrgnn_amd.engine import Engine
+    from nmrgnn_amd.graph import GraphBatch
+    from helpers import oracle_batch_forward_backward
+    hp = make_hp(atom_feature_size=F, edge_feature_size=3, edge_hidden_size=128, fc_activation=fc_activation)
+    b = synth.make_batch(24, 200, 16, 10, 0.05, seed=F + 1)
+    eng = Engine(hp, 10, device=gpu_device, seed=77)
+    sd = randomize_biases(eng, scale=0.05)
+    gb = GraphBatch(b["atoms"], b["nlist"], b["edges"], b["inv_degree"], graph_ptr=b["graph_ptr"], device=gpu_device)
+    N, K = b["edges"].shape
+    xi = eng.randn(N * K, seed=17)
+    mask = eng.dropout_mask(N * (F // 2), seed=18)
+    dpe = np.random.default_rng(F).standard_normal(N).astype(np.float32)
+    import torch
+    peaks = eng.forward(gb, training=True, noise=xi, dropout_mask=mask)
+    eng.backward(torch.from_numpy(dpe).to(gpu_device))
+    pk = peaks.cpu().numpy()
+    grads = eng.params.grads_dict()
+    ref_pk, ref_g = oracle_batch_forward_backward(
+        b, sd, hp_to_oracle(hp), dpe.astype(np.float64), xi=xi.cpu().numpy().reshape(N, K).astype(np.float64),
+        mask=(mask.cpu().numpy().reshape(N, F // 2) > 0).astype(np.float64), workers=16)
+    assert np.max(np.abs(pk - ref_pk)) < PEAK_ATOL, np.max(np.abs(pk - ref_pk))
+    errs = {k: rel_err(grads[k], g) for k, g in ref_g.items()}
+    print(f"F={F} {fc_activation} split-GEMM-sized step gradient rel. errors:", {k: f"{v:.1e}" for k, v in errs.items()})
     assert max(errs.values()) < GRAD_RTOL, errs
 
 
