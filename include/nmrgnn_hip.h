@@ -234,7 +234,7 @@ int ng_positions_grad_csr(ng_ctx*, void* stream, int64_t N, int64_t nnz, const f
 /* ng_positions_grad_pbc / _csr_pbc: the same gradient for lists built in periodic boxes (ng_knn_graph_pbc,
  *   ng_cutoff_fill_rows_pbc): along each edge the minimum-image vector, recomputed from the raw positions by the function
  *   that built the edge.  n = atoms per frame (frame of row i = i / n, N % n == 0), box / triclinic as ng_knn_graph_pbc.
- *   No gradient with respect to the box. */
+ *   The gradient with respect to the box is ng_box_grad. */
 int ng_positions_grad_pbc(ng_ctx*, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist,
                           const float* edges, const float* dd, float scale, const int32_t* csc_ptr, const int32_t* csc_edge,
                           int n, const float* box, int triclinic, float* dpos);
@@ -242,6 +242,21 @@ int ng_positions_grad_csr_pbc(ng_ctx*, void* stream, int64_t N, int64_t nnz, con
                               const int32_t* col, const int32_t* row_of, const float* dd, float scale,
                               const int32_t* csc_ptr, const int32_t* csc_edge, int n, const float* box, int triclinic,
                               float* dpos);
+/* ng_box_grad / _csr: the box side of the same chain rule, per frame g in float64.  For a live slot e = (i -> j) with
+ *   u_e the displacement that built it (csrc/pbc.cuh; r_j - r_i when open), p_e = dd_e * scale * u_e / |u_e| and n_e the
+ *   integer image triple with u_e = (r_j - r_i) + n_e h_g (h_g the frame's rows a, b, c, box [G][9]):
+ *     strain [G][9] = sum_e u_e (x) p_e   (symmetric: d/d(eps) of r -> r (I + eps), h -> h (I + eps); the virial is -strain)
+ *     dvec   [G][9] = sum_e n_e (x) p_e   (dE/dh at fixed positions; zeros when triclinic = -1, open; may be NULL)
+ *   at fixed lists and images.  G frames, graph_ptr [G+1] on the device (uniform frames: arange * n; a ragged batch its own).
+ *   Padded form: nlist / edges / dd [N][K] (live when edges > 0 and dd != 0); CSR form: row_ptr [N+1], col / dd [nnz].
+ *   triclinic: -1 open, 0 / 1 with box as ng_knn_graph_pbc.  Two launches on workspace scratch, no atomics: bitwise
+ *   deterministic. */
+int ng_box_grad(ng_ctx*, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist, const float* edges,
+                const float* dd, float scale, int G, const int32_t* graph_ptr, const float* box, int triclinic, double* strain,
+                double* dvec);
+int ng_box_grad_csr(ng_ctx*, void* stream, int64_t N, int64_t nnz, const float* pos, const int32_t* row_ptr,
+                    const int32_t* col, const float* dd, float scale, int G, const int32_t* graph_ptr, const float* box,
+                    int triclinic, double* strain, double* dvec);
 
 /* ---- node path ----------------------------------------------------------------------------- */
 /* embed_layer, nmrgnn/model.py:241,262: h0 = atoms[N,C] @ Wemb[C,F] */

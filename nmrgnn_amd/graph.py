@@ -279,6 +279,23 @@ class GraphBatch:
             raise ValueError("positions_grad: this batch was not built from positions (frames_to_batch / frames_to_batch_cutoff)")
         return _positions_grad(self._positions_state(), dedges)
 
+    def box_grad(self, dedges):
+        """``(strain, dvec)``, both [G, 3, 3] float64 on the device, from dL/d(edges) ``dedges`` in one library call
+        (include/nmrgnn_hip.h: ng_box_grad), at fixed lists and images.  Per frame, over its live edges u (the displacement
+        that built the edge), p = dL/du and n the image triple with u = r_j - r_i + n h:
+        ``strain`` = sum u (x) p, the derivative with respect to a homogeneous strain of positions and box together (the
+        virial is ``-strain``); ``dvec`` = sum n (x) p = dL/d(lattice vectors) [rows a, b, c] at fixed positions, zero without
+        a box.  Works on batches built from positions (frames_to_batch, frames_to_batch_cutoff, structures_to_batch)."""
+        if self.positions is None:
+            raise ValueError("box_grad: this batch was not built from positions (frames_to_batch / frames_to_batch_cutoff / "
+                             "structures_to_batch)")
+        return _box_grad(self._box_state(), dedges)
+
+    def _box_state(self):
+        """what box_grad reads, without the batch itself (as _positions_state; no incoming-edge lists needed)"""
+        return (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
+                self.edges.detach(), self.row_ptr, self.box, int(self.box_triclinic), self.G, self.graph_ptr)
+
     def _positions_state(self):
         """what positions_grad reads, without the batch itself (an autograd node keeps this, not the batch whose edges are
         its output: no reference cycle)"""
@@ -419,34 +436,79 @@ def _positions_grad(state, dedges):
     return dpos
 
 
+def _box_grad(state, dedges, want_dvec=True):
+    import ctypes as C
+    from . import _lib
+    from ._lib import ptr
+    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, box, tric, G, graph_ptr = state
+    ctx = ctx or _lib.get_context(device.index)
+    dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
+    if dd.numel() != edges.numel():
+        raise ValueError(f"box_grad: dedges has {dd.numel()} entries for {edges.numel()} edges")
+    strain = torch.empty(G, 3, 3, dtype=torch.float64, device=device)
+    dvec = torch.empty(G, 3, 3, dtype=torch.float64, device=device) if want_dvec else None
+    tric = tric if box is not None else -1          # -1: open boundaries, dvec = 0
+    with torch.cuda.device(device):
+        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        if is_csr:
+            ctx.check(ctx.lib.ng_box_grad_csr(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist), ptr(dd),
+                                              scale, G, ptr(graph_ptr), ptr(box), tric, ptr(strain), ptr(dvec)),
+                      "ng_box_grad_csr")
+        else:
+            ctx.check(ctx.lib.ng_box_grad(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale, G,
+                                          ptr(graph_ptr), ptr(box), tric, ptr(strain), ptr(dvec)), "ng_box_grad")
+    return strain, dvec
+
+
+def _box_dims_grad(dims, dvec):
+    """d(loss)/d(a, b, c, alpha, beta, gamma) from dvec = d(loss)/d(lattice vectors) [G, 3, 3]: the chain rule through the
+    float64 restatement of the conversion (pbc.triclinic_vectors_torch); a shared [6] box sums over the frames"""
+    from .pbc import triclinic_vectors_torch
+    with torch.enable_grad():
+        d = dims.detach().to(dtype=torch.float64).requires_grad_(True)
+        h = triclinic_vectors_torch(d.expand(dvec.shape[0], 6) if d.dim() == 1 else d)
+        (g,) = torch.autograd.grad(h, d, dvec.to(device=d.device))
+    return g.to(dtype=dims.dtype)
+
+
 class _EdgesOfPositions(torch.autograd.Function):
     """edges = |r_i - r_j| * scale of a batch built from ``frames`` (the batch's own edges tensor, not a copy); the
-    backward is ng_positions_grad at fixed neighbour lists"""
+    backward is ng_positions_grad at fixed neighbour lists, and, for a ``box`` tensor that requires grad, ng_box_grad
+    chained through the box conversion"""
 
     @staticmethod
-    def forward(ctx, frames, build):
+    def forward(ctx, frames, box, build):
         # a copy of the positions: an in-place update of ``frames`` before the backward must not move the lists' atoms
-        batch = build(frames.detach().clone())
-        ctx.state = batch._positions_state()
-        ctx.frames_shape, ctx.frames_device = frames.shape, frames.device
+        batch = build(frames.detach().clone() if isinstance(frames, torch.Tensor) else frames)
+        ctx.state = batch._positions_state() if ctx.needs_input_grad[0] else None
+        ctx.box_state = batch._box_state() if ctx.needs_input_grad[1] else None
+        ctx.box_dims = box.detach().clone() if ctx.needs_input_grad[1] else None
+        if ctx.needs_input_grad[0]:
+            ctx.frames_shape, ctx.frames_device = frames.shape, frames.device
         return batch.edges
 
     @staticmethod
     def backward(ctx, dedges):
-        dpos = _positions_grad(ctx.state, dedges)
-        return dpos.reshape(ctx.frames_shape).to(ctx.frames_device), None
+        dpos = dbox = None
+        if ctx.needs_input_grad[0]:
+            dpos = _positions_grad(ctx.state, dedges).reshape(ctx.frames_shape).to(ctx.frames_device)
+        if ctx.needs_input_grad[1]:
+            dbox = _box_dims_grad(ctx.box_dims, _box_grad(ctx.box_state, dedges)[1])
+        return dpos, dbox, None
 
 
-def _positions_batch(frames, build):
-    """``build(frames)`` with edges that carry a grad_fn back to ``frames`` when they require grad"""
-    if not (isinstance(frames, torch.Tensor) and frames.requires_grad and torch.is_grad_enabled()):
+def _positions_batch(frames, build, box=None):
+    """``build(frames)`` with edges that carry a grad_fn back to ``frames`` and to a ``box`` tensor when they require
+    grad"""
+    box_grad = isinstance(box, torch.Tensor) and box.requires_grad
+    if not ((isinstance(frames, torch.Tensor) and frames.requires_grad or box_grad) and torch.is_grad_enabled()):
         return build(frames)
     holder = {}
 
     def make(f):
         holder["batch"] = build(f)
         return holder["batch"]
-    edges = _EdgesOfPositions.apply(frames, make)
+    edges = _EdgesOfPositions.apply(frames, box if box_grad else None, make)
     batch = holder.pop("batch")
     batch.edges = edges         # the same storage the kernels read, now with a grad_fn
     return batch
@@ -458,10 +520,13 @@ def _frame_count(frames):
 
 
 def _host_box(box, frames):
-    """None, or (vectors [G, 9] float32, triclinic flag, smallest perpendicular widths [G]): validated on the host"""
+    """None, or (vectors [G, 9] float32, triclinic flag, smallest perpendicular widths [G]): validated on the host.  A torch
+    ``box`` gives what its detached host copy gives."""
     if box is None:
         return None
     from .pbc import prepare
+    if isinstance(box, torch.Tensor):
+        box = box.detach().cpu().numpy()
     return prepare(box, _frame_count(frames))
 
 
@@ -480,9 +545,12 @@ def frames_to_batch(atoms, frames, neighbor_number=16, scale=0.1, device=None, b
     ``box``: periodic boxes under the minimum-image convention (csrc/pbc.cuh), ``(a, b, c, alpha, beta, gamma)`` in
     Angstrom and degrees, [6] for every frame or [G, 6] one per frame (nmrgnn_amd.pbc: orthorhombic and reduced triclinic
     boxes).  Positions may lie anywhere; nothing is wrapped.  The batch keeps the box (``GraphBatch.box``) and its
-    gradient uses the minimum-image vector of each edge.  None: open boundaries, as before."""
+    gradient uses the minimum-image vector of each edge.  None: open boundaries, as before.  A torch ``box`` that requires
+    grad (and grad mode on) gets ``box.grad`` from a loss of ``model(batch)``: ``GraphBatch.box_grad`` chained through the
+    box conversion (nmrgnn_amd.pbc.triclinic_vectors_torch), at fixed lists and images, summed over the frames of a
+    shared [6] box; the lists are those of ``box.detach().cpu().numpy()``."""
     pbc = _host_box(box, frames)
-    return _positions_batch(frames, lambda f: _frames_to_batch(atoms, f, neighbor_number, scale, device, pbc))
+    return _positions_batch(frames, lambda f: _frames_to_batch(atoms, f, neighbor_number, scale, device, pbc), box)
 
 
 def _frames_to_batch(atoms, frames, neighbor_number, scale, device, pbc=None):
@@ -531,7 +599,7 @@ def frames_to_batch_cutoff(atoms, frames, cutoff=4.0, scale=0.1, device=None, bo
     pbc = _host_box(box, frames)
     if pbc is not None and len(pbc[2]) and not float(cutoff) < 0.5 * float(pbc[2].min()):
         raise ValueError(f"cutoff {cutoff} must be below half the smallest box width ({0.5 * float(pbc[2].min()):.6g})")
-    return _positions_batch(frames, lambda f: _frames_to_batch_cutoff(atoms, f, cutoff, scale, device, pbc))
+    return _positions_batch(frames, lambda f: _frames_to_batch_cutoff(atoms, f, cutoff, scale, device, pbc), box)
 
 
 def _frames_to_batch_cutoff(atoms, frames, cutoff, scale, device, pbc=None):

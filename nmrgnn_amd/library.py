@@ -124,7 +124,7 @@ def check_peaks(atoms, peaks, cutoff_sigma=4, warn_sigma=2.5):
     return confident
 
 
-def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_number=16, box=None):
+def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_number=16, box=None, virial=False):
     """Chemical-shift restraint of one structure: ``(energy, forces)`` with
 
         energy = sum_i w_i (delta_pred_i - delta_exp_i)^2          ppm^2, a 0-d device tensor
@@ -141,13 +141,20 @@ def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_num
     overwrites the engine's parameter gradient buffer (``engine.params.grad``) as a side effect.
 
     ``box`` ``(a, b, c, alpha, beta, gamma)``: a periodic box under the minimum-image convention, as ``frames_to_batch``
-    takes it; the forces are then those of ``model(frames_to_batch(atoms, pos, box=box))``."""
+    takes it; the forces are then those of ``model(frames_to_batch(atoms, pos, box=box))``.
+
+    ``virial=True`` returns ``(energy, forces, virial)``: ``virial`` [3, 3] float64 ppm^2 on the device is ``-strain`` of
+    ``GraphBatch.box_grad`` for the same edge gradient, the negative derivative of the energy with respect to a homogeneous
+    strain of positions and box together, at fixed lists and images (its pressure contribution is trace / (3 V)).  One more
+    library call, no torch autograd; energy and forces are bitwise those of ``virial=False``.  Without a box it is the
+    same sum over the open-boundary edges."""
     import torch
     from .graph import frames_to_batch
     if model.engine is None:
         model.build(int(np.asarray(atoms).shape[-1]) if not isinstance(atoms, torch.Tensor) else int(atoms.shape[-1]))
     eng = model.engine
     pos = positions.detach() if isinstance(positions, torch.Tensor) else positions
+    box = box.detach() if isinstance(box, torch.Tensor) else box
     batch = frames_to_batch(atoms, pos, neighbor_number=neighbor_number, device=eng.device, box=box)
     if batch.G != 1:
         raise ValueError("shift_restraint: one structure [n, 3] at a time")
@@ -165,4 +172,7 @@ def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_num
     dedges = torch.empty(batch.edges.shape, dtype=torch.float32, device=eng.device)
     eng.backward(dpeaks, edge_grad=dedges)
     forces = -batch.positions_grad(dedges)[0]
+    if virial:
+        from .graph import _box_grad
+        return energy, forces, -_box_grad(batch._box_state(), dedges, want_dvec=False)[0][0]
     return energy, forces

@@ -6,6 +6,9 @@ and of MDAnalysis ``u.dimensions`` — and converted to lower-triangular lattice
 ``|b_x| <= a_x/2``, ``|c_x| <= a_x/2``, ``|c_y| <= b_y/2`` up to a small relative tolerance for the rounding of the angle
 conversion (the GROMACS rhombic dodecahedron and truncated octahedron qualify; the octahedron sits on the ``c_y`` bound).
 Everything else raises ``ValueError`` here, before any device work.
+
+``triclinic_vectors_torch`` restates the conversion in float64 torch for the Jacobian of the box gradient
+(``GraphBatch.box_grad``); the kernels keep reading what :func:`prepare` gives.
 """
 from __future__ import annotations
 
@@ -42,6 +45,22 @@ def triclinic_vectors(dims):
     if not cz2 > 1e-12 * c * c:
         raise ValueError(f"box: angles {al}, {be}, {ga} give no cell")
     return np.array([[a, 0.0, 0.0], [b * cg, b * sg, 0.0], [cx, cy, np.sqrt(cz2)]])
+
+
+def triclinic_vectors_torch(dims):
+    """float64 torch restatement of :func:`triclinic_vectors`: ``[..., 6]`` -> ``[..., 3, 3]`` (rows a, b, c), differentiable
+    everywhere, at 90 degrees too (cos(pi/2) is then ~6e-17 instead of the exact zero of ``_cos_sin``).  It serves the
+    Jacobian d(vectors)/d(a, b, c, alpha, beta, gamma); the values the kernels see stay those of :func:`prepare`."""
+    import torch
+    d = dims.to(torch.float64)
+    a, b, c = d[..., 0], d[..., 1], d[..., 2]
+    al, be, ga = torch.deg2rad(d[..., 3]), torch.deg2rad(d[..., 4]), torch.deg2rad(d[..., 5])
+    ca, cb, cg, sg = torch.cos(al), torch.cos(be), torch.cos(ga), torch.sin(ga)
+    cx = c * cb
+    cy = c * (ca - cb * cg) / sg
+    cz = torch.sqrt(c * c - cx * cx - cy * cy)
+    z = torch.zeros_like(a)
+    return torch.stack([torch.stack([a, z, z], -1), torch.stack([b * cg, b * sg, z], -1), torch.stack([cx, cy, cz], -1)], -2)
 
 
 def widths(vecs):
