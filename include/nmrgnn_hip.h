@@ -286,7 +286,11 @@ int ng_mp_layer_wants_aggregate(int F, int E, int K);
 
 /* backward of the above.  csc_ptr[N+1], csc_edge[nnz]: incoming-edge lists (edge id = i*K+j
  * grouped by target nlist[i,j]); dh_out [N,F] upstream; writes dh_in (overwrite),
- * de (accumulate if de_accum else overwrite), dw [F,F,E] (overwrite). */
+ * de (accumulate if de_accum else overwrite), dw [F,F,E] (overwrite).
+ * dw == NULL: input gradients only.  No path forms the weight gradient then: no dw products, no per-workgroup partials, no
+ * queued second-stage sums, no rebuilt aggregate (the F = 64 node kernel runs its dh-only form, the generic / layered / CSR
+ * paths skip the dw GEMM).  dh_in and de are bit for bit those of the same call with dw given.  The same holds for
+ * ng_mp_layer_bwd_rec and ng_mp_layer_bwd_csr. */
 int ng_mp_layer_bwd(ng_ctx*, void* stream, int64_t N, int K, int F, int E, int act,
                     const float* h, const int32_t* nlist, const float* e, const float* inv_degree,
                     const float* w, const float* A_save, const float* s_save,
@@ -445,7 +449,10 @@ int ng_fc_block_fwd(ng_ctx*, void* stream, int64_t N, int F, int L, int act, con
 
 /* backward of ng_fc_block_fwd.  x[l] = layer inputs (x[0] = block input, x[l+1] = y[l] of the forward call),
  * g = block output, dg its gradient; writes dx (gradient w.r.t. x[0]) and dW[l], db[l] (overwrites).  The
- * activation outputs are rebuilt as x[l+1] - x[l].  scratch: ng_fc_block_scratch_floats(N, F, L) floats. */
+ * activation outputs are rebuilt as x[l+1] - x[l].  scratch: ng_fc_block_scratch_floats(N, F, L) floats.
+ * dW == db == NULL (the pointer arrays themselves): dx only — the fused kernel (both bodies) runs its form without bias
+ * sums, dW products and partials, the layered path skips the column sums, the dW GEMMs and the reductions; dx is bit for
+ * bit that of the same call with dW / db given.  One of the two NULL is refused. */
 /* floats of scratch ng_fc_block_bwd needs for this shape (0 when the fused kernel handles it) */
 int64_t ng_fc_block_scratch_floats(int64_t N, int F, int L);
 int ng_fc_block_bwd(ng_ctx*, void* stream, int64_t N, int F, int L, int act, const float* const* x,
@@ -472,6 +479,9 @@ int ng_head_fwd(ng_ctx*, void* stream, int64_t N, int Fh, int C, const float* g,
 int ng_head_fwd_dropout(ng_ctx*, void* stream, int64_t N, int Fh, int C, const float* g, uint64_t seed, uint64_t offset,
                         float keep, float* mask_out, const float* Wout, const float* bout, const float* atoms,
                         const float* peak_std, const float* peak_avg, float* peaks);
+/* backward of ng_head_fwd: dg [N,Fh] (overwrite), dWout [Fh,C] and dbout [C] (overwrite).  dWout == dbout == NULL: dg only,
+ * bit for bit that of the same call with them given; no weight-gradient sums, partials or reductions are formed (fast and
+ * generic forms).  One of the two NULL is refused. */
 int ng_head_bwd(ng_ctx*, void* stream, int64_t N, int Fh, int C, const float* g,
                 const float* drop_mask, const float* Wout, const float* atoms,
                 const float* peak_std, const float* dpeaks, float* dg, float* dWout, float* dbout);
@@ -538,6 +548,16 @@ int ng_edge_table_scatter(ng_ctx*, void* stream, int64_t n, int E, int T, int ro
  *   dpred written for backward; loss_out is one device float. */
 int ng_loss_l2(ng_ctx*, void* stream, int64_t N, int G, const int32_t* graph_ptr, const float* y,
                const float* w, const float* pred, float* loss_out, float* dpred);
+
+/* Replica-averaged chemical-shift restraint (library.ShiftRestraint).  peaks [R*n] replica-major (replica r's atom i at
+ * r*n + i, the row order of R frames of one topology in one batch), targets / weights [n]:
+ *   mean_i = (sum_r peaks[r*n+i]) / R        float32, summed in replica order (R = 1: exactly peaks[i])
+ *   energy[0] = sum_i w_i (mean_i - y_i)^2   ONE double: float32 terms (d*d)*w summed in float64 in a fixed order
+ *   dpeaks[r*n+i] = w_i * (2 * (mean_i - y_i)) / R   (R = 1: the bits of w * (2 * diff))
+ * Two launches, no atomics (bitwise deterministic), asynchronous, capturable in a graph once the context's scratch holds
+ * n / 256 doubles.  R * n below 2^31; n = 0 writes energy 0. */
+int ng_restraint_loss(ng_ctx*, void* stream, int R, int64_t n, const float* peaks, const float* targets, const float* weights,
+                      double* energy, float* dpeaks);
 
 /* NameLoss with balance s in [0,1], nmrgnn/losses.py:4-15,30-39, batched over graphs:
  *   loss = mean_g [ s*l2_g + (1-s)*(1 - r_g) ],  r = cov/(m*sqrt(clip(var_x*var_y,0,1e32))) with the

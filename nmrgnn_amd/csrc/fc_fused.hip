@@ -443,7 +443,9 @@ __host__ __device__ inline int fc_part_floats(int L) { return L * FC_F * FC_F + 
 // rows of the tile contracted by MFMA k-step T (0..15), lane group g: conflict-free for row strides == 4 mod 16
 __device__ __forceinline__ int kstep_row(int T, int g) { return (T & 3) + 4 * g + 16 * (T >> 2); }
 
-template <int NL, bool H2, int ACT = -1>      // ACT: compile-time activation (softplus) or -1 = from the arguments, as in the forward
+// ACT: compile-time activation (softplus) or -1 = from the arguments, as in the forward.  DW = false: dx only (ng_fc_block_bwd with
+// dW == db == NULL) — no bias sums, no dW products, no partial; dx is the same bits
+template <int NL, bool H2, bool DW, int ACT = -1>
 __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
   const int act_ = ACT >= 0 ? ACT : a.act;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -494,7 +496,7 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
   for (int l = 0; l < NL; ++l) {
     accW[l][0] = f32x4{0.f, 0.f, 0.f, 0.f};
     accW[l][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (H2) *reinterpret_cast<float4*>(s_accb + (tid >> 4) * (NL * FC_F) + l * FC_F + 4 * (tid & 15)) = f4zero();
+    if (H2 && DW) *reinterpret_cast<float4*>(s_accb + (tid >> 4) * (NL * FC_F) + l * FC_F + 4 * (tid & 15)) = f4zero();
     else accb[H2 ? 0 : l] = f4zero();
   }
 
@@ -581,12 +583,12 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
             p.z *= act_grad_from_out(act_, s.z); p.w *= act_grad_from_out(act_, s.w);
           }
         }
-        if (H2) {
+        if (DW && H2) {
           float4* sa = reinterpret_cast<float4*>(s_accb + er * (NL * FC_F) + l * FC_F + 4 * ec);
           float4 t = *sa;
           t.x += p.x; t.y += p.y; t.z += p.z; t.w += p.w;
           *sa = t;
-        } else {
+        } else if (DW) {
           accb[H2 ? 0 : l].x += p.x; accb[H2 ? 0 : l].y += p.y; accb[H2 ? 0 : l].z += p.z; accb[H2 ? 0 : l].w += p.w;
         }
         if (H2) {
@@ -607,13 +609,13 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
           *reinterpret_cast<float4*>(Pt + o) = p;
         }
       }
-      if (H2) {
+      if (H2 && DW) {
         wm = fc_wave_min(wm);
         if (lane == 63) s_wmin[wave] = wm;
       }
       NG_LDS_BARRIER();
       // ---- dW_l[k][n] += sum_rows x[row][k] P[row][n]: D rows i = n, cols j = k
-      if (H2) {
+      if (DW && H2) {
         // dW on the fp16 pipe: D[n][k] += sum_rows P[row][n] x[row][k], the contraction over the tile's rows in two 32-deep
         // steps.  The P rows carry different scales S_r, so the x operand takes the inverse: x'[r] = x[r] * S_ref / S_r with
         // S_ref the smallest S of the tile (its largest row; ratio <= 1), the step's product goes into a fresh accumulator and
@@ -676,7 +678,7 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
             }
           }
         }
-      } else if (!last || pr == 0) {
+      } else if (DW && (!last || pr == 0)) {
         const float* xb = Xt + 16 * kt + a16;
         const float* p0 = Pt + 16 * (2 * pr) + a16;
 #pragma unroll
@@ -761,6 +763,7 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
     }
   }
 
+  if (!DW) return;
   // ---- this workgroup's partial: dW_l [64][nout] then db_l [nout]
   float* part = a.partial + (int64_t)blockIdx.x * a.part_stride;
 #pragma unroll
@@ -793,13 +796,13 @@ __device__ __forceinline__ void fc_bwd_body(const FcBwdArgs& a) {
 
 // both bodies in one kernel (see fc_fwd_kernel): weights beyond the piece range select the fp32 body for the launch; the
 // gradient operands of the piece body carry per-row scales, its x operand a per-column one — range-safe by construction
-template <int NL, bool H2>
+template <int NL, bool H2, bool DW>
 __global__ __launch_bounds__(512, 1) void fc_bwd_kernel(FcBwdArgs a) {
   if (H2 && !(a.guard.word && (range_guard_raised(a.guard) || wimage_flag_raised(a.wflag)))) {
-    if (a.act == NG_ACT_SOFTPLUS) fc_bwd_body<NL, true, NG_ACT_SOFTPLUS>(a);
-    else fc_bwd_body<NL, true>(a);
+    if (a.act == NG_ACT_SOFTPLUS) fc_bwd_body<NL, true, DW, NG_ACT_SOFTPLUS>(a);
+    else fc_bwd_body<NL, true, DW>(a);
   } else {
-    fc_bwd_body<NL, false>(a);
+    fc_bwd_body<NL, false, DW>(a);
   }
 }
 
@@ -907,9 +910,10 @@ int fc_fused_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int L, int act, const f
   const int grid = (int)std::min<int64_t>(ntiles, (int64_t)ctx->num_cu);
   float* ws = (float*)workspace(ctx, (fc_fused_pack_floats(L) + (size_t)(grid + 1) * part) * 4);
   if (!ws) return NG_ERR_NOMEM;
-  float* partial = ws + fc_fused_pack_floats(L);
-  float* summed = partial + (size_t)grid * part;
-  if (float* dp = deferred_partials(ctx, (size_t)grid * part)) partial = dp;
+  const bool want = dW != nullptr;      // NULL: dx only, no partials, no reduction
+  float* partial = want ? ws + fc_fused_pack_floats(L) : nullptr;
+  if (want)
+    if (float* dp = deferred_partials(ctx, (size_t)grid * part)) partial = dp;
   const bool h2 = fc_h2_on();
   RangeGuard guard{nullptr, 0};
   if (h2) {
@@ -930,8 +934,10 @@ int fc_fused_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int L, int act, const f
     ProfScope ps(ctx, st, "fc_fused_bwd");
 #define NG_FCB(LL)                                                                                           \
   do {                                                                                                       \
-    if (h2) hipLaunchKernelGGL((fc_bwd_kernel<LL, true>), dim3(grid), dim3(512), lds, st, a);                \
-    else hipLaunchKernelGGL((fc_bwd_kernel<LL, false>), dim3(grid), dim3(512), lds, st, a);                  \
+    if (h2 && want) hipLaunchKernelGGL((fc_bwd_kernel<LL, true, true>), dim3(grid), dim3(512), lds, st, a);  \
+    else if (want) hipLaunchKernelGGL((fc_bwd_kernel<LL, false, true>), dim3(grid), dim3(512), lds, st, a);  \
+    else if (h2) hipLaunchKernelGGL((fc_bwd_kernel<LL, true, false>), dim3(grid), dim3(512), lds, st, a);    \
+    else hipLaunchKernelGGL((fc_bwd_kernel<LL, false, false>), dim3(grid), dim3(512), lds, st, a);           \
   } while (0)
     switch (L) {
       case 2: NG_FCB(2); break;
@@ -942,6 +948,7 @@ int fc_fused_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int L, int act, const f
 #undef NG_FCB
     NG_HIP(ctx, hipGetLastError());
   }
+  if (!want) return NG_OK;
   ProfScope ps(ctx, st, "reduce_partials");
   ReduceSegs sg{};
   sg.n = 2 * L;
@@ -950,7 +957,6 @@ int fc_fused_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int L, int act, const f
     sg.begin[l] = l * FC_F * FC_F; sg.len[l] = FC_F * nout; sg.dst[l] = dW[l];
     sg.begin[L + l] = L * FC_F * FC_F + l * FC_F; sg.len[L + l] = nout; sg.dst[L + l] = db[l];
   }
-  (void)summed;
   return reduce_seg_or_defer(ctx, st, partial, grid, fc_part_floats(L), part, sg);
 }
 
@@ -986,18 +992,19 @@ __global__ __launch_bounds__(256) void fc_dp_kernel(int64_t N, int No, int64_t r
         d.z *= act_grad_from_out(act, sv.z); d.w *= act_grad_from_out(act, sv.w);
       }
       reinterpret_cast<float4*>(dP)[o] = d;
-      cs.x += d.x; cs.y += d.y; cs.z += d.z; cs.w += d.w;
+      if (partial) { cs.x += d.x; cs.y += d.y; cs.z += d.z; cs.w += d.w; }
       amax = fmaxf(fmaxf(amax, fmaxf(fabsf(d.x), fabsf(d.y))), fmaxf(fabsf(d.z), fabsf(d.w)));
     }
-    *reinterpret_cast<float4*>(fc_red + r * No + 4 * q) = cs;
+    if (partial) *reinterpret_cast<float4*>(fc_red + r * No + 4 * q) = cs;
   }
+  if (blockmax) block_max_store(amax, blockmax);
+  if (!partial) return;      // no bias gradient wanted
   __syncthreads();
   for (int it = threadIdx.x; it < No; it += 256) {
     float t = 0.f;
     for (int rr = 0; rr < RL; ++rr) t += fc_red[rr * No + it];
     partial[(int64_t)blockIdx.x * No + it] = t;
   }
-  if (blockmax) block_max_store(amax, blockmax);
 }
 }  // namespace ng
 
@@ -1034,7 +1041,9 @@ extern "C" int ng_fc_block_bwd(ng_ctx* ctx, void* stream, int64_t N, int F, int 
   if (!ctx) return NG_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   NG_REQUIRE(ctx, L >= 2, "fc_block: at least two layers");
+  NG_REQUIRE(ctx, (dW == nullptr) == (db == nullptr), "fc_block_bwd: dW and db are both given or both NULL");
   if (N > 0 && fc_fused_bwd_supported(F, L)) return fc_fused_bwd(ctx, st, N, L, act, x, g, W, dg, dx, dW, db);
+  const bool want = dW != nullptr;      // NULL: dx only — no bias sums, no dW GEMMs, no reductions
   // layer by layer.  Per layer ONE pass forms dP = dY * act'(s) (s = x_{l+1} - x_l rebuilt on the fly, or g for the last
   // layer) together with the bias gradient's column sums; the dX and dW GEMMs then read dP (before: a pass that wrote
   // s, then three consumers that each re-read dY and s).  scratch: [3][N][F] = dP | dX ping | dX pong
@@ -1049,6 +1058,7 @@ extern "C" int ng_fc_block_bwd(ng_ctx* ctx, void* stream, int64_t N, int F, int 
     const int No = l == L - 1 ? F / 2 : F;
     const bool resid = l < L - 1;
     if (N == 0) {
+      if (!want) continue;
       NG_HIP(ctx, hipMemsetAsync(dW[l], 0, (size_t)F * No * 4, st));
       NG_HIP(ctx, hipMemsetAsync(db[l], 0, (size_t)No * 4, st));
       continue;
@@ -1057,9 +1067,12 @@ extern "C" int ng_fc_block_bwd(ng_ctx* ctx, void* stream, int64_t N, int F, int 
     const int nb = (int)std::min<int64_t>(cdiv(N, rl), (int64_t)ctx->num_cu * 4);
     const int64_t rows = cdiv(cdiv(N, nb), rl) * rl;
     const int nblk = (int)cdiv(N, rows);
-    float* partial = deferred_partials(ctx, (size_t)nblk * No);
-    if (!partial) partial = (float*)aux_workspace(ctx, (size_t)nblk * No * 4);
-    if (!partial) return NG_ERR_NOMEM;
+    float* partial = nullptr;
+    if (want) {
+      partial = deferred_partials(ctx, (size_t)nblk * No);
+      if (!partial) partial = (float*)aux_workspace(ctx, (size_t)nblk * No * 4);
+      if (!partial) return NG_ERR_NOMEM;
+    }
     const float* gsc = nullptr;         // the same dP feeds both products: one scale, from the dP kernel's block maxima
     {
       ProfScope ps(ctx, st, "fc_dP");
@@ -1068,17 +1081,22 @@ extern "C" int ng_fc_block_bwd(ng_ctx* ctx, void* stream, int64_t N, int F, int 
       hipLaunchKernelGGL(fc_dp_kernel, dim3(nblk), dim3(256), (size_t)rl * No * 4, st, N, No, rows, act, cur,
                          resid ? x[l + 1] : g, resid ? x[l] : nullptr, dP, partial, bmax);
       NG_HIP(ctx, hipGetLastError());
-      const int rcr = reduce_or_defer(ctx, st, partial, nblk, (int64_t)No, db[l]);
-      if (rcr) return rcr;
+      if (want) {
+        const int rcr = reduce_or_defer(ctx, st, partial, nblk, (int64_t)No, db[l]);
+        if (rcr) return rcr;
+      }
       if (bmax) {
         const int rcs = gemm_grad_scale_from_blocks(ctx, st, nblk, &gsc);
         if (rcs) return rcs;
       }
     }
-    float* dwscr = (float*)workspace(ctx, dense_dw_scratch_floats(ctx, N, F, No, false) * sizeof(float));
-    if (!dwscr) return NG_ERR_NOMEM;
-    int rc = dense_dw(ctx, st, N, F, No, NG_ACT_NONE, x[l], dP, nullptr, nullptr, dW[l], nullptr, 0, 0, 0, dwscr, "dense_dw", gsc);
-    if (rc) return rc;
+    int rc = NG_OK;
+    if (want) {
+      float* dwscr = (float*)workspace(ctx, dense_dw_scratch_floats(ctx, N, F, No, false) * sizeof(float));
+      if (!dwscr) return NG_ERR_NOMEM;
+      rc = dense_dw(ctx, st, N, F, No, NG_ACT_NONE, x[l], dP, nullptr, nullptr, dW[l], nullptr, 0, 0, 0, dwscr, "dense_dw", gsc);
+      if (rc) return rc;
+    }
     float* out = l == 0 ? dx : nxt;
     rc = dense_dx(ctx, st, N, F, No, NG_ACT_NONE, dP, nullptr, nullptr, W[l], resid ? cur : nullptr, out, "dense_dx", gsc);
     if (rc) return rc;

@@ -91,8 +91,9 @@ __global__ __launch_bounds__(256) void head_fwd_fast_kernel(int64_t N, int C, co
 }
 
 // ---- head backward: dg + per-workgroup partials of [dWout ; dbout] ---------------------------------------
-// thread = (row lane r = tid / LPR, column lane q); accumulators acc[c][4] for its four f's, plus db[c] on q == 0
-template <int LPR, int CM>
+// thread = (row lane r = tid / LPR, column lane q); accumulators acc[c][4] for its four f's, plus db[c] on q == 0.
+// DW = false: dg only (ng_head_bwd with dWout == dbout == NULL) — no weight-gradient sums, no partial
+template <int LPR, int CM, bool DW>
 __global__ __launch_bounds__(256) void head_bwd_fast_kernel(int64_t N, int C, int64_t rows_per_block,
                                                             const float* __restrict__ g,
                                                             const float* __restrict__ mask,
@@ -128,9 +129,11 @@ __global__ __launch_bounds__(256) void head_bwd_fast_kernel(int64_t N, int C, in
         const float4 w4 = *reinterpret_cast<const float4*>(sWs + c * Fh + 4 * q);
         u0 += a * w4.x; u1 += a * w4.y;
         u2 += a * w4.z; u3 += a * w4.w;
-        const float d = dp * a * sStd[c];            // dfull[i][c]
-        acc[c][0] += x.x * d; acc[c][1] += x.y * d; acc[c][2] += x.z * d; acc[c][3] += x.w * d;
-        db[c] += d;
+        if (DW) {
+          const float d = dp * a * sStd[c];            // dfull[i][c]
+          acc[c][0] += x.x * d; acc[c][1] += x.y * d; acc[c][2] += x.z * d; acc[c][3] += x.w * d;
+          db[c] += d;
+        }
       }
     }
     *reinterpret_cast<float4*>(dg + i * Fh + 4 * q) = make_float4(m.x * dp * u0, m.y * dp * u1, m.z * dp * u2,
@@ -157,6 +160,7 @@ __global__ __launch_bounds__(256) void head_bwd_fast_kernel(int64_t N, int C, in
     row_body(i, xa, ma, dpa, aa);
     if (two) row_body(i2, xb, mb, dpb, ab);
   }
+  if (!DW) return;
   // sum over the row lanes through LDS, one partial per workgroup: layout [f*C + c] then [Fh*C + c]
   const int items = Fh * C + C;
 #pragma unroll
@@ -470,26 +474,35 @@ int head_bwd_fast(ng_ctx* ctx, hipStream_t st, int64_t N, int Fh, int C, const f
   const int grid = (int)std::min<int64_t>(cdiv(N, rl), (int64_t)ctx->num_cu * 2);
   const int64_t rows = cdiv(cdiv(N, grid), rl) * rl;
   const int nb = (int)cdiv(N, rows);
-  float* ws = (float*)workspace(ctx, (size_t)(nb + 1) * items * 4);
-  if (!ws) return NG_ERR_NOMEM;
-  float* partial = ws;
-  float* summed = ws + (size_t)nb * items;
-  if (float* dp = deferred_partials(ctx, (size_t)nb * items)) partial = dp;
-  const size_t lds = (size_t)rl * items * 4;
+  const bool want = dWout != nullptr;      // NULL: dg only, no partials, no reduction
+  float* partial = nullptr;
+  if (want) {
+    float* ws = (float*)workspace(ctx, (size_t)(nb + 1) * items * 4);
+    if (!ws) return NG_ERR_NOMEM;
+    partial = ws;
+    if (float* dp = deferred_partials(ctx, (size_t)nb * items)) partial = dp;
+  }
+  const size_t lds = want ? (size_t)rl * items * 4 : 0;
   ProfScope ps(ctx, st, "head_bwd");
-#define NG_HB(L, CM)                                                                                      \
-  hipLaunchKernelGGL((head_bwd_fast_kernel<L, CM>), dim3(nb), dim3(256), lds, st, N, C, rows, g, mask, Wout, \
-                     atoms, pstd, dpeaks, dg, partial)
+#define NG_HB(L, CM)                                                                                                   \
+  do {                                                                                                                 \
+    if (want)                                                                                                          \
+      hipLaunchKernelGGL((head_bwd_fast_kernel<L, CM, true>), dim3(nb), dim3(256), lds, st, N, C, rows, g, mask, Wout,  \
+                         atoms, pstd, dpeaks, dg, partial);                                                            \
+    else                                                                                                               \
+      hipLaunchKernelGGL((head_bwd_fast_kernel<L, CM, false>), dim3(nb), dim3(256), lds, st, N, C, rows, g, mask, Wout, \
+                         atoms, pstd, dpeaks, dg, partial);                                                            \
+  } while (0)
   if (lpr == 8) { if (C <= 16) NG_HB(8, 16); else NG_HB(8, 32); }
   else if (lpr == 32) { if (C <= 16) NG_HB(32, 16); else NG_HB(32, 32); }     // fc output 128: the default width
   else { if (C <= 16) NG_HB(16, 16); else NG_HB(16, 32); }
 #undef NG_HB
+  NG_HIP(ctx, hipGetLastError());
+  if (!want) return NG_OK;
   ReduceSegs sg{};
   sg.n = 2;
   sg.begin[0] = 0; sg.len[0] = Fh * C; sg.dst[0] = dWout;
   sg.begin[1] = Fh * C; sg.len[1] = C; sg.dst[1] = dbout;
-  (void)summed;
-  NG_HIP(ctx, hipGetLastError());
   return reduce_seg_or_defer(ctx, st, partial, nb, items, items, sg);
 }
 

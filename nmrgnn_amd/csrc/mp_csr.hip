@@ -620,12 +620,14 @@ int mp_generic_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, 
                    const int32_t* csc_ptr, const int32_t* csc_edge, const float* dh_out, float* dh_in, float* de,
                    int de_accum, float* dw, const float* csc_rec, int64_t nnz) {
   const int64_t KF = (int64_t)E * F;
-  const size_t dw_scr = dense_dw_scratch_floats(ctx, N, (int)KF, F, false);
+  // dw == NULL: no weight gradient — no dw GEMM, no partials, and no rebuilt aggregate (its only reader is that GEMM)
+  const size_t dw_scr = dw ? dense_dw_scratch_floats(ctx, N, (int)KF, F, false) : 0;
+  const bool rebuild_A = dw && !A_save;
   // node side as a gather-GEMM over dP rows (gemm_h2.hip) needs the incoming-edge records; built here when the caller has none
   const bool gg = E <= 3 && N > 0 && mp_gg_supported(N, F, E, 0);
   const int64_t n_ent = row_ptr ? nnz : N * K;
   const size_t rec_floats = gg && !csc_rec ? (size_t)std::max<int64_t>(n_ent, 1) * 4 : 0;
-  float* ws = (float*)workspace(ctx, (size_t)(KF * F + N * KF + N * F + dw_scr + (A_save ? 0 : N * KF) + rec_floats) * 4);
+  float* ws = (float*)workspace(ctx, (size_t)(KF * F + N * KF + N * F + dw_scr + (rebuild_A ? N * KF : 0) + rec_floats) * 4);
   if (!ws) return NG_ERR_NOMEM;
   const float* Wp = nullptr;
   float* dA = ws + KF * F;
@@ -633,8 +635,7 @@ int mp_generic_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, 
   float* scr = dP + N * F;
   int rc = mp_plain_weights(ctx, st, N, F, E, w, ws, 1, &Wp);
   if (rc) return rc;
-  const bool A_save_given = A_save != nullptr;
-  if (!A_save) {   // the caller did not keep the forward aggregate: rebuild it
+  if (rebuild_A) {   // the caller did not keep the forward aggregate: rebuild it
     float* Ar = scr + dw_scr;
     rc = row_ptr ? csr_aggregate(ctx, st, N, K, F, E, h, row_ptr, col, e, Ar) : mp_aggregate_padded(ctx, st, N, K, F, E, h, col, e, Ar);
     if (rc) return rc;
@@ -657,8 +658,10 @@ int mp_generic_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, 
       if (rc) return rc;
     }
   }
-  rc = dense_dw(ctx, st, N, (int)KF, F, NG_ACT_NONE, A_save, dP, nullptr, nullptr, dw, nullptr, 1, F, E, scr, "mp_dw", gsc);
-  if (rc) return rc;
+  if (dw) {
+    rc = dense_dw(ctx, st, N, (int)KF, F, NG_ACT_NONE, A_save, dP, nullptr, nullptr, dw, nullptr, 1, F, E, scr, "mp_dw", gsc);
+    if (rc) return rc;
+  }
   rc = dense_dx(ctx, st, N, (int)KF, F, NG_ACT_NONE, dP, nullptr, nullptr, Wp, nullptr, dA, "mp_dA", gsc);
   if (rc) return rc;
   rc = csr_edge_grad(ctx, st, N, K, F, E, h, row_ptr, col, dA, de, de_accum);
@@ -667,7 +670,7 @@ int mp_generic_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, 
   // (1 KB per incoming edge instead of 3 KB of dA; gemm_h2.hip)
   if (gg) {
     if (!csc_rec) {
-      float* rec = scr + dw_scr + (A_save_given ? 0 : N * KF);
+      float* rec = scr + dw_scr + (rebuild_A ? N * KF : 0);
       rc = mp_win_records(ctx, st, N, K, E, csc_ptr, csc_edge, e, rec, row_of, n_ent);
       if (rc) return rc;
       csc_rec = rec;

@@ -591,7 +591,8 @@ __device__ __noinline__ void node_gather_global(int wave, int lane, const int* s
   node_gather<E, 1>(wave, lane, 0, s_ptr, recs, rec_base, tb, ld, nullptr, src4, pl, rs, sbv, wmin);
 }
 
-template <int E, bool H2>
+// DW = false: dh only (ng_mp_layer_bwd with dw == NULL) — no h rows, no dw products, no partial; dh is the same bits
+template <int E, bool H2, bool DW>
 __device__ __forceinline__ void mp_win_bwd_node_body(const MpWinNodeArgs& a) {
   constexpr int KF = E * WF;
   constexpr int LD = KF + 4;
@@ -614,7 +615,6 @@ __device__ __forceinline__ void mp_win_bwd_node_body(const MpWinNodeArgs& a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int64_t T0 = (int64_t)blockIdx.x * a.tiles_per_wg;
   const int64_t T1 = std::min<int64_t>(T0 + a.tiles_per_wg, a.ntiles);
-  float* part = a.partial + (int64_t)blockIdx.x * (KF * WF);
   char* const pl = H2 ? planes : nullptr;
 
   const float4* src4 = reinterpret_cast<const float4*>(a.dP);
@@ -688,7 +688,7 @@ __device__ __forceinline__ void mp_win_bwd_node_body(const MpWinNodeArgs& a) {
     };
     auto issue_rows = [&](int64_t t) {     // h rows of tile t (dw operand) and this lane's dH chunk (epilogue)
       const int64_t rh = t * WTA + (tid >> 4);
-      p_h = rh < a.N ? reinterpret_cast<const float4*>(a.h)[rh * WC4 + (tid & 15)] : f4zero();
+      if (DW) p_h = rh < a.N ? reinterpret_cast<const float4*>(a.h)[rh * WC4 + (tid & 15)] : f4zero();
       const int64_t rd = t * WTA + 16 * hh + a16;
       p_dH = *reinterpret_cast<const float4*>(a.dH + (rd < a.N ? rd : a.N - 1) * WF + col);
     };
@@ -708,7 +708,7 @@ __device__ __forceinline__ void mp_win_bwd_node_body(const MpWinNodeArgs& a) {
       // requests for t+2.  Nothing freshly requested may be live across the gather: its out-of-line
       // global-memory variant is a call, and registers live across a call are saved to scratch — with a
       // vmcnt wait on the loads that fill them (measured: the prefetch latency came back every tile).
-      *reinterpret_cast<float4*>(htile + (tid >> 4) * SDP_LD + 4 * (tid & 15)) = p_h;
+      if (DW) *reinterpret_cast<float4*>(htile + (tid >> 4) * SDP_LD + 4 * (tid & 15)) = p_h;
       const float4 dHc = p_dH;
       if (t + 1 < T1) commit(t + 1);
       {
@@ -783,7 +783,7 @@ __device__ __forceinline__ void mp_win_bwd_node_body(const MpWinNodeArgs& a) {
                                      fmaf(acc0[2] + acc1[2], osc, dHc.z), fmaf(acc0[3] + acc1[3], osc, dHc.w));
         *reinterpret_cast<float4*>(row < a.N ? a.dh + row * WF + col : a.dummy + col) = v;
       }
-      if (H2) {
+      if (DW && H2) {
         // dw on the fp16 pipe.  The contraction runs over the tile's 32 atoms (ONE 32-deep MFMA step), whose B rows carry
         // different power-of-two scales S_a in the piece planes: the h operand takes the inverse, h'[a] = h[a] * S_ref / S_a
         // with S_ref the smallest S of the tile (its largest row; ratio <= 1, a small row's h' may underflow — its
@@ -844,7 +844,7 @@ __device__ __forceinline__ void mp_win_bwd_node_body(const MpWinNodeArgs& a) {
           at = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, bh), at, 0, 0, 0);
           accW[u] += at * osc4;
         }
-      } else {
+      } else if (DW) {
         // D[i = l][j = (n,m)] += sum_atoms h[atom][l] B[atom][(n,m)]: l-tile ct, column tiles NCT*hh + u
         const float* ha = htile + 16 * ct + a16;
         const float* bb = tile + 16 * (NCT * hh) + a16;
@@ -862,7 +862,8 @@ __device__ __forceinline__ void mp_win_bwd_node_body(const MpWinNodeArgs& a) {
     }
   }
   // ---- dw partial of this workgroup, layout [(n,m)][l]: lane holds l = 16ct + 4(lane>>4) + r, column = 16(NCT*hh+u) + (lane&15)
-  {
+  if (DW) {
+    float* part = a.partial + (int64_t)blockIdx.x * (KF * WF);
     const int a16 = lane & 15, g4 = lane >> 4;
 #pragma unroll
     for (int u = 0; u < NCT; ++u) {
@@ -875,13 +876,13 @@ __device__ __forceinline__ void mp_win_bwd_node_body(const MpWinNodeArgs& a) {
 
 // Range guard: as in the edge kernel — the piece operands B (per-row scale) and h' (per-row scale, above) are range-safe by
 // construction, a weight image out of range is known at the first instruction and selects the fp32-input body.
-template <int E, bool H2>
+template <int E, bool H2, bool DW>
 __global__ __launch_bounds__(WTHREADS, 1) void mp_win_bwd_node_kernel(MpWinNodeArgs a) {
   if (H2 && a.guard.word && (range_guard_raised(a.guard) || wimage_flag_raised(a.wflag))) {
     a.WfragN = a.WfragN32;
-    mp_win_bwd_node_body<E, false>(a);
+    mp_win_bwd_node_body<E, false, DW>(a);
   } else {
-    mp_win_bwd_node_body<E, H2>(a);
+    mp_win_bwd_node_body<E, H2, DW>(a);
   }
 }
 
@@ -946,7 +947,8 @@ int mp_win_records(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, const i
 
 size_t mp_win_node_scratch_floats(ng_ctx* ctx, int E) { return (size_t)(ctx->num_cu + 1) * E * WF * WF; }
 
-// dh_in = dh_out + B Wn,  dw = h^T B  with B the incoming-edge aggregate of dP (never materialised).
+// dh_in = dh_out + B Wn,  dw = h^T B  with B the incoming-edge aggregate of dP (never materialised).  dw == NULL: dh only
+// (the kernel's DW = false form: no dw products, no partials, no reduction).
 // guard.word != nullptr: WfragN is the piece image, WfragN32 the fp32 one the kernel switches to when the guard is up.
 int mp_win_bwd_node(ng_ctx* ctx, hipStream_t st, int64_t N, int E, const float* h, const float* dP,
                     const int32_t* csc_ptr, const float* rec, const float* WfragN, const float* dh_out,
@@ -960,19 +962,24 @@ int mp_win_bwd_node(ng_ctx* ctx, hipStream_t st, int64_t N, int E, const float* 
   a.WfragN = WfragN; a.dh = dh_in; a.partial = scratch; a.dummy = dummy; a.guard = guard;
   const int grid = (int)cdiv(a.ntiles, per);
   const bool h2 = mp_win_bwd_h2();
-#define NODE(HH)                                                                                                        \
+#define NODE(HH, DW)                                                                                                    \
   switch (E) {                                                                                                          \
-    case 1: hipLaunchKernelGGL((mp_win_bwd_node_kernel<1, HH>), dim3(grid), dim3(WTHREADS), node_lds_bytes(E, HH), st, a); break; \
-    case 2: hipLaunchKernelGGL((mp_win_bwd_node_kernel<2, HH>), dim3(grid), dim3(WTHREADS), node_lds_bytes(E, HH), st, a); break; \
-    case 3: hipLaunchKernelGGL((mp_win_bwd_node_kernel<3, HH>), dim3(grid), dim3(WTHREADS), node_lds_bytes(E, HH), st, a); break; \
+    case 1: hipLaunchKernelGGL((mp_win_bwd_node_kernel<1, HH, DW>), dim3(grid), dim3(WTHREADS), node_lds_bytes(E, HH), st, a); break; \
+    case 2: hipLaunchKernelGGL((mp_win_bwd_node_kernel<2, HH, DW>), dim3(grid), dim3(WTHREADS), node_lds_bytes(E, HH), st, a); break; \
+    case 3: hipLaunchKernelGGL((mp_win_bwd_node_kernel<3, HH, DW>), dim3(grid), dim3(WTHREADS), node_lds_bytes(E, HH), st, a); break; \
   }
   a.WfragN32 = WfragN32; a.wflag = wflag; a.wflag_ver = wflag_ver;
   {
     ProfScope ps(ctx, st, "mp_win_bwd_node");
-    if (h2) { NODE(true) } else { NODE(false) }
+    if (dw) {
+      if (h2) { NODE(true, true) } else { NODE(false, true) }
+    } else {
+      if (h2) { NODE(true, false) } else { NODE(false, false) }
+    }
     NG_HIP(ctx, hipGetLastError());
   }
 #undef NODE
+  if (!dw) return NG_OK;
   ProfScope ps(ctx, st, "reduce_partials");
   // partial idx = (n*64 + m)*64 + l  ->  dw[(l*64 + m)*E + n]
   return reduce_or_defer(ctx, st, scratch, grid, (int64_t)E * WF * WF, dw, 2, WF, E, WF, (int64_t)E * WF * WF);
@@ -1025,7 +1032,7 @@ int mp_win_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int act, co
                const int32_t* csc_edge, const float* dh_out, float* dh_in, float* de, int de_accum, float* dw,
                const float* csc_rec) {
   const int KF = E * WF;
-  const size_t dw_scr = mp_win_node_scratch_floats(ctx, E);
+  const size_t dw_scr = dw ? mp_win_node_scratch_floats(ctx, E) : 0;
   const bool h2 = mp_win_bwd_h2();
   // guarded call (RangeGuard, ng_internal.h): the pack launch raises the guard for weights out of the piece range and
   // both kernels then run their fp32-input bodies
@@ -1056,7 +1063,8 @@ int mp_win_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int act, co
   float* scr = rec + rec_floats;
   float* dummy = scr + dw_scr;
   // deferred reductions (reduce.cuh): the dw partials of this layer stay in the reduction arena until the flush
-  if (float* dscr = deferred_partials(ctx, dw_scr)) scr = dscr;
+  if (dw)
+    if (float* dscr = deferred_partials(ctx, dw_scr)) scr = dscr;
   int rc = NG_OK;
   if (!have) {
     if (h2) {

@@ -996,14 +996,23 @@ extern "C" int ng_head_bwd(ng_ctx* ctx, void* stream, int64_t N, int Fh, int C, 
   if (!ctx) return NG_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   NG_REQUIRE(ctx, C >= 1 && C <= MAX_C, "head: number of elements <= 32");
+  NG_REQUIRE(ctx, (dWout == nullptr) == (dbout == nullptr), "head_bwd: dWout and dbout are both given or both NULL");
   const int64_t items = (int64_t)Fh * C + C;
   if (N == 0) {
+    if (!dWout) return NG_OK;
     NG_HIP(ctx, hipMemsetAsync(dWout, 0, (size_t)Fh * C * 4, st));
     NG_HIP(ctx, hipMemsetAsync(dbout, 0, (size_t)C * 4, st));
     return NG_OK;
   }
   if (head_fast_supported(Fh, C))
     return head_bwd_fast(ctx, st, N, Fh, C, g, drop_mask, Wout, atoms, peak_std, dpeaks, dg, dWout, dbout);
+  if (!dWout) {       // dg only
+    ProfScope ps(ctx, st, "head_bwd");
+    hipLaunchKernelGGL(head_bwd_dg_kernel, ew_grid(N * Fh), dim3(256), 0, st, N, Fh, C, drop_mask, Wout, atoms, peak_std,
+                       dpeaks, dg);
+    NG_HIP(ctx, hipGetLastError());
+    return NG_OK;
+  }
   const int64_t rows = 512;
   const int64_t nb = cdiv(N, rows);
   float* ws = (float*)workspace(ctx, (size_t)(nb * items + items) * 4);

@@ -456,7 +456,7 @@ class Engine:
         return bool(g[0]), float(g[4:6].view(np.float32)[0]), float(g[4:6].view(np.float32)[1])
 
     # ------------------------------------------------------------------ backward
-    def backward(self, dpeaks, on_node_grads=None, edge_grad=None):
+    def backward(self, dpeaks, on_node_grads=None, edge_grad=None, param_grad=True):
         """fills params.grad (overwrite) from the upstream gradient dpeaks[N] (None: the gradient of the loss
         taken inside ``forward(loss=...)``).
         ``on_node_grads`` is called once every non-edge gradient has been enqueued (the data-parallel
@@ -464,7 +464,19 @@ class Engine:
         ``edge_grad``: a float32 device tensor shaped like ``batch.edges``, OVERWRITTEN with dL/d(edges) — one
         ng_edge_mlp_dinput launch behind the rest, from the tape's distances, de and the current weights; exact on every
         edge path (the table's included: the derivative is of the edge function itself).  In training mode it is the
-        gradient with respect to the un-noised input (d d_eff / d edges = 1).  params.grad is the same bits either way."""
+        gradient with respect to the un-noised input (d d_eff / d edges = 1).  params.grad is the same bits either way.
+        ``param_grad=False`` (needs ``edge_grad``): input gradients only — the head, FC-block and MPLayer backward get NULL
+        weight-gradient outputs (include/nmrgnn_hip.h: no weight-gradient products, partials or queued sums are formed), and
+        nothing whose only output is a parameter gradient is launched (no edge-MLP / table backward, no ng_embed_bwd, no
+        reduction flush).  ``params.grad`` is left untouched; ``edge_grad`` is bit for bit that of ``param_grad=True``."""
+        if not param_grad:
+            if edge_grad is None:
+                raise ValueError("backward(param_grad=False) needs edge_grad: without parameter gradients it is the only output")
+            if on_node_grads is not None:
+                raise ValueError("backward(param_grad=False): on_node_grads hands on parameter gradients, and none are formed")
+            if dpeaks is None:
+                raise ValueError("backward(param_grad=False) needs dpeaks: the fused head + loss launch already formed the "
+                                 "head's weight-gradient partials")
         if edge_grad is not None:
             b = self.tape.batch if self.tape is not None else None
             if b is not None and (edge_grad.dtype != torch.float32 or edge_grad.device != self.device
@@ -477,18 +489,21 @@ class Engine:
         lib, h, st = self.lib, self.ctx.handle, self._st()
         # the seven second-stage sums of the node-side weight gradients (head, FC block, MPLayers, embedding) are queued
         # and run as ONE launch before the node gradients are handed on (ng_defer_reductions: same bits, ~45 us less)
-        self._ck(lib.ng_defer_reductions(h, st, 1 if self.defer_reductions else 0), "ng_defer_reductions")
+        self._ck(lib.ng_defer_reductions(h, st, 1 if self.defer_reductions and param_grad else 0), "ng_defer_reductions")
         if self.cache_images:
             self._ck(lib.ng_weights_frozen(h, self._id), "ng_weights_frozen")
         try:
-            self._backward(tp, dpeaks, on_node_grads, lib, h, st, edge_grad)
+            self._backward(tp, dpeaks, on_node_grads, lib, h, st, edge_grad, bool(param_grad))
         finally:
             if self.cache_images:
                 lib.ng_weights_frozen(h, 0)
             self._ck(lib.ng_defer_reductions(h, st, 0), "ng_defer_reductions")
 
-    def _backward(self, tp, dpeaks, on_node_grads, lib, h, st, edge_grad=None):
+    def _backward(self, tp, dpeaks, on_node_grads, lib, h, st, edge_grad=None, param_grad=True):
         P = self.params
+        # the weight-gradient outputs: views of params.grad, or NULL (param_grad=False)
+        wg = P.g if param_grad else (lambda name: None)
+        warr = ptr_array if param_grad else (lambda ts: None)
         b = tp.batch
         N, K, F, E = b.N, b.K, self.F, self.E
         Fh = F // 2
@@ -512,7 +527,7 @@ class Engine:
             dg = self._new(N, Fh)
             self._ck(lib.ng_head_bwd(h, st, N, Fh, self.C, ptr(tp.g), ptr(tp.drop_mask),
                                      ptr(P["out/kernel"]), ptr(b.atoms), ptr(self.peak_std),
-                                     ptr(dpeaks), ptr(dg), ptr(P.g("out/kernel")), ptr(P.g("out/bias"))),
+                                     ptr(dpeaks), ptr(dg), ptr(wg("out/kernel")), ptr(wg("out/bias"))),
                      "ng_head_bwd")
         dx = self._new(N, F)
         Wfc = [P[f"fc/{t}/kernel"] for t in range(self.Lf)]
@@ -520,8 +535,8 @@ class Engine:
         scratch = self._new(ns) if ns else None
         self._ck(lib.ng_fc_block_bwd(h, st, N, F, self.Lf, self.fc_act, ptr_array(tp.fx), ptr(tp.g),
                                      ptr_array(Wfc), ptr(dg), ptr(dx),
-                                     ptr_array([P.g(f"fc/{t}/kernel") for t in range(self.Lf)]),
-                                     ptr_array([P.g(f"fc/{t}/bias") for t in range(self.Lf)]),
+                                     warr([wg(f"fc/{t}/kernel") for t in range(self.Lf)]),
+                                     warr([wg(f"fc/{t}/bias") for t in range(self.Lf)]),
                                      ptr(scratch)), "ng_fc_block_bwd")
         csc_ptr, csc_edge = b.csc()
         de = self._new(ne, E)
@@ -539,7 +554,7 @@ class Engine:
                                                  ptr(b.nlist), ptr(b.row_of), ptr(tp.e), ptr(b.inv_degree),
                                                  ptr(P[f"mp/{l}/w"]), ptr(tp.A[l]), ptr(tp.S[l]), ptr(csc_ptr),
                                                  ptr(csc_edge), ptr(dh), ptr(dhn), ptr(de),
-                                                 0 if l == self.L - 1 else 1, ptr(P.g(f"mp/{l}/w"))),
+                                                 0 if l == self.L - 1 else 1, ptr(wg(f"mp/{l}/w"))),
                          "ng_mp_layer_bwd_csr")
                 dh = dhn
                 continue
@@ -547,8 +562,12 @@ class Engine:
                                          ptr(tp.e), ptr(b.inv_degree), ptr(P[f"mp/{l}/w"]),
                                          ptr(tp.A[l]), ptr(tp.S[l]), ptr(csc_ptr), ptr(csc_edge),
                                          ptr(dh), ptr(dhn), ptr(de), 0 if l == self.L - 1 else 1,
-                                         ptr(P.g(f"mp/{l}/w")), ptr(rec)), "ng_mp_layer_bwd")
+                                         ptr(wg(f"mp/{l}/w")), ptr(rec)), "ng_mp_layer_bwd")
             dh = dhn
+        if not param_grad:      # the embedding, the reductions and the edge MLP's weights: parameter gradients only
+            self._edge_dinput(tp, de, edge_grad)
+            self.tape = None
+            return
         self._ck(lib.ng_embed_bwd(h, st, N, self.C, F, ptr(b.atoms), ptr(dh),
                                   ptr(P.g("embed/kernel"))), "ng_embed_bwd")
         self._ck(lib.ng_flush_reductions(h, st), "ng_flush_reductions")

@@ -1,6 +1,7 @@
 """Library surface of the reference (nmrgnn/library.py): ``load_model``, ``universe2graph``,
-``check_peaks`` (+ ``save_model``), same names, argument order and return order; and ``shift_restraint``, the
-chemical-shift restraint energy and forces of a structure."""
+``check_peaks`` (+ ``save_model``), same names, argument order and return order; ``shift_restraint``, the
+chemical-shift restraint energy and forces of a structure; and ``ShiftRestraint``, the replica-averaged restraint of R
+structures as one graph-replayed call for an MD engine."""
 from __future__ import annotations
 
 import json
@@ -176,3 +177,207 @@ def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_num
         from .graph import _box_grad
         return energy, forces, -_box_grad(batch._box_state(), dedges, want_dvec=False)[0][0]
     return energy, forces
+
+
+def _restraint_positions(positions, R, n):
+    """host check of a call's positions: [R, n, 3] (or [n, 3] when R == 1); returns the torch view [R, n, 3] (not yet on the
+    device) and whether the caller gave [n, 3]"""
+    import torch
+    shape = tuple(positions.shape) if hasattr(positions, "shape") else np.shape(positions)
+    flat = len(shape) == 2
+    if flat and R != 1:
+        raise ValueError(f"ShiftRestraint: positions [n, 3] only for one replica; this restraint has {R}: pass [{R}, {n}, 3]")
+    if (shape != (n, 3)) if flat else (shape != (R, n, 3)):
+        raise ValueError(f"ShiftRestraint: positions must be [{R}, {n}, 3]" + (" (or [n, 3])" if R == 1 else "")
+                         + f", got {shape}")
+    p = positions.detach() if isinstance(positions, torch.Tensor) else torch.from_numpy(np.asarray(positions, np.float32))
+    return p.reshape(R, n, 3), flat
+
+
+def _restraint_box(box, R, triclinic=None):
+    """host check of a box ([6] or [R, 6], pbc.prepare's refusals included): (vectors [R, 9] float32, triclinic flag).
+    ``triclinic``: the kind the restraint was built for (the displacement policy of its captured kernels)."""
+    from .pbc import prepare
+    import torch
+    if isinstance(box, torch.Tensor):
+        box = box.detach().cpu().numpy()
+    vecs, tric, _ = prepare(box, R)
+    if triclinic is not None and bool(tric) != bool(triclinic):
+        want, got = ("triclinic", "orthorhombic") if triclinic else ("orthorhombic", "triclinic")
+        raise ValueError(f"ShiftRestraint: built for a {want} box, called with a {got} one (the kind of box is fixed at "
+                         "construction)")
+    return vecs, bool(tric)
+
+
+class ShiftRestraint:
+    """Replica-averaged chemical-shift restraint of ``replicas`` structures of one topology, for an MD engine that asks for
+    forces every step:
+
+        energy = sum_i w_i (mean_r delta_pred[r, i] - delta_exp_i)^2     ppm^2, a 0-d float32 device tensor
+        forces = -d energy / d positions                                 ppm^2 / Angstrom, [R, n, 3] ([n, 3] given [n, 3])
+        virial = -strain per replica (``virial=True``)                   [R, 3, 3] float64, as shift_restraint defines it
+
+    ``r(positions)`` / ``r(positions, box=...)`` with positions [R, n, 3] in Angstrom (or [n, 3] when R == 1) and, for a
+    restraint built with a box, the box of this call ([6] or [R, 6], the same kind — orthorhombic or triclinic — as at
+    construction).  Returns ``(energy, forces)`` or ``(energy, forces, virial)``.  Everything is taken at FIXED neighbour
+    lists, as shift_restraint: the kNN lists of every call's positions (and box), held fixed for the derivative.
+
+    The chain — kNN lists of the R frames (ng_knn_graph / _pbc), the inference forward with a tape, ng_restraint_loss,
+    ``Engine.backward(param_grad=False, edge_grad=...)``, ng_positions_grad (/ _pbc) and, with ``virial``, ng_box_grad — is
+    captured ONCE as a HIP graph at construction; a call stages the positions (and box vectors) into static device buffers
+    (one ng_replay_stage) and replays it.  The outputs are static buffers: read them before the next call.  With R = 1 the
+    forces and the virial are bitwise those of ``shift_restraint`` (the energy is summed in another order: float64 here).
+    ``replay=False`` runs the same chain eagerly (the reference of the tests and the debugging path).
+
+    Refused with ValueError before any device work: wrong shapes, a box where none was given at construction or none where
+    one was, a box of the other kind or one pbc.prepare refuses, and a call after the model's weights changed (a training
+    step, a load): the captured chain would read stale packed weights — build a new restraint.  The call leaves
+    ``engine.params.grad`` alone."""
+
+    def __init__(self, model, atoms, targets, weights=None, replicas=1, neighbor_number=16, box=None, virial=False,
+                 replay=True):
+        import torch
+        R = int(replicas)
+        if R < 1 or R != replicas:
+            raise ValueError(f"ShiftRestraint: replicas must be a positive integer, got {replicas!r}")
+        a_shape = tuple(atoms.shape) if hasattr(atoms, "shape") else np.shape(atoms)
+        if len(a_shape) != 2 or a_shape[0] < 1:
+            raise ValueError(f"ShiftRestraint: atoms must be [n, C] one-hot, got {a_shape}")
+        n = int(a_shape[0])
+        K = int(neighbor_number)
+        if K < 1:
+            raise ValueError("ShiftRestraint: neighbor_number must be >= 1")
+        host = lambda x: x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        y = np.asarray(host(targets), np.float32).reshape(-1)
+        w = np.ones(n, np.float32) if weights is None else np.asarray(host(weights), np.float32).reshape(-1)
+        if y.shape[0] != n or w.shape[0] != n:
+            raise ValueError(f"ShiftRestraint: targets and weights need {n} entries (one per atom)")
+        self.R, self.n, self.K = R, n, K
+        self.virial = bool(virial)
+        self.replay = bool(replay)
+        self._tric = None
+        vecs = None
+        if box is not None:
+            vecs, self._tric = _restraint_box(box, R)
+        # ---- device side
+        if model.engine is None:
+            model.build(int(a_shape[1]))
+        eng = self.eng = model.engine
+        dev = eng.device
+        self._wgen = eng._wgen
+        at = (atoms.detach() if isinstance(atoms, torch.Tensor) else torch.from_numpy(np.asarray(atoms, np.float32)))
+        at = at.to(device=dev, dtype=torch.float32).contiguous()
+        self.s_atoms = at.repeat(R, 1).contiguous() if R > 1 else at
+        self.s_y = torch.from_numpy(y).to(dev)
+        self.s_w = torch.from_numpy(w).to(dev)
+        self.s_pos = torch.zeros(R, n, 3, dtype=torch.float32, device=dev)
+        self.s_box = None if vecs is None else torch.from_numpy(vecs).to(dev)
+        self._nlist = torch.empty(R * n, K, dtype=torch.int32, device=dev)
+        self._edges = torch.empty(R * n, K, dtype=torch.float32, device=dev)
+        self._inv = torch.empty(R * n, dtype=torch.float32, device=dev)
+        self._graph_ptr = np.arange(R + 1, dtype=np.int64) * n
+        self._e64 = torch.zeros(1, dtype=torch.float64, device=dev)
+        self.energy = torch.zeros((), dtype=torch.float32, device=dev)
+        self.forces = torch.zeros(R, n, 3, dtype=torch.float32, device=dev)
+        self.virial_out = torch.zeros(R, 3, 3, dtype=torch.float64, device=dev) if self.virial else None
+        # ADVICE (edge path of warm-up vs capture): the host-guarded edge-function table ("table_host", edge shapes without the
+        # fused kernels on >= edge_table_min_edges slots) reads its guard on the host, which a capture cannot, so a captured
+        # call would go per edge while its eager warm-up took the table — a chain the warm-up never sized.  Every call of
+        # this restraint, eager or replayed, takes the per-edge path there; the device-guarded table is capturable and kept.
+        from .engine import edge_path
+        live_k = bool(eng.lib.ng_edge_live_supported(eng.H, eng.E, eng.Le, eng.fc_act))
+        self._no_table = edge_path(eng.edge_table, eng.use_live_edges, live_k, eng.E, R * n * K, eng.edge_table_min_edges,
+                                   False, False) == "table_host"
+        self._graph = None
+        if self.replay:
+            self._capture()
+
+    # ------------------------------------------------------------------ the chain
+    def _chain(self):
+        """one call on the static buffers: every launch reads s_pos / s_box and writes energy / forces / virial_out"""
+        import ctypes as C
+        import torch
+        from ._lib import ptr
+        from .graph import GraphBatch, _box_grad
+        eng = self.eng
+        lib, h = eng.lib, eng.ctx.handle
+        st = C.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream)
+        R, n, K = self.R, self.n, self.K
+        if self.s_box is None:
+            eng._ck(lib.ng_knn_graph(h, st, R, n, K, 0.1, ptr(self.s_pos), ptr(self._nlist), ptr(self._edges), ptr(self._inv)),
+                    "ng_knn_graph")
+        else:
+            eng._ck(lib.ng_knn_graph_pbc(h, st, R, n, K, 0.1, ptr(self.s_pos), ptr(self.s_box), int(self._tric), ptr(self._nlist),
+                                         ptr(self._edges), ptr(self._inv)), "ng_knn_graph_pbc")
+        b = GraphBatch(self.s_atoms, self._nlist, self._edges, self._inv, graph_ptr=self._graph_ptr, device=eng.device,
+                       validate=False, nlist_c=self._nlist if n > K else None)
+        b.positions, b.scale = self.s_pos, 0.1
+        if self.s_box is not None:
+            b.box, b.box_triclinic = self.s_box, bool(self._tric)
+        self._batch = b         # the captured chain reads buffers the batch owns
+        keep = eng.edge_table
+        if self._no_table:
+            eng.edge_table = False
+        try:
+            peaks = eng.forward(b, training=False, keep_tape=True)
+        finally:
+            eng.edge_table = keep
+        dpeaks = torch.empty_like(peaks)
+        eng._ck(lib.ng_restraint_loss(h, st, R, n, ptr(peaks), ptr(self.s_y), ptr(self.s_w), ptr(self._e64), ptr(dpeaks)),
+                "ng_restraint_loss")
+        self.energy.copy_(self._e64[0])
+        dedges = torch.empty_like(self._edges)
+        eng.backward(dpeaks, edge_grad=dedges, param_grad=False)
+        torch.neg(b.positions_grad(dedges), out=self.forces)
+        if self.virial:
+            torch.neg(_box_grad(b._box_state(), dedges, want_dvec=False)[0], out=self.virial_out)
+
+    def _capture(self):
+        import torch
+        eng = self.eng
+        self._stream = torch.cuda.Stream(device=eng.device)
+        self._graph = torch.cuda.CUDAGraph()
+        cur = torch.cuda.current_stream(eng.device)
+        self._stream.wait_stream(cur)
+        with torch.cuda.stream(self._stream):
+            # two eager warm-up calls on the capture stream size every scratch buffer and fill the caches the chain relies on
+            # (the batch's device graph_ptr, the context's workspace); they take the same edge path as the capture
+            for _ in range(2):
+                self._chain()
+            torch.cuda.synchronize(eng.device)
+            with torch.cuda.graph(self._graph, stream=self._stream):
+                self._chain()
+        cur.wait_stream(self._stream)
+
+    # ------------------------------------------------------------------ calls
+    def check(self, positions, box=None):
+        """the host-side refusals of a call (ValueError), without device work; returns (positions [R, n, 3], box vectors or
+        None, whether positions were [n, 3])"""
+        pos, flat = _restraint_positions(positions, self.R, self.n)
+        if (box is None) != (self._tric is None):
+            raise ValueError("ShiftRestraint: built without a box, called with one" if box is not None else
+                             "ShiftRestraint: built with a box, called without one (pass the box of this call)")
+        vecs = None if box is None else _restraint_box(box, self.R, self._tric)[0]
+        if self.eng._wgen != self._wgen:
+            raise ValueError("ShiftRestraint: the model's weights changed since the restraint was built (a training step or "
+                             "a load); build a new ShiftRestraint")
+        return pos, vecs, flat
+
+    def __call__(self, positions, box=None):
+        import torch
+        from .replay import _stage
+        pos, vecs, flat = self.check(positions, box)
+        eng = self.eng
+        p = pos.to(device=eng.device, dtype=torch.float32).contiguous()
+        pairs = [(p, self.s_pos)]
+        if vecs is not None:
+            pairs.append((torch.from_numpy(vecs).to(eng.device), self.s_box))
+        _stage(eng, 0, 1e-4, 1, pairs)
+        if self._graph is not None:
+            self._graph.replay()
+        else:
+            self._chain()
+        forces = self.forces[0] if flat else self.forces
+        if self.virial:
+            return self.energy, forces, self.virial_out
+        return self.energy, forces
