@@ -460,11 +460,16 @@ int ng_fc_block_bwd(ng_ctx*, void* stream, int64_t N, int F, int L, int act, con
                     float* const* db, float* scratch);
 
 /* keras Dense (+ residual), nmrgnn/model.py:191-196:  Y = act(X@W + b) (+ X if residual)
- *   s_save [M,Nout] = act(X@W+b) written when non-NULL */
+ *   X [M,Kin], W [Kin,Nout], b [Nout] (may be NULL: no bias), Y [M,Nout]
+ *   s_save [M,Nout] = act(X@W+b) written when non-NULL
+ * Shape contract of ng_dense_fwd / ng_dense_bwd: Kin and Nout multiples of 4 (any M >= 0); residual needs Kin == Nout;
+ * the bias gradient (db != NULL) needs Nout <= 1024.  Anything else returns NG_ERR_INVALID before an output is written.
+ * M = 0: the forward writes nothing; the backward leaves dX untouched and sets dW (and db) to 0. */
 int ng_dense_fwd(ng_ctx*, void* stream, int64_t M, int Kin, int Nout, int act, int residual,
                  const float* X, const float* W, const float* b, float* Y, float* s_save);
 /* dX = (residual ? dY : 0) + dP @ W^T,  dW = X^T dP,  db = colsum dP,
- * dP = dY * act'(.) recovered from s_save (softplus: 1-exp(-s)).  dX may be NULL. */
+ * dP = dY * act'(.) recovered from s_save (softplus: 1-exp(-s); s_save may be NULL only for NG_ACT_NONE).
+ * dX or db may be NULL: that output is skipped, and the others keep the bits of the call that has it. */
 int ng_dense_bwd(ng_ctx*, void* stream, int64_t M, int Kin, int Nout, int act, int residual,
                  const float* X, const float* W, const float* s_save, const float* dY, float* dX,
                  float* dW, float* db);

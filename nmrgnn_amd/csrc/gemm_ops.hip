@@ -132,7 +132,7 @@ static void launch_gemm(hipStream_t st, int64_t M, int N, int64_t K, int64_t k_c
 int dense_fwd(ng_ctx* ctx, hipStream_t st, int64_t M, int Kin, int Nout, int act, const float* X,
               const float* W, const float* b, const float* rowscale, const float* R, float* Y,
               float* S, const char* tag) {
-  NG_REQUIRE(ctx, Kin % 8 == 0 && Nout % 4 == 0, "dense_fwd: Kin%8, Nout%4");
+  NG_REQUIRE(ctx, Kin % 4 == 0 && Nout % 4 == 0, "dense_fwd: Kin%4, Nout%4");
   if (M == 0) return NG_OK;
   // Split-operand GEMM first where the shape allows; the f32-input GEMM below then runs as its range fallback: its
   // workgroups return at once unless the first kernel raised the guard (an operand beyond the fp16 range).  Not when
@@ -162,7 +162,7 @@ int dense_fwd(ng_ctx* ctx, hipStream_t st, int64_t M, int Kin, int Nout, int act
 int dense_dx(ng_ctx* ctx, hipStream_t st, int64_t M, int Kin, int Nout, int act, const float* dY,
              const float* S, const float* rowscale, const float* W, const float* add, float* dX,
              const char* tag, const float* gscale) {
-  NG_REQUIRE(ctx, Nout % 8 == 0 && Kin % 4 == 0, "dense_dx: Nout%8, Kin%4");
+  NG_REQUIRE(ctx, Nout % 4 == 0 && Kin % 4 == 0, "dense_dx: Nout%4, Kin%4");
   if (M == 0) return NG_OK;
   RangeGuard guard{nullptr, 0};
   if (gemm_h2_fwd_ok(M, Nout, Kin) && dX != dY && dX != add) {      // (see dense_fwd)
@@ -225,6 +225,7 @@ int dense_dw(ng_ctx* ctx, hipStream_t st, int64_t M, int Kin, int Nout, int act,
              int w_map, int F, int E, float* scratch, const char* tag, const float* gscale) {
   if (act == NG_ACT_NONE) S = nullptr;
   NG_REQUIRE(ctx, Kin % 4 == 0 && Nout % 4 == 0, "dense_dw: Kin%4, Nout%4");
+  NG_REQUIRE(ctx, !db || Nout <= 1024, "dense_dw: Nout <= 1024 for the bias gradient");   // (colsum_kernel: one float4 column per thread)
   const int64_t n_elem = (int64_t)Kin * Nout;
   if (M == 0) {
     NG_HIP(ctx, hipMemsetAsync(dW, 0, n_elem * sizeof(float), st));
@@ -260,7 +261,6 @@ int dense_dw(ng_ctx* ctx, hipStream_t st, int64_t M, int Kin, int Nout, int act,
     if (rc) return rc;
   }
   if (db) {
-    NG_REQUIRE(ctx, Nout / 4 <= 256, "dense_dw: Nout <= 1024 for the bias gradient");
     ProfScope ps(ctx, st, "bias_grad");
     LoadGradAct lp{dY, S, rowscale, M, Nout, act};
     hipLaunchKernelGGL((colsum_kernel<LoadGradAct>), dim3((unsigned)p.cs_blocks), dim3(256), 0, st,
@@ -310,6 +310,7 @@ extern "C" int ng_dense_bwd(ng_ctx* ctx, void* stream, int64_t M, int Kin, int N
   if (!ctx) return NG_ERR_INVALID;
   NG_REQUIRE(ctx, !residual || Kin == Nout, "ng_dense_bwd: residual needs Kin == Nout");
   NG_REQUIRE(ctx, act == NG_ACT_NONE || s_save, "ng_dense_bwd: activation backward needs s_save");
+  NG_REQUIRE(ctx, !db || Nout <= 1024, "ng_dense_bwd: Nout <= 1024 for the bias gradient");   // before dX is written
   const float* S = s_save;
   hipStream_t st = (hipStream_t)stream;
   if (dX && ng::tall_dense_ok(Nout, Kin) && Nout <= 128) {

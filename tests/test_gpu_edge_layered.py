@@ -127,6 +127,8 @@ CASES = [
     (32, 4, 1, "softplus", 70001, 1.0),     # every slot dead at many rows
     (256, 4, 2, "softplus", 255, 0.0),      # H = 256 at M = 255: below the short-operand threshold of the split GEMM
     (128, 2, 2, "relu", 256, 0.3),          # M = 256 exactly
+    (64, 3, 12, "relu", 4097, 0.3),         # E = 12 and 20 (a multiple of 4, not of 8): the wide output layer's dX GEMM
+    (32, 2, 20, "softplus", 1001, 0.3),     #   contracts over E
 ]
 
 

@@ -111,7 +111,9 @@ def test_amplayer_matches_oracle(gpu_device, F, E, act):
     np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=2e-4, atol=2e-5)
 
 
-@pytest.mark.parametrize("F,E,act", [(16, 2, None), (64, 3, "softplus"), (256, 8, "tanh"), (20, 5, "relu")])
+@pytest.mark.parametrize("F,E,act", [(16, 2, None), (64, 3, "softplus"), (256, 8, "tanh"), (20, 5, "relu"),
+                                     # F % 8 == 4 outside the tall dX kernel: dense_dx with a contraction of 68 / 100
+                                     (68, 3, "relu"), (100, 4, "softplus")])
 def test_amplayer_backward_matches_oracle(gpu_device, F, E, act):
     """Gradients of AMPLayer (layers.py:48-100) w.r.t. nodes, edges, wq, wk, wv vs the fp64 reverse pass of the oracle;
     padded slots (nlist 0, edges 0) take part in the softmax and receive gradient, as in the reference.  Run twice: the
