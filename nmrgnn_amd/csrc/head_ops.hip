@@ -235,8 +235,8 @@ __global__ __launch_bounds__(HL_NT) void head_loss_kernel(HeadLossArgs a) {
   float4 xr[RPT];
 #pragma unroll
   for (int u = 0; u < RPT; ++u) {
-    const int rr = r + u * RL;
-    xr[u] = *reinterpret_cast<const float4*>(gin + (r0 + (rr < nrows ? rr : 0)) * Fh + 4 * q);
+    const int rr = r + u * RL;      // (a workgroup of trailing empty graphs has r0 == N: no row of g is its own)
+    xr[u] = rr < nrows ? *reinterpret_cast<const float4*>(gin + (r0 + rr) * Fh + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   for (int t = threadIdx.x; t < nrows * C; t += NT) s_at[t] = a.atoms[r0 * C + t];
   for (int t = threadIdx.x; t < nrows; t += NT) { s_y[t] = a.y[r0 + t]; s_w[t] = a.w[r0 + t]; }
@@ -379,6 +379,7 @@ __global__ __launch_bounds__(HL_NT) void head_loss_kernel(HeadLossArgs a) {
 
 // ---- embedding weight gradient --------------------------------------------------------------------------
 // thread = (row lane, float4 column); acc[c] float4 per thread
+constexpr int EB_CM = 16;      // one-hot width limit (the LDS of the final sum: embed_bwd_fast_supported)
 template <int CM>
 __global__ __launch_bounds__(256) void embed_bwd_fast_kernel(int64_t N, int C, int F, int64_t rows_per_block,
                                                              const float* __restrict__ atoms,
@@ -558,9 +559,8 @@ int head_loss_reduce(ng_ctx* ctx, hipStream_t st, const float* partial, int nb, 
 }
 
 bool embed_bwd_fast_supported(int F, int C) {
-  // LDS for the final sum: (256 / (F/4)) * C * F floats
-  return fast_enabled() && F % 4 == 0 && F >= 16 && F <= 256 && 256 % (F / 4) == 0 && C >= 1 && C <= HC_MAX &&
-         (size_t)(256 / (F / 4)) * C * F * 4 <= 64 * 1024;
+  // LDS for the final sum: (256 / (F/4)) * C * F floats = 4096 * C bytes for every F, within 64 KB for C <= EB_CM = 16
+  return fast_enabled() && F % 4 == 0 && F >= 16 && F <= 256 && 256 % (F / 4) == 0 && C >= 1 && C <= EB_CM;
 }
 
 int embed_bwd_fast(ng_ctx* ctx, hipStream_t st, int64_t N, int C, int F, const float* atoms, const float* dh0,
@@ -575,10 +575,7 @@ int embed_bwd_fast(ng_ctx* ctx, hipStream_t st, int64_t N, int C, int F, const f
   if (!partial) return NG_ERR_NOMEM;
   const size_t lds = (size_t)rl * items * 4;
   ProfScope ps(ctx, st, "embed_bwd");
-  if (C <= 16)
-    hipLaunchKernelGGL((embed_bwd_fast_kernel<16>), dim3(nb), dim3(256), lds, st, N, C, F, rows, atoms, dh0, partial);
-  else
-    hipLaunchKernelGGL((embed_bwd_fast_kernel<32>), dim3(nb), dim3(256), lds, st, N, C, F, rows, atoms, dh0, partial);
+  hipLaunchKernelGGL((embed_bwd_fast_kernel<EB_CM>), dim3(nb), dim3(256), lds, st, N, C, F, rows, atoms, dh0, partial);
   NG_HIP(ctx, hipGetLastError());
   return reduce_or_defer(ctx, st, partial, nb, items, dWemb);
 }

@@ -43,6 +43,7 @@ struct LoadHeadY {           // dfull[i][c] = dpeaks[i] * atoms[i][c] * std[c]
 
 // ------------------------------------------------------------------------------------ embedding
 // h0[i][f] = sum_c atoms[i][c] * Wemb[c][f]      (model.py:262; Dense without bias)
+// Every term is taken, zeros included: a non-finite Wemb row gives 0 * inf = NaN, as the dense product does.
 __global__ void embed_fwd_kernel(int64_t N, int C, int F, const float* __restrict__ atoms,
                                  const float* __restrict__ Wemb, float* __restrict__ h0) {
   const int c4n = F / 4;
@@ -54,10 +55,8 @@ __global__ void embed_fwd_kernel(int64_t N, int C, int F, const float* __restric
     float4 acc = f4zero();
     for (int c = 0; c < C; ++c) {
       const float a = atoms[i * C + c];
-      if (a != 0.f) {
-        const float4 w = *reinterpret_cast<const float4*>(Wemb + (int64_t)c * F + c4 * 4);
-        acc.x += a * w.x; acc.y += a * w.y; acc.z += a * w.z; acc.w += a * w.w;
-      }
+      const float4 w = *reinterpret_cast<const float4*>(Wemb + (int64_t)c * F + c4 * 4);
+      acc.x += a * w.x; acc.y += a * w.y; acc.z += a * w.z; acc.w += a * w.w;
     }
     *reinterpret_cast<float4*>(h0 + i * F + c4 * 4) = acc;
   }
