@@ -564,6 +564,37 @@ int ng_loss_l2(ng_ctx*, void* stream, int64_t N, int G, const int32_t* graph_ptr
 int ng_restraint_loss(ng_ctx*, void* stream, int R, int64_t n, const float* peaks, const float* targets, const float* weights,
                       double* energy, float* dpeaks);
 
+/* Restraint forms (library.ShiftRestraint's tolerance / replica_weights / independent / tau): the restraint of
+ * ng_restraint_loss with replica weights, one energy per replica, a flat-bottom tolerance and a running average over calls.
+ * peaks [R*n] replica-major, targets / weights [n] as there.  mode NG_RESTRAINT_ENSEMBLE: G = 1 group (all replicas);
+ * NG_RESTRAINT_INDEPENDENT: G = R groups, group g = replica g.  Every step in float32, each product and sum rounded on its
+ * own (no fused multiply-add), in this order, per group g and atom i:
+ *   1. m   ensemble, c == NULL:  (sum_r peaks[r*n+i]) / R, summed in replica order — the bits of ng_restraint_loss's mean
+ *          ensemble, c [R]:      (..((c_0 p_0) + c_1 p_1) + ..) + c_{R-1} p_{R-1},  p_r = peaks[r*n+i]  (c as given: the
+ *                                caller normalises it)
+ *          independent:          peaks[g*n+i]                                      (c must be NULL)
+ *   2. a   lambda == 0, or primed[0] == 0:  a = m
+ *          otherwise:                       a = (lambda * avg[g*n+i]) + ((1 - lambda) * m)
+ *          lambda > 0: avg[g*n+i] = a is written back, and stage 2 sets primed[0] = 1 after every stage-1 read of it.
+ *          lambda == 0: avg and primed are not touched (may be NULL).
+ *   3. d = a - y_i,  e = |d| - tol_i clamped below at 0 (tol == NULL: e = |d|; a NaN stays a NaN),
+ *      energy[g] = sum_i (e * e) * w_i   (float32 terms summed in float64 in a fixed order, as ng_restraint_loss),
+ *      q = w_i * (2 * copysign(e, d))    (tol NULL or 0: the bits of w * (2 * d); inside the band |d| < tol: +-0)
+ *      q = q * (1 - lambda)              on a call with lambda > 0 and primed[0] != 0 (da/dm; 1 on the first call)
+ *   4. dpeaks[r*n+i] = q / R (ensemble, c NULL), q * c_r (ensemble, c), q for the replica's own atom (independent):
+ *      the exact derivative of this call's energy with respect to this call's shifts, the running average of earlier calls
+ *      held fixed.  Long memories (lambda near 1) thus give small forces, (1 - lambda) of the harmonic ones; the weights w
+ *      set the force constant.
+ * With c = NULL, tol = NULL (or all 0), lambda = 0 and NG_RESTRAINT_ENSEMBLE, energy[0] and dpeaks are the bits of
+ * ng_restraint_loss.  Two launches, no atomics, no host synchronisation: bitwise deterministic, capturable in a graph once the
+ * context's scratch holds G * n / 256 doubles; a replay reads whatever c, tol, avg and primed hold.  Refused: R * n >= 2^31,
+ * lambda outside [0, 1), c in independent mode, avg or primed NULL with lambda > 0.  n = 0 writes energies of 0. */
+#define NG_RESTRAINT_ENSEMBLE 0
+#define NG_RESTRAINT_INDEPENDENT 1
+int ng_restraint_loss_ex(ng_ctx*, void* stream, int R, int64_t n, int mode, const float* peaks, const float* targets,
+                         const float* weights, const float* c, const float* tol, float lambda, float* avg, int32_t* primed,
+                         double* energy, float* dpeaks);
+
 /* NameLoss with balance s in [0,1], nmrgnn/losses.py:4-15,30-39, batched over graphs:
  *   loss = mean_g [ s*l2_g + (1-s)*(1 - r_g) ],  r = cov/(m*sqrt(clip(var_x*var_y,0,1e32))) with the
  *   weighted moments of corr_coeff (divide_no_nan); s = 1 equals ng_loss_l2.  dpred as above. */

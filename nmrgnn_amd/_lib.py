@@ -79,6 +79,7 @@ SIGNATURES = {
     "ng_box_grad": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _int, _vp, _vp, _int, _vp, _vp]),
     "ng_box_grad_csr": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _f, _int, _vp, _vp, _int, _vp, _vp]),
     "ng_restraint_loss": (_int, [_vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ng_restraint_loss_ex": (_int, [_vp, _vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "ng_embed_fwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "ng_embed_bwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
     "ng_mp_aggregate": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp]),

@@ -209,6 +209,47 @@ def _restraint_box(box, R, triclinic=None):
     return vecs, bool(tric)
 
 
+def _host64(x):
+    import torch
+    return np.asarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else x, np.float64)
+
+
+def _restraint_tolerance(tolerance, n):
+    """host check of a flat-bottom tolerance (a scalar or [n] ppm, finite, >= 0): float32 [n]"""
+    t = _host64(tolerance)
+    if t.ndim == 0:
+        t = np.full(n, float(t))
+    if t.shape != (n,):
+        raise ValueError(f"ShiftRestraint: tolerance must be a scalar or [{n}], got {t.shape}")
+    if not np.isfinite(t).all() or (t < 0).any():
+        raise ValueError("ShiftRestraint: tolerance must be finite and >= 0")
+    return t.astype(np.float32)
+
+
+def _restraint_replica_weights(c, R):
+    """host check of replica weights ([R], finite, >= 0, positive sum): normalised in float64, then float32 [R]"""
+    c = _host64(c)
+    if c.shape != (R,):
+        raise ValueError(f"ShiftRestraint: replica_weights must be [{R}], got {c.shape}")
+    if not np.isfinite(c).all() or (c < 0).any() or not c.sum() > 0:
+        raise ValueError("ShiftRestraint: replica_weights must be finite, >= 0, with a positive sum")
+    return (c / c.sum()).astype(np.float32)
+
+
+def _restraint_lambda(tau):
+    """host check of a memory time tau (calls, finite, > 0): lambda = float32(exp(-1 / tau)), below 1 in float32"""
+    try:
+        t = float(tau)
+    except (TypeError, ValueError):
+        t = float("nan")
+    if not (np.isfinite(t) and t > 0):
+        raise ValueError(f"ShiftRestraint: tau must be a finite number of calls > 0, got {tau!r}")
+    lam = np.float32(np.exp(-1.0 / t))
+    if not lam < 1:
+        raise ValueError(f"ShiftRestraint: tau = {tau!r} gives lambda = 1 in float32 (a memory that never forgets)")
+    return float(lam)
+
+
 class ShiftRestraint:
     """Replica-averaged chemical-shift restraint of ``replicas`` structures of one topology, for an MD engine that asks for
     forces every step:
@@ -229,17 +270,34 @@ class ShiftRestraint:
     forces and the virial are bitwise those of ``shift_restraint`` (the energy is summed in another order: float64 here).
     ``replay=False`` runs the same chain eagerly (the reference of the tests and the debugging path).
 
+    Restraint forms (ng_restraint_loss_ex); with all four at their defaults the chain is the one above:
+      ``tolerance``        a scalar or [n] ppm (finite, >= 0): flat bottom, no energy and no force while
+                           |value - delta_exp_i| <= tol_i, and (|value - delta_exp_i| - tol_i)^2 outside
+      ``replica_weights``  [R] (finite, >= 0, positive sum; normalised in float64, then float32): the weighted mean
+                           sum_r c_r delta_pred[r, i] instead of the uniform one.  ``r(positions, replica_weights=...)``
+                           replaces them for this call and the next ones (staged with the positions)
+      ``independent``      one energy per replica, ``r.energies`` [R] float64 on the device; ``energy`` is their sum and
+                           the forces on replica r are -dE_r / dpos_r
+      ``tau``              a running average over calls with memory tau (calls): a = lambda a_prev + (1 - lambda) value,
+                           lambda = float32(exp(-1 / tau)), restrained in place of the value; the forces are the derivative
+                           of this call's energy with the earlier average held fixed, (1 - lambda) times those of the
+                           instantaneous restraint after the first call.  ``r.reset()`` forgets the average.
+    ``r.energies`` is [1] (the energy in float64) without ``independent``.
+
     Refused with ValueError before any device work: wrong shapes, a box where none was given at construction or none where
     one was, a box of the other kind or one pbc.prepare refuses, and a call after the model's weights changed (a training
-    step, a load): the captured chain would read stale packed weights — build a new restraint.  The call leaves
-    ``engine.params.grad`` alone."""
+    step, a load): the captured chain would read stale packed weights — build a new restraint.  Also bad tolerances, replica
+    weights or tau, ``replica_weights`` with ``independent``, and ``replica_weights`` at a call for a restraint built without
+    them or with R = 1.  The call leaves ``engine.params.grad`` alone."""
 
     def __init__(self, model, atoms, targets, weights=None, replicas=1, neighbor_number=16, box=None, virial=False,
-                 replay=True):
+                 replay=True, tolerance=None, replica_weights=None, independent=False, tau=None):
         import torch
         R = int(replicas)
         if R < 1 or R != replicas:
             raise ValueError(f"ShiftRestraint: replicas must be a positive integer, got {replicas!r}")
+        if replica_weights is not None and independent:
+            raise ValueError("ShiftRestraint: replica_weights average the replicas; independent replicas have none")
         a_shape = tuple(atoms.shape) if hasattr(atoms, "shape") else np.shape(atoms)
         if len(a_shape) != 2 or a_shape[0] < 1:
             raise ValueError(f"ShiftRestraint: atoms must be [n, C] one-hot, got {a_shape}")
@@ -252,9 +310,16 @@ class ShiftRestraint:
         w = np.ones(n, np.float32) if weights is None else np.asarray(host(weights), np.float32).reshape(-1)
         if y.shape[0] != n or w.shape[0] != n:
             raise ValueError(f"ShiftRestraint: targets and weights need {n} entries (one per atom)")
+        tol = None if tolerance is None else _restraint_tolerance(tolerance, n)
+        c = None if replica_weights is None else _restraint_replica_weights(replica_weights, R)
+        lam = 0.0 if tau is None else _restraint_lambda(tau)
         self.R, self.n, self.K = R, n, K
         self.virial = bool(virial)
         self.replay = bool(replay)
+        self.independent = bool(independent)
+        self.tau, self._lam = tau, lam
+        # the forms go through ng_restraint_loss_ex; with none of them set the chain keeps ng_restraint_loss, launch for launch
+        self._ex = tol is not None or c is not None or self.independent or tau is not None
         self._tric = None
         vecs = None
         if box is not None:
@@ -276,7 +341,13 @@ class ShiftRestraint:
         self._edges = torch.empty(R * n, K, dtype=torch.float32, device=dev)
         self._inv = torch.empty(R * n, dtype=torch.float32, device=dev)
         self._graph_ptr = np.arange(R + 1, dtype=np.int64) * n
-        self._e64 = torch.zeros(1, dtype=torch.float64, device=dev)
+        G = R if self.independent else 1
+        self._e64 = torch.zeros(G, dtype=torch.float64, device=dev)
+        self.energies = self._e64
+        self.s_tol = None if tol is None else torch.from_numpy(tol).to(dev)
+        self.s_c = None if c is None else torch.from_numpy(c).to(dev)
+        self._avg = torch.zeros(G * n, dtype=torch.float32, device=dev) if lam > 0 else None
+        self._primed = torch.zeros(1, dtype=torch.int32, device=dev) if lam > 0 else None
         self.energy = torch.zeros((), dtype=torch.float32, device=dev)
         self.forces = torch.zeros(R, n, 3, dtype=torch.float32, device=dev)
         self.virial_out = torch.zeros(R, 3, 3, dtype=torch.float64, device=dev) if self.virial else None
@@ -323,9 +394,14 @@ class ShiftRestraint:
         finally:
             eng.edge_table = keep
         dpeaks = torch.empty_like(peaks)
-        eng._ck(lib.ng_restraint_loss(h, st, R, n, ptr(peaks), ptr(self.s_y), ptr(self.s_w), ptr(self._e64), ptr(dpeaks)),
-                "ng_restraint_loss")
-        self.energy.copy_(self._e64[0])
+        if self._ex:
+            eng._ck(lib.ng_restraint_loss_ex(h, st, R, n, 1 if self.independent else 0, ptr(peaks), ptr(self.s_y), ptr(self.s_w),
+                                             ptr(self.s_c), ptr(self.s_tol), self._lam, ptr(self._avg), ptr(self._primed),
+                                             ptr(self._e64), ptr(dpeaks)), "ng_restraint_loss_ex")
+        else:
+            eng._ck(lib.ng_restraint_loss(h, st, R, n, ptr(peaks), ptr(self.s_y), ptr(self.s_w), ptr(self._e64), ptr(dpeaks)),
+                    "ng_restraint_loss")
+        self.energy.copy_(self._e64.sum() if self.independent else self._e64[0])
         dedges = torch.empty_like(self._edges)
         eng.backward(dpeaks, edge_grad=dedges, param_grad=False)
         torch.neg(b.positions_grad(dedges), out=self.forces)
@@ -348,11 +424,30 @@ class ShiftRestraint:
             with torch.cuda.graph(self._graph, stream=self._stream):
                 self._chain()
         cur.wait_stream(self._stream)
+        if self._primed is not None:
+            self.reset()            # the warm-up calls ran the running average: the first call starts it afresh
+
+    def reset(self):
+        """forget the running average (``tau``): the next call restrains its own shifts and starts the average from them.
+        An ordinary write on the current stream, between calls; a no-op without ``tau``."""
+        if self._primed is not None:
+            self._primed.zero_()
 
     # ------------------------------------------------------------------ calls
-    def check(self, positions, box=None):
+    def _call_weights(self, replica_weights):
+        """host check of a call's replica_weights: None (keep the staged ones) or float32 [R]"""
+        if replica_weights is None:
+            return None
+        if self.R == 1:
+            raise ValueError("ShiftRestraint: replica_weights at a call need more than one replica")
+        if self.s_c is None:
+            raise ValueError("ShiftRestraint: built without replica_weights (the chain reads none); pass them at construction")
+        return _restraint_replica_weights(replica_weights, self.R)
+
+    def check(self, positions, box=None, replica_weights=None):
         """the host-side refusals of a call (ValueError), without device work; returns (positions [R, n, 3], box vectors or
         None, whether positions were [n, 3])"""
+        self._call_weights(replica_weights)
         pos, flat = _restraint_positions(positions, self.R, self.n)
         if (box is None) != (self._tric is None):
             raise ValueError("ShiftRestraint: built without a box, called with one" if box is not None else
@@ -363,15 +458,18 @@ class ShiftRestraint:
                              "a load); build a new ShiftRestraint")
         return pos, vecs, flat
 
-    def __call__(self, positions, box=None):
+    def __call__(self, positions, box=None, replica_weights=None):
         import torch
         from .replay import _stage
+        c = self._call_weights(replica_weights)
         pos, vecs, flat = self.check(positions, box)
         eng = self.eng
         p = pos.to(device=eng.device, dtype=torch.float32).contiguous()
         pairs = [(p, self.s_pos)]
         if vecs is not None:
             pairs.append((torch.from_numpy(vecs).to(eng.device), self.s_box))
+        if c is not None:
+            pairs.append((torch.from_numpy(c).to(eng.device), self.s_c))
         _stage(eng, 0, 1e-4, 1, pairs)
         if self._graph is not None:
             self._graph.replay()

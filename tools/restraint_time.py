@@ -4,8 +4,10 @@ call:
   an orthorhombic box and the reduced triclinic box of DESIGN 7.3 (the rhombic dodecahedron), positions and box staged per
   call (the host-to-device copy of the inputs is inside the timed region, as an MD engine would pay it);
   Engine.backward(edge_grad=) with param_grad True against False on the bench batch (512 graphs x 256 atoms, K = 16), per-edge
-  and table edge paths (the forward with a tape is untimed).
-usage: python tools/restraint_time.py [out.json]"""
+  and table edge paths (the forward with a tape is untimed);
+  the restraint forms, replayed, one 7lgi frame and R = 8, no box: harmonic, flat-bottom, weighted replicas
+  (new weights staged every call), independent replicas, time-averaged.
+usage: python tools/restraint_time.py [--forms] [out.json]     (--forms: only the forms rows)"""
 import json
 import os
 import sys
@@ -102,10 +104,52 @@ def backward_rows():
     return out
 
 
+def forms_rows():
+    s = read_pdb("tests/data/7lgi.pdb.gz")
+    atoms = atoms_onehot(s.elements)
+    p = np.asarray(s.frames[0], np.float32)
+    n = p.shape[0]
+    rng = np.random.default_rng(3)
+    y = (rng.standard_normal(n) * 3.0).astype(np.float32)
+    w = rng.random(n).astype(np.float32)
+    hp = declare_gnn_space(HyperParameters(atom_feature_size=64))
+    model = GNNModel(hp, load_standards(), device=dev, seed=3)
+    model.build(atoms.shape[1])
+    out = {}
+    for R in (1, 8):
+        frames = np.stack([p + 0.05 * rng.standard_normal(p.shape).astype(np.float32) for _ in range(R)])
+        pos = frames[0] if R == 1 else frames
+        forms = [("harmonic", {}), ("flat", dict(tolerance=0.3)), ("averaged", dict(tau=10.0))]
+        if R > 1:
+            forms[2:2] = [("weighted", dict(replica_weights=np.ones(R))), ("independent", dict(independent=True))]
+        row = {}
+        for name, kw in forms:
+            r = ShiftRestraint(model, atoms, y, w, replicas=R, **kw)
+            if name == "weighted":
+                cs = [rng.random(R) + 0.1 for _ in range(2)]
+                k = [0]
+
+                def call():
+                    k[0] ^= 1
+                    r(pos, replica_weights=cs[k[0]])
+                row[f"{name}_ms"] = median_ms(call)
+            else:
+                row[f"{name}_ms"] = median_ms(lambda: r(pos))
+            del r
+        out[f"R{R}"] = row
+        print("forms", R, {k: round(v, 4) for k, v in row.items()}, flush=True)
+    return out
+
+
 def main():
-    res = {"restraint_7lgi": restraint_rows(), "backward_bench_batch": backward_rows()}
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    args = [a for a in sys.argv[1:] if a != "--forms"]
+    if "--forms" in sys.argv[1:]:
+        res = {"restraint_forms_7lgi": forms_rows()}
+    else:
+        res = {"restraint_7lgi": restraint_rows(), "backward_bench_batch": backward_rows(),
+               "restraint_forms_7lgi": forms_rows()}
+    if args:
+        with open(args[0], "w") as f:
             json.dump(res, f, indent=1)
 
 
