@@ -6,253 +6,14 @@ at F = 256, and every CSR list.  Each case below names the branch it exists for.
 call, so an entry the kernels never write fails.  Bound per element: |got - ref| <= C_REL * mag + 1e-7 * max(mag), where mag is
 the same expression evaluated on absolute values (activation slopes bounded by 1, plus |act(P)| for the activation's own
 rounding).  Inputs are rounded to float32 first, so the reference is the exact value of what the kernels were handed."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+# the float64 reference, the case builders and the device wrapper are shared with test_gpu_mp_window.py
+from mp_layer_gpu import GpuLayer, de_slots
+from mp_layer_ref import check, csr_case, degrees_with, padded_case, ref_layer
+
 pytestmark = pytest.mark.gpu
-
-C_REL = 3e-5
-ACT = {"none": 0, "softplus": 1, "relu": 2, "tanh": 3}
-
-
-def f32(a):
-    return np.asarray(a, np.float32).astype(np.float64)
-
-
-def act_fwd(act, P):
-    if act == 1:
-        return np.maximum(P, 0) + np.log1p(np.exp(-np.abs(P)))
-    if act == 2:
-        return np.maximum(P, 0)
-    if act == 3:
-        return np.tanh(P)
-    return P
-
-
-def act_grad_from_out(act, S):
-    if act == 1:
-        return -np.expm1(-S)
-    if act == 2:
-        return (S > 0).astype(np.float64)
-    if act == 3:
-        return 1.0 - S * S
-    return np.ones_like(S)
-
-
-def scatter_matrix(nl):
-    """[N, N*K] sparse 0/1 matrix: row t sums the slots (i, j) with nl[i, j] == t"""
-    from scipy.sparse import csr_matrix
-    N, K = nl.shape
-    return csr_matrix((np.ones(N * K), (nl.reshape(-1).astype(np.int64), np.arange(N * K))), shape=(N, N * K))
-
-
-def ref_layer(h, nl, e, inv, w, dH, act, residual):
-    """float64 forward and backward of one MPLayer over padded lists, with the per-element magnitudes of every output.
-    The backward is handed s_save = the float64 S rounded to float32, as the kernels are."""
-    N, K = nl.shape
-    E, F = e.shape[2], h.shape[1]
-    Wp = w.transpose(2, 0, 1).reshape(E * F, F)                 # Wp[n F + l][m] = w[l][m][n]
-    Sc = scatter_matrix(nl)
-    v, mg = {}, {}
-    slope = None
-    for out, hh, ee, WW, dd in ((v, h, e, Wp, dH), (mg, np.abs(h), np.abs(e), np.abs(Wp), np.abs(dH))):
-        hg = hh[nl]                                             # [N, K, F]
-        A = np.matmul(ee.transpose(0, 2, 1), hg)                # [N, E, F]
-        P = inv[:, None] * (A.reshape(N, E * F) @ WW)
-        out["A"] = A
-        out["s"] = act_fwd(act, P) if out is v else P + np.abs(v["s"])   # + the activation's own rounding
-        out["h_out"] = out["s"] + (hh if residual else 0.0)
-        if slope is None:
-            v["s_in"] = f32(out["s"])
-            slope = act_grad_from_out(act, v["s_in"])
-        dP = dd * (slope if out is v else np.abs(slope)) * inv[:, None]
-        out["dw"] = (A.reshape(N, E * F).T @ dP).reshape(E, F, F).transpose(1, 2, 0)
-        dA = (dP @ WW.T).reshape(N, E, F)
-        out["de"] = np.matmul(hg, dA.transpose(0, 2, 1))        # [N, K, E]
-        out["dh"] = dd + Sc @ np.matmul(ee, dA).reshape(N * K, F)
-    return v, mg
-
-
-def check(name, got, ref, mag, sel=None):
-    """per-element bound; returns max|err| / max(mag) for the comparison with the f32-input GEMM run"""
-    got = np.asarray(got, np.float64)
-    if sel is not None:
-        got, ref, mag = got[sel], ref[sel], mag[sel]
-    err = np.abs(got - ref)
-    top = float(mag.max()) if mag.size else 0.0
-    bad = ~(err <= C_REL * mag + 1e-7 * top)                   # NaN fails
-    if bad.any():
-        k = int(np.flatnonzero(bad.reshape(-1))[0])
-        raise AssertionError(f"{name}: {int(bad.sum())} of {bad.size} entries outside the bound; first at flat {k}: "
-                             f"got {got.reshape(-1)[k]!r} ref {ref.reshape(-1)[k]!r} mag {mag.reshape(-1)[k]!r}")
-    return float(err.max()) / top if top > 0 else 0.0
-
-
-# ---------------------------------------------------------------------------------------------------------- cases
-def padded_case(F, E, K, N, span, act, residual, seed, hub=0, p_dead=0.1):
-    """padded lists: graphs of `span` atoms (one graph when span == 0), neighbours inside the own graph; a `hub` > 0 sends
-    that many live slots of every graph to one target"""
-    rng = np.random.default_rng(seed)
-    g = span if span else N
-    base = (np.arange(N) // g) * g
-    size = np.minimum(base + g, N) - base
-    nl = (base[:, None] + (rng.random((N, K)) * size[:, None]).astype(np.int64)).astype(np.int32)
-    live = rng.random((N, K)) >= p_dead
-    if hub:
-        t = min(300, N - 2)
-        nl[(nl == t) & live] = t + 1
-        slots = np.flatnonzero(live.reshape(-1))
-        nl.reshape(-1)[rng.choice(slots, hub, replace=False)] = t
-        assert int(((nl == t) & live).sum()) == hub
-    e = f32(rng.standard_normal((N, K, E)) * np.where(live, 1.0, 0.0)[:, :, None])
-    return dict(kind="padded", F=F, E=E, K=K, N=N, span=span, act=ACT[act], residual=residual, nl=nl, e=e, live=live,
-                **_node_inputs(rng, N, F, E, K))
-
-
-def csr_case(F, E, N, degrees, act, residual, seed, hub=0):
-    """CSR lists with the given row lengths; neighbours anywhere in the batch; `hub` extra entries into one target"""
-    rng = np.random.default_rng(seed)
-    deg = np.asarray(degrees, np.int64)
-    col = rng.integers(0, N, int(deg.sum())).astype(np.int32)
-    if hub:
-        t = N // 2
-        col[col == t] = t + 1
-        col[rng.choice(len(col), hub, replace=False)] = t
-    row_ptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
-    nnz = int(row_ptr[-1])
-    e = f32(rng.standard_normal((nnz, E)))
-    # the reference runs on the padded form with K = the longest row
-    K = max(1, int(deg.max()))
-    rows = np.repeat(np.arange(N), deg)
-    slot = np.arange(nnz) - np.repeat(row_ptr[:-1], deg)
-    nl = np.zeros((N, K), np.int32)
-    nl[rows, slot] = col
-    ep = np.zeros((N, K, E))
-    ep[rows, slot] = e
-    live = np.zeros((N, K), bool)
-    live[rows, slot] = True
-    return dict(kind="csr", F=F, E=E, K=K, N=N, span=0, act=ACT[act], residual=residual, nl=nl, e=ep, live=live,
-                row_ptr=row_ptr, col=col, e_flat=e, rows=rows, slot=slot, **_node_inputs(rng, N, F, E, K))
-
-
-def _node_inputs(rng, N, F, E, K):
-    # weights scaled so that P stays O(1): activation slopes away from 0 (their float32 form is then good to a few ulp)
-    return dict(h=f32(rng.standard_normal((N, F)) * 0.5), inv=f32(rng.uniform(0.05, 1.0, N)),
-                w=f32(rng.standard_normal((F, F, E)) / np.sqrt(F * E * K)), dH=f32(rng.standard_normal((N, F))))
-
-
-def degrees_with(rng, N, hi, must):
-    d = rng.integers(0, hi + 1, N)
-    d[:len(must)] = must
-    return rng.permutation(d)
-
-
-class GpuLayer:
-    """the case's tensors on the device and the C entry points of its list form"""
-
-    def __init__(self, case, dev):
-        import torch
-        from nmrgnn_amd import _lib
-        from nmrgnn_amd.graph import GraphBatch
-        self.c, self.dev = case, dev
-        t = lambda a, dt=np.float32: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
-        self.t = t
-        N, E = case["N"], case["E"]
-        atoms = np.eye(10, dtype=np.float32)[np.arange(N) % 10]
-        if case["kind"] == "padded":
-            gb = GraphBatch(atoms, case["nl"], case["live"].astype(np.float32), case["inv"], device=dev)
-            self.nlist = gb.nlist_c
-            self.te = t(case["e"])
-        else:
-            gb = GraphBatch.from_csr(atoms, case["row_ptr"], case["col"], np.ones(len(case["col"]), np.float32),
-                                     inv_degree=case["inv"], device=dev)
-            self.row_ptr, self.col, self.row_of = gb.row_ptr, gb.nlist, gb.row_of
-            self.te = t(case["e_flat"])
-        self.csc_ptr, self.csc_edge = gb.csc()
-        self.th, self.tinv, self.tw = t(case["h"]), t(case["inv"]), t(case["w"])
-        self.ctx = _lib.get_context(0)
-        self.st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        self.n_ent = N * case["K"] if case["kind"] == "padded" else len(case["col"])
-
-    def nan(self, *shape):
-        import torch
-        return torch.full(shape, float("nan"), device=self.dev)
-
-    def records(self):
-        from nmrgnn_amd._lib import ptr
-        c = self.c
-        rec = self.nan(c["N"] * c["K"], 4)
-        self.ctx.check(self.ctx.lib.ng_mp_edge_records(self.ctx.handle, self.st, c["N"], c["K"], c["E"], ptr(self.csc_ptr),
-                                                       ptr(self.csc_edge), ptr(self.te), ptr(rec)), "records")
-        return rec
-
-    def aggregate(self):
-        from nmrgnn_amd._lib import ptr
-        c = self.c
-        A = self.nan(c["N"], c["E"], c["F"])
-        if c["kind"] == "padded":
-            rc = self.ctx.lib.ng_mp_aggregate(self.ctx.handle, self.st, c["N"], c["K"], c["F"], c["E"], ptr(self.th),
-                                              ptr(self.nlist), ptr(self.te), ptr(A))
-        else:
-            rc = self.ctx.lib.ng_mp_aggregate_csr(self.ctx.handle, self.st, c["N"], c["F"], c["E"], ptr(self.th),
-                                                  ptr(self.row_ptr), ptr(self.col), ptr(self.te), ptr(A))
-        self.ctx.check(rc, "aggregate")
-        return A
-
-    def fwd(self, h=None, keep_A=True):
-        from nmrgnn_amd._lib import ptr
-        c = self.c
-        N, F, E = c["N"], c["F"], c["E"]
-        h_out, s, A = self.nan(N, F), self.nan(N, F), (self.nan(N, E, F) if keep_A else None)
-        th = self.th if h is None else h
-        if c["kind"] == "padded":
-            rc = self.ctx.lib.ng_mp_layer_fwd(self.ctx.handle, self.st, N, c["K"], F, E, c["act"], c["residual"], ptr(th),
-                                              ptr(self.nlist), ptr(self.te), ptr(self.tinv), ptr(self.tw), ptr(h_out),
-                                              ptr(A), ptr(s))
-        else:
-            rc = self.ctx.lib.ng_mp_layer_fwd_csr(self.ctx.handle, self.st, N, self.n_ent, F, E, c["act"], c["residual"],
-                                                  ptr(th), ptr(self.row_ptr), ptr(self.col), ptr(self.te), ptr(self.tinv),
-                                                  ptr(self.tw), ptr(h_out), ptr(A), ptr(s))
-        self.ctx.check(rc, "fwd")
-        return h_out, A, s
-
-    def bwd(self, A, S, dH, h=None, rec=None, de_prior=None):
-        """dh_in, de [entries, E], dw; de accumulates onto de_prior when given"""
-        from nmrgnn_amd._lib import ptr
-        c = self.c
-        N, F, E = c["N"], c["F"], c["E"]
-        dh, dw = self.nan(N, F), self.nan(F, F, E)
-        de = self.nan(self.n_ent, E) if de_prior is None else de_prior.clone()
-        acc = 0 if de_prior is None else 1
-        th = self.th if h is None else h
-        if c["kind"] == "csr":
-            rc = self.ctx.lib.ng_mp_layer_bwd_csr(self.ctx.handle, self.st, N, self.n_ent, F, E, c["act"], ptr(th),
-                                                  ptr(self.row_ptr), ptr(self.col), ptr(self.row_of), ptr(self.te),
-                                                  ptr(self.tinv), ptr(self.tw), ptr(A), ptr(S), ptr(self.csc_ptr),
-                                                  ptr(self.csc_edge), ptr(dH), ptr(dh), ptr(de), acc, ptr(dw))
-        elif rec is None:
-            rc = self.ctx.lib.ng_mp_layer_bwd(self.ctx.handle, self.st, N, c["K"], F, E, c["act"], ptr(th), ptr(self.nlist),
-                                              ptr(self.te), ptr(self.tinv), ptr(self.tw), ptr(A), ptr(S), ptr(self.csc_ptr),
-                                              ptr(self.csc_edge), ptr(dH), ptr(dh), ptr(de), acc, ptr(dw))
-        else:
-            rc = self.ctx.lib.ng_mp_layer_bwd_rec(self.ctx.handle, self.st, N, c["K"], F, E, c["act"], ptr(th),
-                                                  ptr(self.nlist), ptr(self.te), ptr(self.tinv), ptr(self.tw), ptr(A),
-                                                  ptr(S), ptr(self.csc_ptr), ptr(self.csc_edge), ptr(dH), ptr(dh), ptr(de),
-                                                  acc, ptr(dw), ptr(rec))
-        self.ctx.check(rc, "bwd")
-        return dh, de, dw
-
-
-def de_slots(case, de):
-    """de of the kernels ([entries, E]) in the padded [N, K, E] form of the reference"""
-    de = de.cpu().numpy().astype(np.float64)
-    if case["kind"] == "padded":
-        return de.reshape(case["N"], case["K"], case["E"])
-    out = np.zeros((case["N"], case["K"], case["E"]))
-    out[case["rows"], case["slot"]] = de
-    return out
 
 
 def uses_split_gemms(case):
