@@ -25,7 +25,6 @@
 #include "ng_internal.h"
 #include "edge_fused.h"   // NG_LDS_BARRIER
 #include "h2_common.cuh"
-#include "mp_win16_common.cuh"
 #include "mp_wave_common.cuh"
 
 namespace ng {
@@ -378,7 +377,7 @@ int mp_wave_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int act, int r
   Args a{};
   a.N = N; a.K = K;
   // contiguous runs per workgroup: whole groups when the batch is large enough, 64-atom steps below (ng_internal.h)
-  a.atoms_per_wg = win16_tiles_per_wg(cdiv(N, 64), ctx->num_cu) * 64;
+  a.atoms_per_wg = win_tiles_per_wg(cdiv(N, 64), ctx->num_cu, 4) * 64;
   a.h = h; a.nlist = nlist; a.e = e; a.Wfrag = Wfrag; a.Wfrag32 = Wf32; a.rowscale = inv_degree; a.residual = residual;
   a.out = h_out; a.S_save = s_save; a.act = act;
   a.guard = guard; a.wflag = wflag; a.wflag_ver = pack_flag_version(ctx);

@@ -4,15 +4,15 @@
 #include <algorithm>
 
 #include "h2_common.cuh"
-#include "mp_win16_common.cuh"
+#include "mp_win_common.cuh"
 
 namespace ng {
 namespace wv {
 
-using w16c::f32x4;
+using winc::f32x4;
+using winc::WF;
+using winc::WROWS;
 
-constexpr int WF = 64;
-constexpr int WROWS = 288;                 // window rows
 constexpr int MT = 16;                     // atoms per micro-tile
 constexpr int NWV = 8;                     // waves per workgroup
 constexpr int WTHREADS = NWV * 64;

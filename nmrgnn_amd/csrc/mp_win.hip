@@ -35,17 +35,11 @@
 #include "edge_fused.h"   // NG_LDS_BARRIER
 #include "h2_common.cuh"
 #include "pack_bodies.cuh"
+#include "mp_win_common.cuh"
 
 namespace ng {
 
-constexpr int WF = 64;          // feature width
-constexpr int WTA = 32;         // atoms per tile
-constexpr int WROWS = 288;      // window rows
-constexpr int WC4 = WF / 4;     // float4 per row = lanes per atom
-constexpr int WTHREADS = 512;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace w8c;
 
 // ---- weight images (packed by pack_bodies.cuh) ----
 // f32 fragments for v_mfma_f32_16x16x4_f32 (A operand: row i = lane & 15, k = lane >> 4):
@@ -77,27 +71,6 @@ PackJob mpw_bwd_job(int E, const float* w, float* outT, float* outN, float* f32T
 int mpw_pack2(ng_ctx* ctx, hipStream_t st, int E, const float* w, int mode_a, float* out_a, int mode_b, float* out_b) {
   if (int rc = mpw_pack(ctx, st, E, mode_a, w, out_a)) return rc;
   return mpw_pack(ctx, st, E, mode_b, w, out_b);
-}
-
-// ---- shared device pieces ---------------------------------------------------------------------------
-
-// min over the 64 lanes, valid in lane 63: row_shr 1,2,4,8 inside rows of 16, then row_bcast 15 / 31
-__device__ __forceinline__ int wave_min_i32(int v) {
-  const int big = 0x7fffffff;
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x111, 0xf, 0xf, false));   // row_shr:1
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x112, 0xf, 0xf, false));   // row_shr:2
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x114, 0xf, 0xf, false));   // row_shr:4
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x118, 0xf, 0xf, false));   // row_shr:8
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x142, 0xa, 0xf, false));   // row_bcast:15 -> rows 1,3
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x143, 0xc, 0xf, false));   // row_bcast:31 -> rows 2,3
-  return v;
-}
-
-// acc += w * h for one float4 of features, as two v_pk_fma_f32
-__device__ __forceinline__ void pk_axpy(f32x2& lo, f32x2& hi, float w, const float4& h) {
-  const f32x2 ww = {w, w};
-  lo = __builtin_elementwise_fma(ww, f32x2{h.x, h.y}, lo);
-  hi = __builtin_elementwise_fma(ww, f32x2{h.z, h.w}, hi);
 }
 
 // Neighbour lists of one 32-atom tile in flight between global memory and LDS.  K % 4 == 0: whole
@@ -179,124 +152,11 @@ struct WinLists {
   }
 };
 
-// every thread takes the same decision from the eight partial ranges; returns true when the window has
-// to be restaged at the (updated) wlo.  mode: 0 = gather from the window, 1 = gather from global memory
-__device__ __forceinline__ bool win_decide(const int* __restrict__ ctl, int& wlo, int& mode) {
-  int lo = ctl[0], hi = ctl[8];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) { lo = min(lo, ctl[i]); hi = max(hi, ctl[8 + i]); }
-  mode = 0;
-  if (hi < lo) return false;                                  // empty tile
-  if (lo >= wlo && hi < wlo + WROWS) return false;            // window hit
-  if (hi - lo + 1 > WROWS) { mode = 1; return false; }        // too wide
-  wlo = max(0, lo - (WROWS - (hi - lo + 1)) / 2);
-  return true;
-}
-
-__device__ __forceinline__ void win_stage(float4* __restrict__ win4, const float4* __restrict__ src4,
-                                          int wlo, int64_t N, int tid) {
-  float4 v[9];
-#pragma unroll
-  for (int u = 0; u < 9; ++u) {
-    const int idx = tid + WTHREADS * u;
-    const int64_t row = (int64_t)wlo + (idx >> 4);
-    v[u] = row < N ? src4[row * WC4 + (idx & 15)] : f4zero();
-  }
-#pragma unroll
-  for (int u = 0; u < 9; ++u) win4[tid + WTHREADS * u] = v[u];
-}
-static_assert(WROWS * WC4 == 9 * WTHREADS, "window staging assumes 9 float4 per thread");
-
-// ---- aggregate tile in LDS -------------------------------------------------------------------------------
-// H2 = false: fp32 rows [32][E*64 + 4].  H2 = true: two fp16 piece planes [2][32][E*64 + 8] (h2_common.cuh): the gather
-// splits its sums where they are formed and the matrix phase runs on v_mfma_f32_16x16x32_f16 (18 instead of 48 MFMAs
-// per wave and tile at E = 3); aggregates are O(1-10) activations and are split unscaled.
+// the aggregate tile (mp_win_common.cuh) at this geometry
 template <int E>
-struct WinTile {
-  static constexpr int KF = E * WF;
-  static constexpr int LD = KF + 4;                    // fp32 row stride (floats)
-  static constexpr int ROWB = (KF + 8) * 2;            // fp16 plane row stride (bytes): 16 rows on disjoint 4-bank groups
-  static constexpr int PLANE = WTA * ROWB;
-  static constexpr int BYTES_F32 = WTA * LD * 4, BYTES_H2 = 2 * PLANE;
-};
+using WinTile = AggTile<WTA, E>;
 
-template <int S>
-__device__ __forceinline__ int ror_i(int v) {
-  if (S == 0) return v;
-  return __builtin_amdgcn_update_dpp(0, v, 0x120 + (S & 15), 0xf, 0xf, false);
-}
-template <int S>
-__device__ __forceinline__ float ror_f(float v) {
-  return __builtin_bit_cast(float, ror_i<S>(__builtin_bit_cast(int, v)));
-}
-
-// H2 rows carry a power-of-two scale when their largest entry reaches 2^15 (an aggregate of features is a forward quantity
-// of any size — the reference's MPLayer is plain fp32): the 16 lanes of the row's DPP row hold all of it, the inverse goes
-// to rs[atom] for the epilogue.  Every ordinary row has scale 1 and the same bits as without.
-template <int E, bool H2>
-__device__ __forceinline__ void tile_put(float* __restrict__ tb, int al, int c, f32x2 (&lo)[E], f32x2 (&hi)[E],
-                                         float* __restrict__ rs) {
-  if (H2) {
-    float m = 0.f;
-#pragma unroll
-    for (int n = 0; n < E; ++n)
-      m = fmaxf(fmaxf(m, fmaxf(fabsf(lo[n][0]), fabsf(lo[n][1]))), fmaxf(fabsf(hi[n][0]), fabsf(hi[n][1])));
-    float rsv = 1.0f;
-    if (__builtin_amdgcn_ballot_w64(m >= 32768.0f) != 0) {      // wave-uniform and never taken for ordinary activations
-      m = fmaxf(m, ror_f<8>(m)); m = fmaxf(m, ror_f<4>(m)); m = fmaxf(m, ror_f<2>(m)); m = fmaxf(m, ror_f<1>(m));
-      const int ef = (__builtin_bit_cast(int, m) >> 23) & 255;
-      const bool big = ef >= 127 + 15 && ef != 255;
-      const float S = big ? __builtin_bit_cast(float, (268 - ef) << 23) : 1.0f;       // 2^(14 - e): |S x| < 2^15
-      rsv = big ? __builtin_bit_cast(float, (ef - 14) << 23) : 1.0f;
-      const f32x2 S2 = {S, S};
-#pragma unroll
-      for (int n = 0; n < E; ++n) { lo[n] *= S2; hi[n] *= S2; }
-    }
-    if (c == 0) rs[al] = rsv;
-    char* p = reinterpret_cast<char*>(tb) + al * WinTile<E>::ROWB + 8 * c;
-#pragma unroll
-    for (int n = 0; n < E; ++n) {
-      unsigned h0, l0, h1, l1;
-      split2_pair(lo[n][0], lo[n][1], h0, l0);
-      split2_pair(hi[n][0], hi[n][1], h1, l1);
-      *reinterpret_cast<u32x2*>(p + n * (WF * 2)) = u32x2{h0, h1};
-      *reinterpret_cast<u32x2*>(p + n * (WF * 2) + WinTile<E>::PLANE) = u32x2{l0, l1};
-    }
-  } else {
-#pragma unroll
-    for (int n = 0; n < E; ++n)
-      *reinterpret_cast<float4*>(tb + al * WinTile<E>::LD + n * WF + 4 * c) = make_float4(lo[n][0], lo[n][1], hi[n][0], hi[n][1]);
-  }
-}
-
-// ---- rotation gather (K <= 16, window mode) ------------------------------------------------------------
-// Lane c of an atom's 16-lane row owns neighbour slot c: ONE index and E weights per lane instead of
-// every lane reading the whole list (which cost as much LDS bandwidth as the row gather itself).  In
-// step s the lane uses the slot of lane (c + s) mod 16, fetched over the DPP network (row_ror:s) —
-// each lane walks the neighbours in its own rotated order, the sum is the same.  All sixteen lanes of
-// a row read the SAME bank group (4c..4c+3) of sixteen DIFFERENT window rows: still conflict-free.
-// four rotation steps: row reads and FMAs are separate so that the reads of the NEXT four steps can be
-// issued before the FMAs of the current four (the LDS latency is otherwise exposed: both waves of a SIMD
-// run this phase in lockstep and wait at the same time)
-template <int S0>
-__device__ __forceinline__ void rot_load4(const char* __restrict__ wbytes, int roff, float4 (&h)[4]) {
-  h[0] = *reinterpret_cast<const float4*>(wbytes + ror_i<S0 + 0>(roff));
-  h[1] = *reinterpret_cast<const float4*>(wbytes + ror_i<S0 + 1>(roff));
-  h[2] = *reinterpret_cast<const float4*>(wbytes + ror_i<S0 + 2>(roff));
-  h[3] = *reinterpret_cast<const float4*>(wbytes + ror_i<S0 + 3>(roff));
-}
-template <int E, int S0>
-__device__ __forceinline__ void rot_fma4(const float4 (&h)[4], const float (&w)[E], f32x2 (&lo)[E], f32x2 (&hi)[E]) {
-#pragma unroll
-  for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ror_f<S0 + 0>(w[n]), h[0]);
-#pragma unroll
-  for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ror_f<S0 + 1>(w[n]), h[1]);
-#pragma unroll
-  for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ror_f<S0 + 2>(w[n]), h[2]);
-#pragma unroll
-  for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ror_f<S0 + 3>(w[n]), h[3]);
-}
-
+// ---- rotation gather (K <= 16, window mode; the steps are in mp_win_common.cuh) ----------------------------------
 template <int E, bool H2>
 __device__ __forceinline__ void win_gather_rot(int K, int wave, int lane, int wlo,
                                                const int32_t* __restrict__ nl, const float* __restrict__ ee,
@@ -327,7 +187,7 @@ __device__ __forceinline__ void win_gather_rot(int K, int wave, int lane, int wl
   __builtin_amdgcn_sched_barrier(0);
   rot_fma4<E, 8>(ha, w, lo, hi);
   rot_fma4<E, 12>(hb, w, lo, hi);
-  tile_put<E, H2>(tb, al, c, lo, hi, rs);
+  tile_put<WTA, E, H2>(tb, al, c, lo, hi, rs);
 }
 
 // gather + edge-weighted sum of one 32-atom tile: 16 lanes per atom, 4 atoms per wave, 8 waves.
@@ -405,7 +265,7 @@ __device__ __forceinline__ void win_gather(int K, int wave, int lane, int wlo,
       for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ee[(al * K + j) * E + n], hv);
     }
   }
-  tile_put<E, H2>(tb, al, c, lo, hi, rs);
+  tile_put<WTA, E, H2>(tb, al, c, lo, hi, rs);
 }
 
 // The global-memory variant is kept out of line: inlined next to the window variant it makes the
@@ -983,7 +843,7 @@ int egrad_win(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, const
               const float* dA, float* de, int accumulate) {
   EGradWinArgs a{};
   a.N = N; a.K = K; a.F = F; a.ntiles = cdiv(N, WTA);
-  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu);
+  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu, 8);
   a.tiles_per_wg = (int)per;
   a.h = h; a.nlist = nlist; a.dA = dA; a.de = de; a.accumulate = accumulate;
   const int grid = (int)cdiv(a.ntiles, per);
@@ -1007,7 +867,7 @@ int agg_win(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, const f
             const float* e, float* A) {
   AggWinArgs a{};
   a.N = N; a.K = K; a.F = F; a.ntiles = cdiv(N, WTA);
-  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu);
+  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu, 8);
   a.tiles_per_wg = (int)per;
   a.h = h; a.nlist = nlist; a.e = e; a.A = A;
   const int grid = (int)cdiv(a.ntiles, per);
@@ -1085,7 +945,7 @@ int mp_win_fwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int act, in
   a.N = N; a.K = K; a.ntiles = cdiv(N, WTA);
   // contiguous runs of tiles per workgroup, a multiple of 8 tiles (256 atoms) so that runs start on
   // molecule boundaries for the common 256-atom padding
-  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu);
+  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu, 8);
   a.tiles_per_wg = (int)per;
   a.h = h; a.nlist = nlist; a.e = e; a.Wfrag = Wfrag; a.rowscale = inv_degree; a.residual = residual;
   a.out = h_out; a.S_save = s_save; a.act = act; a.dummy = Wfrag + KF * WF;

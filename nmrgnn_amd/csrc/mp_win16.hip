@@ -22,7 +22,7 @@
 #include "ng_internal.h"
 #include "edge_fused.h"   // NG_LDS_BARRIER
 #include "h2_common.cuh"
-#include "mp_win16_common.cuh"
+#include "mp_win_common.cuh"
 
 namespace ng {
 namespace w16 {
@@ -50,51 +50,9 @@ struct Args {
   unsigned wflag_ver;
 };
 
+// the aggregate tile (mp_win_common.cuh) at this geometry
 template <int E>
-struct Tile {
-  static constexpr int KF = E * WF;
-  static constexpr int LD = KF + 4;                    // fp32 row stride (floats)
-  static constexpr int ROWB = (KF + 8) * 2;            // fp16 plane row stride (bytes)
-  static constexpr int PLANE = WTA * ROWB;
-  static constexpr int BYTES = (2 * PLANE > WTA * LD * 4) ? 2 * PLANE : WTA * LD * 4;
-};
-
-// as mp_win.hip: tile_put (piece planes with a power-of-two row scale when a row reaches 2^15, or fp32 rows)
-template <int E, bool H2>
-__device__ __forceinline__ void tile_put(float* __restrict__ tb, int al, int c, f32x2 (&lo)[E], f32x2 (&hi)[E],
-                                         float* __restrict__ rs) {
-  if (H2) {
-    float m = 0.f;
-#pragma unroll
-    for (int n = 0; n < E; ++n)
-      m = fmaxf(fmaxf(m, fmaxf(fabsf(lo[n][0]), fabsf(lo[n][1]))), fmaxf(fabsf(hi[n][0]), fabsf(hi[n][1])));
-    float rsv = 1.0f;
-    if (__builtin_amdgcn_ballot_w64(m >= 32768.0f) != 0) {      // wave-uniform and never taken for ordinary activations
-      m = fmaxf(m, ror_f<8>(m)); m = fmaxf(m, ror_f<4>(m)); m = fmaxf(m, ror_f<2>(m)); m = fmaxf(m, ror_f<1>(m));
-      const int ef = (__builtin_bit_cast(int, m) >> 23) & 255;
-      const bool big = ef >= 127 + 15 && ef != 255;
-      const float S = big ? __builtin_bit_cast(float, (268 - ef) << 23) : 1.0f;
-      rsv = big ? __builtin_bit_cast(float, (ef - 14) << 23) : 1.0f;
-      const f32x2 S2 = {S, S};
-#pragma unroll
-      for (int n = 0; n < E; ++n) { lo[n] *= S2; hi[n] *= S2; }
-    }
-    if (c == 0) rs[al] = rsv;
-    char* p = reinterpret_cast<char*>(tb) + al * Tile<E>::ROWB + 8 * c;
-#pragma unroll
-    for (int n = 0; n < E; ++n) {
-      unsigned h0, l0, h1, l1;
-      split2_pair(lo[n][0], lo[n][1], h0, l0);
-      split2_pair(hi[n][0], hi[n][1], h1, l1);
-      *reinterpret_cast<u32x2*>(p + n * (WF * 2)) = u32x2{h0, h1};
-      *reinterpret_cast<u32x2*>(p + n * (WF * 2) + Tile<E>::PLANE) = u32x2{l0, l1};
-    }
-  } else {
-#pragma unroll
-    for (int n = 0; n < E; ++n)
-      *reinterpret_cast<float4*>(tb + al * Tile<E>::LD + n * WF + 4 * c) = make_float4(lo[n][0], lo[n][1], hi[n][0], hi[n][1]);
-  }
-}
+using Tile = AggTile<WTA, E>;
 
 // one lane's list entry: neighbour index and E edge weights of (atom, slot)
 template <int E>
@@ -126,32 +84,6 @@ __device__ __forceinline__ void slot_mask(Slot<E>& s, bool live) {
   }
 }
 
-template <int S0>
-__device__ __forceinline__ void rot_load4(const char* __restrict__ wbytes, int roff, float4 (&h)[4]) {
-  h[0] = *reinterpret_cast<const float4*>(wbytes + ror_i<S0 + 0>(roff));
-  h[1] = *reinterpret_cast<const float4*>(wbytes + ror_i<S0 + 1>(roff));
-  h[2] = *reinterpret_cast<const float4*>(wbytes + ror_i<S0 + 2>(roff));
-  h[3] = *reinterpret_cast<const float4*>(wbytes + ror_i<S0 + 3>(roff));
-}
-template <int S0>
-__device__ __forceinline__ void rot_load4_global(const float4* __restrict__ src4, int c, int idx, float4 (&h)[4]) {
-  h[0] = src4[(int64_t)ror_i<S0 + 0>(idx) * WC4 + c];
-  h[1] = src4[(int64_t)ror_i<S0 + 1>(idx) * WC4 + c];
-  h[2] = src4[(int64_t)ror_i<S0 + 2>(idx) * WC4 + c];
-  h[3] = src4[(int64_t)ror_i<S0 + 3>(idx) * WC4 + c];
-}
-template <int E, int S0>
-__device__ __forceinline__ void rot_fma4(const float4 (&h)[4], const float (&w)[E], f32x2 (&lo)[E], f32x2 (&hi)[E]) {
-#pragma unroll
-  for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ror_f<S0 + 0>(w[n]), h[0]);
-#pragma unroll
-  for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ror_f<S0 + 1>(w[n]), h[1]);
-#pragma unroll
-  for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ror_f<S0 + 2>(w[n]), h[2]);
-#pragma unroll
-  for (int n = 0; n < E; ++n) pk_axpy(lo[n], hi[n], ror_f<S0 + 3>(w[n]), h[3]);
-}
-
 // rotation gather of one atom row (mp_win.hip: win_gather_rot) with the lane's slot in registers; GLOBAL: rows from HBM / L2
 template <int E, bool H2, bool GLOBAL>
 __device__ __forceinline__ void gather(int lane, int al, int wlo, int idx, const float (&w)[E], float* __restrict__ tb,
@@ -171,7 +103,7 @@ __device__ __forceinline__ void gather(int lane, int al, int wlo, int idx, const
   __builtin_amdgcn_sched_barrier(0);
   NG_W16_STEP(0) NG_W16_STEP(4) NG_W16_STEP(8) NG_W16_STEP(12)
 #undef NG_W16_STEP
-  tile_put<E, H2>(tb, al, c, lo, hi, rs);
+  tile_put<WTA, E, H2>(tb, al, c, lo, hi, rs);
 }
 
 // kept out of line: inlined next to the window variant its global loads make the compiler put vmcnt waits into the window path
@@ -363,7 +295,7 @@ int mp_win16_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int ac
   Args a{};
   a.N = N; a.K = K; a.ntiles = cdiv(N, WTA);
   // contiguous runs of tiles per workgroup: multiples of 4 (256 atoms) when the batch is large enough (ng_internal.h)
-  const int64_t per = win16_tiles_per_wg(a.ntiles, ctx->num_cu);
+  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu, 4);
   a.tiles_per_wg = (int)per;
   a.h = h; a.nlist = nlist; a.e = e; a.Wfrag = Wfrag; a.Wfrag32 = Wf32; a.rowscale = inv_degree; a.residual = residual;
   a.out = h_out; a.S_save = s_save; a.act = act; a.dummy = const_cast<float*>(Wfrag) + (size_t)E * WF * WF;

@@ -18,7 +18,7 @@
 #include "ng_internal.h"
 #include "edge_fused.h"   // NG_LDS_BARRIER
 #include "h2_common.cuh"
-#include "mp_win16_common.cuh"
+#include "mp_win_common.cuh"
 
 namespace ng {
 namespace w16b {
@@ -51,64 +51,6 @@ struct Args {
   const unsigned* wflag;
   unsigned wflag_ver;
 };
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }
-
-// one rotation step of the edge-gradient dot (mp_win_bwd.hip: edge_step): this lane's chunk of dA[i][n][:] against the row
-// of the slot that the rotation brings here; the partial goes back to the accumulator of that slot's lane
-template <int E, int S, bool GLOBAL>
-__device__ __forceinline__ void edge_step(const char* __restrict__ wbytes, const float4* __restrict__ src4, int c, int roff,
-                                          int gidx, const float4 (&da)[E], float (&out)[E]) {
-  float4 hrow;
-  if (!GLOBAL) hrow = *reinterpret_cast<const float4*>(wbytes + ror_i<S>(roff));
-  else hrow = src4[(int64_t)ror_i<S>(gidx) * WC4 + c];
-#pragma unroll
-  for (int n = 0; n < E; ++n) {
-    const float p = dot4(da[n], hrow);
-    out[n] += ror_f<(16 - S) & 15>(p);
-  }
-}
-template <int E, bool GLOBAL>
-__device__ __forceinline__ void edge_dot(int lane, int al, int wlo, int idx, const float* __restrict__ tb, int ld,
-                                         const float4* __restrict__ win4, const float4* __restrict__ src4, float (&out)[E]) {
-  const int c = lane & 15;
-  const int roff = min(max(idx - wlo, 0), WROWS - 1) * (WF * 4);
-  const char* wbytes = reinterpret_cast<const char*>(win4) + 16 * c;
-  float4 da[E];
-#pragma unroll
-  for (int n = 0; n < E; ++n) {
-    da[n] = *reinterpret_cast<const float4*>(tb + al * ld + n * WF + 4 * c);
-    out[n] = 0.f;
-  }
-  edge_step<E, 0, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 1, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 2, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 3, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 4, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 5, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 6, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 7, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 8, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 9, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 10, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 11, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 12, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 13, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 14, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 15, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
-}
-template <int E>
-struct EdgeDots { float v[E]; };
-// out of line: its global loads must not put vmcnt waits into the window path
-template <int E>
-__device__ __noinline__ EdgeDots<E> edge_dot_global(int lane, int al, int idx, const float* tb, int ld, const float4* src4) {
-  float out[E];
-  edge_dot<E, true>(lane, al, 0, idx, tb, ld, nullptr, src4, out);
-  EdgeDots<E> r;
-#pragma unroll
-  for (int n = 0; n < E; ++n) r.v[n] = out[n];
-  return r;
-}
 
 template <int E, bool H2, int ACT = -1>      // ACT: compile-time activation (softplus) or -1 = from the arguments (mp_wave.hip: body)
 __device__ __forceinline__ void body(const Args& a) {
@@ -306,7 +248,7 @@ int mp_win16_bwd_edge_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int 
   Args a{};
   a.N = N; a.K = K; a.ntiles = cdiv(N, WTA);
   // contiguous runs of tiles per workgroup: multiples of 4 (256 atoms) when the batch is large enough (ng_internal.h)
-  const int64_t per = win16_tiles_per_wg(a.ntiles, ctx->num_cu);
+  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu, 4);
   a.tiles_per_wg = (int)per;
   a.dH = dh_out; a.S = act == NG_ACT_NONE ? nullptr : s_save; a.rowscale = inv_degree; a.h = h;
   a.nlist = nlist; a.WfragT = WfragT; a.WfragT32 = WfragT32; a.dP = dP; a.de = de; a.dummy = dummy; a.act = act;

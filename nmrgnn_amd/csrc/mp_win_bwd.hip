@@ -25,74 +25,24 @@
 #include "reduce.cuh"
 #include "h2_common.cuh"
 #include "pack_bodies.cuh"
+#include "mp_win_common.cuh"
 
 namespace ng {
 
 namespace {
 
-constexpr int WF = 64;
-constexpr int WTA = 32;
-constexpr int WROWS = 288;
-constexpr int WC4 = WF / 4;
-constexpr int WTHREADS = 512;
+using namespace w8c;
+
 constexpr int SDP_LD = 68;      // dP / h tile row stride (== 4 mod 16: conflict-free K-strided reads)
 constexpr int SDP_SLOT = 2304;  // floats per dP tile slot of the edge kernel: [32][68] fp32, or two fp16 piece planes [32][72]
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef short gs16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ int wave_min_i32(int v) {
-  const int big = 0x7fffffff;
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x111, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x112, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x114, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x118, 0xf, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x142, 0xa, 0xf, false));
-  v = min(v, __builtin_amdgcn_update_dpp(big, v, 0x143, 0xc, 0xf, false));
-  return v;
-}
-
-template <int S>
-__device__ __forceinline__ int ror_i(int v) {
-  if (S == 0) return v;
-  return __builtin_amdgcn_update_dpp(0, v, 0x120 + (S & 15), 0xf, 0xf, false);
-}
-template <int S>
-__device__ __forceinline__ float ror_f(float v) {
-  return __builtin_bit_cast(float, ror_i<S>(__builtin_bit_cast(int, v)));
-}
-
-__device__ __forceinline__ bool win_decide(const int* __restrict__ ctl, int& wlo, int& mode) {
-  int lo = ctl[0], hi = ctl[8];
-#pragma unroll
-  for (int i = 1; i < 8; ++i) { lo = min(lo, ctl[i]); hi = max(hi, ctl[8 + i]); }
-  mode = 0;
-  if (hi < lo) return false;
-  if (lo >= wlo && hi < wlo + WROWS) return false;
-  if (hi - lo + 1 > WROWS) { mode = 1; return false; }
-  wlo = max(0, lo - (WROWS - (hi - lo + 1)) / 2);
-  return true;
-}
-
-__device__ __forceinline__ void win_stage(float4* __restrict__ win4, const float4* __restrict__ src4,
-                                          int wlo, int64_t N, int tid) {
-  float4 v[9];
-#pragma unroll
-  for (int u = 0; u < 9; ++u) {
-    const int idx = tid + WTHREADS * u;
-    const int64_t row = (int64_t)wlo + (idx >> 4);
-    v[u] = row < N ? src4[row * WC4 + (idx & 15)] : f4zero();
-  }
-#pragma unroll
-  for (int u = 0; u < 9; ++u) win4[tid + WTHREADS * u] = v[u];
-}
 
 // The window by LDS-DMA (round 4): its 288 rows are one contiguous 72-KB block of the source array — 72 wave-instructions
 // of 1 KB, nine per wave, straight into LDS with no registers in between, so the request can be made as soon as no wave
 // reads the old window any more and awaited (s_waitcnt vmcnt(0)) in front of the barrier before the next gather: the
 // HBM / L2 round trip runs beside the matrix interval.  Rows past the end read as zeros (buffer bounds).  32-bit byte
-// offsets: up to 16.7 M rows, beyond that the register staging above.
+// offsets: up to 16.7 M rows, beyond that the register staging (win_stage).
 __device__ __forceinline__ void win_dma(float* __restrict__ win, dma_i4 rs, int wlo, int wave, int lane) {
 #pragma unroll
   for (int j = 0; j < WROWS * WF * 4 / 1024 / 8; ++j) {
@@ -101,10 +51,6 @@ __device__ __forceinline__ void win_dma(float* __restrict__ win, dma_i4 rs, int 
   }
 }
 static_assert(WROWS * WF * 4 == 72 * 1024 && WTHREADS == 512, "win_dma: nine 1-KB instructions for each of eight waves");
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-  return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
-}
 
 // ---- edge kernel ---------------------------------------------------------------------------------------
 struct MpWinEdgeArgs {
@@ -129,26 +75,14 @@ struct MpWinEdgeArgs {
   unsigned wflag_ver;
 };
 
-// one rotation step of the edge-gradient dot: this lane's chunk of dA[i][n][:] against the row of the slot
-// that the rotation brings here; the partial lands in the accumulator of THAT slot's lane afterwards
-template <int E, int S, int MODE>
-__device__ __forceinline__ void edge_step(const char* __restrict__ wbytes, const float4* __restrict__ src4,
-                                          int c, int roff, int gidx, const float4 (&da)[E], float (&out)[E]) {
-  float4 hrow;
-  if (MODE == 0) hrow = *reinterpret_cast<const float4*>(wbytes + ror_i<S>(roff));
-  else hrow = src4[(int64_t)ror_i<S>(gidx) * WC4 + c];
-#pragma unroll
-  for (int n = 0; n < E; ++n) {
-    const float p = dot4(da[n], hrow);
-    // slot (c + S) was processed here; rotate the partial back to its owner: out_j = sum_S ror_{16-S}(p_S)
-    out[n] += ror_f<(16 - S) & 15>(p);
-  }
-}
-
-template <int E, int MODE>
-__device__ __forceinline__ void edge_dot(int K, int wave, int lane, int wlo, const int32_t* __restrict__ nl,
-                                         const float* __restrict__ tb, int ld, const float4* __restrict__ win4,
-                                         const float4* __restrict__ src4, float (&out)[E]) {
+// The edge-gradient dot over the shared edge_step, with the lane's neighbour index read from the tile's list in LDS.
+// This kernel keeps the walk itself instead of calling the shared edge_dot (mp_win_common.cuh) behind the list read: with
+// the read outside the function whose __restrict__ pointers cover the other loads, every mp_win_bwd_edge_kernel came out
+// with another register allocation (one or two more instructions; the other kernels of this file were unchanged).
+template <int E, bool GLOBAL>
+__device__ __forceinline__ void edge_dot_list(int K, int wave, int lane, int wlo, const int32_t* __restrict__ nl,
+                                              const float* __restrict__ tb, int ld, const float4* __restrict__ win4,
+                                              const float4* __restrict__ src4, float (&out)[E]) {
   const int c = lane & 15;
   const int al = wave * 4 + (lane >> 4);
   const int idx = nl[al * K + (c < K ? c : 0)];
@@ -160,34 +94,30 @@ __device__ __forceinline__ void edge_dot(int K, int wave, int lane, int wlo, con
     da[n] = *reinterpret_cast<const float4*>(tb + al * ld + n * WF + 4 * c);
     out[n] = 0.f;
   }
-  edge_step<E, 0, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 1, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 2, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 3, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 4, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 5, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 6, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 7, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 8, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 9, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 10, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 11, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 12, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 13, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 14, MODE>(wbytes, src4, c, roff, idx, da, out);
-  edge_step<E, 15, MODE>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 0, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 1, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 2, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 3, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 4, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 5, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 6, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 7, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 8, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 9, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 10, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 11, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 12, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 13, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 14, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
+  edge_step<E, 15, GLOBAL>(wbytes, src4, c, roff, idx, da, out);
 }
 
-// kept out of line: inlined next to the window variant its global loads make the compiler put vmcnt
-// waits into the window path (see mp_win.hip)
+// out of line for the reason given at edge_dot_global (mp_win_common.cuh); takes the list, so it is a function of its own
 template <int E>
-struct EdgeDots { float v[E]; };      // returned in registers: an array passed out by pointer lived on the stack
-
-template <int E>
-__device__ __noinline__ EdgeDots<E> edge_dot_global(int K, int wave, int lane, const int32_t* nl, const float* tb,
-                                                    int ld, const float4* src4) {
+__device__ __noinline__ EdgeDots<E> edge_dot_list_global(int K, int wave, int lane, const int32_t* nl, const float* tb,
+                                                         int ld, const float4* src4) {
   float out[E];
-  edge_dot<E, 1>(K, wave, lane, 0, nl, tb, ld, nullptr, src4, out);
+  edge_dot_list<E, true>(K, wave, lane, 0, nl, tb, ld, nullptr, src4, out);
   EdgeDots<E> r;
 #pragma unroll
   for (int n = 0; n < E; ++n) r.v[n] = out[n];
@@ -397,9 +327,9 @@ __device__ __forceinline__ void mp_win_bwd_edge_body(const MpWinEdgeArgs& a) {
     {
       float out[E];
       const int32_t* nl = s_nl + (t & 1) * per_tile;
-      if (mode == 0) edge_dot<E, 0>(K, wave, lane, wlo, nl, tile, LD, win4, src4, out);
+      if (mode == 0) edge_dot_list<E, false>(K, wave, lane, wlo, nl, tile, LD, win4, src4, out);
       else {
-        const EdgeDots<E> r = edge_dot_global<E>(K, wave, lane, nl, tile, LD, src4);
+        const EdgeDots<E> r = edge_dot_list_global<E>(K, wave, lane, nl, tile, LD, src4);
 #pragma unroll
         for (int n = 0; n < E; ++n) out[n] = r.v[n];
       }
@@ -453,12 +383,6 @@ struct MpWinNodeArgs {
   const unsigned* wflag;    // as in MpWinEdgeArgs
   unsigned wflag_ver;
 };
-
-__device__ __forceinline__ void pk_axpy(f32x2& lo, f32x2& hi, float w, const float4& h) {
-  const f32x2 ww = {w, w};
-  lo = __builtin_elementwise_fma(ww, f32x2{h.x, h.y}, lo);
-  hi = __builtin_elementwise_fma(ww, f32x2{h.z, h.w}, hi);
-}
 
 template <int E, int S0, int MODE>
 __device__ __forceinline__ void node_steps4(const char* __restrict__ wbytes, const float4* __restrict__ src4,
@@ -956,7 +880,7 @@ int mp_win_bwd_node(ng_ctx* ctx, hipStream_t st, int64_t N, int E, const float* 
                     const unsigned* wflag, unsigned wflag_ver) {
   MpWinNodeArgs a{};
   a.N = N; a.ntiles = cdiv(N, WTA);
-  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu);
+  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu, 8);
   a.tiles_per_wg = (int)per;
   a.dP = dP; a.dH = dh_out; a.h = h; a.csc_ptr = csc_ptr; a.rec = reinterpret_cast<const float4*>(rec);
   a.WfragN = WfragN; a.dh = dh_in; a.partial = scratch; a.dummy = dummy; a.guard = guard;
@@ -998,7 +922,7 @@ int mp_win_bwd_edge(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int ac
                                     WfragT32, wflag, wflag_ver);
   MpWinEdgeArgs a{};
   a.N = N; a.K = K; a.ntiles = cdiv(N, WTA);
-  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu);
+  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu, 8);
   a.tiles_per_wg = (int)per;
   a.dH = dh_out; a.S = act == NG_ACT_NONE ? nullptr : s_save; a.rowscale = inv_degree; a.h = h;
   a.nlist = nlist; a.WfragT = WfragT; a.dP = dP; a.de = de; a.dummy = dummy; a.act = act;

@@ -24,9 +24,9 @@ Variants (kernel bodies), each forward and backward against float64:
 K in 17..32 or K % 4 != 0: window forward (win_gather with K4 true and false) and the generic backward in one layer, with the
 aggregate kept as ng_mp_layer_wants_aggregate asks.
 
-Run lengths follow the library's own rule (win_tiles_per_wg, win16_tiles_per_wg): the N of the cases long, two32, two64 and one
+Run lengths follow the library's own rule (win_tiles_per_wg): the N of the cases long, two32, two64 and one
 is searched from the device's compute-unit count (n_with) and the length reached is asserted.  The wave kernel walks 256-atom
-groups of a run of win16_tiles_per_wg * 64 atoms: on 256 CUs that is a part of one group below N = 16384 and two groups
+groups of a run of win_tiles_per_wg * 64 atoms: on 256 CUs that is a part of one group below N = 16384 and two groups
 (256 + 64 atoms) at N = 69985.  A fifth (partial) group per workgroup needs more than 1024 atoms per run, N > 262,144 on 256 CUs,
 five whole ones N > 311,296: beyond the size this file may use, so that length is not reached.
 The forward kernels' power-of-two row scale (aggregates that reach 2^15) is the subject of test_gpu_mp_range.py and
@@ -67,7 +67,7 @@ def cdiv(a, b):
 
 
 def tiles_per_wg(ntiles, num_cu, first_align):
-    """win_tiles_per_wg (first_align 8) / win16_tiles_per_wg (first_align 4) of csrc/ng_internal.h"""
+    """win_tiles_per_wg of csrc/ng_internal.h: first_align 8 for 32-atom tiles, 4 for 64-atom tiles"""
     base = max(cdiv(ntiles, num_cu), 1)
     want = min(num_cu, ntiles)
     align = first_align

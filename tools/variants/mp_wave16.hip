@@ -22,7 +22,7 @@
 #include "ng_internal.h"
 #include "edge_fused.h"   // NG_LDS_BARRIER
 #include "h2_common.cuh"
-#include "mp_win16_common.cuh"
+#include "mp_win_common.cuh"
 #include "mp_wave_common.cuh"
 
 namespace ng {
@@ -355,7 +355,7 @@ int mp_wave16_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int act, int
   using namespace wv16;
   Args a{};
   a.N = N; a.K = K;
-  a.atoms_per_wg = win16_tiles_per_wg(cdiv(N, 64), ctx->num_cu) * 64;
+  a.atoms_per_wg = win_tiles_per_wg(cdiv(N, 64), ctx->num_cu, 4) * 64;
   a.h = h; a.nlist = nlist; a.e = e; a.Wfrag = Wfrag; a.Wfrag32 = Wf32; a.rowscale = inv_degree; a.residual = residual;
   a.out = h_out; a.S_save = s_save; a.act = act;
   a.guard = guard; a.wflag = wflag;

@@ -22,7 +22,7 @@
 #include "ng_internal.h"
 #include "edge_fused.h"   // NG_LDS_BARRIER
 #include "h2_common.cuh"
-#include "mp_win16_common.cuh"
+#include "mp_win_common.cuh"
 #include "mp_wave_common.cuh"
 
 namespace ng {
@@ -304,7 +304,7 @@ int mp_wave_bwd_edge_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int a
   using namespace wvb;
   Args a{};
   a.N = N; a.K = K;
-  a.atoms_per_wg = win16_tiles_per_wg(cdiv(N, 64), ctx->num_cu) * 64;
+  a.atoms_per_wg = win_tiles_per_wg(cdiv(N, 64), ctx->num_cu, 4) * 64;
   a.dH = dh_out; a.S = act == NG_ACT_NONE ? nullptr : s_save; a.rowscale = inv_degree; a.h = h;
   a.nlist = nlist; a.WfragT = WfragT; a.WfragT32 = WfragT32; a.dP = dP; a.de = de; a.act = act;
   a.accumulate = de_accum; a.guard = guard; a.wflag = wflag;

@@ -25,7 +25,7 @@
 #include "ng_internal.h"
 #include "edge_fused.h"   // NG_LDS_BARRIER
 #include "h2_common.cuh"
-#include "mp_win16_common.cuh"
+#include "mp_win_common.cuh"
 
 namespace ng {
 namespace w16n {
@@ -533,7 +533,7 @@ int mp_win16_bwd_node_launch(ng_ctx* ctx, hipStream_t st, int64_t N, int E, cons
   Args a{};
   a.N = N; a.ntiles = cdiv(N, WTA);
   // contiguous runs of tiles per workgroup: multiples of 4 (256 atoms) when the batch is large enough (ng_internal.h)
-  const int64_t per = win16_tiles_per_wg(a.ntiles, ctx->num_cu);
+  const int64_t per = win_tiles_per_wg(a.ntiles, ctx->num_cu, 4);
   a.tiles_per_wg = (int)per;
   a.dP = dP; a.dH = dh_out; a.h = h; a.csc_ptr = csc_ptr; a.rec = reinterpret_cast<const float4*>(rec);
   a.WfragN = WfragN; a.WfragN32 = WfragN32; a.dh = dh_in; a.partial = scratch; a.dummy = dummy;
