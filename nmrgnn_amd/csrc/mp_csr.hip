@@ -390,7 +390,7 @@ struct PullWinArgs {
 // A workgroup (one per CU, sixteen waves) takes tiles of 256 consecutive targets.  Per tile: every thread owns 4 float4 of
 // FOUR target rows (16 lanes per target, 64 targets per pass, 4 passes: 64 accumulator registers — the tile's whole
 // [256][256] gradient block lives in registers), the tile's records are staged in LDS once (64 KB), and the source rows
-// [lo, hi] of the tile are walked in blocks of 24 full rows x E (72 KB, the next block travelling in registers meanwhile).
+// [lo, hi] of the tile are walked in blocks of PW_BR = 16 full rows x E (48 KB, the next block travelling in registers meanwhile).
 // The records of a target are in ascending source order (CSC order = ascending entry id = source-major), so each (thread,
 // pass) just advances a pointer through its target's list as the blocks go by.  dA, base and out cross HBM once, whole rows.
 // Measured (same box, ms per launch at 512 x 256 atoms, profiles/r05c_pull_win.txt): through L2 0.384 | this kernel 0.335 | its

@@ -1,4 +1,5 @@
 """The device side of the MPLayer tests: a case of tests/mp_layer_ref.py on the GPU and the C entry points of its list form."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -36,9 +37,25 @@ class GpuLayer:
         import torch
         return torch.full(shape, float("nan"), device=self.dev)
 
-    def records(self):
+    @contextlib.contextmanager
+    def graph_span(self, span=None):
+        """the batch's largest graph announced to the shared context (ng_ctx_set_graph_span; the case's own span by default)
+        for the calls inside, and 0 = unknown again behind them"""
+        lib, handle = self.ctx.lib, self.ctx.handle
+        self.ctx.check(lib.ng_ctx_set_graph_span(handle, self.c["span"] if span is None else span), "span")
+        try:
+            yield self
+        finally:
+            self.ctx.check(lib.ng_ctx_set_graph_span(handle, 0), "span")
+
+    def records(self, host=None):
+        """the incoming-edge records of ng_mp_edge_records, or caller-built ones (`host` [entries, 4], mp_layer_ref.host_records)"""
         from nmrgnn_amd._lib import ptr
         c = self.c
+        if host is not None:
+            rec = self.nan(max(len(host), 1), 4)
+            rec[:len(host)] = self.t(host)
+            return rec
         rec = self.nan(c["N"] * c["K"], 4)
         self.ctx.check(self.ctx.lib.ng_mp_edge_records(self.ctx.handle, self.st, c["N"], c["K"], c["E"], ptr(self.csc_ptr),
                                                        ptr(self.csc_edge), ptr(self.te), ptr(rec)), "records")

@@ -122,8 +122,29 @@ def incoming(nl, e, dP, Sc=None):
     return np.stack([Sc @ (e[:, :, n, None] * dP[:, None, :]).reshape(N * K, -1) for n in range(e.shape[2])], axis=1)
 
 
-def layer_stats(h, nl, e, inv, w, dH, act, residual, v, mg, live):
-    """{key: (r32, r_drop)} for key in STAT_KEYS, against the float64 values v and magnitudes mg of ref_layer.  The backward
+def f32_layer(h, nl, e, inv, w, dH, act, residual, slope):
+    """plain float32 NumPy evaluation of ref_layer's formulas (every operand and every intermediate float32); the backward takes
+    the slope it is handed, as the kernels take it from s_save"""
+    N, K = nl.shape
+    E, F = e.shape[2], h.shape[1]
+    t = np.float32
+    Wp = w.transpose(2, 0, 1).reshape(E * F, F)
+    h_, e_, inv_, W_, dd_ = h.astype(t), e.astype(t), inv.astype(t), Wp.astype(t), dH.astype(t)
+    hg = h_[nl]
+    A = np.matmul(e_.transpose(0, 2, 1), hg)
+    s = act_fwd(act, inv_[:, None] * (A.reshape(N, E * F) @ W_)).astype(t)
+    dP = dd_ * slope.astype(t) * inv_[:, None]
+    dA = (dP @ W_.T).reshape(N, E, F)
+    g32 = {"A": A, "s": s, "h_out": s + (h_ if residual else t(0)),
+           "dw": (A.reshape(N, E * F).T @ dP).reshape(E, F, F).transpose(1, 2, 0),
+           "de": np.matmul(hg, dA.transpose(0, 2, 1)),
+           "dh": dd_ + scatter_matrix(nl, t) @ np.matmul(e_, dA).reshape(N * K, F)}
+    assert all(a.dtype == t for a in g32.values())
+    return g32
+
+
+def layer_stats(h, nl, e, inv, w, dH, act, residual, v, mg, live, keys=STAT_KEYS):
+    """{key: (r32, r_drop)} for key in keys, against the float64 values v and magnitudes mg of ref_layer.  The backward
     of both emulations takes the slope from v["s_in"], as the kernels take it from the s_save they are handed."""
     N, K = nl.shape
     E, F = e.shape[2], h.shape[1]
@@ -132,56 +153,74 @@ def layer_stats(h, nl, e, inv, w, dH, act, residual, v, mg, live):
     Wn = w.transpose(2, 1, 0).reshape(E * F, F)                 # Wn[n F + m][l] = w[l][m][n]
     sel = {"de": live}
     # ---- plain float32 evaluation of the formula of ref_layer
-    t = np.float32
-    h_, e_, inv_, W_, dd_ = h.astype(t), e.astype(t), inv.astype(t), Wp.astype(t), dH.astype(t)
-    hg = h_[nl]
-    A = np.matmul(e_.transpose(0, 2, 1), hg)
-    s = act_fwd(act, inv_[:, None] * (A.reshape(N, E * F) @ W_)).astype(t)
-    dP = dd_ * slope.astype(t) * inv_[:, None]
-    dA = (dP @ W_.T).reshape(N, E, F)
-    g32 = {"s": s, "h_out": s + (h_ if residual else t(0)),
-           "dw": (A.reshape(N, E * F).T @ dP).reshape(E, F, F).transpose(1, 2, 0),
-           "de": np.matmul(hg, dA.transpose(0, 2, 1)),
-           "dh": dd_ + scatter_matrix(nl, t) @ np.matmul(e_, dA).reshape(N * K, F)}
-    assert all(a.dtype == t for a in g32.values())
-    r32 = {k: rstat(g32[k], v[k], mg[k], sel.get(k)) for k in STAT_KEYS}
-    del g32, hg, A, dA
+    g32 = f32_layer(h, nl, e, inv, w, dH, act, residual, slope)
+    r32 = {k: rstat(g32[k], v[k], mg[k], sel.get(k)) for k in keys}
+    del g32
     # ---- float64 with the small piece of one operand missing (module docstring)
     s = act_fwd(act, inv[:, None] * (lead_piece(v["A"].reshape(N, E * F)) @ Wp))
-    dP = dH * slope * inv[:, None]
-    dA = (lead_piece(dP) @ Wp.T).reshape(N, E, F)
-    B = lead_piece(incoming(nl, e, dP).reshape(N, E * F))
-    gd = {"s": s, "h_out": s + (h if residual else 0.0), "de": np.matmul(h[nl], dA.transpose(0, 2, 1)),
-          "dh": dH + B @ Wn, "dw": (h.T @ B).reshape(F, E, F).transpose(0, 2, 1)}
-    return {k: (r32[k], rstat(gd[k], v[k], mg[k], sel.get(k))) for k in STAT_KEYS}
+    gd = {"s": s, "h_out": s + (h if residual else 0.0)}
+    if set(keys) - set(gd):                                     # a backward key is asked for
+        dP = dH * slope * inv[:, None]
+        dA = (lead_piece(dP) @ Wp.T).reshape(N, E, F)
+        B = lead_piece(incoming(nl, e, dP).reshape(N, E * F))
+        gd.update(de=np.matmul(h[nl], dA.transpose(0, 2, 1)), dh=dH + B @ Wn, dw=(h.T @ B).reshape(F, E, F).transpose(0, 2, 1))
+    return {k: (r32[k], rstat(gd[k], v[k], mg[k], sel.get(k))) for k in keys}
 
 
 # ---------------------------------------------------------------------------------------------------------- cases
-def padded_case(F, E, K, N, span, act, residual, seed, hub=0, p_dead=0.1):
-    """padded lists: graphs of `span` atoms (one graph when span == 0), neighbours inside the own graph; a `hub` > 0 sends
-    that many live slots of every graph to one target"""
+def graph_layout(N, span):
+    """graph index, first row and size of every atom's graph.  span: an int (graphs of that many atoms; one graph when 0) or a
+    sequence of graph sizes whose last one repeats (mixed spans in one batch)"""
+    if np.ndim(span) == 0:
+        g = int(span) if span else N
+        gi = np.arange(N) // g
+        base = gi * g
+        return gi, base, np.minimum(base + g, N) - base
+    sizes, starts, at = list(span), [], 0
+    while at < N:
+        starts.append(at)
+        at += int(sizes[min(len(starts) - 1, len(sizes) - 1)])
+    starts = np.array(starts + [at], np.int64)
+    gi = np.searchsorted(starts, np.arange(N), side="right") - 1
+    return gi, starts[gi], np.minimum(starts[gi + 1], N) - starts[gi]
+
+
+def padded_case(F, E, K, N, span, act, residual, seed, hub=0, p_dead=0.1, bias=None, hub_local=False):
+    """padded lists: graphs of `span` atoms (graph_layout), neighbours inside the own graph; a `hub` > 0 sends that many live
+    slots (of the whole batch, or with hub_local of the target's own graph) to one target.  bias = (form, p) draws a slot's
+    local index as size * u^p: "low" favours the lower-numbered atoms of every graph, "ends" the higher-numbered atoms of the
+    even graphs and the lower-numbered ones of the odd graphs (targets on both sides of every second graph boundary crowd)"""
     rng = np.random.default_rng(seed)
-    g = span if span else N
-    base = (np.arange(N) // g) * g
-    size = np.minimum(base + g, N) - base
-    nl = (base[:, None] + (rng.random((N, K)) * size[:, None]).astype(np.int64)).astype(np.int32)
+    gi, base, size = graph_layout(N, span)
+    u = rng.random((N, K))
+    if bias is not None:
+        u = u ** bias[1]
+        if bias[0] == "ends":
+            u = np.where((gi % 2 == 0)[:, None], np.nextafter(1.0, 0.0) - u, u)
+    nl = (base[:, None] + (u * size[:, None]).astype(np.int64)).astype(np.int32)
     live = rng.random((N, K)) >= p_dead
     if hub:
         t = min(300, N - 2)
         nl[(nl == t) & live] = t + 1
-        slots = np.flatnonzero(live.reshape(-1))
+        pool = live & (gi == gi[t])[:, None] if hub_local else live
+        slots = np.flatnonzero(pool.reshape(-1))
         nl.reshape(-1)[rng.choice(slots, hub, replace=False)] = t
         assert int(((nl == t) & live).sum()) == hub
     e = f32(rng.standard_normal((N, K, E)) * np.where(live, 1.0, 0.0)[:, :, None])
-    return dict(kind="padded", F=F, E=E, K=K, N=N, span=span, act=ACT[act], residual=residual, nl=nl, e=e, live=live,
+    return dict(kind="padded", F=F, E=E, K=K, N=N, span=int(np.max(span)), act=ACT[act], residual=residual, nl=nl, e=e, live=live,
                 **_node_inputs(rng, N, F, E, K))
 
 
-def csr_case(F, E, N, degrees, act, residual, seed, hub=0):
-    """CSR lists with the given row lengths; neighbours anywhere in the batch; `hub` extra entries into one target"""
+def csr_case(F, E, N, degrees, act, residual, seed, hub=0, local=0):
+    """CSR lists with the given row lengths; neighbours anywhere in the batch, or with `local` inside the row's own graph of that
+    many atoms; `hub` extra entries into one target"""
     rng = np.random.default_rng(seed)
     deg = np.asarray(degrees, np.int64)
-    col = rng.integers(0, N, int(deg.sum())).astype(np.int32)
+    if local:
+        _, base, size = graph_layout(N, local)
+        col = (np.repeat(base, deg) + (rng.random(int(deg.sum())) * np.repeat(size, deg)).astype(np.int64)).astype(np.int32)
+    else:
+        col = rng.integers(0, N, int(deg.sum())).astype(np.int32)
     if hub:
         t = N // 2
         col[col == t] = t + 1
@@ -199,7 +238,7 @@ def csr_case(F, E, N, degrees, act, residual, seed, hub=0):
     ep[rows, slot] = e
     live = np.zeros((N, K), bool)
     live[rows, slot] = True
-    return dict(kind="csr", F=F, E=E, K=K, N=N, span=0, act=ACT[act], residual=residual, nl=nl, e=ep, live=live,
+    return dict(kind="csr", F=F, E=E, K=K, N=N, span=local, act=ACT[act], residual=residual, nl=nl, e=ep, live=live,
                 row_ptr=row_ptr, col=col, e_flat=e, rows=rows, slot=slot, **_node_inputs(rng, N, F, E, K))
 
 
@@ -213,3 +252,76 @@ def degrees_with(rng, N, hi, must):
     d = rng.integers(0, hi + 1, N)
     d[:len(must)] = must
     return rng.permutation(d)
+
+
+# ---------------------------------------------------------------------------------------------------------- exact family
+# Inputs on coarse binary grids: every output of the layer is then a sum of multiples of one power of two (its granule), and
+# while mag / granule stays below 2^24 every partial sum in any order is a float32 number: a kernel must give the float64
+# statement bit for bit.  (h, dH in {-3..3}; e in {-2..2}/2; w in {-4..4}/8; inv_degree in {1, 1/2, 1/4, 1/8}; activation none
+# or relu.)  granule: A = e h -> 1/2; P = inv A w -> 1/128; dP = dH inv -> 1/8; dw = A dP -> 1/16; dA = dP w -> 1/64; de = h dA
+# -> 1/64; dh = dH + e dA -> 1/128.  The operands of the split products (A, dP, dA, B) must fit two fp16 pieces: at most 20
+# significant bits (test_mp_layer_ref_host.py).
+GRANULE = {"A": 2.0 ** -1, "s": 2.0 ** -7, "h_out": 2.0 ** -7, "dw": 2.0 ** -4, "de": 2.0 ** -6, "dh": 2.0 ** -7}
+# incoming edges one target may have in the exact family: one edge adds at most sum_n |e_n| * mag(dA) to mag(dh), mag(dA) about
+# 256 * mean|dP| * mean|w| = 60 on average and a few hundred at most (inv_degree = 1, |dP| = 3): 2^24 / 128 / (3 * 300) = 145
+EXACT_HUB = 128
+
+
+def exact_inputs(case, seed):
+    """the case with its numbers replaced by the exact family's (lists, live slots and shape kept)"""
+    assert case["act"] in (ACT["none"], ACT["relu"])
+    rng = np.random.default_rng(seed)
+    N, K, E, F = case["N"], case["K"], case["E"], case["F"]
+    c = dict(case, family="exact")
+    c["h"] = rng.integers(-3, 4, (N, F)).astype(np.float64)
+    c["dH"] = rng.integers(-3, 4, (N, F)).astype(np.float64)
+    c["e"] = rng.integers(-2, 3, (N, K, E)) / 2.0 * case["live"][:, :, None]
+    c["w"] = rng.integers(-4, 5, (F, F, E)) / 8.0
+    c["inv"] = 2.0 ** -rng.integers(0, 4, N).astype(np.float64)
+    if case["kind"] == "csr":
+        c["e_flat"] = c["e"][case["rows"], case["slot"]]
+    return c
+
+
+def sigbits(x):
+    """the largest number of significant bits among the non-zero elements of x"""
+    x = np.abs(np.asarray(x, np.float64)).reshape(-1)
+    x = x[x > 0]
+    if not x.size:
+        return 0
+    m, _ = np.frexp(x)
+    mi = np.round(m * 2.0 ** 53).astype(np.int64)
+    low = mi & -mi                                              # lowest set bit
+    return int(53 - np.log2(low.min().astype(np.float64)))
+
+
+def host_records(case, permute=None):
+    """csc_ptr [N + 1] and the incoming-edge records [live entries, 4] = {source row (int bits), e_0, e_1, e_2} in CSC order
+    (stable by target: ascending entry id, hence ascending source), as ng_mp_edge_records writes them; `permute` (a seed)
+    shuffles the records inside every target's segment — a caller-built order"""
+    N, K, E = case["N"], case["K"], case["E"]
+    if case["kind"] == "padded":
+        eid = np.flatnonzero(case["live"].reshape(-1))
+        tgt, src, ev = case["nl"].reshape(-1)[eid].astype(np.int64), eid // K, case["e"].reshape(-1, E)[eid]
+    else:
+        tgt, src, ev = case["col"].astype(np.int64), case["rows"], case["e_flat"]
+    order = np.argsort(tgt, kind="stable")
+    if permute is not None:
+        key = tgt[order] + np.random.default_rng(permute).random(len(order))
+        order = order[np.argsort(key, kind="stable")]
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(tgt, minlength=N))]).astype(np.int32)
+    rec = np.zeros((len(order), 4), np.float32)
+    rec[:, 0] = src[order].astype(np.int32).view(np.float32)
+    rec[:, 1:1 + min(E, 3)] = ev[order][:, :3]
+    return ptr, rec
+
+
+def sub_case(case, rows):
+    """the padded case restricted to `rows` (whole graphs: every neighbour of a kept row is kept), lists renumbered"""
+    rows = np.asarray(rows)
+    nl = np.searchsorted(rows, case["nl"][rows])
+    assert (rows[np.minimum(nl, len(rows) - 1)] == case["nl"][rows]).all()
+    c = dict(case, N=len(rows), nl=nl.astype(np.int32))
+    for k in ("e", "live", "h", "inv", "dH"):
+        c[k] = case[k][rows]
+    return c

@@ -5,11 +5,16 @@ Backward: dh, de, dw against central finite differences in float64 of L = sum(dH
 adds the upstream gradient to dh_in (ng_mp_layer_bwd takes no residual flag), so that is the function ref_layer differentiates
 for both values of `residual`.
 The two emulations behind the statistical criterion: the float32 evaluation must sit at float32's rounding scale, the
-dropped-cross-term evaluation well above it, and the node-side formulas (dh = dH + B Wn, dw = h^T B) must equal ref_layer's."""
+dropped-cross-term evaluation well above it, and the node-side formulas (dh = dH + B Wn, dw = h^T B) must equal ref_layer's.
+The exact family (mp_layer_ref.exact_inputs) at every shape test_gpu_mp_default_width.py uses it: the float64 statement is made of
+float32 numbers that a float32 evaluation reaches bit for bit, every magnitude stays below 2^24 granules (so does every partial
+sum in any order), and the operands of the split products fit two fp16 pieces."""
 import numpy as np
 import pytest
 
-from mp_layer_ref import ACT, act_fwd, incoming, layer_stats, lead_piece, padded_case, ref_layer, rstat
+from mp_layer_ref import (ACT, GRANULE, act_fwd, act_grad_from_out, f32_layer, graph_layout, host_records, incoming, layer_stats,
+                          lead_piece, padded_case, ref_layer, rstat, sigbits, sub_case)
+from test_gpu_mp_default_width import CASES, EXACT_CASES, big_case, build
 from oracle import nmrgnn_oracle as O
 
 ORACLE_ACT = {"none": None, "softplus": "softplus", "relu": "relu", "tanh": "tanh"}
@@ -102,3 +107,54 @@ def test_the_two_emulations_bracket_a_threshold(act):
         assert 1e-6 < r_drop < 1e-4, (k, r_drop)
         assert r_drop > 100 * r32, (k, r32, r_drop)
     assert rstat(v["s"], v["s"], mg["s"]) == 0.0
+
+
+@pytest.mark.parametrize("name", EXACT_CASES + ["big"])
+def test_exact_family_is_exact_in_float32(name):
+    """per exact case of test_gpu_mp_default_width.py (256 compute units assumed for the sizes that follow the device; the
+    two-tiles case on the graphs it samples): float32 evaluation == float64 bit for bit; A, dP, dA and B within 20 significant
+    bits; mag / granule < 2^24 for every output the case compares"""
+    if name == "big":
+        c, rows = big_case("exact", 256)
+        c, keys = sub_case(c, rows), ("dh", "de")
+    else:
+        c = build(name, "exact", 256)
+        keys = ("A", "s", "h_out") + (("dh", "de", "dw") if CASES[name]["bwd"] else ())
+    v, mg = _ref(c)
+    slope = act_grad_from_out(c["act"], v["s_in"])
+    g32 = f32_layer(c["h"], c["nl"], c["e"], c["inv"], c["w"], c["dH"], c["act"], c["residual"], slope)
+    for k in keys:
+        assert np.array_equal(g32[k].astype(np.float64), v[k]), k
+        assert np.array_equal(v[k].astype(np.float32).astype(np.float64), v[k]), k
+        top = float(mg[k].max()) + (3.0 if k == "de" else 0.0)                   # de may be added to a prior in {-3..3}
+        assert top / GRANULE[k] < 2.0 ** 24, (k, top / GRANULE[k])
+    assert sigbits(v["A"]) <= 20
+    if "dh" in keys:
+        E, Fw = c["E"], c["F"]
+        dP = c["dH"] * slope * c["inv"][:, None]
+        dA = dP @ c["w"].transpose(2, 0, 1).reshape(E * Fw, Fw).T
+        B = incoming(c["nl"], c["e"], dP)
+        bits = {"dP": sigbits(dP), "dA": sigbits(dA), "B": sigbits(B)}
+        assert max(bits.values()) <= 20, bits
+
+
+def test_mixed_spans_and_host_records():
+    """graph_layout with a list of sizes (the last one repeats); host_records: CSC order, and a permutation that stays inside
+    every target's segment"""
+    gi, base, size = graph_layout(700, [100, 100, 500])
+    assert list(np.unique(base)) == [0, 100, 200] and size[0] == 100 and size[250] == 500 and gi[699] == 2
+    _, base, size = graph_layout(1300, [100, 500])
+    assert list(np.unique(base)) == [0, 100, 600, 1100] and size[1299] == 200
+    c = padded_case(16, 2, 4, 50, [7, 20], "none", 1, seed=1)
+    assert c["span"] == 20 and (c["nl"] >= graph_layout(50, [7, 20])[1][:, None]).all()
+    ptr, rec = host_records(c)
+    src, tgt_sorted = rec[:, 0].view(np.int32), np.repeat(np.arange(50), np.diff(ptr))
+    assert len(rec) == int(c["live"].sum()) and (rec[:, 3] == 0).all()
+    for a, b in zip(ptr[:-1], ptr[1:]):
+        assert (np.diff(src[a:b]) >= 0).all()
+    hit = {(int(i), int(t)) for i, t in zip(src, tgt_sorted)}
+    assert hit == {(int(i), int(c["nl"][i, j])) for i, j in zip(*np.nonzero(c["live"]))}
+    _, rec_p = host_records(c, permute=3)
+    assert not np.array_equal(rec_p, rec)
+    for a, b in zip(ptr[:-1], ptr[1:]):
+        assert sorted(map(tuple, rec_p[a:b].view(np.int32))) == sorted(map(tuple, rec[a:b].view(np.int32)))
