@@ -289,7 +289,7 @@ __global__ __launch_bounds__(TM * 4, TM == 64 ? 2 : 1) void edge_fused_fwd_kerne
         const float m = sMask[r];
         const int64_t go = a.perm ? (int64_t)a.perm[gr] : gr;     // (a dependent load: this kernel is the strict-fp32 / fallback form)
 #pragma unroll
-        for (int n = 0; n < E; ++n) a.e_out[go * E + n] = m * (acc[n] + a.bo[n]);
+        for (int n = 0; n < E; ++n) a.e_out[go * E + n] = m * (acc[n] + a.bo[n]) + 0.f;   // (+ 0: a dead row is +0, not -0)
       }
     }
     // (the barrier after the next tile's RBF phase orders these X1 / sMask reads before they are

@@ -425,7 +425,7 @@ __global__ __launch_bounds__(512, 1) void edge_fwd_h2_kernel(EdgeH2Args a) {
           int ne = r + 4 * hf;
           asm volatile("" : "+v"(ne));      // (not a tile-loop invariant to be kept in — and spilled from — a register)
           if (ne < a.E) {
-            const float v = mask * fmaf(acc[r], H2_WINV, sBo[ne]);
+            const float v = mask * fmaf(acc[r], H2_WINV, sBo[ne]) + 0.f;   // (+ 0: a dead row is +0, not 0 * negative = -0)
             bad |= not_finite(v);
             a.e_out[(int64_t)gout * a.E + ne] = v;
           }

@@ -444,7 +444,9 @@ __global__ __launch_bounds__(256, 1) void mp_layer_short_kernel(MpShortArgs a) {
       for (int t = 0; t < 16; ++t) chk += fabsf(acc[j][t]);
     if (tid == 0) *sMask = 0u;
     __syncthreads();
-    if (not_finite(chk)) atomicOr(sMask, 1u << l31);
+    // rows past the end of the list hold a zero aggregate, and 0 x (an inf piece of the image) is NaN as well: they are not stored,
+    // and the CSR form has no row_ptr entry to repair them from
+    if (not_finite(chk) && l31 < n_at) atomicOr(sMask, 1u << l31);
     __syncthreads();
     const unsigned mask = *sMask;
     if (mask != 0u) {
