@@ -257,6 +257,24 @@ int ng_box_grad(ng_ctx*, void* stream, int64_t N, int K, const float* pos, const
 int ng_box_grad_csr(ng_ctx*, void* stream, int64_t N, int64_t nnz, const float* pos, const int32_t* row_ptr,
                     const int32_t* col, const float* dd, float scale, int G, const int32_t* graph_ptr, const float* box,
                     int triclinic, double* strain, double* dvec);
+/* The gradients of a ragged batch whose structures have boundary kinds of their own (ng_knn_graph_ragged_pbc below): graph_ptr
+ *   [G+1], box [G][9] and kind [G] on the device, kind_host as there (checked when given, may be NULL).  A row's structure is
+ *   found by a search of graph_ptr, and its edges use that structure's own policy.  ng_box_grad(_csr)_ragged: strain and dvec
+ *   per structure, dvec = 0 for an open one.  Otherwise as ng_positions_grad_pbc / ng_box_grad. */
+int ng_positions_grad_ragged_pbc(ng_ctx*, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist,
+                                 const float* edges, const float* dd, float scale, const int32_t* csc_ptr,
+                                 const int32_t* csc_edge, int G, const int32_t* graph_ptr, const float* box,
+                                 const int32_t* kind, const int32_t* kind_host, float* dpos);
+int ng_positions_grad_csr_ragged_pbc(ng_ctx*, void* stream, int64_t N, int64_t nnz, const float* pos, const int32_t* row_ptr,
+                                     const int32_t* col, const int32_t* row_of, const float* dd, float scale,
+                                     const int32_t* csc_ptr, const int32_t* csc_edge, int G, const int32_t* graph_ptr,
+                                     const float* box, const int32_t* kind, const int32_t* kind_host, float* dpos);
+int ng_box_grad_ragged(ng_ctx*, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist, const float* edges,
+                       const float* dd, float scale, int G, const int32_t* graph_ptr, const float* box, const int32_t* kind,
+                       const int32_t* kind_host, double* strain, double* dvec);
+int ng_box_grad_csr_ragged(ng_ctx*, void* stream, int64_t N, int64_t nnz, const float* pos, const int32_t* row_ptr,
+                           const int32_t* col, const float* dd, float scale, int G, const int32_t* graph_ptr,
+                           const float* box, const int32_t* kind, const int32_t* kind_host, double* strain, double* dvec);
 
 /* ---- node path ----------------------------------------------------------------------------- */
 /* embed_layer, nmrgnn/model.py:241,262: h0 = atoms[N,C] @ Wemb[C,F] */
@@ -413,7 +431,7 @@ int ng_knn_graph_pbc(ng_ctx*, void* stream, int G, int n, int K, float scale, co
  *   ng_knn_graph_ragged: structures of >= 16384 atoms take the cell grid (as ng_knn_graph does) one call each, found from
  *   graph_ptr_host, the same [G+1] array in host memory (required when max_n >= 16384, else may be NULL).  NG_KNN as ng_knn_graph.
  *   ng_cutoff_count_ragged / ng_cutoff_fill_rows_ragged: brute force at every size; the caller's exclusive scan of deg [N]
- *   is row_ptr [N+1]; row_of may be NULL.  No periodic boxes. */
+ *   is row_ptr [N+1]; row_of may be NULL.  Open boundaries; the _pbc forms below take boxes. */
 int ng_knn_graph_ragged(ng_ctx*, void* stream, int G, int64_t N, int K, float scale, const float* pos, const int32_t* graph_ptr,
                         const int32_t* graph_ptr_host, int max_n, int32_t* nlist, float* edges, float* inv_degree);
 int ng_cutoff_count_ragged(ng_ctx*, void* stream, int G, int64_t N, float cutoff, const float* pos, const int32_t* graph_ptr,
@@ -421,6 +439,24 @@ int ng_cutoff_count_ragged(ng_ctx*, void* stream, int G, int64_t N, float cutoff
 int ng_cutoff_fill_rows_ragged(ng_ctx*, void* stream, int G, int64_t N, float cutoff, float scale, const float* pos,
                                const int32_t* graph_ptr, int max_n, const int32_t* row_ptr, int32_t* col, float* dist,
                                float* inv_degree, int32_t* row_of);
+/* The ragged builders with one boundary kind PER STRUCTURE: kind [G] int32 on the device, -1 open, 0 orthorhombic, 1 reduced
+ *   triclinic, next to box [G][9] on the device (lattice vectors as ng_knn_graph_pbc; an open structure's are not read).
+ *   Each structure's rows are bit for bit what ng_knn_graph_pbc / ng_cutoff_count_pbc / ng_cutoff_fill_rows_pbc give for that
+ *   structure alone with its own box and triclinic flag (the open builders for kind -1), indices shifted by gp[g]: an
+ *   orthorhombic structure beside a triclinic one keeps the orthorhombic arithmetic.  kind_host: the same [G] kinds in host
+ *   memory; when given, a kind outside {-1, 0, 1} is refused; ng_knn_graph_ragged_pbc requires it when max_n >= 16384 (the
+ *   cell grid runs once per such structure with that structure's box and kind), otherwise it may be NULL.  Asynchronous like
+ *   the open forms.  The caller keeps cutoff below half the smallest perpendicular width of every periodic structure. */
+int ng_knn_graph_ragged_pbc(ng_ctx*, void* stream, int G, int64_t N, int K, float scale, const float* pos,
+                            const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, const float* box,
+                            const int32_t* kind, const int32_t* kind_host, int32_t* nlist, float* edges, float* inv_degree);
+int ng_cutoff_count_ragged_pbc(ng_ctx*, void* stream, int G, int64_t N, float cutoff, const float* pos,
+                               const int32_t* graph_ptr, int max_n, const float* box, const int32_t* kind,
+                               const int32_t* kind_host, int32_t* deg);
+int ng_cutoff_fill_rows_ragged_pbc(ng_ctx*, void* stream, int G, int64_t N, float cutoff, float scale, const float* pos,
+                                   const int32_t* graph_ptr, int max_n, const float* box, const int32_t* kind,
+                                   const int32_t* kind_host, const int32_t* row_ptr, int32_t* col, float* dist,
+                                   float* inv_degree, int32_t* row_of);
 
 /* AMPLayer attention aggregation, nmrgnn/layers.py:89-96 (the layer is exported by the reference package but not
  * used by its model):

@@ -78,6 +78,11 @@ SIGNATURES = {
     "ng_positions_grad_csr_pbc": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _int, _vp, _int, _vp]),
     "ng_box_grad": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _int, _vp, _vp, _int, _vp, _vp]),
     "ng_box_grad_csr": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _f, _int, _vp, _vp, _int, _vp, _vp]),
+    "ng_positions_grad_ragged_pbc": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    "ng_positions_grad_csr_ragged_pbc": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _int, _vp, _vp, _vp,
+                                                _vp, _vp]),
+    "ng_box_grad_ragged": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ng_box_grad_csr_ragged": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _f, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ng_restraint_loss": (_int, [_vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ng_restraint_loss_ex": (_int, [_vp, _vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "ng_embed_fwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp]),
@@ -128,6 +133,10 @@ SIGNATURES = {
     "ng_knn_graph_ragged": (_int, [_vp, _vp, _int, _i64, _int, _f, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
     "ng_cutoff_count_ragged": (_int, [_vp, _vp, _int, _i64, _f, _vp, _vp, _int, _vp]),
     "ng_cutoff_fill_rows_ragged": (_int, [_vp, _vp, _int, _i64, _f, _f, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
+    "ng_knn_graph_ragged_pbc": (_int, [_vp, _vp, _int, _i64, _int, _f, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ng_cutoff_count_ragged_pbc": (_int, [_vp, _vp, _int, _i64, _f, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
+    "ng_cutoff_fill_rows_ragged_pbc": (_int, [_vp, _vp, _int, _i64, _f, _f, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                              _vp]),
     "ng_amp_attend": (_int, [_vp, _vp, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ng_amp_attend_bwd": (_int, [_vp, _vp, _i64, _int, _int, _int] + [_vp] * 13),
     "ng_loss_l2": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),

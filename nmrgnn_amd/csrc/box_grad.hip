@@ -27,6 +27,9 @@ namespace ng {
 constexpr int BG_ROWS = 256;   // rows per stage-1 chunk (= threads of its workgroup)
 constexpr int BG_S = 6;        // xx yy zz xy xz yz
 constexpr int BG_V = 15;       // 6 of S, 9 of B (row-major n_a p_b)
+// the policy of a launch: the public triclinic flag (-1 open, 0 orthorhombic, 1 triclinic: one for the whole batch), or every
+// frame by its own kind [G] (the ragged entry points; never a value a caller passes)
+constexpr int BG_OPEN = -1, BG_TRIC = 1, BG_PER_FRAME = 2;      // 0: orthorhombic
 
 // the frame of row i: the g with gp[g] <= i < gp[g + 1] (empty frames skipped), clamped to [0, G) (ragged.hip: rg_range)
 __device__ __forceinline__ int bg_frame(const int32_t* __restrict__ gp, int G, int64_t i) {
@@ -57,6 +60,13 @@ __device__ __forceinline__ void bg_image(const DispTric& D, double dx, double dy
 __device__ __forceinline__ void bg_image(const DispOpen&, double, double, double, double& nx, double& ny, double& nz) {
   nx = ny = nz = 0.0;
 }
+// a structure of a ragged batch: by its own kind (an open structure has no images, so its B stays zero)
+__device__ __forceinline__ void bg_image(const DispPer& D, double dx, double dy, double dz, double& nx, double& ny,
+                                         double& nz) {
+  if (D.kind == 0) bg_image(D.O, dx, dy, dz, nx, ny, nz);
+  else if (D.kind == 1) bg_image(D.T, dx, dy, dz, nx, ny, nz);
+  else nx = ny = nz = 0.0;
+}
 
 // one frame's S [9] (symmetric, from the 6) and B [9]; dvec may be NULL; open boundaries write B = 0
 template <bool PERIODIC>
@@ -69,7 +79,8 @@ __device__ __forceinline__ void bg_store(const double* v, int64_t g, double* __r
     for (int k = 0; k < 9; ++k) dvec[g * 9 + k] = PERIODIC ? v[BG_S + k] : 0.0;
 }
 
-// row_ptr == NULL: padded lists (slots i*K .. i*K+K-1, live when edges > 0); otherwise CSR (row_ptr[i] .. row_ptr[i+1])
+// row_ptr == NULL: padded lists (slots i*K .. i*K+K-1, live when edges > 0); otherwise CSR (row_ptr[i] .. row_ptr[i+1]).
+// kind [G]: the boundary kind of every frame, read by DispPer alone (NULL otherwise)
 template <class Disp>
 __global__ __launch_bounds__(BG_ROWS) void box_grad_chunk_kernel(int64_t N, int K, const float* __restrict__ pos,
                                                                  const int32_t* __restrict__ row_ptr,
@@ -77,7 +88,8 @@ __global__ __launch_bounds__(BG_ROWS) void box_grad_chunk_kernel(int64_t N, int 
                                                                  const float* __restrict__ edges, const float* __restrict__ dd,
                                                                  float scale, int G, const int32_t* __restrict__ gp,
                                                                  const float* __restrict__ box, double* __restrict__ partial,
-                                                                 double* __restrict__ strain, double* __restrict__ dvec) {
+                                                                 double* __restrict__ strain, double* __restrict__ dvec,
+                                                                 const int32_t* __restrict__ kind) {
   constexpr int NV = Disp::periodic ? BG_V : BG_S;
   __shared__ double sv[NV][BG_ROWS];
   __shared__ int fr[BG_ROWS];
@@ -93,7 +105,7 @@ __global__ __launch_bounds__(BG_ROWS) void box_grad_chunk_kernel(int64_t N, int 
   if (active) {
     f = bg_frame(gp, G, i);
     Disp D;
-    if (Disp::periodic) D.load(box, f);
+    if (Disp::periodic) disp_load(D, box, kind, f);
     const float qx = pos[3 * i], qy = pos[3 * i + 1], qz = pos[3 * i + 2];
     const int64_t s0 = row_ptr ? row_ptr[i] : i * K, s1 = row_ptr ? row_ptr[i + 1] : i * K + K;
     for (int64_t s = s0; s < s1; ++s) {
@@ -185,14 +197,15 @@ using namespace ng;
 
 static int box_grad_common(ng_ctx* ctx, void* stream, int64_t N, int K, const float* pos, const int32_t* row_ptr,
                            const int32_t* col, const float* edges, const float* dd, float scale, int G,
-                           const int32_t* graph_ptr, const float* box, int triclinic, double* strain, double* dvec) {
+                           const int32_t* graph_ptr, const float* box, int policy, const int32_t* kind, double* strain,
+                           double* dvec) {
   NG_REQUIRE(ctx, N >= 0 && N < ((int64_t)1 << 31), "box_grad: atom count below 2^31");
   NG_REQUIRE(ctx, G >= 0, "box_grad: frame count G >= 0");
-  NG_REQUIRE(ctx, triclinic >= -1 && triclinic <= 1, "box_grad: triclinic flag -1 (open), 0 or 1");
   NG_REQUIRE(ctx, N == 0 || G >= 1, "box_grad: atoms need at least one frame");
   if (G == 0) return NG_OK;
   NG_REQUIRE(ctx, graph_ptr && strain, "box_grad: graph_ptr and strain required");
-  NG_REQUIRE(ctx, triclinic < 0 || box, "box_grad (pbc): box required");
+  NG_REQUIRE(ctx, policy == BG_OPEN || box, "box_grad (pbc): box required");
+  NG_REQUIRE(ctx, policy != BG_PER_FRAME || kind, "box_grad (ragged): kind required");
   NG_REQUIRE(ctx, N == 0 || (pos && col && dd), "box_grad: arguments");
   hipStream_t st = (hipStream_t)stream;
   DeviceGuard dg(ctx->device);
@@ -205,11 +218,12 @@ static int box_grad_common(ng_ctx* ctx, void* stream, int64_t N, int K, const fl
   do {                                                                                                                      \
     if (nchunks > 0)                                                                                                        \
       hipLaunchKernelGGL(box_grad_chunk_kernel<Disp>, dim3((unsigned)nchunks), block, 0, st, N, K, pos, row_ptr, col, edges, \
-                         dd, scale, G, graph_ptr, box, partial, strain, dvec);                                              \
+                         dd, scale, G, graph_ptr, box, partial, strain, dvec, kind);                                        \
     hipLaunchKernelGGL(box_grad_frame_kernel<Disp::periodic>, grid2, block, 0, st, N, G, graph_ptr, partial, strain, dvec); \
   } while (0)
-  if (triclinic < 0) NG_BG(DispOpen);
-  else if (triclinic) NG_BG(DispTric);
+  if (policy == BG_OPEN) NG_BG(DispOpen);
+  else if (policy == BG_PER_FRAME) NG_BG(DispPer);
+  else if (policy == BG_TRIC) NG_BG(DispTric);
   else NG_BG(DispOrtho);
 #undef NG_BG
   NG_HIP(ctx, hipGetLastError());
@@ -222,7 +236,9 @@ extern "C" int ng_box_grad(ng_ctx* ctx, void* stream, int64_t N, int K, const fl
   if (!ctx) return NG_ERR_INVALID;
   NG_REQUIRE(ctx, K >= 1 && N * K < ((int64_t)1 << 31), "box_grad: K >= 1, N * K below 2^31");
   NG_REQUIRE(ctx, N == 0 || edges, "box_grad: edges required (dead slots)");
-  return box_grad_common(ctx, stream, N, K, pos, nullptr, nlist, edges, dd, scale, G, graph_ptr, box, triclinic, strain, dvec);
+  NG_REQUIRE(ctx, triclinic >= -1 && triclinic <= 1, "box_grad: triclinic flag -1 (open), 0 or 1");
+  return box_grad_common(ctx, stream, N, K, pos, nullptr, nlist, edges, dd, scale, G, graph_ptr, box, triclinic, nullptr, strain,
+                         dvec);
 }
 
 extern "C" int ng_box_grad_csr(ng_ctx* ctx, void* stream, int64_t N, int64_t nnz, const float* pos, const int32_t* row_ptr,
@@ -231,5 +247,41 @@ extern "C" int ng_box_grad_csr(ng_ctx* ctx, void* stream, int64_t N, int64_t nnz
   if (!ctx) return NG_ERR_INVALID;
   NG_REQUIRE(ctx, nnz >= 0 && nnz < ((int64_t)1 << 31), "box_grad_csr: nnz below 2^31");
   NG_REQUIRE(ctx, N == 0 || row_ptr, "box_grad_csr: row_ptr required");
-  return box_grad_common(ctx, stream, N, 0, pos, row_ptr, col, nullptr, dd, scale, G, graph_ptr, box, triclinic, strain, dvec);
+  NG_REQUIRE(ctx, triclinic >= -1 && triclinic <= 1, "box_grad: triclinic flag -1 (open), 0 or 1");
+  return box_grad_common(ctx, stream, N, 0, pos, row_ptr, col, nullptr, dd, scale, G, graph_ptr, box, triclinic, nullptr, strain,
+                         dvec);
+}
+
+// ragged batches in boxes: every frame with a kind of its own, kind [G] (-1 open, 0 orthorhombic, 1 reduced triclinic) on the
+// device next to box [G][9]; kind_host: the kinds in host memory, checked when given (may be NULL).  dvec of an open frame is 0
+static int box_grad_ragged_check(ng_ctx* ctx, int G, const float* box, const int32_t* kind, const int32_t* kind_host) {
+  NG_REQUIRE(ctx, G <= 0 || (box && kind), "box_grad (ragged): box and kind required");
+  if (kind_host)
+    for (int g = 0; g < G; ++g)
+      NG_REQUIRE(ctx, kind_host[g] >= -1 && kind_host[g] <= 1, "box_grad (ragged): kind -1 (open), 0 or 1");
+  return NG_OK;
+}
+
+extern "C" int ng_box_grad_ragged(ng_ctx* ctx, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist,
+                                  const float* edges, const float* dd, float scale, int G, const int32_t* graph_ptr,
+                                  const float* box, const int32_t* kind, const int32_t* kind_host, double* strain,
+                                  double* dvec) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, K >= 1 && N * K < ((int64_t)1 << 31), "box_grad: K >= 1, N * K below 2^31");
+  NG_REQUIRE(ctx, N == 0 || edges, "box_grad: edges required (dead slots)");
+  if (const int rc = box_grad_ragged_check(ctx, G, box, kind, kind_host)) return rc;
+  return box_grad_common(ctx, stream, N, K, pos, nullptr, nlist, edges, dd, scale, G, graph_ptr, box, BG_PER_FRAME, kind, strain,
+                         dvec);
+}
+
+extern "C" int ng_box_grad_csr_ragged(ng_ctx* ctx, void* stream, int64_t N, int64_t nnz, const float* pos,
+                                      const int32_t* row_ptr, const int32_t* col, const float* dd, float scale, int G,
+                                      const int32_t* graph_ptr, const float* box, const int32_t* kind,
+                                      const int32_t* kind_host, double* strain, double* dvec) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, nnz >= 0 && nnz < ((int64_t)1 << 31), "box_grad_csr: nnz below 2^31");
+  NG_REQUIRE(ctx, N == 0 || row_ptr, "box_grad_csr: row_ptr required");
+  if (const int rc = box_grad_ragged_check(ctx, G, box, kind, kind_host)) return rc;
+  return box_grad_common(ctx, stream, N, 0, pos, row_ptr, col, nullptr, dd, scale, G, graph_ptr, box, BG_PER_FRAME, kind, strain,
+                         dvec);
 }

@@ -21,6 +21,7 @@
 #include "mfma_gemm.cuh"
 #include "ng_common.h"
 #include "pbc.cuh"
+#include "ragged.cuh"
 
 namespace ng {
 
@@ -217,20 +218,14 @@ __device__ __forceinline__ float3 pg_term(const Disp& D, const float* __restrict
 
 // row_ptr == NULL: padded lists (slots i*K .. i*K+K-1, a slot is live when edges > 0, source of slot s = s / K);
 // otherwise CSR (entries row_ptr[i] .. row_ptr[i+1], all live, source of entry s = row_of[s]).
-// Periodic policies: atom i belongs to frame i / n and both ends of its edges to the same frame.
+// D: the policy of row i's frame or structure, loaded by the kernel; both ends of an edge belong to the same one.
 template <class Disp>
-__global__ __launch_bounds__(256) void positions_grad_kernel(int64_t N, int K, const float* __restrict__ pos,
-                                                             const int32_t* __restrict__ row_ptr,
-                                                             const int32_t* __restrict__ col,
-                                                             const int32_t* __restrict__ row_of,
-                                                             const float* __restrict__ edges, const float* __restrict__ dd,
-                                                             float scale, const int32_t* __restrict__ csc_ptr,
-                                                             const int32_t* __restrict__ csc_edge, int n,
-                                                             const float* __restrict__ box, float* __restrict__ dpos) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  Disp D;
-  if (Disp::periodic) D.load(box, (int)(i / n));
+__device__ __forceinline__ void positions_grad_row(const Disp& D, int64_t i, int K, const float* __restrict__ pos,
+                                                   const int32_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
+                                                   const int32_t* __restrict__ row_of, const float* __restrict__ edges,
+                                                   const float* __restrict__ dd, float scale,
+                                                   const int32_t* __restrict__ csc_ptr, const int32_t* __restrict__ csc_edge,
+                                                   float* __restrict__ dpos) {
   const int64_t s0 = row_ptr ? row_ptr[i] : i * K, s1 = row_ptr ? row_ptr[i + 1] : i * K + K;
   float ax = 0.f, ay = 0.f, az = 0.f;
   for (int64_t s = s0; s < s1; ++s) {
@@ -254,6 +249,43 @@ __global__ __launch_bounds__(256) void positions_grad_kernel(int64_t N, int K, c
   dpos[3 * i] = ax;
   dpos[3 * i + 1] = ay;
   dpos[3 * i + 2] = az;
+}
+
+// Periodic policies: atom i belongs to frame i / n.
+template <class Disp>
+__global__ __launch_bounds__(256) void positions_grad_kernel(int64_t N, int K, const float* __restrict__ pos,
+                                                             const int32_t* __restrict__ row_ptr,
+                                                             const int32_t* __restrict__ col,
+                                                             const int32_t* __restrict__ row_of,
+                                                             const float* __restrict__ edges, const float* __restrict__ dd,
+                                                             float scale, const int32_t* __restrict__ csc_ptr,
+                                                             const int32_t* __restrict__ csc_edge, int n,
+                                                             const float* __restrict__ box, float* __restrict__ dpos) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  Disp D;
+  if (Disp::periodic) D.load(box, (int)(i / n));
+  positions_grad_row(D, i, K, pos, row_ptr, col, row_of, edges, dd, scale, csc_ptr, csc_edge, dpos);
+}
+
+// The same rows on a ragged batch in boxes: atom i belongs to the structure the search of graph_ptr finds (ragged.cuh), and
+// its edges use that structure's kind and box (pbc.cuh: DispPer).
+__global__ __launch_bounds__(256) void positions_grad_ragged_kernel(int64_t N, int K, const float* __restrict__ pos,
+                                                                    const int32_t* __restrict__ row_ptr,
+                                                                    const int32_t* __restrict__ col,
+                                                                    const int32_t* __restrict__ row_of,
+                                                                    const float* __restrict__ edges,
+                                                                    const float* __restrict__ dd, float scale,
+                                                                    const int32_t* __restrict__ csc_ptr,
+                                                                    const int32_t* __restrict__ csc_edge, int G,
+                                                                    const int32_t* __restrict__ gp,
+                                                                    const float* __restrict__ box,
+                                                                    const int32_t* __restrict__ kind, float* __restrict__ dpos) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  DispPer D;
+  D.load(box, kind, rg_range(gp, G, (int)N, (int)i).g);
+  positions_grad_row(D, i, K, pos, row_ptr, col, row_of, edges, dd, scale, csc_ptr, csc_edge, dpos);
 }
 
 }  // namespace ng
@@ -377,4 +409,51 @@ extern "C" int ng_positions_grad_csr_pbc(ng_ctx* ctx, void* stream, int64_t N, i
   NG_REQUIRE(ctx, triclinic == 0 || triclinic == 1, "positions_grad (pbc): triclinic flag 0 or 1");
   return positions_grad_common(ctx, stream, N, 0, pos, row_ptr, col, row_of, nullptr, dd, scale, csc_ptr, csc_edge, dpos, n, box,
                                triclinic);
+}
+
+// ragged batches in boxes: graph_ptr [G+1], box [G][9] and kind [G] (-1 open, 0 orthorhombic, 1 reduced triclinic) on the
+// device; kind_host: the kinds in host memory, checked when given (may be NULL)
+static int positions_grad_ragged_common(ng_ctx* ctx, void* stream, int64_t N, int K, const float* pos, const int32_t* row_ptr,
+                                        const int32_t* col, const int32_t* row_of, const float* edges, const float* dd,
+                                        float scale, const int32_t* csc_ptr, const int32_t* csc_edge, int G,
+                                        const int32_t* graph_ptr, const float* box, const int32_t* kind,
+                                        const int32_t* kind_host, float* dpos) {
+  NG_REQUIRE(ctx, N >= 0 && N < ((int64_t)1 << 31), "positions_grad: atom count below 2^31");
+  NG_REQUIRE(ctx, G >= 0 && (N == 0 || G >= 1), "positions_grad (ragged): atoms need at least one structure");
+  if (kind_host)
+    for (int g = 0; g < G; ++g)
+      NG_REQUIRE(ctx, kind_host[g] >= -1 && kind_host[g] <= 1, "positions_grad (ragged): kind -1 (open), 0 or 1");
+  if (N == 0) return NG_OK;
+  NG_REQUIRE(ctx, pos && col && dd && csc_ptr && csc_edge && dpos, "positions_grad: arguments");
+  NG_REQUIRE(ctx, graph_ptr && box && kind, "positions_grad (ragged): graph_ptr, box and kind required");
+  hipStream_t st = (hipStream_t)stream;
+  DeviceGuard dg(ctx->device);
+  ProfScope ps(ctx, st, "positions_grad_ragged");
+  hipLaunchKernelGGL(positions_grad_ragged_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, N, K, pos, row_ptr, col, row_of,
+                     edges, dd, scale, csc_ptr, csc_edge, G, graph_ptr, box, kind, dpos);
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}
+
+extern "C" int ng_positions_grad_ragged_pbc(ng_ctx* ctx, void* stream, int64_t N, int K, const float* pos, const int32_t* nlist,
+                                            const float* edges, const float* dd, float scale, const int32_t* csc_ptr,
+                                            const int32_t* csc_edge, int G, const int32_t* graph_ptr, const float* box,
+                                            const int32_t* kind, const int32_t* kind_host, float* dpos) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, K >= 1 && N * K < ((int64_t)1 << 31), "positions_grad: K >= 1, N * K below 2^31");
+  NG_REQUIRE(ctx, N == 0 || edges, "positions_grad: edges required (dead slots)");
+  return positions_grad_ragged_common(ctx, stream, N, K, pos, nullptr, nlist, nullptr, edges, dd, scale, csc_ptr, csc_edge, G,
+                                      graph_ptr, box, kind, kind_host, dpos);
+}
+
+extern "C" int ng_positions_grad_csr_ragged_pbc(ng_ctx* ctx, void* stream, int64_t N, int64_t nnz, const float* pos,
+                                                const int32_t* row_ptr, const int32_t* col, const int32_t* row_of,
+                                                const float* dd, float scale, const int32_t* csc_ptr, const int32_t* csc_edge,
+                                                int G, const int32_t* graph_ptr, const float* box, const int32_t* kind,
+                                                const int32_t* kind_host, float* dpos) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, nnz >= 0 && nnz < ((int64_t)1 << 31), "positions_grad_csr: nnz below 2^31");
+  NG_REQUIRE(ctx, N == 0 || (row_ptr && row_of), "positions_grad_csr: row_ptr and row_of required");
+  return positions_grad_ragged_common(ctx, stream, N, 0, pos, row_ptr, col, row_of, nullptr, dd, scale, csc_ptr, csc_edge, G,
+                                      graph_ptr, box, kind, kind_host, dpos);
 }

@@ -14,6 +14,11 @@
 //   DispTric   c - q, sequential z / y / x wrap; when the wrapped vector is not shorter than w_min / 2 (w_min: the smallest
 //              perpendicular width) the nearest of its 27 neighbouring images.  Below w_min / 2 it is provably the minimum
 //              image: every other image is at least w_min - |d| away.
+//   DispPer    a ragged batch, where every structure has a boundary kind of its own (-1 open, 0 orthorhombic, 1 reduced
+//              triclinic; kind [G] int32 next to box [G][9]): loads the structure's kind and vectors and calls, at run time,
+//              the operator() of the policy of that kind as it stands above.  An orthorhombic structure next to a triclinic
+//              one runs DispOrtho's arithmetic, not DispTric's on zero off-diagonals (the two may differ in the last bit
+//              when a wrapped component rounds just past L/2).
 // Which policy runs is chosen on the host from the box values: a template argument, not a user switch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -88,5 +93,36 @@ struct DispTric {
     }
   }
 };
+
+// Lanes of one wave may sit in structures of different kinds: the switch runs per call, inside the candidate loops of the
+// builders, and a wave pays for every kind it holds (the triclinic 27-image search included).
+struct DispPer {
+  static constexpr bool periodic = true;
+  int kind = -1;
+  DispOrtho O;
+  DispTric T;
+  __device__ __forceinline__ void load(const float* box, const int32_t* kinds, int g) {
+    kind = kinds[g];
+    if (kind == 0) O.load(box, g);
+    else if (kind == 1) T.load(box, g);
+  }
+  __device__ __forceinline__ void operator()(float qx, float qy, float qz, float cx, float cy, float cz, float& dx, float& dy,
+                                             float& dz) const {
+    if (kind == 0) O(qx, qy, qz, cx, cy, cz, dx, dy, dz);
+    else if (kind == 1) T(qx, qy, qz, cx, cy, cz, dx, dy, dz);
+    else DispOpen()(qx, qy, qz, cx, cy, cz, dx, dy, dz);
+  }
+};
+
+// true for the policy that takes a kind array and a structure index in load()
+template <class Disp> struct disp_per_structure { static constexpr bool value = false; };
+template <> struct disp_per_structure<DispPer> { static constexpr bool value = true; };
+
+// D.load for structure (or frame) g, whichever form the policy takes; kinds is read by DispPer alone
+template <class Disp>
+__device__ __forceinline__ void disp_load(Disp& D, const float* box, const int32_t* kinds, int g) {
+  if constexpr (disp_per_structure<Disp>::value) D.load(box, kinds, g);
+  else D.load(box, g);
+}
 
 }  // namespace ng

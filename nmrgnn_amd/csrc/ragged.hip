@@ -21,12 +21,19 @@
 // kNN structures of >= 16384 atoms (the uniform path's switch point) take the cell grid of knn_cells.hip, one call per such
 // structure on its own rows: the ragged launch skips their rows, and a fix-up launch adds gp[g] to the frame-local indices the
 // grid writes.  The cutoff builder is brute force at every size, as the uniform one is.
+//
+// Periodic boxes: every structure has a boundary kind of its own (the _pbc entry points: box [G][9], kind [G]).  The three
+// kernels take the displacement policy as a template argument: DispOpen for the open entry points, DispPer (pbc.cuh) for the
+// boxed ones, where a row loads the kind and box of ITS structure and each structure's rows are what ng_knn_graph_pbc /
+// ng_cutoff_fill_rows_pbc give for it alone with its own box and flag.  The cell grid runs per structure with that structure's
+// box pointer and kind, from a host copy of the kinds.
 #include <algorithm>
 #include <climits>
 
 #include "ng_common.h"
 #include "ng_internal.h"
 #include "pbc.cuh"
+#include "ragged.cuh"
 
 namespace ng {
 
@@ -34,21 +41,6 @@ constexpr int RG_TILE = 1024;        // candidates per LDS tile: 16 KiB of float
 constexpr int RG_CELLS_MIN = 16384;  // kNN structures from this size on take the cell grid (knn.hip: knn_graph_impl)
 constexpr int RG_WAVE_MIN = 256;     // kNN structures of more atoms, up to 4096, take one wave per query row
 typedef unsigned long long knn_u64;
-
-// the structure of row i: the g with gp[g] <= i < gp[g + 1] (gp non-decreasing, gp[0] = 0, gp[G] = N > i; empty structures
-// are skipped over), and its row range clamped to [0, N) around i, so that a malformed graph_ptr cannot send a read out of
-// the batch
-struct RgRange {
-  int lo, hi;
-};
-__device__ __forceinline__ RgRange rg_range(const int32_t* __restrict__ gp, int G, int N, int i) {
-  int a = 0, b = G;
-  while (b - a > 1) {
-    const int m = (a + b) >> 1;
-    if (gp[m] <= i) a = m; else b = m;
-  }
-  return {max(0, min(gp[a], i)), min(N, max(gp[a + 1], i + 1))};
-}
 
 // the candidate span of a workgroup: the union of the ranges of its active rows (block-wide min / max through LDS);
 // returns false when no row of the workgroup is active
@@ -74,22 +66,27 @@ __device__ __forceinline__ void rg_stage(float4* sp, const float* __restrict__ p
 
 // kNN: the search of knn_kernel (knn.hip) over the row's own structure.  Rows of structures of (wlo, whi] atoms are left to
 // knn_ragged_wave_kernel, rows of structures of `big` atoms or more to the cell grid (neither is written here).
-template <int KMAX>
+// Disp: DispOpen (box / kind unused: the lists of the open entry points), or DispPer with box [G][9] and kind [G]: a row loads
+// the box of its own structure; the candidate span and its LDS tiles stay shared over the workgroup.
+template <int KMAX, class Disp>
 __global__ __launch_bounds__(256) void knn_ragged_kernel(int G, int N, int K, float scale, int wlo, int whi, int big,
                                                          const float* __restrict__ pos,       // [N][3]
                                                          const int32_t* __restrict__ gp,      // [G+1]
                                                          int32_t* __restrict__ nlist,         // [N][K]
                                                          float* __restrict__ edges,           // [N][K]
-                                                         float* __restrict__ inv_degree) {    // [N]
+                                                         float* __restrict__ inv_degree,      // [N]
+                                                         const float* __restrict__ box,       // [G][9] or unused
+                                                         const int32_t* __restrict__ kind) {  // [G] or unused
   __shared__ float4 sp[RG_TILE];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  RgRange r{0, 0};
+  RgRange r{0, 0, 0};
   if (i < N) r = rg_range(gp, G, N, i);
   const int n = r.hi - r.lo;
   const bool active = i < N && n < big && !(n > wlo && n <= whi);
   int s0, s1;
   if (!rg_span(active, r, s0, s1)) return;          // uniform over the workgroup
-  DispOpen D;
+  Disp D;
+  if (active) disp_load(D, box, kind, r.g);
   float qx = 0.f, qy = 0.f, qz = 0.f;
   if (active) { qx = pos[3 * (int64_t)i]; qy = pos[3 * (int64_t)i + 1]; qz = pos[3 * (int64_t)i + 2]; }
   float bd[KMAX];
@@ -152,11 +149,12 @@ __device__ __forceinline__ knn_u64 rg_shr1(knn_u64 v) {                         
   return ((knn_u64)hi << 32) | lo;
 }
 
-template <int STEPS>
+template <int STEPS, class Disp>
 __global__ __launch_bounds__(256) void knn_ragged_wave_kernel(int G, int N, int K, float scale, int wlo,
                                                               const float* __restrict__ pos, const int32_t* __restrict__ gp,
                                                               int32_t* __restrict__ nlist, float* __restrict__ edges,
-                                                              float* __restrict__ inv_degree) {
+                                                              float* __restrict__ inv_degree, const float* __restrict__ box,
+                                                              const int32_t* __restrict__ kind) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int i = blockIdx.x * 4 + wave;
@@ -166,7 +164,8 @@ __global__ __launch_bounds__(256) void knn_ragged_wave_kernel(int G, int N, int 
   if (n <= wlo || n > 64 * STEPS) return;
   const float qx = pos[3 * (int64_t)i], qy = pos[3 * (int64_t)i + 1], qz = pos[3 * (int64_t)i + 2];
   const float* sp = pos + 3 * (int64_t)lo;
-  DispOpen D;
+  Disp D;
+  disp_load(D, box, kind, __builtin_amdgcn_readfirstlane(r.g));     // one structure, one kind per wave
   // A: keys of this lane's candidates t = 64 s + lane, and their minimum
   knn_u64 key[STEPS];
   knn_u64 mn = ~0ull;
@@ -225,21 +224,23 @@ __global__ __launch_bounds__(256) void knn_ragged_offset_kernel(int64_t count, i
 }
 
 // cutoff: count (FILL = false: deg[N]) or fill pass (col / dist / row_of at row_ptr, inv_degree) of cutoff_kernel
-// (mp_csr.hip) over the row's own structure
-template <bool FILL>
+// (mp_csr.hip) over the row's own structure; Disp / box / kind as knn_ragged_kernel
+template <bool FILL, class Disp>
 __global__ __launch_bounds__(256) void cutoff_ragged_kernel(int G, int N, float cutoff2, float scale,
                                                             const float* __restrict__ pos, const int32_t* __restrict__ gp,
                                                             int32_t* __restrict__ deg, const int32_t* __restrict__ row_ptr,
                                                             int32_t* __restrict__ col, float* __restrict__ dist,
-                                                            float* __restrict__ inv_degree, int32_t* __restrict__ row_of) {
+                                                            float* __restrict__ inv_degree, int32_t* __restrict__ row_of,
+                                                            const float* __restrict__ box, const int32_t* __restrict__ kind) {
   __shared__ float4 sp[RG_TILE];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  RgRange r{0, 0};
+  RgRange r{0, 0, 0};
   if (i < N) r = rg_range(gp, G, N, i);
   const bool active = i < N;
   int s0, s1;
   if (!rg_span(active, r, s0, s1)) return;
-  DispOpen D;
+  Disp D;
+  if (active) disp_load(D, box, kind, r.g);
   float qx = 0.f, qy = 0.f, qz = 0.f;
   if (active) { qx = pos[3 * (int64_t)i]; qy = pos[3 * (int64_t)i + 1]; qz = pos[3 * (int64_t)i + 2]; }
   int cnt = 0, cnt_pos = 0;
@@ -281,22 +282,24 @@ static int ragged_check(ng_ctx* ctx, int G, int64_t N, int max_n, const float* p
   return NG_OK;
 }
 
-}  // namespace ng
+// the boxed entry points: box [G][9] and kind [G] on the device; a host copy of the kinds, where given, holds -1, 0 or 1
+static int ragged_box_check(ng_ctx* ctx, int G, int64_t N, const float* box, const int32_t* kind, const int32_t* kind_host) {
+  NG_REQUIRE(ctx, N == 0 || (box && kind), "ragged graph (pbc): box and kind required");
+  if (kind_host)
+    for (int g = 0; g < G; ++g)
+      NG_REQUIRE(ctx, kind_host[g] >= -1 && kind_host[g] <= 1, "ragged graph (pbc): kind -1 (open), 0 or 1");
+  return NG_OK;
+}
 
-using namespace ng;
-
-extern "C" int ng_knn_graph_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, int K, float scale, const float* pos,
-                                   const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, int32_t* nlist,
-                                   float* edges, float* inv_degree) {
-  if (!ctx) return NG_ERR_INVALID;
-  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn (ragged): neighbour count must be in [1,64]");
-  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
-  NG_REQUIRE(ctx, N * K < ((int64_t)1 << 31), "knn (ragged): N * K exceeds int32 slots");
-  if (N == 0) return NG_OK;
-  hipStream_t st = (hipStream_t)stream;
+// Disp = DispOpen: box / kind / kind_host NULL
+template <class Disp>
+static int knn_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t N, int K, float scale, const float* pos,
+                           const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, const float* box,
+                           const int32_t* kind, const int32_t* kind_host, int32_t* nlist, float* edges, float* inv_degree) {
   // structures of the cell grid: only when one may be that large, from the host copy of graph_ptr
   const bool cells = !sw().knn_brute && !sw().knn_serial && max_n >= RG_CELLS_MIN;
   NG_REQUIRE(ctx, !cells || graph_ptr_host, "knn (ragged): graph_ptr_host required when max_n >= 16384");
+  NG_REQUIRE(ctx, !cells || !Disp::periodic || kind_host, "knn (ragged, pbc): kind_host required when max_n >= 16384");
   const int big = cells ? RG_CELLS_MIN : INT_MAX;
   // one wave per query for structures of (256, 4096] atoms, sized by the largest of them (NG_KNN=serial / lanes: off, as the
   // uniform path's wave kernel)
@@ -305,17 +308,17 @@ extern "C" int ng_knn_graph_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, 
                     : wmax <= 3072 ? 48 : 64;
   const int whi = 64 * steps;
   {
-    ProfScope ps(ctx, st, "knn_graph_ragged");
+    ProfScope ps(ctx, st, Disp::periodic ? "knn_graph_ragged_pbc" : "knn_graph_ragged");
     const dim3 grid((unsigned)cdiv(N, 256)), block(256);
-#define NG_RG(KM) hipLaunchKernelGGL(knn_ragged_kernel<KM>, grid, block, 0, st, G, (int)N, K, scale, RG_WAVE_MIN, whi, big, pos, \
-                                     graph_ptr, nlist, edges, inv_degree)
+#define NG_RG(KM) hipLaunchKernelGGL((knn_ragged_kernel<KM, Disp>), grid, block, 0, st, G, (int)N, K, scale, RG_WAVE_MIN, whi, big, \
+                                     pos, graph_ptr, nlist, edges, inv_degree, box, kind)
     if (K <= 16) NG_RG(16); else if (K <= 32) NG_RG(32); else NG_RG(64);
 #undef NG_RG
     NG_HIP(ctx, hipGetLastError());
     if (steps) {
       const dim3 gw((unsigned)cdiv(N, 4));
-#define NG_RGW(S) hipLaunchKernelGGL(knn_ragged_wave_kernel<S>, gw, block, 0, st, G, (int)N, K, scale, RG_WAVE_MIN, pos, graph_ptr, \
-                                     nlist, edges, inv_degree)
+#define NG_RGW(S) hipLaunchKernelGGL((knn_ragged_wave_kernel<S, Disp>), gw, block, 0, st, G, (int)N, K, scale, RG_WAVE_MIN, pos, \
+                                     graph_ptr, nlist, edges, inv_degree, box, kind)
       if (steps == 16) NG_RGW(16); else if (steps == 32) NG_RGW(32); else if (steps == 48) NG_RGW(48); else NG_RGW(64);
 #undef NG_RGW
       NG_HIP(ctx, hipGetLastError());
@@ -329,8 +332,10 @@ extern "C" int ng_knn_graph_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, 
     // the rows the ragged launch skipped; the brute-force kernel cannot take them back, so a size the grid refuses is an error
     NG_REQUIRE(ctx, knn_cells_supported(1, n, K), "knn (ragged): structure too large for the cell grid");
     const int64_t s0 = (int64_t)lo * K;
+    // the structure's own box and kind: the call ng_knn_graph_pbc makes for it alone
+    const int kg = Disp::periodic ? kind_host[g] : -1;
     if (const int rc = knn_cells(ctx, st, 1, n, K, scale, pos + 3 * (int64_t)lo, nlist + s0, edges + s0, inv_degree + lo,
-                                 nullptr, 0))
+                                 kg >= 0 ? box + 9 * (int64_t)g : nullptr, kg == 1 ? 1 : 0))
       return rc;
     if (lo > 0) {
       hipLaunchKernelGGL(knn_ragged_offset_kernel, dim3((unsigned)cdiv((int64_t)n * K, 256)), dim3(256), 0, st,
@@ -341,18 +346,50 @@ extern "C" int ng_knn_graph_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, 
   return NG_OK;
 }
 
+template <class Disp>
+static int cutoff_count_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t N, float cutoff, const float* pos,
+                                    const int32_t* graph_ptr, const float* box, const int32_t* kind, int32_t* deg) {
+  ProfScope ps(ctx, st, Disp::periodic ? "cutoff_count_ragged_pbc" : "cutoff_count_ragged");
+  hipLaunchKernelGGL((cutoff_ragged_kernel<false, Disp>), dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, G, (int)N,
+                     cutoff * cutoff, 1.0f, pos, graph_ptr, deg, nullptr, nullptr, nullptr, nullptr, nullptr, box, kind);
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}
+
+template <class Disp>
+static int cutoff_fill_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t N, float cutoff, float scale, const float* pos,
+                                   const int32_t* graph_ptr, const float* box, const int32_t* kind, const int32_t* row_ptr,
+                                   int32_t* col, float* dist, float* inv_degree, int32_t* row_of) {
+  ProfScope ps(ctx, st, Disp::periodic ? "cutoff_fill_ragged_pbc" : "cutoff_fill_ragged");
+  hipLaunchKernelGGL((cutoff_ragged_kernel<true, Disp>), dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, G, (int)N,
+                     cutoff * cutoff, scale, pos, graph_ptr, nullptr, row_ptr, col, dist, inv_degree, row_of, box, kind);
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}
+
+}  // namespace ng
+
+using namespace ng;
+
+extern "C" int ng_knn_graph_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, int K, float scale, const float* pos,
+                                   const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, int32_t* nlist,
+                                   float* edges, float* inv_degree) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn (ragged): neighbour count must be in [1,64]");
+  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  NG_REQUIRE(ctx, N * K < ((int64_t)1 << 31), "knn (ragged): N * K exceeds int32 slots");
+  if (N == 0) return NG_OK;
+  return knn_ragged_impl<DispOpen>(ctx, (hipStream_t)stream, G, N, K, scale, pos, graph_ptr, graph_ptr_host, max_n, nullptr,
+                                   nullptr, nullptr, nlist, edges, inv_degree);
+}
+
 extern "C" int ng_cutoff_count_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, const float* pos,
                                       const int32_t* graph_ptr, int max_n, int32_t* deg) {
   if (!ctx) return NG_ERR_INVALID;
   NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
   if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
   if (N == 0) return NG_OK;
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(ctx, st, "cutoff_count_ragged");
-  hipLaunchKernelGGL(cutoff_ragged_kernel<false>, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, G, (int)N, cutoff * cutoff,
-                     1.0f, pos, graph_ptr, deg, nullptr, nullptr, nullptr, nullptr, nullptr);
-  NG_HIP(ctx, hipGetLastError());
-  return NG_OK;
+  return cutoff_count_ragged_impl<DispOpen>(ctx, (hipStream_t)stream, G, N, cutoff, pos, graph_ptr, nullptr, nullptr, deg);
 }
 
 extern "C" int ng_cutoff_fill_rows_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, float scale,
@@ -363,10 +400,47 @@ extern "C" int ng_cutoff_fill_rows_ragged(ng_ctx* ctx, void* stream, int G, int6
   if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
   if (N == 0) return NG_OK;
   NG_REQUIRE(ctx, row_ptr && inv_degree, "cutoff graph (ragged): row_ptr and inv_degree required");
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(ctx, st, "cutoff_fill_ragged");
-  hipLaunchKernelGGL(cutoff_ragged_kernel<true>, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, G, (int)N, cutoff * cutoff,
-                     scale, pos, graph_ptr, nullptr, row_ptr, col, dist, inv_degree, row_of);
-  NG_HIP(ctx, hipGetLastError());
-  return NG_OK;
+  return cutoff_fill_ragged_impl<DispOpen>(ctx, (hipStream_t)stream, G, N, cutoff, scale, pos, graph_ptr, nullptr, nullptr,
+                                           row_ptr, col, dist, inv_degree, row_of);
+}
+
+// every structure with a boundary kind of its own: box [G][9] (pbc.cuh; zeros for an open structure) and kind [G] (-1 open,
+// 0 orthorhombic, 1 reduced triclinic) on the device
+extern "C" int ng_knn_graph_ragged_pbc(ng_ctx* ctx, void* stream, int G, int64_t N, int K, float scale, const float* pos,
+                                       const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, const float* box,
+                                       const int32_t* kind, const int32_t* kind_host, int32_t* nlist, float* edges,
+                                       float* inv_degree) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn (ragged): neighbour count must be in [1,64]");
+  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  NG_REQUIRE(ctx, N * K < ((int64_t)1 << 31), "knn (ragged): N * K exceeds int32 slots");
+  if (const int rc = ragged_box_check(ctx, G, N, box, kind, kind_host)) return rc;
+  if (N == 0) return NG_OK;
+  return knn_ragged_impl<DispPer>(ctx, (hipStream_t)stream, G, N, K, scale, pos, graph_ptr, graph_ptr_host, max_n, box, kind,
+                                  kind_host, nlist, edges, inv_degree);
+}
+
+extern "C" int ng_cutoff_count_ragged_pbc(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, const float* pos,
+                                          const int32_t* graph_ptr, int max_n, const float* box, const int32_t* kind,
+                                          const int32_t* kind_host, int32_t* deg) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
+  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  if (const int rc = ragged_box_check(ctx, G, N, box, kind, kind_host)) return rc;
+  if (N == 0) return NG_OK;
+  return cutoff_count_ragged_impl<DispPer>(ctx, (hipStream_t)stream, G, N, cutoff, pos, graph_ptr, box, kind, deg);
+}
+
+extern "C" int ng_cutoff_fill_rows_ragged_pbc(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, float scale,
+                                              const float* pos, const int32_t* graph_ptr, int max_n, const float* box,
+                                              const int32_t* kind, const int32_t* kind_host, const int32_t* row_ptr,
+                                              int32_t* col, float* dist, float* inv_degree, int32_t* row_of) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
+  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  if (const int rc = ragged_box_check(ctx, G, N, box, kind, kind_host)) return rc;
+  if (N == 0) return NG_OK;
+  NG_REQUIRE(ctx, row_ptr && inv_degree, "cutoff graph (ragged): row_ptr and inv_degree required");
+  return cutoff_fill_ragged_impl<DispPer>(ctx, (hipStream_t)stream, G, N, cutoff, scale, pos, graph_ptr, box, kind, row_ptr,
+                                          col, dist, inv_degree, row_of);
 }

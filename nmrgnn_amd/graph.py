@@ -69,6 +69,8 @@ class GraphBatch:
     scale = None
     box = None         # [G, 9] lattice vectors on the device (nmrgnn_amd.pbc) when the lists were built in periodic boxes
     box_triclinic = False
+    box_kind = None    # [G] int32 on the device (-1 open, 0 orthorhombic, 1 reduced triclinic): a ragged batch whose structures
+    box_kind_host = None   # have boundary kinds of their own (structures_to_batch(boxes=)); then ``box`` holds zeros for open ones
 
     _ctx = None        # library context for the list builders; None = the device's shared one (BatchPrefetcher sets its own)
 
@@ -293,16 +295,20 @@ class GraphBatch:
 
     def _box_state(self):
         """what box_grad reads, without the batch itself (as _positions_state; no incoming-edge lists needed)"""
-        return (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
-                self.edges.detach(), self.row_ptr, self.box, int(self.box_triclinic), self.G, self.graph_ptr)
+        state = (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
+                 self.edges.detach(), self.row_ptr, self.box, int(self.box_triclinic), self.G, self.graph_ptr)
+        # a boxed ragged batch appends its kinds: _box_grad then calls the per-structure entry points
+        return state if self.box_kind is None else state + (self.box_kind, self.box_kind_host)
 
     def _positions_state(self):
         """what positions_grad reads, without the batch itself (an autograd node keeps this, not the batch whose edges are
         its output: no reference cycle)"""
         csc_ptr, csc_edge = self.csc()
-        return (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
-                self.edges.detach(), self.row_ptr, getattr(self, "row_of", None), csc_ptr, csc_edge, self.box,
-                int(self.box_triclinic))
+        state = (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
+                 self.edges.detach(), self.row_ptr, getattr(self, "row_of", None), csc_ptr, csc_edge, self.box,
+                 int(self.box_triclinic))
+        # a boxed ragged batch appends what finds a row's structure and its kind (_positions_grad)
+        return state if self.box_kind is None else state + (self.G, self.graph_ptr, self.box_kind, self.box_kind_host)
 
     def as_tuple(self):
         if self.is_csr:
@@ -408,7 +414,8 @@ def _positions_grad(state, dedges):
     import ctypes as C
     from . import _lib
     from ._lib import ptr
-    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, row_of, csc_ptr, csc_edge, box, tric = state
+    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, row_of, csc_ptr, csc_edge, box, tric = state[:15]
+    ragged = state[15:]                  # (G, graph_ptr, kind, kind_host) of a boxed ragged batch
     ctx = ctx or _lib.get_context(device.index)
     dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
     if dd.numel() != edges.numel():
@@ -416,7 +423,19 @@ def _positions_grad(state, dedges):
     dpos = torch.empty_like(pos)
     with torch.cuda.device(device):
         st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        if box is not None:             # minimum-image vectors along the edges (csrc/pbc.cuh)
+        if ragged:                      # every structure by its own boundary kind (csrc/pbc.cuh: DispPer)
+            G, graph_ptr, kind, kind_host = ragged
+            kh = C.c_void_p(kind_host.ctypes.data)
+            if is_csr:
+                ctx.check(ctx.lib.ng_positions_grad_csr_ragged_pbc(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr),
+                                                                   ptr(nlist), ptr(row_of), ptr(dd), scale, ptr(csc_ptr),
+                                                                   ptr(csc_edge), G, ptr(graph_ptr), ptr(box), ptr(kind), kh,
+                                                                   ptr(dpos)), "ng_positions_grad_csr_ragged_pbc")
+            else:
+                ctx.check(ctx.lib.ng_positions_grad_ragged_pbc(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd),
+                                                               scale, ptr(csc_ptr), ptr(csc_edge), G, ptr(graph_ptr), ptr(box),
+                                                               ptr(kind), kh, ptr(dpos)), "ng_positions_grad_ragged_pbc")
+        elif box is not None:           # minimum-image vectors along the edges (csrc/pbc.cuh)
             n = pos.shape[-2]
             if is_csr:
                 ctx.check(ctx.lib.ng_positions_grad_csr_pbc(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist),
@@ -440,7 +459,8 @@ def _box_grad(state, dedges, want_dvec=True):
     import ctypes as C
     from . import _lib
     from ._lib import ptr
-    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, box, tric, G, graph_ptr = state
+    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, box, tric, G, graph_ptr = state[:14]
+    ragged = state[14:]                  # (kind, kind_host) of a boxed ragged batch
     ctx = ctx or _lib.get_context(device.index)
     dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
     if dd.numel() != edges.numel():
@@ -450,7 +470,18 @@ def _box_grad(state, dedges, want_dvec=True):
     tric = tric if box is not None else -1          # -1: open boundaries, dvec = 0
     with torch.cuda.device(device):
         st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        if is_csr:
+        if ragged:
+            kind, kind_host = ragged
+            kh = C.c_void_p(kind_host.ctypes.data)
+            if is_csr:
+                ctx.check(ctx.lib.ng_box_grad_csr_ragged(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist),
+                                                         ptr(dd), scale, G, ptr(graph_ptr), ptr(box), ptr(kind), kh,
+                                                         ptr(strain), ptr(dvec)), "ng_box_grad_csr_ragged")
+            else:
+                ctx.check(ctx.lib.ng_box_grad_ragged(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale, G,
+                                                     ptr(graph_ptr), ptr(box), ptr(kind), kh, ptr(strain), ptr(dvec)),
+                          "ng_box_grad_ragged")
+        elif is_csr:
             ctx.check(ctx.lib.ng_box_grad_csr(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist), ptr(dd),
                                               scale, G, ptr(graph_ptr), ptr(box), tric, ptr(strain), ptr(dvec)),
                       "ng_box_grad_csr")
@@ -710,8 +741,35 @@ def _ragged_inputs(atoms, positions, sizes, graph_ptr, device):
     return atoms, positions, gp
 
 
+def _ragged_count(atoms, sizes, graph_ptr):
+    """the number of structures as the caller states it, or None where _ragged_inputs will refuse the call anyway"""
+    if isinstance(atoms, (list, tuple)):
+        return len(atoms)
+    if sizes is not None:
+        return int(np.size(sizes))
+    if graph_ptr is not None:
+        return int(np.size(graph_ptr)) - 1
+    return None
+
+
+def _host_boxes(boxes, G, cutoff):
+    """None (every structure open), or pbc.prepare_ragged's (vectors, kinds, widths) for G structures, validated on the host"""
+    if boxes is None:
+        return None
+    from .pbc import prepare_ragged
+    pr = prepare_ragged(boxes, G)
+    if not (pr[1] >= 0).any():
+        return None
+    if cutoff is not None:
+        for g in np.nonzero(pr[1] >= 0)[0]:
+            if not float(cutoff) < 0.5 * float(pr[2][g]):
+                raise ValueError(f"structures_to_batch: structure {int(g)}: cutoff {cutoff} must be below half the smallest box "
+                                 f"width ({0.5 * float(pr[2][g]):.6g})")
+    return pr
+
+
 def structures_to_batch(atoms, positions, neighbor_number=16, cutoff=None, scale=0.1, device=None, sizes=None,
-                        graph_ptr=None, box=None):
+                        graph_ptr=None, box=None, boxes=None):
     """Build the graphs of G DIFFERENT structures on the GPU in one launch per pass and return them as one device-resident
     GraphBatch with ``graph_ptr`` set: a library of small molecules, several proteins, a training set given as coordinates.
 
@@ -723,23 +781,41 @@ def structures_to_batch(atoms, positions, neighbor_number=16, cutoff=None, scale
     the structure alone, with indices shifted to the batch; a one-atom structure has only padded slots and inv_degree 0.
 
     The batch keeps the concatenated positions [N, 3] and ``scale``; with a ``positions`` tensor (or list of tensors) that
-    requires grad its ``edges`` carry a grad_fn back to them, as in :func:`frames_to_batch`.  Periodic boxes are not
-    supported on ragged batches (``box=`` raises ValueError)."""
+    requires grad its ``edges`` carry a grad_fn back to them, as in :func:`frames_to_batch`.
+
+    ``boxes``: one periodic box, or none, per structure (csrc/pbc.cuh: DispPer): a sequence of G entries, each ``None`` (open
+    boundaries) or ``(a, b, c, alpha, beta, gamma)`` as in :func:`frames_to_batch`, or a ``[G, 6]`` array or tensor (every
+    structure periodic).  Every structure keeps a boundary kind of its own (open, orthorhombic or reduced triclinic): its rows
+    are bit for bit what :func:`frames_to_batch` / :func:`frames_to_batch_cutoff` give for it alone with its own box, or
+    without one.  Positions may lie anywhere; nothing is wrapped.  ``cutoff`` must stay below half the smallest perpendicular
+    width of every periodic structure.  The batch keeps ``box`` [G, 9] (zeros for open structures) and ``box_kind`` [G];
+    ``positions_grad`` and ``box_grad`` use each structure's own minimum-image vectors.  A ``[G, 6]`` tensor that requires grad
+    gets ``boxes.grad`` as ``box`` does in :func:`frames_to_batch`; entries of the list form are not differentiated.
+    ``boxes=None``, or only ``None`` entries: open boundaries, the same calls as without the argument.  The singular ``box=``
+    of the uniform builders raises ValueError here."""
     if box is not None:
-        raise ValueError("structures_to_batch: periodic boxes are not supported on ragged batches; use frames_to_batch")
+        raise ValueError("structures_to_batch: periodic boxes are not supported through box= on ragged batches; give one box "
+                         "(or None) per structure with boxes=, or use frames_to_batch")
     K = int(neighbor_number)
     if not 1 <= K <= 64:
         raise ValueError(f"structures_to_batch: neighbor_number must be in [1, 64], got {neighbor_number}")
     if cutoff is not None and not float(cutoff) > 0:
         raise ValueError(f"structures_to_batch: cutoff must be > 0, got {cutoff}")
     device = _norm_device(device)
+    # the boxes are validated before any device work, against the count the caller states; where the caller states none
+    # (_ragged_inputs refuses such a call), or states one that the arrays contradict, against the count _ragged_inputs finds
+    G = _ragged_count(atoms, sizes, graph_ptr)
+    pr = _host_boxes(boxes, G, cutoff) if G is not None else None
     atoms, pos, gp = _ragged_inputs(atoms, positions, sizes, graph_ptr, device)
+    if G != len(gp) - 1:
+        pr = _host_boxes(boxes, len(gp) - 1, cutoff)
     if cutoff is None and int(gp[-1]) * K >= 2 ** 31:
         raise ValueError("structures_to_batch: N * neighbor_number exceeds 2^31 - 1 slots")
-    return _positions_batch(pos, lambda f: _structures_to_batch(atoms, f, gp, K, cutoff, scale, device))
+    return _positions_batch(pos, lambda f: _structures_to_batch(atoms, f, gp, K, cutoff, scale, device, pr),
+                            boxes if pr is not None and isinstance(boxes, torch.Tensor) else None)
 
 
-def _structures_to_batch(atoms, positions, gp, K, cutoff, scale, device):
+def _structures_to_batch(atoms, positions, gp, K, cutoff, scale, device, pr=None):
     import ctypes as C
     from . import _lib
     from ._lib import ptr
@@ -750,22 +826,34 @@ def _structures_to_batch(atoms, positions, gp, K, cutoff, scale, device):
     gp_host = gp.astype(np.int32)
     gp_dev = _graph_ptr_dev(gp_host, device)
     ctx = _lib.get_context(device.index)
+    if pr is not None:          # boxes [G, 9] and kinds [G] on the device, the kinds on the host as well
+        box, kind_host = torch.from_numpy(pr[0]).to(device), np.ascontiguousarray(pr[1], dtype=np.int32)
+        kind, kh = torch.from_numpy(kind_host).to(device), C.c_void_p(kind_host.ctypes.data)
     with torch.cuda.device(device):
         st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         if cutoff is None:
             nlist = torch.empty(N, K, dtype=torch.int32, device=device)
             edges = torch.empty(N, K, dtype=torch.float32, device=device)
             inv = torch.empty(N, dtype=torch.float32, device=device)
-            ctx.check(ctx.lib.ng_knn_graph_ragged(ctx.handle, st, G, N, K, float(scale), ptr(pos), ptr(gp_dev),
-                                                  C.c_void_p(gp_host.ctypes.data), max_n, ptr(nlist), ptr(edges), ptr(inv)),
-                      "ng_knn_graph_ragged")
+            if pr is None:
+                ctx.check(ctx.lib.ng_knn_graph_ragged(ctx.handle, st, G, N, K, float(scale), ptr(pos), ptr(gp_dev),
+                                                      C.c_void_p(gp_host.ctypes.data), max_n, ptr(nlist), ptr(edges),
+                                                      ptr(inv)), "ng_knn_graph_ragged")
+            else:
+                ctx.check(ctx.lib.ng_knn_graph_ragged_pbc(ctx.handle, st, G, N, K, float(scale), ptr(pos), ptr(gp_dev),
+                                                          C.c_void_p(gp_host.ctypes.data), max_n, ptr(box), ptr(kind), kh,
+                                                          ptr(nlist), ptr(edges), ptr(inv)), "ng_knn_graph_ragged_pbc")
             # every structure larger than K: no padded slot, the compute-side list IS the list (as _frames_to_batch)
             b = GraphBatch(at, nlist, edges, inv, graph_ptr=gp_host, device=device, validate=False,
                            nlist_c=nlist if int(np.min(np.diff(gp))) > K else None)
         else:
             deg = torch.empty(N, dtype=torch.int32, device=device)
-            ctx.check(ctx.lib.ng_cutoff_count_ragged(ctx.handle, st, G, N, float(cutoff), ptr(pos), ptr(gp_dev), max_n,
-                                                     ptr(deg)), "ng_cutoff_count_ragged")
+            if pr is None:
+                ctx.check(ctx.lib.ng_cutoff_count_ragged(ctx.handle, st, G, N, float(cutoff), ptr(pos), ptr(gp_dev), max_n,
+                                                         ptr(deg)), "ng_cutoff_count_ragged")
+            else:
+                ctx.check(ctx.lib.ng_cutoff_count_ragged_pbc(ctx.handle, st, G, N, float(cutoff), ptr(pos), ptr(gp_dev), max_n,
+                                                             ptr(box), ptr(kind), kh, ptr(deg)), "ng_cutoff_count_ragged_pbc")
             row_ptr = torch.empty(N + 1, dtype=torch.int32, device=device)
             ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, N, ptr(deg), ptr(row_ptr)), "ng_exclusive_scan_i32")
             nnz = int(deg.sum(dtype=torch.int64))      # the one host synchronisation, as in _frames_to_batch_cutoff
@@ -775,10 +863,18 @@ def _structures_to_batch(atoms, positions, gp, K, cutoff, scale, device):
             dist = torch.empty(nnz, dtype=torch.float32, device=device)
             row_of = torch.empty(nnz, dtype=torch.int32, device=device)
             inv = torch.empty(N, dtype=torch.float32, device=device)
-            ctx.check(ctx.lib.ng_cutoff_fill_rows_ragged(ctx.handle, st, G, N, float(cutoff), float(scale), ptr(pos),
-                                                         ptr(gp_dev), max_n, ptr(row_ptr), ptr(col), ptr(dist), ptr(inv),
-                                                         ptr(row_of)), "ng_cutoff_fill_rows_ragged")
+            if pr is None:
+                ctx.check(ctx.lib.ng_cutoff_fill_rows_ragged(ctx.handle, st, G, N, float(cutoff), float(scale), ptr(pos),
+                                                             ptr(gp_dev), max_n, ptr(row_ptr), ptr(col), ptr(dist), ptr(inv),
+                                                             ptr(row_of)), "ng_cutoff_fill_rows_ragged")
+            else:
+                ctx.check(ctx.lib.ng_cutoff_fill_rows_ragged_pbc(ctx.handle, st, G, N, float(cutoff), float(scale), ptr(pos),
+                                                                 ptr(gp_dev), max_n, ptr(box), ptr(kind), kh, ptr(row_ptr),
+                                                                 ptr(col), ptr(dist), ptr(inv), ptr(row_of)),
+                          "ng_cutoff_fill_rows_ragged_pbc")
             b = GraphBatch.from_csr(at, row_ptr, col, dist, inv, graph_ptr=gp_host, device=device, validate=False,
                                     row_of=row_of)
     b.positions, b.scale = pos, float(scale)
+    if pr is not None:
+        b.box, b.box_kind, b.box_kind_host = box, kind, kind_host
     return b

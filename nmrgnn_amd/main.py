@@ -36,18 +36,22 @@ def _open_structure(struct_files):
 
 
 def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16, stride=1,
-                   frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False, separate=False):
+                   frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False, separate=False, boxes=False):
     """Predict shifts for every ``stride``-th frame and write the reference's CSV.  Returns the timing
     buckets in seconds.  ``pbc``: neighbour lists under the minimum-image convention in each frame's box (its CRYST1
     record); a frame without one is an error.  ``separate``: every file is a structure of its own (see
-    :func:`_eval_separate`)."""
+    :func:`_eval_separate`); with ``boxes`` every (file, frame) structure uses its own CRYST1 box when it has one and open
+    boundaries otherwise."""
     if len(struct_files) == 0:
         raise ValueError('Must pass at least on structure file')
     if separate and pbc:
-        raise ValueError('--separate and --pbc cannot be combined: periodic boxes are not supported on ragged batches')
+        raise ValueError('--separate and --pbc cannot be combined: --pbc wants a box on every frame of one topology; '
+                         'use --separate --boxes for one box, or none, per structure')
+    if boxes and not separate:
+        raise ValueError('--boxes goes with --separate (one box, or none, per structure); use --pbc for frames of one topology')
     if separate:
         return _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going,
-                              device, echo)
+                              device, echo, boxes)
     import torch
     from .graph import frames_to_batch
     from .library import check_peaks, load_model
@@ -105,10 +109,12 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     return timing
 
 
-def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, device, echo):
+def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, device, echo,
+                   boxes=False):
     """``eval-struct --separate``: every file is a structure of its own, with all of its MODEL frames (every ``stride``-th,
     counted per file).  The structure-frames of all files go ``frames_per_batch`` at a time into one ragged device batch
-    (graph.structures_to_batch); the CSV has a leading ``file`` column (the path as given), then the reference's."""
+    (graph.structures_to_batch); the CSV has a leading ``file`` column (the path as given), then the reference's.  ``boxes``:
+    minimum-image lists in the CRYST1 box of every structure-frame that has one, open boundaries for the others."""
     import torch
     from .graph import structures_to_batch
     from .library import check_peaks, load_model
@@ -129,7 +135,8 @@ def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride
         t = time.perf_counter()
         dev = model.engine.device
         batch = structures_to_batch([atoms[k] for k, _ in chunk], [structs[k].frames[fr] for k, fr in chunk],
-                                    neighbor_number, device=dev)
+                                    neighbor_number, device=dev,
+                                    boxes=[structs[k].dimensions[fr] for k, fr in chunk] if boxes else None)
         torch.cuda.synchronize(dev)
         timing['Structure'] += time.perf_counter() - t
         t = time.perf_counter()
@@ -175,12 +182,19 @@ def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride
 @click.option('--pbc', is_flag=True, help='Minimum-image neighbour lists in each frame\'s periodic box (CRYST1)')
 @click.option('--separate', is_flag=True,
               help='Treat every struct file as a structure of its own (CSV gains a leading file column)')
-def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, pbc, separate):
+@click.option('--boxes', is_flag=True,
+              help='With --separate: minimum-image neighbour lists in each structure\'s own box (CRYST1), open boundaries '
+                   'for structures without one')
+def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, pbc, separate,
+                boxes):
     '''Predict NMR chemical shifts with specific file'''
     if separate and pbc:
-        raise click.UsageError('--separate and --pbc cannot be combined')
+        raise click.UsageError('--separate and --pbc cannot be combined; use --separate --boxes for one box, or none, per '
+                               'structure')
+    if boxes and not separate:
+        raise click.UsageError('--boxes goes with --separate; use --pbc for frames of one topology')
     eval_structure(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch,
-                   keep_going, echo=click.echo, pbc=pbc, separate=separate)
+                   keep_going, echo=click.echo, pbc=pbc, separate=separate, boxes=boxes)
 
 
 if __name__ == '__main__':

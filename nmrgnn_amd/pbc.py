@@ -96,3 +96,37 @@ def prepare(box, G):
     tric = any([check_reduced(v) for v in vecs])
     w_min = np.array([widths(v).min() for v in vecs])
     return np.ascontiguousarray(vecs.reshape(G, 9), dtype=np.float32), tric, w_min
+
+
+def prepare_ragged(boxes, G):
+    """host side of a periodic build on a ragged batch, where every structure has a boundary kind of its own: ``boxes`` is a
+    sequence of G entries, each ``None`` (open boundaries) or ``(a, b, c, alpha, beta, gamma)``, or a ``[G, 6]`` array (every
+    structure periodic) -> (vectors [G, 9] float32, kinds [G] int32, smallest perpendicular width [G]).  Kinds: -1 open,
+    0 orthorhombic, 1 reduced triclinic, decided per structure (:func:`prepare` decides once for a whole uniform batch).  An
+    open structure has zero vectors and an infinite width.  A periodic entry's vectors are those :func:`prepare` gives for
+    that box alone; the refusals are the same, with the structure index in front."""
+    if hasattr(boxes, "detach"):                        # a torch tensor: its detached host copy
+        boxes = boxes.detach().cpu().numpy()
+    if isinstance(boxes, np.ndarray):
+        if boxes.ndim != 2 or boxes.shape[1:] != (6,):
+            raise ValueError(f"boxes: a sequence of G entries or a [G, 6] array expected, got shape {boxes.shape}")
+    elif not isinstance(boxes, (list, tuple)):
+        raise ValueError("boxes: a sequence of G entries (None or (a, b, c, alpha, beta, gamma)) or a [G, 6] array expected")
+    if len(boxes) != G:
+        raise ValueError(f"boxes: {len(boxes)} entries for {G} structures")
+    vecs = np.zeros((G, 9), dtype=np.float32)
+    kinds = np.full(G, -1, dtype=np.int32)
+    w_min = np.full(G, np.inf)
+    for g, entry in enumerate(boxes):
+        if entry is None:
+            continue
+        if hasattr(entry, "detach"):
+            entry = entry.detach().cpu().numpy()
+        try:
+            v = triclinic_vectors(entry)
+            kinds[g] = 1 if check_reduced(v) else 0
+            w_min[g] = widths(v).min()
+        except ValueError as e:
+            raise ValueError(f"structure {g}: {e}") from None
+        vecs[g] = v.reshape(9)
+    return vecs, kinds, w_min

@@ -7,11 +7,19 @@ warm-up, ms per call.
   (b) one 7lgi frame + 108M + 2000 of those molecules in one batch: ragged kNN and cutoff; and the 7lgi frame alone through
       the uniform builder (ng_knn_graph) and the ragged one
   (c) model inference on (a) end to end (structures_to_batch + model, baseline architecture, seeded weights)
-usage: python tools/ragged_time.py [out.json]"""
+--boxes: periodic boxes per structure (structures_to_batch(boxes=), the _ragged_pbc entry points) on (a) and (b): all open
+  through the open entry points, all orthorhombic, all triclinic (b_x = a_x / 4, c_x = -a_x / 5, c_y = 0.3 b_y), and one third
+  of each kind; kNN kernels, cutoff count and fill, and the whole calls, each also as a ratio to the open figure of the same run.
+  The open figures of another build of the library (the parent commit's, to show the open path did not move) come from a run
+  of the plain mode with NMRGNN_HIP_LIB set to that build, alternating with this one on the same machine.
+Each mode is one process: run it under a time limit of its own (timeout -k 10 300 python tools/ragged_time.py --boxes out.json)
+and start nothing more on the GPU after a run that faulted or timed out.
+usage: python tools/ragged_time.py [--boxes] [out.json]"""
 import ctypes as C
 import json
 import os
 import sys
+import time
 import warnings
 
 import numpy as np
@@ -153,7 +161,105 @@ def set_c(out, atoms, pos):
                 "build_plus_model_ms": median_ms(lambda: model(structures_to_batch(A, P, K, sizes=sizes, device=dev)))}
 
 
+def boxes_of(sizes, kinds, min_width=8.5):
+    """one box per structure at 0.1 atoms / A^3, grown where needed until its smallest width is min_width (above twice the
+    4 A cutoff); kinds -1 open, 0 orthorhombic, 1 triclinic"""
+    from nmrgnn_amd.pbc import triclinic_vectors, widths
+    out = []
+    for n, k in zip(sizes, kinds):
+        if k < 0:
+            out.append(None)
+            continue
+        L = (n / 0.1) ** (1.0 / 3.0)
+        if k == 0:
+            d = np.array([L, L, L, 90.0, 90.0, 90.0])
+        else:
+            v = np.array([[L, 0, 0], [L / 4, L, 0], [-L / 5, 0.3 * L, L]])
+            nv = np.linalg.norm(v, axis=1)
+            ang = lambda x, y: np.degrees(np.arccos(np.dot(x, y) / np.linalg.norm(x) / np.linalg.norm(y)))
+            d = np.array([nv[0], nv[1], nv[2], ang(v[1], v[2]), ang(v[0], v[2]), ang(v[0], v[1])])
+        w = widths(triclinic_vectors(d)).min()
+        if w < min_width:
+            d[:3] *= 1.01 * min_width / w
+        out.append(tuple(float(x) for x in d))
+    return out
+
+
+def kernels_boxed(pos_dev, gp_host, cutoff, boxes):
+    """kernels() through the per-structure entry points"""
+    from nmrgnn_amd.pbc import prepare_ragged
+    N, G = int(gp_host[-1]), len(gp_host) - 1
+    max_n = int(np.max(np.diff(gp_host)))
+    vec, kind_host, _ = prepare_ragged(boxes, G)
+    gp_dev, box, kind = torch.from_numpy(gp_host).to(dev), torch.from_numpy(vec).to(dev), torch.from_numpy(kind_host).to(dev)
+    gph, kh = C.c_void_p(gp_host.ctypes.data), C.c_void_p(kind_host.ctypes.data)
+    nl = torch.empty((N, K), dtype=torch.int32, device=dev)
+    ed = torch.empty((N, K), device=dev)
+    inv = torch.empty(N, device=dev)
+    deg = torch.empty(N, dtype=torch.int32, device=dev)
+    rp = torch.empty(N + 1, dtype=torch.int32, device=dev)
+    knn = lambda: ctx.check(ctx.lib.ng_knn_graph_ragged_pbc(ctx.handle, st, G, N, K, 0.1, ptr(pos_dev), ptr(gp_dev), gph, max_n,
+                                                             ptr(box), ptr(kind), kh, ptr(nl), ptr(ed), ptr(inv)), "knn")
+    count = lambda: ctx.check(ctx.lib.ng_cutoff_count_ragged_pbc(ctx.handle, st, G, N, cutoff, ptr(pos_dev), ptr(gp_dev), max_n,
+                                                                 ptr(box), ptr(kind), kh, ptr(deg)), "count")
+    count()
+    ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, N, ptr(deg), ptr(rp)), "scan")
+    nnz = int(deg.sum(dtype=torch.int64))
+    col = torch.empty(nnz, dtype=torch.int32, device=dev)
+    dist = torch.empty(nnz, device=dev)
+    row_of = torch.empty(nnz, dtype=torch.int32, device=dev)
+    fill = lambda: ctx.check(ctx.lib.ng_cutoff_fill_rows_ragged_pbc(ctx.handle, st, G, N, cutoff, 0.1, ptr(pos_dev), ptr(gp_dev),
+                                                                    max_n, ptr(box), ptr(kind), kh, ptr(rp), ptr(col),
+                                                                    ptr(dist), ptr(inv), ptr(row_of)), "fill")
+    return {"knn_kernel_ms": median_ms(knn), "cutoff_count_ms": median_ms(count), "cutoff_fill_ms": median_ms(fill),
+            "nnz": nnz}
+
+
+def boxed_set(A, P, sizes, with_calls=True):
+    """open / orthorhombic / triclinic / one third each on one batch; ratios to the open figures of this run"""
+    from nmrgnn_amd.pbc import prepare_ragged
+    gp = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    G = len(sizes)
+    r = {"open": kernels(P, gp, 4.0)}
+    if with_calls:
+        r["open"]["knn_call_ms"] = median_ms(lambda: structures_to_batch(A, P, K, sizes=sizes, device=dev))
+        r["open"]["cutoff_call_ms"] = median_ms(lambda: structures_to_batch(A, P, cutoff=4.0, sizes=sizes, device=dev))
+    for name, kinds in (("ortho", np.zeros(G, int)), ("tric", np.ones(G, int)), ("mixed", np.arange(G) % 3 - 1)):
+        boxes = boxes_of(sizes, kinds)
+        q = kernels_boxed(P, gp, 4.0, boxes)
+        if with_calls:
+            q["knn_call_ms"] = median_ms(lambda: structures_to_batch(A, P, K, sizes=sizes, device=dev, boxes=boxes))
+            q["cutoff_call_ms"] = median_ms(lambda: structures_to_batch(A, P, cutoff=4.0, sizes=sizes, device=dev, boxes=boxes))
+            t0 = time.perf_counter()
+            prepare_ragged(boxes, G)
+            q["host_prepare_ms"] = 1e3 * (time.perf_counter() - t0)     # the host validation inside the whole calls
+        for k in [k for k in q if k.endswith("_ms") and k in r["open"]]:
+            q[k.replace("_ms", "_over_open")] = q[k] / r["open"][k]
+        r[name] = q
+    return r
+
+
+def main_boxes(path):
+    out = {}
+    atoms, pos = molecules(4096)
+    sizes = np.array([len(p) for p in pos])
+    out["a"] = boxed_set(np.concatenate(atoms), torch.from_numpy(np.concatenate(pos)).to(dev), sizes)
+    print(json.dumps({"a": out["a"]}), flush=True)
+    s1 = read_pdb("tests/data/7lgi.pdb.gz")
+    s2 = read_pdb("tests/data/108M.pdb")
+    at = [atoms_onehot(s1.elements), atoms_onehot(s2.elements)] + atoms[:2000]
+    ps = [np.asarray(s1.frames[0], np.float32), np.asarray(s2.frames[0], np.float32)] + pos[:2000]
+    out["b"] = boxed_set(np.concatenate(at), torch.from_numpy(np.concatenate(ps)).to(dev), np.array([len(p) for p in ps]))
+    print(json.dumps({"b": out["b"]}), flush=True)
+    if path:
+        with open(path, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
+    args = [a for a in sys.argv[1:] if a != "--boxes"]
+    if "--boxes" in sys.argv[1:]:
+        return main_boxes(args[0] if args else None)
     out = {}
     atoms, pos = set_a(out)
     print(json.dumps({"a": out["a"]}), flush=True)
@@ -161,8 +267,8 @@ def main():
     print(json.dumps({"b": out["b"]}), flush=True)
     set_c(out, atoms, pos)
     print(json.dumps({"c": out["c"]}), flush=True)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if args:
+        with open(args[0], "w") as f:
             json.dump(out, f, indent=1)
 
 
