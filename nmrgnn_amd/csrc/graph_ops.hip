@@ -505,7 +505,7 @@ extern "C" int ng_exclusive_scan_i32(ng_ctx* ctx, void* stream, int64_t n, const
     NG_HIP(ctx, hipGetLastError());
     return NG_OK;
   }
-  if (n > 0) NG_HIP(ctx, hipMemcpyAsync(out, in, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  if (n > 0 && in != out) NG_HIP(ctx, hipMemcpyAsync(out, in, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   NG_HIP(ctx, hipMemsetAsync(out + n, 0, sizeof(int32_t), st));
   hipLaunchKernelGGL(gl_scan_local_kernel, dim3(nb), dim3(GL_BLOCK), 0, st, n1, out, bsum);
   hipLaunchKernelGGL(gl_scan_sums_kernel, dim3(1), dim3(GL_BLOCK), 0, st, nb, bsum);

@@ -12,8 +12,17 @@
 //   DispOpen   c - q: today's arithmetic, bit for bit (the open-boundary instantiations stay what they were)
 //   DispOrtho  c - q, then rint per axis
 //   DispTric   c - q, sequential z / y / x wrap; when the wrapped vector is not shorter than w_min / 2 (w_min: the smallest
-//              perpendicular width) the nearest of its 27 neighbouring images.  Below w_min / 2 it is provably the minimum
-//              image: every other image is at least w_min - |d| away.
+//              perpendicular width) the nearest of its neighbouring images.  Below w_min / 2 it is provably the minimum
+//              image: every other image is at least w_min - |d| away.  The neighbouring images are i a + j b + k c with
+//              |k| <= nk, |j| <= nj, |i| <= ni.  The wrapped vector d has |d_x| <= a_x / 2, |d_y| <= b_y / 2, |d_z| <= c_z / 2,
+//              so |d| <= R = sqrt(a_x^2 + b_y^2 + c_z^2) / 2, and the minimum image m = d + i a + j b + k c is no longer:
+//              |d_z + k c_z| <= R gives |k| <= R / c_z + 1/2, |d_y + k c_y + j b_y| <= R gives |j| <= R / b_y + 1/2 +
+//              nk |c_y| / b_y.  Along x, a = (a_x, 0, 0) moves nothing else: for given j and k the best i is the integer nearest to
+//              -(d_x + j b_x + k c_x) / a_x, and |d_x + j b_x + k c_x| <= a_x / 2 + nj |b_x| + nk |c_x| puts it within
+//              ni = ceil((nj |b_x| + nk |c_x|) / a_x) (on the tie at a whole quotient both candidates are equally long).
+//              For the usual cells (cube-like boxes, the rhombic dodecahedron, the truncated octahedron) that is 1, 1, 1:
+//              the 27 images, unrolled.  A box that is thin along c (c_z well below a_x, b_y) needs |k| = 2 and more:
+//              a rolled search.
 //   DispPer    a ragged batch, where every structure has a boundary kind of its own (-1 open, 0 orthorhombic, 1 reduced
 //              triclinic; kind [G] int32 next to box [G][9]): loads the structure's kind and vectors and calls, at run time,
 //              the operator() of the policy of that kind as it stands above.  An orthorhombic structure next to a triclinic
@@ -57,6 +66,7 @@ struct DispOrtho {
 struct DispTric {
   static constexpr bool periodic = true;
   float ax, bx, by, cx, cy, cz, iax, iby, icz, h2;
+  int nk, nj, ni;      // the reach of the image search along c, b, a (see above)
   __device__ __forceinline__ void load(const float* box, int frame) {
     const float* b = box + (int64_t)frame * 9;
     ax = b[0]; bx = b[3]; by = b[4]; cx = b[6]; cy = b[7]; cz = b[8];
@@ -68,6 +78,18 @@ struct DispTric {
     const float wb = by * cz / sqrtf(cy * cy + cz * cz);
     const float w = fminf(fminf(wa, wb), cz);
     h2 = 0.25f * w * w;
+    const float r = 0.5f * sqrtf(ax * ax + by * by + cz * cz) * 1.0001f;      // rounded up: one image too many is harmless
+    nk = (int)(r * icz + 0.5f);
+    nj = (int)(r * iby + 0.5f + (float)nk * fabsf(cy) * iby);
+    ni = max((int)ceilf(((float)nj * fabsf(bx) + (float)nk * fabsf(cx)) * iax), 1);
+  }
+  __device__ __forceinline__ void image(int i, int j, int k, float ox, float oy, float oz, float& best, float& dx, float& dy,
+                                        float& dz) const {
+    const float ex = fmaf((float)k, cx, fmaf((float)j, bx, fmaf((float)i, ax, ox)));
+    const float ey = fmaf((float)k, cy, fmaf((float)j, by, oy));
+    const float ez = fmaf((float)k, cz, oz);
+    const float e2 = pbc_dist2(ex, ey, ez);
+    if (e2 < best) { best = e2; dx = ex; dy = ey; dz = ez; }
   }
   __device__ __forceinline__ void operator()(float qx, float qy, float qz, float px, float py, float pz, float& dx, float& dy,
                                              float& dz) const {
@@ -81,15 +103,18 @@ struct DispTric {
     float best = pbc_dist2(dx, dy, dz);
     if (best >= h2) {
       const float ox = dx, oy = dy, oz = dz;
-      for (int k = -1; k <= 1; ++k)
-        for (int j = -1; j <= 1; ++j)
-          for (int i = -1; i <= 1; ++i) {
-            const float ex = fmaf((float)k, cx, fmaf((float)j, bx, fmaf((float)i, ax, ox)));
-            const float ey = fmaf((float)k, cy, fmaf((float)j, by, oy));
-            const float ez = fmaf((float)k, cz, oz);
-            const float e2 = pbc_dist2(ex, ey, ez);
-            if (e2 < best) { best = e2; dx = ex; dy = ey; dz = ez; }
-          }
+      if ((nk | nj | ni) <= 1) {
+        for (int k = -1; k <= 1; ++k)
+          for (int j = -1; j <= 1; ++j)
+            for (int i = -1; i <= 1; ++i) image(i, j, k, ox, oy, oz, best, dx, dy, dz);
+      } else {      // a thin box: every image within reach
+#pragma unroll 1
+        for (int k = -nk; k <= nk; ++k)
+#pragma unroll 1
+          for (int j = -nj; j <= nj; ++j)
+#pragma unroll 1
+            for (int i = -ni; i <= ni; ++i) image(i, j, k, ox, oy, oz, best, dx, dy, dz);
+      }
     }
   }
 };
