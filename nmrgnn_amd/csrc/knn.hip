@@ -16,14 +16,9 @@
 
 #include "ng_common.h"
 #include "ng_internal.h"
-#include "pbc.cuh"
+#include "nlist_common.cuh"
 
 namespace ng {
-
-constexpr int KNN_TILE = 1024;
-
-// the distance expression of every kNN kernel (knn_cells.hip has the same one): identical lists need identical rounding
-__device__ __forceinline__ float knn_dist2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
 // Disp: the displacement policy of pbc.cuh (DispOpen: open boundaries, box unused)
 template <int KMAX, class Disp>
@@ -33,7 +28,7 @@ __global__ __launch_bounds__(256) void knn_kernel(int n, int K, float scale,
                                                   int32_t* __restrict__ nlist,        // [G*n][K]
                                                   float* __restrict__ edges,          // [G*n][K]
                                                   float* __restrict__ inv_degree) {   // [G*n]
-  __shared__ float sx[KNN_TILE], sy[KNN_TILE], sz[KNN_TILE];
+  __shared__ float sx[NL_TILE], sy[NL_TILE], sz[NL_TILE];
   const int frame = blockIdx.y;
   Disp D;
   D.load(box, frame);
@@ -46,45 +41,21 @@ __global__ __launch_bounds__(256) void knn_kernel(int n, int K, float scale,
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) { bd[k] = INFINITY; bi[k] = 0; }
 
-  for (int t0 = 0; t0 < n; t0 += KNN_TILE) {
-    const int cnt = min(KNN_TILE, n - t0);
-    __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += 256) {
-      sx[t] = fp[3 * (t0 + t)]; sy[t] = fp[3 * (t0 + t) + 1]; sz[t] = fp[3 * (t0 + t) + 2];
-    }
-    __syncthreads();
+  for (int t0 = 0; t0 < n; t0 += NL_TILE) {
+    const int cnt = min(NL_TILE, n - t0);
+    NG_NL_STAGE(sx, sy, sz, fp, t0, cnt);
     if (i < n) {
       for (int t = 0; t < cnt; ++t) {
         float dx, dy, dz;
         D(qx, qy, qz, sx[t], sy[t], sz[t], dx, dy, dz);
-        const float d2 = knn_dist2(dx, dy, dz);
+        const float d2 = pbc_dist2(dx, dy, dz);
         const int j = t0 + t;
-        if (d2 < bd[KMAX - 1] && j != i) {
-#pragma unroll
-          for (int k = KMAX - 1; k >= 1; --k) {
-            const bool shift = bd[k - 1] > d2;          // old element k-1 moves up
-            const bool here = !shift && bd[k] > d2;     // candidate lands in slot k
-            bi[k] = shift ? bi[k - 1] : (here ? j : bi[k]);
-            bd[k] = shift ? bd[k - 1] : (here ? d2 : bd[k]);
-          }
-          if (bd[0] > d2) { bd[0] = d2; bi[0] = j; }
-        }
+        NG_KNN_INSERT(KMAX, bd, bi, d2, j, i);
       }
     }
   }
   if (i >= n) return;
-  const int64_t row = (int64_t)frame * n + i;
-  int deg = 0;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    if (k < K) {
-      const bool ok = bd[k] < INFINITY;
-      nlist[row * K + k] = ok ? frame * n + bi[k] : 0;
-      edges[row * K + k] = ok ? sqrtf(bd[k]) * scale : 0.f;
-      deg += (ok && bi[k] > 0) ? 1 : 0;
-    }
-  }
-  inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+  NG_KNN_WRITE_ROW(KMAX, K, bd, bi, (int64_t)frame * n + i, frame * n, 0, scale, nlist, edges, inv_degree);
 }
 
 // The same search with S = 8 lanes per query atom: lane s of a group scans the candidates t = s (mod 8) of every tile
@@ -97,7 +68,7 @@ template <int KMAX, int S, class Disp>
 __global__ __launch_bounds__(256) void knn_kernel_s8(int n, int K, float scale, const float* __restrict__ pos,
                                                      const float* __restrict__ box, int32_t* __restrict__ nlist,
                                                      float* __restrict__ edges, float* __restrict__ inv_degree) {
-  __shared__ float sx[KNN_TILE], sy[KNN_TILE], sz[KNN_TILE];
+  __shared__ float sx[NL_TILE], sy[NL_TILE], sz[NL_TILE];
   const int frame = blockIdx.y;
   Disp D;
   D.load(box, frame);
@@ -111,29 +82,16 @@ __global__ __launch_bounds__(256) void knn_kernel_s8(int n, int K, float scale, 
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) { bd[k] = INFINITY; bi[k] = 0x7fffffff; }
 
-  for (int t0 = 0; t0 < n; t0 += KNN_TILE) {
-    const int cnt = min(KNN_TILE, n - t0);
-    __syncthreads();
-    for (int t = threadIdx.x; t < cnt; t += 256) {
-      sx[t] = fp[3 * (t0 + t)]; sy[t] = fp[3 * (t0 + t) + 1]; sz[t] = fp[3 * (t0 + t) + 2];
-    }
-    __syncthreads();
+  for (int t0 = 0; t0 < n; t0 += NL_TILE) {
+    const int cnt = min(NL_TILE, n - t0);
+    NG_NL_STAGE(sx, sy, sz, fp, t0, cnt);
     if (i < n) {
       for (int t = sl; t < cnt; t += S) {
         float dx, dy, dz;
         D(qx, qy, qz, sx[t], sy[t], sz[t], dx, dy, dz);
-        const float d2 = knn_dist2(dx, dy, dz);
+        const float d2 = pbc_dist2(dx, dy, dz);
         const int j = t0 + t;
-        if (d2 < bd[KMAX - 1] && j != i) {
-#pragma unroll
-          for (int k = KMAX - 1; k >= 1; --k) {
-            const bool shift = bd[k - 1] > d2;
-            const bool here = !shift && bd[k] > d2;
-            bi[k] = shift ? bi[k - 1] : (here ? j : bi[k]);
-            bd[k] = shift ? bd[k - 1] : (here ? d2 : bd[k]);
-          }
-          if (bd[0] > d2) { bd[0] = d2; bi[0] = j; }
-        }
+        NG_KNN_INSERT(KMAX, bd, bi, d2, j, i);
       }
     }
   }
@@ -168,18 +126,7 @@ __global__ __launch_bounds__(256) void knn_kernel_s8(int n, int K, float scale, 
     bi[KMAX - 1] = mine ? 0x7fffffff : bi[KMAX - 1];
   }
   if (i >= n || sl != 0) return;
-  const int64_t row = (int64_t)frame * n + i;
-  int deg = 0;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    if (k < K) {
-      const bool ok = rd[k] < INFINITY;
-      nlist[row * K + k] = ok ? frame * n + ri[k] : 0;
-      edges[row * K + k] = ok ? sqrtf(rd[k]) * scale : 0.f;
-      deg += (ok && ri[k] > 0) ? 1 : 0;
-    }
-  }
-  inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+  NG_KNN_WRITE_ROW(KMAX, K, rd, ri, (int64_t)frame * n + i, frame * n, 0, scale, nlist, edges, inv_degree);
 }
 
 // ---- one WAVE per query atom, for molecule-sized calls (round 4).  A single 2770-atom frame gives the lane kernels above 693
@@ -193,18 +140,7 @@ __global__ __launch_bounds__(256) void knn_kernel_s8(int n, int K, float scale, 
 //   C  only keys at or below that bound are inserted (a few more than K) into a sorted list held ACROSS the lanes (lane k = k-th
 //      smallest): one wave-wide shift and two compares per insertion, whatever K is.
 // The frame's positions are staged in LDS once per workgroup (n <= 4096); the four waves of a workgroup take four queries.
-typedef unsigned long long knn_u64;
-__device__ __forceinline__ knn_u64 knn_readlane64(knn_u64 v, int l) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return ((knn_u64)hi << 32) | lo;
-}
-// lane l gets lane l - 1's value, lane 0 gets 0 (DPP wave_shr:1)
-__device__ __forceinline__ knn_u64 knn_shr1(knn_u64 v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, 0x138, 0xf, 0xf, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), 0x138, 0xf, 0xf, false);
-  return ((knn_u64)hi << 32) | lo;
-}
+// Phases B and C and the write-out are nlist_common.cuh's NG_KNN_WAVE_SELECT / NG_KNN_WAVE_WRITE_ROW, shared with ragged.hip.
 constexpr int KNN_WAVE_MAXN = 4096;
 
 template <int STEPS, class Disp>
@@ -234,46 +170,14 @@ __global__ __launch_bounds__(256) void knn_wave_kernel(int n, int K, float scale
     const int tc = min(t, n - 1);
     float dx, dy, dz;
     D(qx, qy, qz, sx[tc], sy[tc], sz[tc], dx, dy, dz);
-    const float d2 = knn_dist2(dx, dy, dz);
-    knn_u64 k = ((knn_u64)__builtin_bit_cast(unsigned, d2) << 32) | (unsigned)t;
+    const float d2 = pbc_dist2(dx, dy, dz);
+    knn_u64 k = NG_KNN_KEY(d2, (unsigned)t);
     if (t >= n || t == i) k = ~0ull;
     key[s] = k;
     mn = k < mn ? k : mn;
   }
-  // B: the K-th smallest lane minimum (keys of real candidates are distinct; absent ones are ~0 and rank last)
-  knn_u64 tau = ~0ull;
-  {
-    int rank = 0;
-    for (int b = 0; b < 64; ++b) rank += knn_readlane64(mn, b) < mn ? 1 : 0;
-    const unsigned long long hit = __ballot(rank == K - 1 && mn != ~0ull);
-    if (hit) tau = knn_readlane64(mn, __builtin_ctzll(hit));
-  }
-  // C: insert what lies at or below the bound
-  knn_u64 list = ~0ull, kth = ~0ull;
-#pragma unroll
-  for (int s = 0; s < STEPS; ++s) {
-    unsigned long long m = __ballot(key[s] <= tau && key[s] != ~0ull);
-    while (m) {
-      const int b = __builtin_ctzll(m);
-      m &= m - 1;
-      const knn_u64 c = knn_readlane64(key[s], b);
-      if (c < kth) {
-        const knn_u64 prev = knn_shr1(list);
-        list = c < prev ? prev : (c < list ? c : list);
-        kth = knn_readlane64(list, K - 1);
-      }
-    }
-  }
-  const int64_t row = (int64_t)frame * n + i;
-  const bool ok = lane < K && list != ~0ull;
-  const int idx = (int)(unsigned)list;
-  const float d2 = __builtin_bit_cast(float, (unsigned)(list >> 32));
-  if (lane < K) {
-    nlist[row * K + lane] = ok ? frame * n + idx : 0;
-    edges[row * K + lane] = ok ? sqrtf(d2) * scale : 0.f;
-  }
-  const int deg = __popcll(__ballot(ok && idx > 0));
-  if (lane == 0) inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+  NG_KNN_WAVE_SELECT(STEPS, key, mn, K, list);
+  NG_KNN_WAVE_WRITE_ROW(list, lane, K, (int64_t)frame * n + i, frame * n, scale, nlist, edges, inv_degree);
 }
 
 // the launch of every brute-force kernel for one displacement policy; the cell grid for large frames
@@ -302,12 +206,11 @@ static int knn_graph_impl(ng_ctx* ctx, hipStream_t st, int G, int n, int K, floa
       hipLaunchKernelGGL((knn_kernel_s8<16, 8, Disp>), dim3((unsigned)cdiv(n, 32), (unsigned)G), block, 0, st, n, K, scale, pos,
                          box, nlist, edges, inv_degree);
   }
-  else if (K <= 16)
-    hipLaunchKernelGGL((knn_kernel<16, Disp>), grid, block, 0, st, n, K, scale, pos, box, nlist, edges, inv_degree);
-  else if (K <= 32)
-    hipLaunchKernelGGL((knn_kernel<32, Disp>), grid, block, 0, st, n, K, scale, pos, box, nlist, edges, inv_degree);
-  else
-    hipLaunchKernelGGL((knn_kernel<64, Disp>), grid, block, 0, st, n, K, scale, pos, box, nlist, edges, inv_degree);
+  else {
+#define NG_KNN1(KM) hipLaunchKernelGGL((knn_kernel<KM, Disp>), grid, block, 0, st, n, K, scale, pos, box, nlist, edges, inv_degree)
+    NG_KNN_LADDER(K, NG_KNN1);
+#undef NG_KNN1
+  }
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
 }

@@ -9,12 +9,12 @@
 //      r = 0, 1, 2, ... around its cell — a row of cells along x is one contiguous range of records — until the K-th
 //      distance found is within r L of the query (everything unvisited is at least that far away) or the grid is exhausted
 // Result: EXACTLY the lists of the brute-force kernels — (distance, index) ascending, ties to the lower index, the same
-// fp32 distance expression (knn_dist2) — whatever the grid; tests compare the two bit for bit.
+// fp32 distance expression (pbc_dist2) — whatever the grid; tests compare the two bit for bit.
 #include <algorithm>
 
 #include "ng_common.h"
 #include "ng_internal.h"
-#include "pbc.cuh"
+#include "nlist_common.cuh"
 
 extern "C" int ng_exclusive_scan_i32(ng_ctx*, void*, int64_t, const int32_t*, int32_t*);
 
@@ -25,9 +25,6 @@ struct KcGrid {          // per frame
   float inv_l, l;        // 1 / cell edge, cell edge
   int nx, ny, nz;
 };
-
-// the distance expression of every kNN kernel (knn.hip uses the same one): bit-identical orders need identical rounding
-__device__ __forceinline__ float knn_dist2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
 __device__ __forceinline__ int kc_coord(float x, float o, float inv_l, int n) {
   return min(max((int)floorf((x - o) * inv_l), 0), n - 1);
@@ -122,23 +119,22 @@ __global__ __launch_bounds__(256) void kc_fill_kernel(int n, int cap, const floa
 }
 
 // ---- 3. the search ------------------------------------------------------------------------------------------------------
-// A list entry is ONE 64-bit key, (bits of the squared distance) << 32 | index: squared distances are non-negative floats,
-// whose bit patterns order like the values, so key order IS (distance, index) order — one compare per slot instead of
-// three.  The insertion appears once in the kernel (one loop over the one or two record ranges of a row of cells): with
-// a copy per call site, and four more for a four-deep prefetch, the kernel was instruction-fetch bound (6 us per ROW).
+// A list entry is ONE 64-bit key (nlist_common.cuh: NG_KNN_KEY), an empty slot KNN_KEY_EMPTY.  The insertion appears once in
+// the kernel (one loop over the one or two record ranges of a row of cells): with a copy per call site, and four more for a
+// four-deep prefetch, the kernel was instruction-fetch bound (6 us per ROW).
 // the candidates of one row of cells — the record ranges [a0, b0) and [a1, b1) — into the query's list, distances through the
 // displacement policy D (pbc.cuh); the one call site of each query kernel
 template <int KMAX, class Disp>
 __device__ __forceinline__ void kc_scan(const Disp& D, float4 q, int i, const float4* __restrict__ rec, int a0, int b0, int a1,
-                                        int b1, uint64_t (&key)[KMAX]) {
+                                        int b1, knn_u64 (&key)[KMAX]) {
   const int len0 = b0 - a0, total = len0 + (b1 - a1);
   for (int u = 0; u < total; ++u) {
     const float4 c = rec[u < len0 ? a0 + u : a1 + (u - len0)];
     float dx, dy, dz;
     D(q.x, q.y, q.z, c.x, c.y, c.z, dx, dy, dz);
-    const float d2 = knn_dist2(dx, dy, dz);
+    const float d2 = pbc_dist2(dx, dy, dz);
     const unsigned j = __builtin_bit_cast(unsigned, c.w);
-    const uint64_t kk = ((uint64_t)__builtin_bit_cast(unsigned, d2) << 32) | j;
+    const knn_u64 kk = NG_KNN_KEY(d2, j);
     if (kk < key[KMAX - 1] && (int)j != i) {
 #pragma unroll
       for (int k = KMAX - 1; k >= 1; --k) {
@@ -163,10 +159,9 @@ __global__ __launch_bounds__(256) void kc_query_kernel(int n, int K, int cap, fl
   const int i = __builtin_bit_cast(int, q.w);
   const int cx = kc_coord(q.x, g.ox, g.inv_l, g.nx), cy = kc_coord(q.y, g.oy, g.inv_l, g.ny), cz = kc_coord(q.z, g.oz, g.inv_l, g.nz);
   const int32_t* st = start + (int64_t)frame * cap;
-  constexpr uint64_t EMPTY = ((uint64_t)0x7f800000u << 32) | 0x7fffffffu;      // (inf, no index)
-  uint64_t key[KMAX];
+  knn_u64 key[KMAX];
 #pragma unroll
-  for (int k = 0; k < KMAX; ++k) key[k] = EMPTY;
+  for (int k = 0; k < KMAX; ++k) key[k] = KNN_KEY_EMPTY;
 
   const int rmax = max(max(max(cx, g.nx - 1 - cx), max(cy, g.ny - 1 - cy)), max(cz, g.nz - 1 - cz));
   for (int r = 0; r <= rmax; ++r) {
@@ -193,26 +188,13 @@ __global__ __launch_bounds__(256) void kc_query_kernel(int n, int K, int cap, fl
     // every atom outside the cube of shells 0..r is at least r L from the query (it is at least r whole cells away along
     // some axis; 0.1 % off for the rounding of the cell assignment).  Enough once the K-th distance is inside that.
     const float reach = (float)r * g.l * 0.999f;
-    uint64_t kth = EMPTY;
+    knn_u64 kth = KNN_KEY_EMPTY;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) kth = k == K - 1 ? key[k] : kth;      // (a run-time index would put the list on the stack)
-    if (__builtin_bit_cast(float, (unsigned)(kth >> 32)) <= reach * reach) break;
+    if (knn_key_d2(kth) <= reach * reach) break;
   }
 
-  const int64_t row = (int64_t)frame * n + i;
-  int deg = 0;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    if (k < K) {
-      const float d2 = __builtin_bit_cast(float, (unsigned)(key[k] >> 32));
-      const int j = (int)(unsigned)key[k];
-      const bool ok = d2 < INFINITY;
-      nlist[row * K + k] = ok ? frame * n + j : 0;
-      edges[row * K + k] = ok ? sqrtf(d2) * scale : 0.f;
-      deg += (ok && j > 0) ? 1 : 0;
-    }
-  }
-  inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+  NG_KNN_WRITE_KEY_ROW(KMAX, K, key, (int64_t)frame * n + i, frame * n, scale, nlist, edges, inv_degree);
 }
 
 // ---- periodic boxes: the grid lives in fractional coordinates ----------------------------------------------------------
@@ -296,10 +278,9 @@ __global__ __launch_bounds__(256) void kp_query_kernel(int n, int K, int cap, fl
   const int loy = (g.ny - 1) / 2, hiy = g.ny - 1 - loy;
   const int loz = (g.nz - 1) / 2, hiz = g.nz - 1 - loz;
   const int32_t* st = start + (int64_t)frame * cap;
-  constexpr uint64_t EMPTY = ((uint64_t)0x7f800000u << 32) | 0x7fffffffu;      // (inf, no index)
-  uint64_t key[KMAX];
+  knn_u64 key[KMAX];
 #pragma unroll
-  for (int k = 0; k < KMAX; ++k) key[k] = EMPTY;
+  for (int k = 0; k < KMAX; ++k) key[k] = KNN_KEY_EMPTY;
 
   const int rmax = max(max(hix, hiy), hiz);
   for (int r = 0; r <= rmax; ++r) {
@@ -336,26 +317,13 @@ __global__ __launch_bounds__(256) void kp_query_kernel(int n, int K, int cap, fl
     if (r < hiz) w = fminf(w, g.wz);
     if (w == INFINITY) break;                          // every cell visited
     const float reach = (float)r * w * 0.999f;
-    uint64_t kth = EMPTY;
+    knn_u64 kth = KNN_KEY_EMPTY;
 #pragma unroll
     for (int k = 0; k < KMAX; ++k) kth = k == K - 1 ? key[k] : kth;
-    if (__builtin_bit_cast(float, (unsigned)(kth >> 32)) <= reach * reach) break;
+    if (knn_key_d2(kth) <= reach * reach) break;
   }
 
-  const int64_t row = (int64_t)frame * n + i;
-  int deg = 0;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    if (k < K) {
-      const float d2 = __builtin_bit_cast(float, (unsigned)(key[k] >> 32));
-      const int j = (int)(unsigned)key[k];
-      const bool ok = d2 < INFINITY;
-      nlist[row * K + k] = ok ? frame * n + j : 0;
-      edges[row * K + k] = ok ? sqrtf(d2) * scale : 0.f;
-      deg += (ok && j > 0) ? 1 : 0;
-    }
-  }
-  inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+  NG_KNN_WRITE_KEY_ROW(KMAX, K, key, (int64_t)frame * n + i, frame * n, scale, nlist, edges, inv_degree);
 }
 
 // cells per frame: about n / 4 (the grid kernel shrinks its grid to fit), a power of two in [64, 2^21]
@@ -405,25 +373,18 @@ int knn_cells(ng_ctx* ctx, hipStream_t st, int G, int n, int K, float scale, con
     NG_HIP(ctx, hipGetLastError());
   }
   ProfScope ps(ctx, st, "knn_cells_query");
-#define NG_KP(KM, DISP)                                                                                                \
-  hipLaunchKernelGGL((kp_query_kernel<KM, DISP>), grid, block, 0, st, n, K, cap, scale, pgrids, box, cell_of, start, rec, nlist, \
-                     edges, inv_degree)
-  if (box) {
-    if (triclinic) {
-      if (K <= 16) NG_KP(16, DispTric); else if (K <= 32) NG_KP(32, DispTric); else NG_KP(64, DispTric);
-    } else {
-      if (K <= 16) NG_KP(16, DispOrtho); else if (K <= 32) NG_KP(32, DispOrtho); else NG_KP(64, DispOrtho);
-    }
-    NG_HIP(ctx, hipGetLastError());
-    return NG_OK;
-  }
-#undef NG_KP
-  if (K <= 16)
-    hipLaunchKernelGGL(kc_query_kernel<16>, grid, block, 0, st, n, K, cap, scale, grids, start, rec, nlist, edges, inv_degree);
-  else if (K <= 32)
-    hipLaunchKernelGGL(kc_query_kernel<32>, grid, block, 0, st, n, K, cap, scale, grids, start, rec, nlist, edges, inv_degree);
-  else
-    hipLaunchKernelGGL(kc_query_kernel<64>, grid, block, 0, st, n, K, cap, scale, grids, start, rec, nlist, edges, inv_degree);
+#define NG_KP_TRIC(KM) hipLaunchKernelGGL((kp_query_kernel<KM, DispTric>), grid, block, 0, st, n, K, cap, scale, pgrids, box, \
+                                          cell_of, start, rec, nlist, edges, inv_degree)
+#define NG_KP_ORTHO(KM) hipLaunchKernelGGL((kp_query_kernel<KM, DispOrtho>), grid, block, 0, st, n, K, cap, scale, pgrids, box, \
+                                           cell_of, start, rec, nlist, edges, inv_degree)
+#define NG_KC(KM) hipLaunchKernelGGL(kc_query_kernel<KM>, grid, block, 0, st, n, K, cap, scale, grids, start, rec, nlist, edges, \
+                                     inv_degree)
+  if (box && triclinic) NG_KNN_LADDER(K, NG_KP_TRIC);
+  else if (box) NG_KNN_LADDER(K, NG_KP_ORTHO);
+  else NG_KNN_LADDER(K, NG_KC);
+#undef NG_KP_TRIC
+#undef NG_KP_ORTHO
+#undef NG_KC
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
 }

@@ -1,5 +1,5 @@
 // Periodic boxes under the minimum-image convention: the displacement policies of the neighbour-list builders (knn.hip,
-// knn_cells.hip, mp_csr.hip's cutoff kernels) and of the position gradient (input_grad.hip).
+// knn_cells.hip, cutoff.hip, ragged.hip) and of the position gradient (input_grad.hip).
 //
 // A box is three lattice vectors in lower-triangular form, [9] floats per frame, row-major: a = (ax, 0, 0),
 // b = (bx, by, 0), c = (cx, cy, cz) — the GROMACS / MDAnalysis triclinic_vectors convention.  The host converts
@@ -34,7 +34,7 @@
 
 namespace ng {
 
-// the squared-distance expression of every builder (knn.hip: knn_dist2, mp_csr.hip: cut_dist2)
+// the squared-distance expression of every builder, the only copy (nlist_common.cuh says why it is an explicit fma chain)
 __device__ __forceinline__ float pbc_dist2(float dx, float dy, float dz) { return fmaf(dz, dz, fmaf(dy, dy, dx * dx)); }
 
 struct DispOpen {

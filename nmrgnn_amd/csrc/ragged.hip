@@ -1,5 +1,5 @@
 // Neighbour lists of a RAGGED batch: G structures of different sizes, concatenated along the rows (graph_ptr [G+1] on the
-// device), built in one launch per pass.  The uniform builders (knn.hip, mp_csr.hip's cutoff kernels) take G frames of one
+// device), built in one launch per pass.  The uniform builders (knn.hip, cutoff.hip) take G frames of one
 // topology with the frames on gridDim.y (G <= 65535); here a library of small molecules or a few proteins of different sizes
 // is one call, G limited only by int32 rows.
 //
@@ -32,7 +32,7 @@
 
 #include "ng_common.h"
 #include "ng_internal.h"
-#include "pbc.cuh"
+#include "nlist_common.cuh"
 #include "ragged.cuh"
 
 namespace ng {
@@ -40,7 +40,6 @@ namespace ng {
 constexpr int RG_TILE = 1024;        // candidates per LDS tile: 16 KiB of float4
 constexpr int RG_CELLS_MIN = 16384;  // kNN structures from this size on take the cell grid (knn.hip: knn_graph_impl)
 constexpr int RG_WAVE_MIN = 256;     // kNN structures of more atoms, up to 4096, take one wave per query row
-typedef unsigned long long knn_u64;
 
 // the candidate span of a workgroup: the union of the ranges of its active rows (block-wide min / max through LDS);
 // returns false when no row of the workgroup is active
@@ -105,32 +104,12 @@ __global__ __launch_bounds__(256) void knn_ragged_kernel(int G, int N, int K, fl
         D(qx, qy, qz, c.x, c.y, c.z, dx, dy, dz);
         const float d2 = pbc_dist2(dx, dy, dz);
         const int j = t0 + t;
-        if (d2 < bd[KMAX - 1] && j != i) {
-#pragma unroll
-          for (int k = KMAX - 1; k >= 1; --k) {
-            const bool shift = bd[k - 1] > d2;          // old element k-1 moves up
-            const bool here = !shift && bd[k] > d2;     // candidate lands in slot k
-            bi[k] = shift ? bi[k - 1] : (here ? j : bi[k]);
-            bd[k] = shift ? bd[k - 1] : (here ? d2 : bd[k]);
-          }
-          if (bd[0] > d2) { bd[0] = d2; bi[0] = j; }
-        }
+        NG_KNN_INSERT(KMAX, bd, bi, d2, j, i);
       }
     }
   }
   if (!active) return;
-  const int64_t row = i;
-  int deg = 0;
-#pragma unroll
-  for (int k = 0; k < KMAX; ++k) {
-    if (k < K) {
-      const bool ok = bd[k] < INFINITY;
-      nlist[row * K + k] = ok ? bi[k] : 0;
-      edges[row * K + k] = ok ? sqrtf(bd[k]) * scale : 0.f;
-      deg += (ok && bi[k] > r.lo) ? 1 : 0;        // structure-local index > 0
-    }
-  }
-  inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+  NG_KNN_WRITE_ROW(KMAX, K, bd, bi, i, 0, r.lo, scale, nlist, edges, inv_degree);      // batch-global indices in the list
 }
 
 // One WAVE per query row for the rows of mid-sized structures (wlo, 64 * STEPS] atoms: the algorithm of knn_wave_kernel
@@ -138,17 +117,6 @@ __global__ __launch_bounds__(256) void knn_ragged_kernel(int G, int N, int K, fl
 // bit for bit.  One thread per query leaves a 2770-atom structure with 44 waves that each walk all 2770 candidates (0.44 ms);
 // here it is 2770 waves of 44 steps.  Candidates are read from global memory (a structure of <= 4096 atoms is <= 48 KiB, held
 // by the caches); the waves of rows outside (wlo, 64 * STEPS] leave after the search of graph_ptr.
-__device__ __forceinline__ knn_u64 rg_readlane64(knn_u64 v, int l) {            // knn.hip: knn_readlane64
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return ((knn_u64)hi << 32) | lo;
-}
-__device__ __forceinline__ knn_u64 rg_shr1(knn_u64 v) {                         // knn.hip: knn_shr1 (DPP wave_shr:1)
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, 0x138, 0xf, 0xf, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), 0x138, 0xf, 0xf, false);
-  return ((knn_u64)hi << 32) | lo;
-}
-
 template <int STEPS, class Disp>
 __global__ __launch_bounds__(256) void knn_ragged_wave_kernel(int G, int N, int K, float scale, int wlo,
                                                               const float* __restrict__ pos, const int32_t* __restrict__ gp,
@@ -176,45 +144,13 @@ __global__ __launch_bounds__(256) void knn_ragged_wave_kernel(int G, int N, int 
     float dx, dy, dz;
     D(qx, qy, qz, sp[3 * tc], sp[3 * tc + 1], sp[3 * tc + 2], dx, dy, dz);
     const float d2 = pbc_dist2(dx, dy, dz);
-    knn_u64 k = ((knn_u64)__builtin_bit_cast(unsigned, d2) << 32) | (unsigned)t;
+    knn_u64 k = NG_KNN_KEY(d2, (unsigned)t);
     if (t >= n || lo + t == i) k = ~0ull;
     key[s] = k;
     mn = k < mn ? k : mn;
   }
-  // B: the K-th smallest lane minimum bounds the K-th smallest key
-  knn_u64 tau = ~0ull;
-  {
-    int rank = 0;
-    for (int b = 0; b < 64; ++b) rank += rg_readlane64(mn, b) < mn ? 1 : 0;
-    const unsigned long long hit = __ballot(rank == K - 1 && mn != ~0ull);
-    if (hit) tau = rg_readlane64(mn, __builtin_ctzll(hit));
-  }
-  // C: insert what lies at or below the bound into the list held across the lanes
-  knn_u64 list = ~0ull, kth = ~0ull;
-#pragma unroll
-  for (int s = 0; s < STEPS; ++s) {
-    unsigned long long m = __ballot(key[s] <= tau && key[s] != ~0ull);
-    while (m) {
-      const int b = __builtin_ctzll(m);
-      m &= m - 1;
-      const knn_u64 c = rg_readlane64(key[s], b);
-      if (c < kth) {
-        const knn_u64 prev = rg_shr1(list);
-        list = c < prev ? prev : (c < list ? c : list);
-        kth = rg_readlane64(list, K - 1);
-      }
-    }
-  }
-  const int64_t row = i;
-  const bool ok = lane < K && list != ~0ull;
-  const int idx = (int)(unsigned)list;
-  const float d2 = __builtin_bit_cast(float, (unsigned)(list >> 32));
-  if (lane < K) {
-    nlist[row * K + lane] = ok ? lo + idx : 0;
-    edges[row * K + lane] = ok ? sqrtf(d2) * scale : 0.f;
-  }
-  const int deg = __popcll(__ballot(ok && idx > 0));
-  if (lane == 0) inv_degree[row] = deg > 0 ? 1.0f / (float)deg : 0.f;
+  NG_KNN_WAVE_SELECT(STEPS, key, mn, K, list);
+  NG_KNN_WAVE_WRITE_ROW(list, lane, K, i, lo, scale, nlist, edges, inv_degree);
 }
 
 // frame-local -> batch-global indices of one structure's rows from the cell grid (n >= 16384 > K: every slot is real)
@@ -224,7 +160,7 @@ __global__ __launch_bounds__(256) void knn_ragged_offset_kernel(int64_t count, i
 }
 
 // cutoff: count (FILL = false: deg[N]) or fill pass (col / dist / row_of at row_ptr, inv_degree) of cutoff_kernel
-// (mp_csr.hip) over the row's own structure; Disp / box / kind as knn_ragged_kernel
+// (cutoff.hip) over the row's own structure; Disp / box / kind as knn_ragged_kernel
 template <bool FILL, class Disp>
 __global__ __launch_bounds__(256) void cutoff_ragged_kernel(int G, int N, float cutoff2, float scale,
                                                             const float* __restrict__ pos, const int32_t* __restrict__ gp,
@@ -257,15 +193,7 @@ __global__ __launch_bounds__(256) void cutoff_ragged_kernel(int G, int N, float 
         D(qx, qy, qz, c.x, c.y, c.z, dx, dy, dz);
         const float d2 = pbc_dist2(dx, dy, dz);
         const int j = t0 + t;
-        if (d2 < cutoff2 && j != i) {
-          if (FILL && out + cnt < lim) {
-            col[out + cnt] = j;
-            dist[out + cnt] = sqrtf(d2) * scale;
-            if (row_of) row_of[out + cnt] = i;
-          }
-          ++cnt;
-          cnt_pos += j > r.lo ? 1 : 0;
-        }
+        NG_CUTOFF_HIT(FILL, d2, j, i, 0, r.lo, i, cutoff2, scale, out, lim, col, dist, row_of, cnt, cnt_pos);
       }
     }
   }
@@ -274,7 +202,10 @@ __global__ __launch_bounds__(256) void cutoff_ragged_kernel(int G, int N, float 
   else deg[i] = cnt;
 }
 
-static int ragged_check(ng_ctx* ctx, int G, int64_t N, int max_n, const float* pos, const int32_t* graph_ptr) {
+// The checks every entry point makes, in the order they fire: those of the batch first, then (the kNN builder puts its slot
+// count between the two) those of the boxed entry points (Disp::periodic): box [G][9] and kind [G] on the device; a host copy
+// of the kinds, where given, holds -1, 0 or 1.
+static int ragged_check_batch(ng_ctx* ctx, int G, int64_t N, int max_n, const float* pos, const int32_t* graph_ptr) {
   NG_REQUIRE(ctx, G >= 0 && N >= 0 && max_n >= 0, "ragged graph: negative size");
   NG_REQUIRE(ctx, N < ((int64_t)1 << 31), "ragged graph: batch exceeds int32 rows");
   NG_REQUIRE(ctx, max_n <= N, "ragged graph: max_n exceeds the batch");
@@ -282,8 +213,9 @@ static int ragged_check(ng_ctx* ctx, int G, int64_t N, int max_n, const float* p
   return NG_OK;
 }
 
-// the boxed entry points: box [G][9] and kind [G] on the device; a host copy of the kinds, where given, holds -1, 0 or 1
-static int ragged_box_check(ng_ctx* ctx, int G, int64_t N, const float* box, const int32_t* kind, const int32_t* kind_host) {
+template <class Disp>
+static int ragged_check_boxes(ng_ctx* ctx, int G, int64_t N, const float* box, const int32_t* kind, const int32_t* kind_host) {
+  if (!Disp::periodic) return NG_OK;
   NG_REQUIRE(ctx, N == 0 || (box && kind), "ragged graph (pbc): box and kind required");
   if (kind_host)
     for (int g = 0; g < G; ++g)
@@ -291,11 +223,19 @@ static int ragged_box_check(ng_ctx* ctx, int G, int64_t N, const float* box, con
   return NG_OK;
 }
 
-// Disp = DispOpen: box / kind / kind_host NULL
+// The three builders, each the whole of an open entry point (Disp = DispOpen; box / kind / kind_host NULL) and of its _pbc twin
+// (DispPer).
 template <class Disp>
-static int knn_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t N, int K, float scale, const float* pos,
-                           const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, const float* box,
-                           const int32_t* kind, const int32_t* kind_host, int32_t* nlist, float* edges, float* inv_degree) {
+static int knn_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, int K, float scale, const float* pos,
+                      const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, const float* box, const int32_t* kind,
+                      const int32_t* kind_host, int32_t* nlist, float* edges, float* inv_degree) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn (ragged): neighbour count must be in [1,64]");
+  if (const int rc = ragged_check_batch(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  NG_REQUIRE(ctx, N * K < ((int64_t)1 << 31), "knn (ragged): N * K exceeds int32 slots");
+  if (const int rc = ragged_check_boxes<Disp>(ctx, G, N, box, kind, kind_host)) return rc;
+  if (N == 0) return NG_OK;
+  hipStream_t st = (hipStream_t)stream;
   // structures of the cell grid: only when one may be that large, from the host copy of graph_ptr
   const bool cells = !sw().knn_brute && !sw().knn_serial && max_n >= RG_CELLS_MIN;
   NG_REQUIRE(ctx, !cells || graph_ptr_host, "knn (ragged): graph_ptr_host required when max_n >= 16384");
@@ -312,7 +252,7 @@ static int knn_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t N, int K,
     const dim3 grid((unsigned)cdiv(N, 256)), block(256);
 #define NG_RG(KM) hipLaunchKernelGGL((knn_ragged_kernel<KM, Disp>), grid, block, 0, st, G, (int)N, K, scale, RG_WAVE_MIN, whi, big, \
                                      pos, graph_ptr, nlist, edges, inv_degree, box, kind)
-    if (K <= 16) NG_RG(16); else if (K <= 32) NG_RG(32); else NG_RG(64);
+    NG_KNN_LADDER(K, NG_RG);
 #undef NG_RG
     NG_HIP(ctx, hipGetLastError());
     if (steps) {
@@ -347,8 +287,15 @@ static int knn_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t N, int K,
 }
 
 template <class Disp>
-static int cutoff_count_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t N, float cutoff, const float* pos,
-                                    const int32_t* graph_ptr, const float* box, const int32_t* kind, int32_t* deg) {
+static int cutoff_count_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, const float* pos,
+                               const int32_t* graph_ptr, int max_n, const float* box, const int32_t* kind,
+                               const int32_t* kind_host, int32_t* deg) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
+  if (const int rc = ragged_check_batch(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  if (const int rc = ragged_check_boxes<Disp>(ctx, G, N, box, kind, kind_host)) return rc;
+  if (N == 0) return NG_OK;
+  hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ctx, st, Disp::periodic ? "cutoff_count_ragged_pbc" : "cutoff_count_ragged");
   hipLaunchKernelGGL((cutoff_ragged_kernel<false, Disp>), dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, G, (int)N,
                      cutoff * cutoff, 1.0f, pos, graph_ptr, deg, nullptr, nullptr, nullptr, nullptr, nullptr, box, kind);
@@ -357,9 +304,17 @@ static int cutoff_count_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t 
 }
 
 template <class Disp>
-static int cutoff_fill_ragged_impl(ng_ctx* ctx, hipStream_t st, int G, int64_t N, float cutoff, float scale, const float* pos,
-                                   const int32_t* graph_ptr, const float* box, const int32_t* kind, const int32_t* row_ptr,
-                                   int32_t* col, float* dist, float* inv_degree, int32_t* row_of) {
+static int cutoff_fill_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, float scale, const float* pos,
+                              const int32_t* graph_ptr, int max_n, const float* box, const int32_t* kind,
+                              const int32_t* kind_host, const int32_t* row_ptr, int32_t* col, float* dist, float* inv_degree,
+                              int32_t* row_of) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
+  if (const int rc = ragged_check_batch(ctx, G, N, max_n, pos, graph_ptr)) return rc;
+  if (const int rc = ragged_check_boxes<Disp>(ctx, G, N, box, kind, kind_host)) return rc;
+  if (N == 0) return NG_OK;
+  NG_REQUIRE(ctx, row_ptr && inv_degree, "cutoff graph (ragged): row_ptr and inv_degree required");
+  hipStream_t st = (hipStream_t)stream;
   ProfScope ps(ctx, st, Disp::periodic ? "cutoff_fill_ragged_pbc" : "cutoff_fill_ragged");
   hipLaunchKernelGGL((cutoff_ragged_kernel<true, Disp>), dim3((unsigned)cdiv(N, 256)), dim3(256), 0, st, G, (int)N,
                      cutoff * cutoff, scale, pos, graph_ptr, nullptr, row_ptr, col, dist, inv_degree, row_of, box, kind);
@@ -374,34 +329,20 @@ using namespace ng;
 extern "C" int ng_knn_graph_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, int K, float scale, const float* pos,
                                    const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, int32_t* nlist,
                                    float* edges, float* inv_degree) {
-  if (!ctx) return NG_ERR_INVALID;
-  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn (ragged): neighbour count must be in [1,64]");
-  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
-  NG_REQUIRE(ctx, N * K < ((int64_t)1 << 31), "knn (ragged): N * K exceeds int32 slots");
-  if (N == 0) return NG_OK;
-  return knn_ragged_impl<DispOpen>(ctx, (hipStream_t)stream, G, N, K, scale, pos, graph_ptr, graph_ptr_host, max_n, nullptr,
-                                   nullptr, nullptr, nlist, edges, inv_degree);
+  return knn_ragged<DispOpen>(ctx, stream, G, N, K, scale, pos, graph_ptr, graph_ptr_host, max_n, nullptr, nullptr, nullptr,
+                              nlist, edges, inv_degree);
 }
 
 extern "C" int ng_cutoff_count_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, const float* pos,
                                       const int32_t* graph_ptr, int max_n, int32_t* deg) {
-  if (!ctx) return NG_ERR_INVALID;
-  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
-  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
-  if (N == 0) return NG_OK;
-  return cutoff_count_ragged_impl<DispOpen>(ctx, (hipStream_t)stream, G, N, cutoff, pos, graph_ptr, nullptr, nullptr, deg);
+  return cutoff_count_ragged<DispOpen>(ctx, stream, G, N, cutoff, pos, graph_ptr, max_n, nullptr, nullptr, nullptr, deg);
 }
 
 extern "C" int ng_cutoff_fill_rows_ragged(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, float scale,
                                           const float* pos, const int32_t* graph_ptr, int max_n, const int32_t* row_ptr,
                                           int32_t* col, float* dist, float* inv_degree, int32_t* row_of) {
-  if (!ctx) return NG_ERR_INVALID;
-  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
-  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
-  if (N == 0) return NG_OK;
-  NG_REQUIRE(ctx, row_ptr && inv_degree, "cutoff graph (ragged): row_ptr and inv_degree required");
-  return cutoff_fill_ragged_impl<DispOpen>(ctx, (hipStream_t)stream, G, N, cutoff, scale, pos, graph_ptr, nullptr, nullptr,
-                                           row_ptr, col, dist, inv_degree, row_of);
+  return cutoff_fill_ragged<DispOpen>(ctx, stream, G, N, cutoff, scale, pos, graph_ptr, max_n, nullptr, nullptr, nullptr,
+                                      row_ptr, col, dist, inv_degree, row_of);
 }
 
 // every structure with a boundary kind of its own: box [G][9] (pbc.cuh; zeros for an open structure) and kind [G] (-1 open,
@@ -410,37 +351,20 @@ extern "C" int ng_knn_graph_ragged_pbc(ng_ctx* ctx, void* stream, int G, int64_t
                                        const int32_t* graph_ptr, const int32_t* graph_ptr_host, int max_n, const float* box,
                                        const int32_t* kind, const int32_t* kind_host, int32_t* nlist, float* edges,
                                        float* inv_degree) {
-  if (!ctx) return NG_ERR_INVALID;
-  NG_REQUIRE(ctx, K >= 1 && K <= 64, "knn (ragged): neighbour count must be in [1,64]");
-  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
-  NG_REQUIRE(ctx, N * K < ((int64_t)1 << 31), "knn (ragged): N * K exceeds int32 slots");
-  if (const int rc = ragged_box_check(ctx, G, N, box, kind, kind_host)) return rc;
-  if (N == 0) return NG_OK;
-  return knn_ragged_impl<DispPer>(ctx, (hipStream_t)stream, G, N, K, scale, pos, graph_ptr, graph_ptr_host, max_n, box, kind,
-                                  kind_host, nlist, edges, inv_degree);
+  return knn_ragged<DispPer>(ctx, stream, G, N, K, scale, pos, graph_ptr, graph_ptr_host, max_n, box, kind, kind_host, nlist,
+                             edges, inv_degree);
 }
 
 extern "C" int ng_cutoff_count_ragged_pbc(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, const float* pos,
                                           const int32_t* graph_ptr, int max_n, const float* box, const int32_t* kind,
                                           const int32_t* kind_host, int32_t* deg) {
-  if (!ctx) return NG_ERR_INVALID;
-  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
-  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
-  if (const int rc = ragged_box_check(ctx, G, N, box, kind, kind_host)) return rc;
-  if (N == 0) return NG_OK;
-  return cutoff_count_ragged_impl<DispPer>(ctx, (hipStream_t)stream, G, N, cutoff, pos, graph_ptr, box, kind, deg);
+  return cutoff_count_ragged<DispPer>(ctx, stream, G, N, cutoff, pos, graph_ptr, max_n, box, kind, kind_host, deg);
 }
 
 extern "C" int ng_cutoff_fill_rows_ragged_pbc(ng_ctx* ctx, void* stream, int G, int64_t N, float cutoff, float scale,
                                               const float* pos, const int32_t* graph_ptr, int max_n, const float* box,
                                               const int32_t* kind, const int32_t* kind_host, const int32_t* row_ptr,
                                               int32_t* col, float* dist, float* inv_degree, int32_t* row_of) {
-  if (!ctx) return NG_ERR_INVALID;
-  NG_REQUIRE(ctx, cutoff > 0.f, "cutoff graph (ragged): cutoff > 0");
-  if (const int rc = ragged_check(ctx, G, N, max_n, pos, graph_ptr)) return rc;
-  if (const int rc = ragged_box_check(ctx, G, N, box, kind, kind_host)) return rc;
-  if (N == 0) return NG_OK;
-  NG_REQUIRE(ctx, row_ptr && inv_degree, "cutoff graph (ragged): row_ptr and inv_degree required");
-  return cutoff_fill_ragged_impl<DispPer>(ctx, (hipStream_t)stream, G, N, cutoff, scale, pos, graph_ptr, box, kind, row_ptr,
-                                          col, dist, inv_degree, row_of);
+  return cutoff_fill_ragged<DispPer>(ctx, stream, G, N, cutoff, scale, pos, graph_ptr, max_n, box, kind, kind_host, row_ptr,
+                                     col, dist, inv_degree, row_of);
 }

@@ -1,4 +1,4 @@
-"""Exact reference of the neighbour-list builders (knn.hip, knn_cells.hip, mp_csr.hip's cutoff kernels, ragged.hip): NumPy and
+"""Exact reference of the neighbour-list builders (knn.hip, knn_cells.hip, cutoff.hip, ragged.hip): NumPy and
 integers only.
 
 Every builder orders candidates by the float32 value fmaf(dz, dz, fmaf(dy, dy, dx * dx)) and then by index.  On positions that are

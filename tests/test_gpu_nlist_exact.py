@@ -1,5 +1,5 @@
 """The neighbour-list builders against the exact integer reference of tests/nlist_ref.py, bit for bit: every kernel of knn.hip,
-knn_cells.hip, the cutoff kernels of mp_csr.hip, ragged.hip and ng_exclusive_scan_i32, at the sizes where the dispatch changes.
+knn_cells.hip, cutoff.hip, ragged.hip and ng_exclusive_scan_i32, at the sizes where the dispatch changes.
 
 Positions are multiples of 1/8 (box lengths powers of two), where the kernels' float32 distance expression is exact however it
 is rounded (nlist_ref.check_exact_domain, asserted on every case's own data), so every output is compared with
@@ -219,7 +219,9 @@ for _t in (False, True):
     PERIODIC.append(_pcase("lanes16_forced", "lanes", 1025, 1, 16, (32, 16, 16), _t))
     PERIODIC.append(_pcase("lanes8_default", None, 1025, 17, 16, (32, 16, 16), _t))
     PERIODIC.append(_pcase("serial_kmax16", "serial", 700, 1, 16, (16, 16, 16), _t))
+    PERIODIC.append(_pcase("serial_kmax32", "serial", 700, 1, 17, (16, 16, 16), _t))
     PERIODIC.append(_pcase("serial_kmax64", "serial", 700, 3, 64, (16, 16, 16), _t))
+    PERIODIC.append(_pcase("cells_kmax32", "cells", 64, 1, 17, (8, 16, 32), _t, "knn_cells_query"))
     for _K in (16, 40):
         PERIODIC.append(_pcase("cells", "cells", 64, 1, _K, (8, 16, 32), _t, "knn_cells_query"))
         PERIODIC.append(_pcase("cells", "cells", 64, 1, _K, (8, 8, 8), _t, "knn_cells_query", kind="ties"))
@@ -363,15 +365,15 @@ def test_cutoff_periodic(gpu_device, monkeypatch, mode, n, G, diag, off, kind, c
 RAGGED_TOP = {16: (1024,), 32: (1024, 1025), 48: (1024, 1025, 2100), 64: (1024, 1025, 4096)}
 
 
-def _ragged_keys(K, steps=64):
+def _ragged_keys(K, steps=64, boxed=True):
     """structures of 1, 2, K, K + 1, 255, 256, 257, 1024, 1025 and 4096 atoms, boundaries cycling open / orthorhombic /
-    triclinic, each in a box of its own size.  The largest structure sizes the wave kernel's template: ``steps`` = 16, 32 and
-    48 end the list at 1024, 1025 and 2100 atoms instead"""
+    triclinic, each in a box of its own size (``boxed`` = False: all open).  The largest structure sizes the wave kernel's
+    template: ``steps`` = 16, 32 and 48 end the list at 1024, 1025 and 2100 atoms instead"""
     keys = []
     for g, n in enumerate((1, 2, K, K + 1, 255, 256, 257) + RAGGED_TOP[steps]):
         diag = (8, 8, 8) if n <= 64 else (16, 16, 8) if n <= 257 else (32, 16, 16) if n <= 1025 else (32, 32, 32)
         kinds = ("ties", "spread")
-        if g % 3 == 0:
+        if g % 3 == 0 or not boxed:
             keys.append(_okey(kinds[g % 2], n, g))
         else:
             keys.append(_bkey(n, g, diag, ORTHO if g % 3 == 1 else TRIC_OFF[diag], kinds[g % 2]))
@@ -388,16 +390,12 @@ def _ragged_inputs(dev, keys):
     return sizes, gp, pos, kind, torch.from_numpy(box).to(dev), torch.from_numpy(kind).to(dev), torch.from_numpy(gp).to(dev)
 
 
-@pytest.mark.parametrize("steps", [16, 32, 48, 64], ids=lambda v: f"wave_per_row_steps{v}")
-@pytest.mark.parametrize("K", [16, 40], ids=["thread_per_row_kmax16-K16", "thread_per_row_kmax64-K40"])
-def test_ragged_knn(gpu_device, monkeypatch, K, steps):
-    """knn_ragged_kernel (structures up to 256 atoms) and knn_ragged_wave_kernel (257 .. 4096, its template sized by the largest
-    structure) through ng_knn_graph_ragged_pbc, every structure against the reference directly"""
+def _run_ragged_knn(dev, K, steps, boxed):
+    """the structures of _ragged_keys through ng_knn_graph_ragged_pbc (``boxed``) or ng_knn_graph_ragged, every structure
+    against the reference directly"""
     import torch
     from nmrgnn_amd._lib import ptr
-    monkeypatch.delenv("NG_KNN", raising=False)
-    dev = gpu_device
-    keys = _ragged_keys(K, steps)
+    keys = _ragged_keys(K, steps, boxed)
     sizes, gp, pos, kind_host, box, kind, gp_dev = _ragged_inputs(dev, keys)
     assert 64 * (steps // 16 - 1) * 16 < max(sizes) <= 64 * steps
     N = int(gp[-1])
@@ -405,10 +403,24 @@ def test_ragged_knn(gpu_device, monkeypatch, K, steps):
     ed = torch.full((N, K), float("nan"), device=dev)
     inv = torch.full((N,), float("nan"), device=dev)
     ctx = _ctx()
-    ctx.check(ctx.lib.ng_knn_graph_ragged_pbc(ctx.handle, _stream(dev), len(keys), N, K, SCALE, ptr(pos), ptr(gp_dev),
-                                              C.c_void_p(gp.ctypes.data), max(sizes), ptr(box), ptr(kind),
-                                              C.c_void_p(kind_host.ctypes.data), ptr(nl), ptr(ed), ptr(inv)), "knn_ragged_pbc")
-    torch.cuda.synchronize()
+
+    def call():
+        if boxed:
+            ctx.check(ctx.lib.ng_knn_graph_ragged_pbc(ctx.handle, _stream(dev), len(keys), N, K, SCALE, ptr(pos), ptr(gp_dev),
+                                                      C.c_void_p(gp.ctypes.data), max(sizes), ptr(box), ptr(kind),
+                                                      C.c_void_p(kind_host.ctypes.data), ptr(nl), ptr(ed), ptr(inv)),
+                      "knn_ragged_pbc")
+        else:
+            assert (kind_host == -1).all()
+            ctx.check(ctx.lib.ng_knn_graph_ragged(ctx.handle, _stream(dev), len(keys), N, K, SCALE, ptr(pos), ptr(gp_dev),
+                                                  C.c_void_p(gp.ctypes.data), max(sizes), ptr(nl), ptr(ed), ptr(inv)),
+                      "knn_ragged")
+        torch.cuda.synchronize()
+
+    # the scope says which displacement policy the kernels were built with: DispPer behind _pbc, DispOpen behind the open entry
+    _, names = _scopes(call)
+    scope, other = ("knn_graph_ragged_pbc", "knn_graph_ragged") if boxed else ("knn_graph_ragged", "knn_graph_ragged_pbc")
+    assert scope in names and other not in names and "knn_cells_query" not in names, names
     nl, ed, inv = nl.cpu().numpy(), ed.cpu().numpy(), inv.cpu().numpy()
     for g, key in enumerate(keys):
         q8, box8 = _frame_of(key)
@@ -420,6 +432,23 @@ def test_ragged_knn(gpu_device, monkeypatch, K, steps):
         np.testing.assert_array_equal(nl[sl], want[0], err_msg=f"nlist, structure {g} (n={sizes[g]})")
         np.testing.assert_array_equal(ed[sl], want[1], err_msg=f"edges, structure {g} (n={sizes[g]})")
         np.testing.assert_array_equal(inv[sl], want[2], err_msg=f"inv_degree, structure {g} (n={sizes[g]})")
+
+
+@pytest.mark.parametrize("steps", [16, 32, 48, 64], ids=lambda v: f"wave_per_row_steps{v}")
+@pytest.mark.parametrize("K", [16, 40], ids=["thread_per_row_kmax16-K16", "thread_per_row_kmax64-K40"])
+def test_ragged_knn(gpu_device, monkeypatch, K, steps):
+    """knn_ragged_kernel (structures up to 256 atoms) and knn_ragged_wave_kernel (257 .. 4096, its template sized by the largest
+    structure) through ng_knn_graph_ragged_pbc"""
+    monkeypatch.delenv("NG_KNN", raising=False)
+    _run_ragged_knn(gpu_device, K, steps, True)
+
+
+@pytest.mark.parametrize("boxed", [True, False], ids=["pbc_entry", "open_entry"])
+def test_ragged_knn_kmax32(gpu_device, monkeypatch, boxed):
+    """K = 17: the 32-slot lists of knn_ragged_kernel for both displacement policies; the open entry point with a largest
+    structure of 2100 atoms also runs the open knn_ragged_wave_kernel of 48 steps"""
+    monkeypatch.delenv("NG_KNN", raising=False)
+    _run_ragged_knn(gpu_device, 17, 48, boxed)
 
 
 def test_ragged_cutoff(gpu_device, monkeypatch):

@@ -155,7 +155,7 @@ def _dist2(dx, dy, dz):
 
 
 def _chain_f32(q8, rows, box8, tric, reach=None):
-    """the squared distances of knn_dist2 after DispOpen / DispOrtho / DispTric, in NumPy float32.  ``reach``: (nk, nj, ni) of
+    """the squared distances of pbc_dist2 after DispOpen / DispOrtho / DispTric, in NumPy float32.  ``reach``: (nk, nj, ni) of
     DispTric's image search instead of the reach DispTric::load works out from the box"""
     p = R.positions_f32(q8)
     dx, dy, dz = [(p[None, :, a] - p[rows, None, a]).astype(F32) for a in range(3)]
