@@ -217,7 +217,8 @@ int ng_edge_mlp_bwd_live(ng_ctx*, void* stream, int64_t n_slots, int H, int E, i
  *   recomputed from d_eff: no tape).  perm == n_live == NULL: every slot in slot order, d_src / d_eff [n_slots]; otherwise the
  *   live view of ng_edge_mlp_fwd_live (d_src / d_eff compacted, slot of row r = perm[r], rows >= *n_live dead).  de, J_out
  *   [n_slots][E] and dd_out [n_slots] in slot layout; dead slots (d_src <= 0) get exactly 0.  J_out may be NULL.  No atomics:
- *   bitwise deterministic.  H % 16 == 0, H <= 512, 1 <= E <= 256, 2 <= Le <= 6, any activation code.
+ *   bitwise deterministic.  H % 16 == 0, H <= 512, 1 <= E <= 256, 2 <= Le <= 6, any activation code.  *n_live < 0 (the
+ *   convention of _fwd_live / _bwd_live): the launch has nothing to do and returns at once, J_out and dd_out untouched.
  * ng_positions_grad / _csr: dpos [N][3] (N = G*n, batch-global rows) = sum over the live slots (i -> j) of
  *   dd * scale * (r_i - r_j) / |r_i - r_j| on atom i and its negative on atom j, the gradient of a function of the edges
  *   (edges = |r_i - r_j| * scale, ng_knn_graph / ng_cutoff_fill) with respect to the positions pos [N][3] at fixed lists.
@@ -573,7 +574,14 @@ int ng_head_loss_reduce(ng_ctx*, void* stream, const float* partial, int blocks,
  *   ng_edge_table_interp   e_out[i][c] = m_i sum_k w_k(d_i) e_tab[i0 + k][c]   (E <= 8, T * E <= 16384: T = 2048 for E > 4); skipped on gate[0]
  *   ng_edge_table_scatter  de_tab[t][c] = sum_i m_i w_k(d_i) de[i][c] over the stencils that contain t, rows T .. rows_out-1
  *                          of de_tab zeroed (the midpoint rows of the table's backward); writes range[2].  Terms rounded to
- *                          q = 2^(ex - sh), max|de| < 2^ex, sh = 38 - max(0, ceil(log2 n) - 24); a non-finite live de: NaN rows */
+ *                          q = 2^(ex - sh), max|de| < 2^ex, sh = 38 - max(0, ceil(log2 n) - 24); a non-finite live de: NaN rows
+ * INPUT GRADIENT of the table path.  J = d f_W / d d is a function of the same scalar: the caller tabulates it with
+ * ng_edge_mlp_dinput (J_out) on the table's 2T rows, guards it with ng_edge_table_check (e_all = the J rows, prev = the value
+ * gate of the call: one gate word says "per edge" for either reason) and launches ng_edge_mlp_dinput with n_live = &gate[1] and
+ * ng_edge_table_dinput with the gate: exactly one of the two writes dd.
+ *   ng_edge_table_dinput   dd_out[i] = m_i sum_c de[i][c] sum_k w_k(d_i) j_tab[i0 + k][c]   (limits of ng_edge_table_interp, the same
+ *                          stencil); de [n][E] read as whole rows (even E: de 16-byte aligned); dead slots get +0 whatever their de
+ *                          holds; gate != NULL and gate[0] != 0: returns at once, dd_out untouched.  No atomics: deterministic. */
 int ng_edge_table_range(ng_ctx*, void* stream, int64_t n, int E, const float* d_src, const float* d_eff, const int32_t* pos,
                         const float* de, float pad, float* range);
 int ng_edge_table_points(ng_ctx*, void* stream, int T, int midpoints, const float* range, float* d_tab, float* ones, int32_t* perm);
@@ -583,6 +591,9 @@ int ng_edge_table_interp(ng_ctx*, void* stream, int64_t n, int E, int T, const f
                          const int32_t* pos, const float* range, const float* e_tab, const int32_t* gate, float* e_out);
 int ng_edge_table_scatter(ng_ctx*, void* stream, int64_t n, int E, int T, int rows_out, const float* d_src, const float* d_eff,
                           const int32_t* pos, float* range, const float* de, float* de_tab);
+int ng_edge_table_dinput(ng_ctx*, void* stream, int64_t n, int E, int T, const float* d_src, const float* d_eff,
+                         const int32_t* pos, const float* range, const float* j_tab, const int32_t* gate, const float* de,
+                         float* dd_out);
 
 /* ---- training: NameLoss (s = 1), nmrgnn/losses.py:30-39, batched over graphs -----------------
  *   loss = mean_g  sum_{i in g} w_i (y_i - pred_i)^2 / sum_{i in g} w_i   (divide_no_nan)

@@ -239,6 +239,64 @@ __global__ __launch_bounds__(ET_WIDE) void et_interp_kernel(int64_t n, int T, co
   }
 }
 
+// the table path's input gradient: dd[i] = m_i * sum_c de[i][c] * J_i[c], J_i[c] = sum_k w_k(d_i) j_tab[i0 + k][c] — the Jacobian
+// d f_W / d d, tabulated on the same T points by ng_edge_mlp_dinput (J_out) and interpolated with the stencil of e.  (The
+// derivative of the interpolant of e would divide the table's own fp32 noise by h: DESIGN 7.11.)  The table (T x E floats) sits
+// in LDS; de is read as whole rows.  J_i in the order of et_interp_kernel, then the dot in column order: no atomics, the same
+// bits on every launch.  A dead slot gets +0 and its de row is not read.
+template <int EC>
+__device__ __forceinline__ void et_load_row(const float* __restrict__ p, float (&g)[EC]) {
+  if constexpr (EC % 4 == 0) {
+#pragma unroll
+    for (int q = 0; q < EC / 4; ++q) {
+      const float4 v = reinterpret_cast<const float4*>(p)[q];
+      g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
+    }
+  } else if constexpr (EC % 2 == 0) {
+#pragma unroll
+    for (int q = 0; q < EC / 2; ++q) {
+      const float2 v = reinterpret_cast<const float2*>(p)[q];
+      g[2 * q] = v.x; g[2 * q + 1] = v.y;
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < EC; ++c) g[c] = p[c];
+  }
+}
+template <int EC>
+__global__ __launch_bounds__(ET_WIDE) void et_dinput_kernel(int64_t n, int T, const float* __restrict__ d_src,
+                                                           const float* __restrict__ d_eff, const int32_t* __restrict__ pos,
+                                                           const float* __restrict__ range, const float* __restrict__ j_tab,
+                                                           const int32_t* __restrict__ gate, const float* __restrict__ de,
+                                                           float* __restrict__ dd_out) {
+  extern __shared__ float et_s[];
+  if (gate && gate[0] != 0) return;      // the guard is up: the per-edge launch has written dd
+  for (int t = threadIdx.x; t < T * EC; t += ET_WIDE) et_s[t] = j_tab[t];
+  __syncthreads();
+  float lo, inv_h, h;
+  et_geom(range, T, lo, inv_h, h);
+  for (int64_t i = (int64_t)blockIdx.x * ET_WIDE + threadIdx.x; i < n; i += (int64_t)gridDim.x * ET_WIDE) {
+    float s = 0.f;
+    if (d_src[i] > 0.f) {
+      float g[EC];
+      et_load_row<EC>(de + i * EC, g);
+      int i0;
+      float w[4];
+      et_stencil(d_eff[pos ? pos[i] : i], lo, inv_h, T, i0, w);
+      float r[EC];
+#pragma unroll
+      for (int c = 0; c < EC; ++c) r[c] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < EC; ++c) r[c] = fmaf(w[k], et_s[(i0 + k) * EC + c], r[c]);
+#pragma unroll
+      for (int c = 0; c < EC; ++c) s = fmaf(g[c], r[c], s);
+    }
+    dd_out[i] = s;
+  }
+}
+
 // adjoint: table[i0 + k][c] += w_k * m_i * de[i][c], in 64-bit fixed point (quantum q = 2^(ex - sh), see the top of the file),
 // per workgroup in LDS, partial tables to memory.  Nothing to do when max |de| is not finite (the final pass writes NaN)
 template <int EC>
@@ -369,6 +427,28 @@ extern "C" int ng_edge_table_interp(ng_ctx* ctx, void* stream, int64_t n, int E,
 #define NG_ETI(EC) case EC: hipLaunchKernelGGL((et_interp_kernel<EC>), dim3(nb), dim3(ET_WIDE), lds, st, n, T, d_src, d_eff, pos, range, e_tab, gate, e_out); break;
     NG_ETI(1) NG_ETI(2) NG_ETI(3) NG_ETI(4) NG_ETI(5) NG_ETI(6) NG_ETI(7) NG_ETI(8)
 #undef NG_ETI
+  }
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}
+
+extern "C" int ng_edge_table_dinput(ng_ctx* ctx, void* stream, int64_t n, int E, int T, const float* d_src, const float* d_eff,
+                                    const int32_t* pos, const float* range, const float* j_tab, const int32_t* gate, const float* de,
+                                    float* dd_out) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, E >= 1 && E <= ET_EMAX && T >= 8 && (size_t)T * E * 4 <= 64 * 1024, "edge_table_dinput: E <= 8, table <= 64 KB");
+  NG_REQUIRE(ctx, n >= 0, "edge_table_dinput: slot count >= 0");
+  if (n == 0) return NG_OK;
+  NG_REQUIRE(ctx, d_src && d_eff && range && j_tab && de && dd_out, "edge_table_dinput: arguments");
+  NG_REQUIRE(ctx, E % 2 != 0 || ((uintptr_t)de & 15) == 0, "edge_table_dinput: de 16-byte aligned (even E: rows are loaded as vectors)");
+  hipStream_t st = (hipStream_t)stream;
+  const int nb = std::max(1, (int)std::min<int64_t>(cdiv(n, ET_WIDE), (int64_t)ctx->num_cu));
+  const size_t lds = (size_t)T * E * 4;
+  ProfScope ps(ctx, st, "edge_table_dinput");
+  switch (E) {
+#define NG_ETD(EC) case EC: hipLaunchKernelGGL((et_dinput_kernel<EC>), dim3(nb), dim3(ET_WIDE), lds, st, n, T, d_src, d_eff, pos, range, j_tab, gate, de, dd_out); break;
+    NG_ETD(1) NG_ETD(2) NG_ETD(3) NG_ETD(4) NG_ETD(5) NG_ETD(6) NG_ETD(7) NG_ETD(8)
+#undef NG_ETD
   }
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;

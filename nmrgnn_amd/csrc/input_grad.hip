@@ -80,7 +80,10 @@ __global__ __launch_bounds__(DI_THREADS) void edge_dinput_kernel(
   const int l15 = lane & 15, l4 = lane >> 4;
   const int HB = H / 16;
   int64_t nl = n_rows;
-  if (perm) nl = std::min<int64_t>(std::max(*n_live, 0), n_rows);
+  if (perm) {
+    if (*n_live < 0) return;      // nothing to do (a gate of the edge-function tables hands the call to the table): J_out, dd_out stay
+    nl = std::min<int64_t>(*n_live, n_rows);
+  }
   const int64_t n_tiles = (n_rows + TR - 1) / TR;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t r0 = tile * TR;

@@ -58,7 +58,7 @@ def edge_path(edge_table, use_live_edges, live_kernels, E, n_edges, min_edges, i
 class Tape:
     """activations kept between forward(training=True) and backward()"""
     __slots__ = ("batch", "d_eff", "z_save", "z_layout", "e", "h", "A", "S", "fx", "g", "drop_mask",
-                 "peaks", "edge_path", "live", "table", "loss", "dpeaks", "dg", "head_partial")
+                 "peaks", "edge_path", "live", "table", "loss", "dpeaks", "dg", "head_partial", "inputs_only")
 
 
 class Engine:
@@ -131,6 +131,15 @@ class Engine:
         self.edge_table_min_edges = 262144    # below, the table's extra launches (range, check, gated per-edge launch, interpolation:
                                               # ~60 us) cost more than the per-edge MLP itself (7lgi, one 44 K-edge frame per call: 0.161 against 0.154 ms)
         self.edge_table_force_fallback = False   # tests: raise the guard whatever the check finds (tol = -1)
+        # OPT-IN (NG_EDGE_GRAD_TABLE=1): backward(edge_grad=) on a tape of the table path interpolates a table of the edge
+        # Jacobian J = d f_W / d d (ng_edge_mlp_dinput's J_out on the table's 2T rows, ng_edge_table_dinput per edge) instead of
+        # re-evaluating the MLP in forward mode on every edge.  Guarded like the table of e: where the cubic interpolant of J
+        # misses the midpoints by more than ``edge_grad_table_tol`` x max |J| (a relu edge MLP: J has kinks), or the value guard
+        # of the call was up, the SAME call is answered per edge.  Off: one ng_edge_mlp_dinput launch on every path.
+        self.edge_grad_table = os.environ.get("NG_EDGE_GRAD_TABLE", "0") == "1"
+        self.edge_grad_table_tol = 6.7e-6     # bound on |interpolant - J| at the midpoints, relative to max |J| of the table: four times the
+                                              # largest floor of the forward-mode fp32 J measured (1.67e-6: DESIGN 7.11)
+        self._jgate = None                    # the gate words of the last backward's J check (edge_grad_table_report)
         self._wgen = 0                        # bumped whenever the weights change: a table kept over calls (frozen weights)
         self._table_cache = None
         # the row count of the table's own MLP launches (2T: the table and its midpoints), a device word the live kernels read
@@ -182,6 +191,9 @@ class Engine:
     def forward(self, batch: GraphBatch, training=False, noise=None, dropout_mask=None, seed=0, keep_tape=None, loss=None):
         """peaks[N].  training=True keeps the tape for backward(); ``keep_tape=True`` keeps it for an inference-mode
         forward too (no noise, no dropout — what autograd through ``model(g, training=False)`` differentiates).
+        ``keep_tape="inputs"``: a tape for ``backward(param_grad=False)`` only — the edge MLP keeps no activations (its
+        input gradient recomputes them, or reads the Jacobian table), so with frozen weights the edge-function table of an
+        earlier call is reused; ``backward(param_grad=True)`` on such a tape raises.
         ``noise`` (xi[N,K], standard normal) / ``dropout_mask`` ([N,F/2], values 0 or 1/keep) may be
         supplied explicitly (parity tests); otherwise they are drawn on the GPU from ``seed``.
         ``loss = (y, w, grad_weight)``: the L2 NameLoss (``loss_l2``) of the peaks is taken inside the forward —
@@ -190,6 +202,11 @@ class Engine:
         other reductions (``ng_head_loss_bwd``; ``fuse_head_loss = False`` / NG_HEAD_LOSS=0: three calls)."""
         if loss is not None and not (training if keep_tape is None else keep_tape):
             raise ValueError("forward(loss=...) needs a tape (training=True)")
+        if isinstance(keep_tape, str):
+            if keep_tape != "inputs":
+                raise ValueError(f"forward: keep_tape is True, False, None or \"inputs\", got {keep_tape!r}")
+            if loss is not None:
+                raise ValueError("forward(loss=...) forms parameter gradients; keep_tape=\"inputs\" keeps no tape for them")
         if not (self._frozen or self.cache_images):
             return self._forward(batch, training, noise, dropout_mask, seed, keep_tape, loss)
         self._ck(self.lib.ng_weights_frozen(self.ctx.handle, self._id), "ng_weights_frozen")
@@ -200,6 +217,8 @@ class Engine:
 
     def _forward(self, batch, training, noise, dropout_mask, seed, keep_tape=None, loss=None):
         tape = bool(training) if keep_tape is None else bool(keep_tape)
+        inputs_only = isinstance(keep_tape, str)      # "inputs": the node side keeps its tape, the edge MLP none
+        edge_tape = tape and not inputs_only
         lib, h, st = self.lib, self.ctx.handle, self._st()
         P = self.params
         N, K, F, E, H = batch.N, batch.K, self.F, self.E, self.H
@@ -236,7 +255,7 @@ class Engine:
                          "ng_add_scaled")
         # the table of the edge function and the guard's verdict — before the per-edge launch, which on the "table" path runs
         # over gate[1] rows: none unless the guard is up
-        table = self._edge_table_build(batch, live, d_eff, tape, training) if path in ("table", "table_host") else None
+        table = self._edge_table_build(batch, live, d_eff, edge_tape, training) if path in ("table", "table_host") else None
         if path == "table_host" and table is None:      # the guard, read on the host, is up
             path = "slots"
         if path == "table":
@@ -244,7 +263,7 @@ class Engine:
         e = self._new(ne, E)
         z_save, z_layout = None, 0
         if path != "table_host":
-            z_save, z_layout = self._edge_mlp_fwd(ne, d_src, d_eff, e, tape, perm, rows)
+            z_save, z_layout = self._edge_mlp_fwd(ne, d_src, d_eff, e, edge_tape, perm, rows)
         if table is not None:       # every slot from the table — unless the device guard is up: then the launch returns at once
             self._ck(lib.ng_edge_table_interp(h, st, ne, E, table["T"], ptr(batch.edges), ptr(d_eff), ptr(pos),
                                               ptr(table["rng"]), ptr(table["e_all"]), ptr(table["gate"]), ptr(e)),
@@ -339,6 +358,7 @@ class Engine:
             tp.batch, tp.d_eff, tp.z_save, tp.e = batch, d_eff, z_save, e
             tp.z_layout = z_layout
             tp.edge_path, tp.live, tp.table = path, live, table
+            tp.inputs_only = inputs_only
             tp.h, tp.A, tp.S, tp.fx, tp.g, tp.drop_mask, tp.peaks = hs, As, Ss, fx, g, mask, peaks
             self.tape = tp
         return peaks
@@ -399,8 +419,9 @@ class Engine:
         RBF (noise already added when training), in the compacted row order of the live view ``live``.
         ``live`` None: the host-guarded table of an edge shape without the fused kernels — the every-slot MLP on the 2T rows,
         and the guard's verdict read on the host; None when the guard is up.
-        With a live view, frozen weights and no tape the table of an earlier call is reused while the weights stay the same:
-        then only the call's distance range is checked against the table's."""
+        With a live view, frozen weights and no edge tape (``tape``: that of the edge MLP — none for keep_tape="inputs") the
+        table of an earlier call is reused while the weights stay the same: then only the call's distance range is checked
+        against the table's."""
         lib, h, st = self.lib, self.ctx.handle, self._st()
         pos, n_live = (None, None) if live is None else (live[1], live[3])
         ne, E, T = batch.n_edges, self.E, self._table_points()
@@ -417,7 +438,7 @@ class Engine:
             c = self._table_cache
             self._ck(lib.ng_edge_table_check(h, st, T, E, None, 0.0, ptr(c["rng"]), ptr(rng), ptr(n_live), 2 * T,
                                              ptr(c["gate"]), ptr(gate)), "ng_edge_table_check")
-            return {"e_all": c["e_all"], "rng": c["rng"], "gate": gate, "T": T}
+            return {"e_all": c["e_all"], "rng": c["rng"], "gate": gate, "T": T, "kept": c, "cover": rng}
         d_tab, ones = self._new(2 * T), self._new(2 * T)
         perm_tab = None if live is None else torch.empty(2 * T, dtype=torch.int32, device=self.device)
         self._ck(lib.ng_edge_table_points(h, st, T, 1, ptr(rng), ptr(d_tab), ptr(ones), ptr(perm_tab)), "ng_edge_table_points")
@@ -428,10 +449,12 @@ class Engine:
                  "ng_edge_table_check")
         if live is None and int(gate[0].item()) != 0:      # the host read of the guard: the one synchronisation of "table_host"
             return None
+        kept = None
         if reuse:
-            self._table_cache = {"key": (self._wgen, T, E), "e_all": e_all, "rng": rng, "gate": gate}
+            kept = self._table_cache = {"key": (self._wgen, T, E), "e_all": e_all, "rng": rng, "gate": gate}
+        # "kept": the entry of _table_cache this call's table is (its Jacobian table is kept beside it); "cover": the call's range
         return {"e_all": e_all, "rng": rng, "gate": gate, "T": T, "d_tab": d_tab, "ones": ones, "perm_tab": perm_tab,
-                "z_tab": z_tab, "z_layout": z_layout}
+                "z_tab": z_tab, "z_layout": z_layout, "kept": kept, "cover": rng}
 
     def _edge_table_backward(self, tp, de, grads):
         """the table's share of the edge-weight gradients, into ``grads``: de scattered onto the table's points (the exact
@@ -463,7 +486,8 @@ class Engine:
         trainer launches the node-side all-reduce there, overlapping the edge-MLP backward).
         ``edge_grad``: a float32 device tensor shaped like ``batch.edges``, OVERWRITTEN with dL/d(edges) — one
         ng_edge_mlp_dinput launch behind the rest, from the tape's distances, de and the current weights; exact on every
-        edge path (the table's included: the derivative is of the edge function itself).  In training mode it is the
+        edge path (the table's included: the derivative is of the edge function itself).  With ``edge_grad_table`` on, a tape
+        of the table path interpolates the guarded table of the Jacobian instead (``_edge_dinput``).  In training mode it is the
         gradient with respect to the un-noised input (d d_eff / d edges = 1).  params.grad is the same bits either way.
         ``param_grad=False`` (needs ``edge_grad``): input gradients only — the head, FC-block and MPLayer backward get NULL
         weight-gradient outputs (include/nmrgnn_hip.h: no weight-gradient products, partials or queued sums are formed), and
@@ -486,6 +510,9 @@ class Engine:
         tp = self.tape
         if tp is None:
             raise RuntimeError("backward() without forward(training=True)")
+        if tp.inputs_only and param_grad:
+            raise RuntimeError("backward(param_grad=True) on a tape of forward(keep_tape=\"inputs\"): the edge MLP kept no "
+                               "activations; call backward(param_grad=False, edge_grad=...)")
         lib, h, st = self.lib, self.ctx.handle, self._st()
         # the seven second-stage sums of the node-side weight gradients (head, FC block, MPLayers, embedding) are queued
         # and run as ONE launch before the node gradients are handed on (ng_defer_reductions: same bits, ~45 us less)
@@ -601,15 +628,77 @@ class Engine:
         """dL/d(edges) into ``out`` (slot layout): de . de/dd per edge (ng_edge_mlp_dinput), over the live view where the
         forward had one (the per-edge "live" path and the device-guarded table), over every slot otherwise"""
         b = tp.batch
-        W, B = self._edge_weights()
         if tp.live is not None:
             perm, _, d_src, n_live = tp.live
         else:
             perm = n_live = None
             d_src = b.edges.reshape(-1)
-        self._ck(self.lib.ng_edge_mlp_dinput(self.ctx.handle, self._st(), b.n_edges, self.H, self.E, self.Le, self.fc_act,
-                                             ptr(d_src), ptr(tp.d_eff), ptr(perm), ptr(n_live), ptr(self.centers), self.gap,
-                                             ptr_array(W), ptr_array(B), ptr(de), None, ptr(out)), "ng_edge_mlp_dinput")
+        if not (self.edge_grad_table and tp.table is not None and tp.edge_path in ("table", "table_host")):
+            self._jgate = None
+            self._edge_mlp_dinput(b.n_edges, d_src, tp.d_eff, perm, n_live, de, None, out)
+            return
+        # the table path: the Jacobian table and its gate; then the per-edge launch over jgate[1] rows (skipped unless the guard
+        # is up) and the interpolation (skipped when it is) — one of the two writes ``out``
+        J_all, rng, jgate = self._edge_jacobian_table(tp)
+        self._jgate = jgate
+        lib, h, st = self.lib, self.ctx.handle, self._st()
+        if tp.edge_path == "table":
+            self._edge_mlp_dinput(b.n_edges, d_src, tp.d_eff, perm, jgate[1:], de, None, out)
+        elif int(jgate[0].item()) != 0:      # "table_host": the guard is read on the host, one of the two launches is issued
+            self._edge_mlp_dinput(b.n_edges, d_src, tp.d_eff, None, None, de, None, out)
+            return
+        self._ck(lib.ng_edge_table_dinput(h, st, b.n_edges, self.E, tp.table["T"], ptr(b.edges), ptr(tp.d_eff),
+                                          ptr(None if tp.live is None else tp.live[1]), ptr(rng), ptr(J_all), ptr(jgate), ptr(de),
+                                          ptr(out)), "ng_edge_table_dinput")
+
+    def _edge_mlp_dinput(self, n, d_src, d_eff, perm, n_live, de, J_out, out):
+        W, B = self._edge_weights()
+        self._ck(self.lib.ng_edge_mlp_dinput(self.ctx.handle, self._st(), n, self.H, self.E, self.Le, self.fc_act,
+                                             ptr(d_src), ptr(d_eff), ptr(perm), ptr(n_live), ptr(self.centers), self.gap,
+                                             ptr_array(W), ptr_array(B), ptr(de), ptr(J_out), ptr(out)), "ng_edge_mlp_dinput")
+
+    def _edge_jacobian_table(self, tp):
+        """(J_all [2T, E], the table's range, jgate) for the backward of a call that took the edge-function table: J = d f_W / d d
+        at the table's points and midpoints (ng_edge_mlp_dinput's J_out, exact: forward mode on the same rows as e_all) and the
+        gate of its check, chained to the value gate of the call — up when the value guard was up, the call's distances left
+        the table, J fails at the midpoints or is not finite.  A table kept over calls keeps J_all and its own gate (chained
+        to the kept value gate) beside e_all; later calls run the range-only form of the check."""
+        lib, h, st = self.lib, self.ctx.handle, self._st()
+        tb, E, T = tp.table, self.E, tp.table["T"]
+        n_live = None if tp.live is None else tp.live[3]
+        # (a forced fallback is this call's alone: its gate is not kept beside a table that later calls read)
+        c = None if self.edge_table_force_fallback else tb["kept"]
+        jgate = torch.empty(8, dtype=torch.int32, device=self.device)
+        if c is None or "J_all" not in c:
+            tol = -1.0 if self.edge_table_force_fallback else float(self.edge_grad_table_tol)
+            if "d_tab" in tb:
+                d_tab, ones, perm_tab = tb["d_tab"], tb["ones"], tb["perm_tab"]
+            else:       # a kept table: its points again, from its range
+                d_tab, ones = self._new(2 * T), self._new(2 * T)
+                perm_tab = None if tp.live is None else torch.empty(2 * T, dtype=torch.int32, device=self.device)
+                self._ck(lib.ng_edge_table_points(h, st, T, 1, ptr(tb["rng"]), ptr(d_tab), ptr(ones), ptr(perm_tab)),
+                         "ng_edge_table_points")
+            J_all, de0, dd0 = self._new(2 * T, E), torch.zeros(2 * T, E, dtype=torch.float32, device=self.device), self._new(2 * T)
+            self._edge_mlp_dinput(2 * T, ones, d_tab, perm_tab, None if perm_tab is None else self._rows_2t, de0, J_all, dd0)
+            own = jgate if c is None else torch.empty(8, dtype=torch.int32, device=self.device)
+            self._ck(lib.ng_edge_table_check(h, st, T, E, ptr(J_all), tol, ptr(tb["rng"]), None, ptr(n_live), 2 * T,
+                                             ptr(tb["gate"] if c is None else c["gate"]), ptr(own)), "ng_edge_table_check")
+            if c is None:
+                return J_all, tb["rng"], jgate
+            c["J_all"], c["jgate"] = J_all, own
+        self._ck(lib.ng_edge_table_check(h, st, T, E, None, 0.0, ptr(c["rng"]), ptr(tb["cover"]), ptr(n_live), 2 * T,
+                                         ptr(c["jgate"]), ptr(jgate)), "ng_edge_table_check")
+        return c["J_all"], c["rng"], jgate
+
+    def edge_grad_table_report(self):
+        """(guard up?, interpolation error of J at the midpoints, largest |J| of the table) of the J check of the last backward
+        (a call on a kept table reports the error and scale measured when its Jacobian table was built).  Reads device words:
+        synchronises; for tests and diagnostics.  Raises RuntimeError when the last backward took no Jacobian table."""
+        if self._jgate is None:
+            raise RuntimeError("edge_grad_table_report: the last backward took no Jacobian table (edge_grad_table off, no "
+                               "edge_grad, or a per-edge tape)")
+        g = self._jgate.cpu().numpy()
+        return bool(g[0]), float(g[4:6].view(np.float32)[0]), float(g[4:6].view(np.float32)[1])
 
     # ------------------------------------------------------------------ loss / optimiser
     def loss_l2(self, batch, y, w, peaks):

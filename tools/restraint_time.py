@@ -6,8 +6,10 @@ call:
   Engine.backward(edge_grad=) with param_grad True against False on the bench batch (512 graphs x 256 atoms, K = 16), per-edge
   and table edge paths (the forward with a tape is untimed);
   the restraint forms, replayed, one 7lgi frame and R = 8, no box: harmonic, flat-bottom, weighted replicas
-  (new weights staged every call), independent replicas, time-averaged.
-usage: python tools/restraint_time.py [--forms] [out.json]     (--forms: only the forms rows)"""
+  (new weights staged every call), independent replicas, time-averaged;
+  the Jacobian table of DESIGN 7.11: Engine.backward(edge_grad=, param_grad=False) on the bench batch's table path with
+  edge_grad_table off and on.
+usage: python tools/restraint_time.py [--forms | --table] [out.json]     (--forms / --table: only those rows)"""
 import json
 import os
 import sys
@@ -141,13 +143,43 @@ def forms_rows():
     return out
 
 
+def table_rows():
+    out = {}
+    eng = Engine(declare_gnn_space(HyperParameters(atom_feature_size=64)), 10, device=dev, seed=1234)
+    b = synth.make_batch(512, 256, 16, 10, 0.05, seed=42)
+    gb = GraphBatch(b["atoms"], b["nlist"], b["edges"], b["inv_degree"], graph_ptr=b["graph_ptr"], device=dev)
+    dpeaks = torch.from_numpy(np.random.default_rng(2).standard_normal(gb.N).astype(np.float32)).to(dev)
+    dedges = torch.empty(gb.edges.shape, dtype=torch.float32, device=dev)
+    row = {}
+    for on in (False, True):
+        eng.edge_grad_table = on
+        ts = []
+        for _ in range(22):
+            eng.forward(gb, training=False, keep_tape=True)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            eng.backward(dpeaks, edge_grad=dedges, param_grad=False)
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        row[f"edge_grad_table_{on}_ms"] = float(np.median(ts[2:]))
+    row["j_guard"] = list(eng.edge_grad_table_report())
+    out["backward_bench_batch_table_path"] = row
+    print("table backward", row, flush=True)
+    return out
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--forms"]
+    flags = ("--forms", "--table")
+    args = [a for a in sys.argv[1:] if a not in flags]
     if "--forms" in sys.argv[1:]:
         res = {"restraint_forms_7lgi": forms_rows()}
+    elif "--table" in sys.argv[1:]:
+        res = {"jacobian_table": table_rows()}
     else:
         res = {"restraint_7lgi": restraint_rows(), "backward_bench_batch": backward_rows(),
-               "restraint_forms_7lgi": forms_rows()}
+               "restraint_forms_7lgi": forms_rows(), "jacobian_table": table_rows()}
     if args:
         with open(args[0], "w") as f:
             json.dump(res, f, indent=1)
