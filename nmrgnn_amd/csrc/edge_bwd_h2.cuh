@@ -12,17 +12,14 @@
 
 namespace ng {
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-#define HX_LDS(T) __attribute__((address_space(3))) T
-
 constexpr int HX_THREADS = 512;
 // Image geometry.  G images are read as rows (ds_read_b128: stride must be a multiple of 16 B; 272 B = 68 dwords
 // puts 16 consecutive rows on disjoint 4-bank slots) and as columns (transposing reads); the Z image only as
 // columns (stride 264 B: the 8-B piece writes of 32 rows then cost the minimum of 2 LDS cycles).  A transposing
 // read fetches 4 consecutive edges x 32 B per 16-lane group, and the LDS serves 32 lanes (two groups, the two 32-B
 // column blocks of a slab) per clock over 64 banks: the ROWS are stored permuted so that the 4 edges of a quad sit 16
-// banks apart (hx_prow_*: 4 rows of 272 B, 8 rows of 264 B) and the two groups interleave in 8-bank runs.  Measured
-// (tools/ubench/trbank2.hip, ns per wave read with 8 waves reading): 9.8 this way, 14.8 with the quad 8 banks apart
+// banks apart (h2_prow of h2_common.cuh: 4 rows of 272 B; hx_prow_z: 8 rows of 264 B) and the two groups interleave
+// in 8-bank runs.  Measured (tools/ubench/trbank2.hip, ns per wave read with 8 waves reading): 9.8 this way, 14.8 with the quad 8 banks apart
 // (the G images until late round 2), 27.3 unpermuted.
 constexpr int HX_ROWG = 272, HX_ROWZ = 264;
 constexpr int HX_PIECE_G = FTM * HX_ROWG, HX_PIECE_Z = FTM * HX_ROWZ;
@@ -35,14 +32,10 @@ constexpr int HX_LDS_BYTES = HX_IMGS + HX_MISC_FLOATS * 4;   // 140,544 of 163,8
 constexpr int HX_WS = 8;                     // log2 of the W^T scale
 constexpr float HX_WSCALE = (float)(1 << HX_WS), HX_WINV = 1.0f / (float)(1 << HX_WS);
 
-// physical row of edge e (0..63) in the Z image / in a G image
+// physical row of edge e (0..63) in the Z image (in a G image: h2_prow)
 __device__ __forceinline__ int hx_prow_z(int e) {
   const int hi = e >> 4, a = (e >> 2) & 3, b = e & 3;
   return 2 * (a + 4 * b) + (hi & 1) + 32 * (hi >> 1);
-}
-__device__ __forceinline__ int hx_prow_g(int e) {
-  const int hi = e >> 4, a = (e >> 2) & 3, b = e & 3;
-  return 16 * hi + 4 * b + a;
 }
 
 struct EdgeBwdH2Args {
@@ -102,24 +95,15 @@ __device__ __forceinline__ void hx_img_write_q(char* __restrict__ img, int row, 
   *reinterpret_cast<u32x2*>(p + FTM * ROWB) = u32x2{l0, l1};
 }
 
-// one MFMA operand (8 consecutive edges of this lane's column) = two transposing reads of 4 edges each; `step` is
-// the byte distance between the two quads' first rows
-__device__ __forceinline__ u32x4 hx_tr_frag(const char* p, int step) {
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((HX_LDS(s16x4)*)p);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((HX_LDS(s16x4)*)(p + step));
-  const u32x2 a = __builtin_bit_cast(u32x2, lo), b = __builtin_bit_cast(u32x2, hi);
-  return u32x4{a[0], a[1], b[0], b[1]};
-}
-
 struct HxDwFrags { u32x4 b[2], a0[2], a1[2]; };
 
-// operands of k-step ks (edges 16 ks .. 16 ks + 15): physical rows per hx_prow_z / hx_prow_g
+// operands of k-step ks (edges 16 ks .. 16 ks + 15): physical rows per hx_prow_z / h2_prow
 __device__ __forceinline__ void hx_dw_load(HxDwFrags& f, const char* zb, const char* g0, int ks) {
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
-    f.b[p] = hx_tr_frag(zb + p * HX_PIECE_Z + ((ks & 1) + 32 * (ks >> 1)) * HX_ROWZ, 2 * HX_ROWZ);
-    f.a0[p] = hx_tr_frag(g0 + p * HX_PIECE_G + 16 * ks * HX_ROWG, HX_ROWG);
-    f.a1[p] = hx_tr_frag(g0 + 64 + p * HX_PIECE_G + 16 * ks * HX_ROWG, HX_ROWG);
+    f.b[p] = h2_tr_frag(zb + p * HX_PIECE_Z + ((ks & 1) + 32 * (ks >> 1)) * HX_ROWZ, 2 * HX_ROWZ);
+    f.a0[p] = h2_tr_frag(g0 + p * HX_PIECE_G + 16 * ks * HX_ROWG, HX_ROWG);
+    f.a1[p] = h2_tr_frag(g0 + 64 + p * HX_PIECE_G + 16 * ks * HX_ROWG, HX_ROWG);
   }
 }
 

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(HX_THREADS, 1) void edge_bwd_h2_kernel(EdgeBwdH2Arg
   const int cn = tid & 127, rq = tid >> 7;              // dWo ownership
   const int row = 32 * zrt + l31;                       // this lane's edge row in the tile
   const int col0 = 32 * zk + 4 * half;                  // its columns: col0 + 8q + j
-  const int prz = hx_prow_z(row), prg = hx_prow_g(row); // where that row lives in the images
+  const int prz = hx_prow_z(row), prg = h2_prow(row); // where that row lives in the images
   const int E = a.E;
   // a NEGATIVE live row count: nothing to do and nothing to write — the reduction behind this launch then writes zero gradients
   // without reading the partials (the edge-function table's guard is down, edge_table.hip)

@@ -14,12 +14,21 @@
 // the same dP share it), so pieces cannot overflow and keep their bits whatever the loss scaling is; epilogues
 // multiply by 2^-8 / S.
 //
-// 256 threads = 4 waves, tile 128 rows x 256 columns (128 when N % 256 != 0), two workgroups per CU; per 32-wide k-step:
-//   W pieces: fragment-ordered image packed once per call, 32 / 16 KB per (column tile, k-step) copied to LDS by LDS-DMA;
-//   X pieces: each thread loads 16 consecutive floats of one row (prefetched one step ahead), splits them and writes
-//             the two piece planes [128][32 + 8] fp16;
-//   wave (n-half, m-half): 4 x 2 (2 x 2) blocks of 32 x 32, v_mfma_f32_32x32x16_f16, A = W^T pieces (rows n), B = X pieces
-//   (columns m), so a lane ends with 4 consecutive n of one row m: 16-byte stores.
+// Which kernel takes which shape (gx_launch, gemm_h2_dw).  Forward and dX: 256 threads = 4 waves, two workgroups per CU,
+// W as a fragment-ordered image packed once per call (cached), X split by the threads into two piece planes in LDS
+// (gx_request / gx_fill), v_mfma_f32_32x32x16_f16 with A = W^T pieces (rows n), B = X pieces (columns m), so a lane ends with 4
+// consecutive n of one row m (16-byte stores, gx_epilogue_block):
+//   gemm_h2_short_kernel  N % 256 == 0, K % 128 == 0 and fewer 128-row tiles than half the CUs (one molecule per call):
+//                         32 rows x 256 columns, W fragments from L2 into registers three k-halves ahead;
+//   gemm_h2_fwdr_kernel   N % 256 == 0 otherwise: 128 rows x 256 columns, W fragments from L2 into registers, X planes in a
+//                         two-stage ring;
+//   gemm_h2_fwd_kernel    N % 256 != 0 (N % 128 == 0): 128 rows x 128 columns, the 16 KB of W pieces of a (column tile, k-step)
+//                         copied to LDS by LDS-DMA, wave (n-half, m-half) takes 2 x 2 blocks of 32 x 32.
+// dW (the contraction runs over the rows: both operands as piece images read by columns):
+//   gemm_h2_dw8_kernel    Kin % 256 == 0 and Nout % 256 == 0: 256 x 256 tiles, 512 threads, one workgroup per CU;
+//   gemm_h2_dw_kernel     otherwise (Kin % 128 == 0, Nout % 128 == 0): 128 x 128 tiles, 256 threads, two per CU.
+// The software-pipelined main loops are written out per kernel — their order of requests, fills, barriers and
+// sched_barriers is what was measured; the pieces they are made of are shared (below, h2_common.cuh).
 #include <algorithm>
 #include <cstdlib>
 #include <string>
@@ -36,13 +45,11 @@ namespace ng {
 constexpr int GX_BM = 128, GX_BN = 128, GX_BK = 32;
 constexpr int GX_XROW = 80;                       // bytes per row of an X piece plane (64 + 16: conflict-free b128 rows)
 constexpr int GX_XPLANE = GX_BM * GX_XROW;        // 10,240
-// NBW = 32-column blocks per wave (2 -> 128-column tiles, 4 -> 256-column tiles: half the barriers and X splits per MFMA)
-constexpr int gx_wchunk(int nbw) { return 2 * nbw * 2 * 2 * 1024; }   // [n-block][k-step of 16][piece][1 KB]
-constexpr int gx_lds(int nbw) { return 2 * GX_XPLANE + gx_wchunk(nbw); } // 36,864 / 53,248: two workgroups per CU
-constexpr float GX_WSCALE = 256.0f, GX_WINV = 1.0f / 256.0f;      // weight pieces are taken from 2^8 W
-
-// weight image: pack_bodies.cuh gx_img (PK_GX), [(ct * KT + kt)][nb][ks][p][lane][8 fp16], pieces of 2^8 W
-static_assert(GX_BK == pk::GXP_BK && GX_WSCALE == pk::GXP_WSCALE, "pack_bodies.cuh");
+// weight image: pack_bodies.cuh gx_img (PK_GX), [(ct * KT + kt)][nb][ks][p][lane][8 fp16], pieces of 2^8 W (pk::GXP_WSCALE);
+// nbw = 32-column blocks per wave (2 -> 128-column tiles, 4 -> 256-column tiles: half the barriers and X splits per MFMA)
+using pk::gxp_wchunk;                             // bytes per (column tile, k-step)
+static_assert(GX_BK == pk::GXP_BK, "pack_bodies.cuh");
+constexpr int GX_LDS = 2 * GX_XPLANE + gxp_wchunk(2);   // gemm_h2_fwd_kernel: 36,864, two workgroups per CU
 static int gx_image_kind(int trans, int nbw) { return 3 + 16 * trans + 32 * nbw; }       // cache kind of the image
 static PackJob gx_pack_job(int K, int N, int mode, int nbw, const float* W, void* img) {
   PackJob j;
@@ -227,47 +234,105 @@ __device__ __forceinline__ void gx_epilogue_block(const GxArgs& a, const f32x16 
     }
 }
 
-template <bool GRAD, int NBW>
-__global__ __launch_bounds__(256, 2) void gemm_h2_fwd_kernel(GxArgs a) {
-  constexpr int WCHUNK = gx_wchunk(NBW), BN = 64 * NBW;
-  extern __shared__ __attribute__((aligned(16))) char smem_gx[];
-  char* sX = smem_gx;                       // [2][128][80 B]
-  char* sW = smem_gx + 2 * GX_XPLANE;       // [2 NBW][2][2][1 KB]
-  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int nh = wave & 1, mh = wave >> 1;
-  // column tiles of a row tile on one XCD, consecutive in time (see gemm_h2_fwdr_kernel)
-  int bx = blockIdx.x, by = blockIdx.y;
+// ---- shared pieces of the tile kernels
+// 16 consecutive values of one row -> the two piece planes of an image (PLANE bytes apart): two 16-byte stores per plane
+template <int PLANE>
+__device__ __forceinline__ void gx_split16(char* d, const float (&v)[16]) {
+  unsigned h[8], l[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) split2_pair(v[2 * j], v[2 * j + 1], h[j], l[j]);
+  *reinterpret_cast<u32x4*>(d) = u32x4{h[0], h[1], h[2], h[3]};
+  *reinterpret_cast<u32x4*>(d + 16) = u32x4{h[4], h[5], h[6], h[7]};
+  *reinterpret_cast<u32x4*>(d + PLANE) = u32x4{l[0], l[1], l[2], l[3]};
+  *reinterpret_cast<u32x4*>(d + PLANE + 16) = u32x4{l[4], l[5], l[6], l[7]};
+}
+
+// Workgroup -> (row tile, column tile) of the forward / dX grids.  The column tiles of a row tile read the same X rows; dealt
+// to the XCDs by linear id, the plain (x, y) order puts them rounds apart and on different L2s.  With a multiple of 8 row
+// tiles, ids r, r + 8, r + 16, ... (one XCD, consecutive in time) take the column tiles of row tile 8 q + r.
+__device__ __forceinline__ void gx_tile(int& bx, int& by) {
+  bx = blockIdx.x; by = blockIdx.y;
   if (gridDim.y > 1 && (gridDim.x & 7) == 0) {
     const int L = blockIdx.x + gridDim.x * blockIdx.y;
     const int r = L & 7, q = L >> 3;
     by = q % gridDim.y;
     bx = (q / gridDim.y) * 8 + r;
   }
+}
+
+// ---- a thread's slice of the X tiles of the forward / dX kernels: 16 consecutive floats of one row per tile (xp) and, under
+// GRAD with an activation, of Sin (sp, else nullptr), requested as four float4 each and later unpacked, taken through the
+// GRAD prologue  X := X * act'(Sin) * rs_in[m] * S,  split and stored.
+// The scales of a call: rsi for the slice's row xrow (the prologue's row factor), oscale for the epilogue.
+struct GxScales { float oscale, rsi; };
+template <bool GRAD>
+__device__ __forceinline__ GxScales gx_scales(const GxArgs& a, int64_t xrow) {
+  const float gS = GRAD && a.gscale ? a.gscale[0] : 1.0f;          // power of two (gemm_grad_scale)
+  GxScales r;
+  r.oscale = pk::GXP_WINV * (GRAD && a.gscale ? a.gscale[1] : 1.0f);
+  r.rsi = gS * (GRAD && a.rs_in ? a.rs_in[xrow] : 1.0f);
+  return r;
+}
+// Plain loads: a dY row is re-read by every column tile, non-temporal loads measured 1.4x slower.  xp and sp come by
+// reference, as the kernels' lambdas used to capture them: by value (or as members of a struct that owns the slice) hipcc
+// tests sp once around the four loads and lays out the GRAD kernels differently — same instructions but for the branches,
+// and gemm_h2_fwdr_kernel<true> (mp_dA at the default width) measured 1 % slower, beyond the run-to-run spread.
+template <bool GRAD>
+__device__ __forceinline__ void gx_request(float4 (&xv)[4], float4 (&sv)[4], const float* const& xp, const float* const& sp,
+                                           int64_t koff) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    xv[i] = *reinterpret_cast<const float4*>(xp + koff + 4 * i);
+    if (GRAD && sp) sv[i] = *reinterpret_cast<const float4*>(sp + koff + 4 * i);
+  }
+}
+// into row xr, 16-column group xc of the piece planes at sX (ROWB bytes per row, PLANE between the planes)
+template <bool GRAD, int ROWB, int PLANE>
+__device__ __forceinline__ void gx_fill(const GxArgs& a, const float4 (&xv)[4], const float4 (&sv)[4], const float* sp, float rsi,
+                                        char* sX, int xr, int xc) {
+  float v[16] = {xv[0].x, xv[0].y, xv[0].z, xv[0].w, xv[1].x, xv[1].y, xv[1].z, xv[1].w,
+                 xv[2].x, xv[2].y, xv[2].z, xv[2].w, xv[3].x, xv[3].y, xv[3].z, xv[3].w};
+  if (GRAD) {
+    if (sp) {
+      const float sg[16] = {sv[0].x, sv[0].y, sv[0].z, sv[0].w, sv[1].x, sv[1].y, sv[1].z, sv[1].w,
+                            sv[2].x, sv[2].y, sv[2].z, sv[2].w, sv[3].x, sv[3].y, sv[3].z, sv[3].w};
+#pragma unroll
+      for (int j = 0; j < 16; ++j) v[j] *= act_grad_from_out(a.act_in, sg[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] *= rsi;
+  }
+  gx_split16<PLANE>(sX + xr * ROWB + 32 * xc, v);
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(256, 2) void gemm_h2_fwd_kernel(GxArgs a) {
+  constexpr int WCHUNK = gxp_wchunk(2);
+  extern __shared__ __attribute__((aligned(16))) char smem_gx[];
+  char* sX = smem_gx;                       // [2][128][80 B]
+  char* sW = smem_gx + 2 * GX_XPLANE;       // [4][2][2][1 KB]
+  const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int nh = wave & 1, mh = wave >> 1;
+  int bx, ct;
+  gx_tile(bx, ct);
   const int64_t m0 = (int64_t)bx * GX_BM;
-  const int ct = by;
   const int KT = a.K / GX_BK;
 
   // this thread's slice of the X tile: row tid >> 1, 16 floats at column 16 (tid & 1) of the k-step
   const int xr = tid >> 1, xh = tid & 1;
-  const float* xp = a.X + std::min<int64_t>(m0 + xr, a.M - 1) * a.K + 16 * xh;
-  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<char*>(a.Wimg), 0, (unsigned)((int64_t)(a.N / BN) * KT * WCHUNK), 0x00020000);
-
-  const float* sp = GRAD && a.Sin ? a.Sin + std::min<int64_t>(m0 + xr, a.M - 1) * a.K + 16 * xh : nullptr;
-  const float gS = GRAD && a.gscale ? a.gscale[0] : 1.0f;          // power of two (gemm_grad_scale)
-  const float oscale = GX_WINV * (GRAD && a.gscale ? a.gscale[1] : 1.0f);
-  const float rsi = gS * (GRAD && a.rs_in ? a.rs_in[std::min<int64_t>(m0 + xr, a.M - 1)] : 1.0f);
+  const int64_t xrow = std::min<int64_t>(m0 + xr, a.M - 1);
+  const float* xp = a.X + xrow * a.K + 16 * xh;
+  const float* sp = GRAD && a.Sin ? a.Sin + xrow * a.K + 16 * xh : nullptr;
+  const GxScales sc = gx_scales<GRAD>(a, xrow);
   float4 xv[4], sv[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    xv[i] = *reinterpret_cast<const float4*>(xp + 4 * i);
-    if (GRAD && sp) sv[i] = *reinterpret_cast<const float4*>(sp + 4 * i);
-  }
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<char*>(a.Wimg), 0, (unsigned)((int64_t)(a.N / GX_BN) * KT * WCHUNK), 0x00020000);
+  gx_request<GRAD>(xv, sv, xp, sp, 0);
 
-  f32x16 acc[NBW][2];
+  f32x16 acc[2][2];
 #pragma unroll
-  for (int j = 0; j < NBW; ++j)
+  for (int j = 0; j < 2; ++j)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -276,56 +341,28 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_fwd_kernel(GxArgs a) {
 #pragma unroll 1
   for (int kt = 0; kt < KT; ++kt) {
     NG_LDS_BARRIER();                       // the previous step's fragment reads are done
-    // W pieces of this step: one-KB wave copies, 2 NBW per wave
+    // W pieces of this step: one-KB wave copies, 4 per wave
 #pragma unroll
-    for (int c = 0; c < 2 * NBW; ++c) {
+    for (int c = 0; c < 4; ++c) {
       const int kb = wave + 4 * c;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)(sW + kb * 1024), 16,
                                                lane * 16, (ct * KT + kt) * WCHUNK + kb * 1024, 0, 0);
     }
     // X pieces: split the 16 prefetched values, two 16-B stores per plane
-    {
-      float v[16] = {xv[0].x, xv[0].y, xv[0].z, xv[0].w, xv[1].x, xv[1].y, xv[1].z, xv[1].w,
-                     xv[2].x, xv[2].y, xv[2].z, xv[2].w, xv[3].x, xv[3].y, xv[3].z, xv[3].w};
-      if (GRAD) {
-        if (sp) {
-          const float sg[16] = {sv[0].x, sv[0].y, sv[0].z, sv[0].w, sv[1].x, sv[1].y, sv[1].z, sv[1].w,
-                                sv[2].x, sv[2].y, sv[2].z, sv[2].w, sv[3].x, sv[3].y, sv[3].z, sv[3].w};
-#pragma unroll
-          for (int j = 0; j < 16; ++j) v[j] *= act_grad_from_out(a.act_in, sg[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] *= rsi;
-      }
-      unsigned h[8], l[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) split2_pair(v[2 * j], v[2 * j + 1], h[j], l[j]);
-      char* d = sX + xr * GX_XROW + 32 * xh;
-      *reinterpret_cast<u32x4*>(d) = u32x4{h[0], h[1], h[2], h[3]};
-      *reinterpret_cast<u32x4*>(d + 16) = u32x4{h[4], h[5], h[6], h[7]};
-      *reinterpret_cast<u32x4*>(d + GX_XPLANE) = u32x4{l[0], l[1], l[2], l[3]};
-      *reinterpret_cast<u32x4*>(d + GX_XPLANE + 16) = u32x4{l[4], l[5], l[6], l[7]};
-    }
+    gx_fill<GRAD, GX_XROW, GX_XPLANE>(a, xv, sv, sp, sc.rsi, sX, xr, xh);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's share of the W copies has landed
     NG_LDS_BARRIER();
     // next step's X slice, requested behind the wait so that its HBM latency hides under this step's MFMAs
     // (clamped k: the last prefetch re-reads the last step)
-    {
-      const int64_t koff = (int64_t)GX_BK * std::min(kt + 1, KT - 1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        xv[i] = *reinterpret_cast<const float4*>(xp + koff + 4 * i);
-        if (GRAD && sp) sv[i] = *reinterpret_cast<const float4*>(sp + koff + 4 * i);
-      }
-    }
+    gx_request<GRAD>(xv, sv, xp, sp, (int64_t)GX_BK * std::min(kt + 1, KT - 1));
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      u32x4 wa[NBW][2], xb[2][2];
+      u32x4 wa[2][2], xb[2][2];
 #pragma unroll
-      for (int j = 0; j < NBW; ++j)
+      for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-          wa[j][p] = *reinterpret_cast<const u32x4*>(sW + (((NBW * nh + j) * 2 + ks) * 2 + p) * 1024 + lane * 16);
+          wa[j][p] = *reinterpret_cast<const u32x4*>(sW + (((2 * nh + j) * 2 + ks) * 2 + p) * 1024 + lane * 16);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -333,22 +370,18 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_fwd_kernel(GxArgs a) {
           xb[i][p] = *reinterpret_cast<const u32x4*>(sX + p * GX_XPLANE + (32 * (2 * mh + i) + l31) * GX_XROW +
                                                      (16 * ks + 8 * half) * 2);
 #pragma unroll
-      for (int j = 0; j < NBW; j += 2)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) mma3_2a(wa[j], wa[j + 1], xb[i], acc[j][i], acc[j + 1][i]);
+      for (int i = 0; i < 2; ++i) mma3_2a(wa[0], wa[1], xb[i], acc[0][i], acc[1][i]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
 
-  // epilogue: lane holds, for row m = m0 + 32 (2 mh + i) + l31, columns n = BN ct + 32 (NBW nh + j) + 8 q + 4 half + (0..3)
+  // epilogue: lane holds, for row m = m0 + 32 (2 mh + i) + l31, columns n = 128 ct + 32 (2 nh + j) + 8 q + 4 half + (0..3)
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int64_t m = m0 + 32 * (2 * mh + i) + l31;
     if (m >= a.M) continue;
-    f32x16 blk[NBW];
-#pragma unroll
-    for (int j = 0; j < NBW; ++j) blk[j] = acc[j][i];
-    gx_epilogue_block<NBW>(a, blk, m, BN * ct + 32 * NBW * nh + 4 * half, oscale * (a.rowscale ? a.rowscale[m] : 1.0f));
+    const f32x16 blk[2] = {acc[0][i], acc[1][i]};
+    gx_epilogue_block<2>(a, blk, m, GX_BN * ct + 64 * nh + 4 * half, sc.oscale * (a.rowscale ? a.rowscale[m] : 1.0f));
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -370,65 +403,25 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_fwdr_kernel(GxArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_g4[];
   const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
   const int nq = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // Workgroup -> (row tile, column tile).  The column tiles of a row tile read the same X rows; dealt to the XCDs by linear
-  // id, the plain (x, y) order puts them rounds apart and on different L2s.  With a multiple of 8 row tiles, ids r, r + 8,
-  // r + 16, ... (one XCD, consecutive in time) take the column tiles of row tile 8 q + r.
-  int bx = blockIdx.x, by = blockIdx.y;
-  if (gridDim.y > 1 && (gridDim.x & 7) == 0) {
-    const int L = blockIdx.x + gridDim.x * blockIdx.y;
-    const int r = L & 7, q = L >> 3;
-    by = q % gridDim.y;
-    bx = (q / gridDim.y) * 8 + r;
-  }
+  int bx, ct;
+  gx_tile(bx, ct);
   const int64_t m0 = (int64_t)bx * GX_BM;
-  const int ct = by;
   const int KT = a.K / GX_BK;
-  constexpr int WCHUNK = gx_wchunk(4);
+  constexpr int WCHUNK = gxp_wchunk(4);
 
   // this thread's slice of an X tile: row tid >> 1, 16 floats at column 16 (tid & 1) of the k-step
   const int xr = tid >> 1, xh = tid & 1;
   const int64_t xrow = std::min<int64_t>(m0 + xr, a.M - 1);
   const float* xp = a.X + xrow * a.K + 16 * xh;
   const float* sp = GRAD && a.Sin ? a.Sin + xrow * a.K + 16 * xh : nullptr;
-  const float gS = GRAD && a.gscale ? a.gscale[0] : 1.0f;          // power of two (gemm_grad_scale)
-  const float oscale = GX_WINV * (GRAD && a.gscale ? a.gscale[1] : 1.0f);
-  const float rsi = gS * (GRAD && a.rs_in ? a.rs_in[xrow] : 1.0f);
+  const GxScales sc = gx_scales<GRAD>(a, xrow);
+  float4 xv[4], sv[4];
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(a.Wimg), 0, (unsigned)((int64_t)(a.N / 256) * KT * WCHUNK), 0x00020000);
 
   auto kstep = [&](int i) { return std::min(i, KT - 1); };
-  float4 xv[4], sv[4];
-  auto x_request = [&](int i) {            // clamped: the last requests re-read the last step
-    const int64_t koff = (int64_t)GX_BK * kstep(i);
-#pragma unroll
-    for (int i4 = 0; i4 < 4; ++i4) {
-      // plain loads: a dY row is re-read by every column tile, non-temporal loads measured 1.4x slower
-      xv[i4] = *reinterpret_cast<const float4*>(xp + koff + 4 * i4);
-      if (GRAD && sp) sv[i4] = *reinterpret_cast<const float4*>(sp + koff + 4 * i4);
-    }
-  };
-  auto x_fill = [&](char* sX) {
-    float v[16] = {xv[0].x, xv[0].y, xv[0].z, xv[0].w, xv[1].x, xv[1].y, xv[1].z, xv[1].w,
-                   xv[2].x, xv[2].y, xv[2].z, xv[2].w, xv[3].x, xv[3].y, xv[3].z, xv[3].w};
-    if (GRAD) {
-      if (sp) {
-        const float sg[16] = {sv[0].x, sv[0].y, sv[0].z, sv[0].w, sv[1].x, sv[1].y, sv[1].z, sv[1].w,
-                              sv[2].x, sv[2].y, sv[2].z, sv[2].w, sv[3].x, sv[3].y, sv[3].z, sv[3].w};
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] *= act_grad_from_out(a.act_in, sg[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] *= rsi;
-    }
-    unsigned h[8], l[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) split2_pair(v[2 * j], v[2 * j + 1], h[j], l[j]);
-    char* d = sX + xr * GX_XROW + 32 * xh;
-    *reinterpret_cast<u32x4*>(d) = u32x4{h[0], h[1], h[2], h[3]};
-    *reinterpret_cast<u32x4*>(d + 16) = u32x4{h[4], h[5], h[6], h[7]};
-    *reinterpret_cast<u32x4*>(d + GX_XPLANE) = u32x4{l[0], l[1], l[2], l[3]};
-    *reinterpret_cast<u32x4*>(d + GX_XPLANE + 16) = u32x4{l[4], l[5], l[6], l[7]};
-  };
+  auto x_request = [&](int i) { gx_request<GRAD>(xv, sv, xp, sp, (int64_t)GX_BK * kstep(i)); };    // clamped: the last requests re-read the last step
+  auto x_fill = [&](char* sX) { gx_fill<GRAD, GX_XROW, GX_XPLANE>(a, xv, sv, sp, sc.rsi, sX, xr, xh); };
   // W^T fragments of the k-half (kt, ks) for this wave's two 32-column blocks
   auto w_request = [&](u32x4 (&wa)[2][2], int i, int ks) {
     const int ktc = kstep(i);
@@ -484,7 +477,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_fwdr_kernel(GxArgs a) {
   // epilogue: lane holds, for row m = m0 + 32 i + l31, columns n = 256 ct + 32 (2 nq + j) + 8 q + 4 half + (0..3)
   float rsv[4];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) rsv[i] = oscale * (a.rowscale ? a.rowscale[std::min<int64_t>(m0 + 32 * i + l31, a.M - 1)] : 1.0f);
+  for (int i = 0; i < 4; ++i) rsv[i] = sc.oscale * (a.rowscale ? a.rowscale[std::min<int64_t>(m0 + 32 * i + l31, a.M - 1)] : 1.0f);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int64_t m = m0 + 32 * i + l31;
@@ -512,50 +505,20 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_short_kernel(GxArgs a) {
   const int64_t m0 = (int64_t)blockIdx.x * 32;
   const int ct = blockIdx.y;
   const int KT = a.K / GX_BK, NT = a.K / 128;
-  constexpr int WCHUNK = gx_wchunk(4);
+  constexpr int WCHUNK = gxp_wchunk(4);
 
   // this thread's slice of an X tile: row tid >> 3, 16 floats at column 16 (tid & 7) of the 128-wide k-tile
   const int xr = tid >> 3, xc = tid & 7;
   const int64_t xrow = std::min<int64_t>(m0 + xr, a.M - 1);
   const float* xp = a.X + xrow * a.K + 16 * xc;
   const float* sp = GRAD && a.Sin ? a.Sin + xrow * a.K + 16 * xc : nullptr;
-  const float gS = GRAD && a.gscale ? a.gscale[0] : 1.0f;          // power of two (gemm_grad_scale)
-  const float oscale = GX_WINV * (GRAD && a.gscale ? a.gscale[1] : 1.0f);
-  const float rsi = gS * (GRAD && a.rs_in ? a.rs_in[xrow] : 1.0f);
+  const GxScales sc = gx_scales<GRAD>(a, xrow);
+  float4 xv[4], sv[4];
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(a.Wimg), 0, (unsigned)((int64_t)(a.N / 256) * KT * WCHUNK), 0x00020000);
 
-  float4 xv[4], sv[4];
-  auto x_request = [&](int t) {            // clamped: the last request re-reads the last tile
-    const int64_t koff = (int64_t)128 * std::min(t, NT - 1);
-#pragma unroll
-    for (int i4 = 0; i4 < 4; ++i4) {
-      xv[i4] = *reinterpret_cast<const float4*>(xp + koff + 4 * i4);
-      if (GRAD && sp) sv[i4] = *reinterpret_cast<const float4*>(sp + koff + 4 * i4);
-    }
-  };
-  auto x_fill = [&](char* sX) {
-    float v[16] = {xv[0].x, xv[0].y, xv[0].z, xv[0].w, xv[1].x, xv[1].y, xv[1].z, xv[1].w,
-                   xv[2].x, xv[2].y, xv[2].z, xv[2].w, xv[3].x, xv[3].y, xv[3].z, xv[3].w};
-    if (GRAD) {
-      if (sp) {
-        const float sg[16] = {sv[0].x, sv[0].y, sv[0].z, sv[0].w, sv[1].x, sv[1].y, sv[1].z, sv[1].w,
-                              sv[2].x, sv[2].y, sv[2].z, sv[2].w, sv[3].x, sv[3].y, sv[3].z, sv[3].w};
-#pragma unroll
-        for (int j = 0; j < 16; ++j) v[j] *= act_grad_from_out(a.act_in, sg[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] *= rsi;
-    }
-    unsigned h[8], l[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) split2_pair(v[2 * j], v[2 * j + 1], h[j], l[j]);
-    char* d = sX + xr * GS_ROW + 32 * xc;
-    *reinterpret_cast<u32x4*>(d) = u32x4{h[0], h[1], h[2], h[3]};
-    *reinterpret_cast<u32x4*>(d + 16) = u32x4{h[4], h[5], h[6], h[7]};
-    *reinterpret_cast<u32x4*>(d + GS_PLANE) = u32x4{l[0], l[1], l[2], l[3]};
-    *reinterpret_cast<u32x4*>(d + GS_PLANE + 16) = u32x4{l[4], l[5], l[6], l[7]};
-  };
+  auto x_request = [&](int t) { gx_request<GRAD>(xv, sv, xp, sp, (int64_t)128 * std::min(t, NT - 1)); };   // clamped: the last request re-reads the last tile
+  auto x_fill = [&](char* sX) { gx_fill<GRAD, GS_ROW, GS_PLANE>(a, xv, sv, sp, sc.rsi, sX, xr, xc); };
   // W^T fragments of k-half q (= 32-wide step q >> 1, half q & 1) for this wave's two 32-column blocks; requests
   // past the end re-read the last half (never multiplied)
   auto w_request = [&](u32x4 (&wa)[2][2], int q) {
@@ -602,7 +565,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_short_kernel(GxArgs a) {
 
   // epilogue: lane holds, for row m = m0 + l31, columns n = 256 ct + 32 (2 nq + j) + 8 q + 4 half + (0..3)
   const int64_t m = m0 + l31;
-  if (m < a.M) gx_epilogue_block<2>(a, acc, m, 256 * ct + 64 * nq + 4 * half, oscale * (a.rowscale ? a.rowscale[m] : 1.0f));
+  if (m < a.M) gx_epilogue_block<2>(a, acc, m, 256 * ct + 64 * nq + 4 * half, sc.oscale * (a.rowscale ? a.rowscale[m] : 1.0f));
 }
 
 // the short kernel: N % 256 (its column tiling), K % 128 (its k-tiles)
@@ -644,8 +607,8 @@ static int gx_launch(ng_ctx* ctx, hipStream_t st, GxArgs& a, const float* W, int
     if (grad) hipLaunchKernelGGL((gemm_h2_fwdr_kernel<true>), grid, dim3(256), G4_LDS, st, a);
     else hipLaunchKernelGGL((gemm_h2_fwdr_kernel<false>), grid, dim3(256), G4_LDS, st, a);
   } else {
-    if (grad) hipLaunchKernelGGL((gemm_h2_fwd_kernel<true, 2>), grid, dim3(256), gx_lds(2), st, a);
-    else hipLaunchKernelGGL((gemm_h2_fwd_kernel<false, 2>), grid, dim3(256), gx_lds(2), st, a);
+    if (grad) hipLaunchKernelGGL((gemm_h2_fwd_kernel<true>), grid, dim3(256), GX_LDS, st, a);
+    else hipLaunchKernelGGL((gemm_h2_fwd_kernel<false>), grid, dim3(256), GX_LDS, st, a);
   }
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
@@ -697,11 +660,10 @@ int gemm_h2_prepack_mp(ng_ctx* ctx, hipStream_t st, int64_t M, int F, int E, con
 // ------------------------------------------------------------------------------------------------------------------
 // dW[k][n] = sum_m X[m][k] dP[m][n]   (dP = dY * act'(S) * rowscale), the contraction runs over the ROWS of both
 // operands: both live in LDS as fp16 piece images [32 rows][128 + 8] and are read as COLUMNS with ds_read_b64_tr_b16
-// (rows stored permuted so that the four rows of a read sit 16 banks apart — see edge_bwd_h2.hip).  256 threads, output
+// (h2_tr_frag; rows stored permuted so that the four rows of a read sit 16 banks apart: h2_prow).  256 threads, output
 // tile 128 (k) x 128 (n), 32 rows per step, the rows split over blockIdx.z into partials [z][K][N] that the caller
 // reduces (dense_dw).  MFMA: A = dP columns (rows n of D), B = X columns (columns k of D): a lane ends with 4
 // consecutive n of one k.
-typedef short gx_s16x4 __attribute__((ext_vector_type(4)));
 constexpr int GT_ROWB = 272;                    // image row stride (bytes)
 constexpr int GT_PLANE = 32 * GT_ROWB;          // 8,704
 constexpr int GT_LDS = 2 * 2 * GT_PLANE;        // 34,816
@@ -719,22 +681,56 @@ struct GtArgs {
   RangeGuard guard;        // raised when an accumulator comes out non-finite
 };
 
-__device__ __forceinline__ u32x4 gt_tr_frag(const char* p) {
-  const gx_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) gx_s16x4*)p);
-  const gx_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) gx_s16x4*)(p + GT_ROWB));
-  const u32x2 a = __builtin_bit_cast(u32x2, lo), b = __builtin_bit_cast(u32x2, hi);
-  return u32x4{a[0], a[1], b[0], b[1]};
+// ---- shared pieces of the two dW kernels (the image geometry ROWB / PLANE of each goes to gx_split16 and h2_tr_frag)
+// 16 columns of one operand row: X from column kc, dP = dY * act'(S) * rowscale * S from column nc.  Rows past r1 read
+// row M - 1 and contribute zero.
+__device__ __forceinline__ void gt_load_row(const GtArgs& a, float (&xv)[16], float (&pv)[16], int64_t row, int64_t r1,
+                                            int kc, int nc, float gS) {
+  const bool ok = row < r1;
+  const int64_t rc = ok ? row : a.M - 1;
+  const float* xp = a.X + rc * a.K + kc;
+  const float* dp = a.dY + rc * a.N + nc;
+  const float rs = ok ? gS * (a.rowscale ? a.rowscale[rc] : 1.0f) : 0.0f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float4 x = *reinterpret_cast<const float4*>(xp + 4 * i);
+    float4 d = *reinterpret_cast<const float4*>(dp + 4 * i);
+    if (a.S) {
+      const float4 s = *reinterpret_cast<const float4*>(a.S + rc * a.N + nc + 4 * i);
+      d.x *= act_grad_from_out(a.act, s.x); d.y *= act_grad_from_out(a.act, s.y);
+      d.z *= act_grad_from_out(a.act, s.z); d.w *= act_grad_from_out(a.act, s.w);
+    }
+    xv[4 * i + 0] = x.x; xv[4 * i + 1] = x.y; xv[4 * i + 2] = x.z; xv[4 * i + 3] = x.w;
+    pv[4 * i + 0] = d.x * rs; pv[4 * i + 1] = d.y * rs; pv[4 * i + 2] = d.z * rs; pv[4 * i + 3] = d.w * rs;
+  }
 }
 
-__device__ __forceinline__ void gt_store16(char* img, int prow, int col0, const float (&v)[16]) {
-  unsigned h[8], l[8];
+// Range guard and stores of a wave's NJ x 2 blocks.  D rows = n (from dP), D cols = k (from X): the lane holds
+// k = kl + 32 i, n = nl + 32 j + 8 q + (0..3) in acc[j][i][4 q ..]; the partial is written as acc / S.
+template <int NJ>
+__device__ __forceinline__ void gt_epilogue(const GtArgs& a, const f32x16 (&acc)[NJ][2], float* part, int kl, int nl, float gI) {
+  {
+    float chk = 0.f;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) split2_pair(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  char* d = img + prow * GT_ROWB + col0 * 2;
-  *reinterpret_cast<u32x4*>(d) = u32x4{h[0], h[1], h[2], h[3]};
-  *reinterpret_cast<u32x4*>(d + 16) = u32x4{h[4], h[5], h[6], h[7]};
-  *reinterpret_cast<u32x4*>(d + GT_PLANE) = u32x4{l[0], l[1], l[2], l[3]};
-  *reinterpret_cast<u32x4*>(d + GT_PLANE + 16) = u32x4{l[4], l[5], l[6], l[7]};
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) chk += fabsf(acc[j][i][t]);
+    range_guard_raise(a.guard, not_finite(chk * gI));
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int k = kl + 32 * i;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int n = nl + 32 * j + 8 * q;
+        *reinterpret_cast<float4*>(part + (int64_t)k * a.N + n) =
+            make_float4(gI * acc[j][i][4 * q + 0], gI * acc[j][i][4 * q + 1], gI * acc[j][i][4 * q + 2], gI * acc[j][i][4 * q + 3]);
+      }
+  }
 }
 
 __global__ __launch_bounds__(256, 2) void gemm_h2_dw_kernel(GtArgs a) {
@@ -751,28 +747,9 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_dw_kernel(GtArgs a) {
   const float gS = a.gscale[0], gI = a.gscale[1];       // dP is split as S * dP, the partial is written as acc / S
   // loader: thread -> row tid >> 3 of the 32-row step, 16 columns at 16 (tid & 7)
   const int lr = tid >> 3, lc = 16 * (tid & 7);
-  const int e16 = lr & 15;
-  const int prow = 16 * (lr >> 4) + 4 * (e16 & 3) + (e16 >> 2);   // see hx_prow_g in edge_bwd_h2.hip
+  const int simg = h2_prow(lr) * GT_ROWB + lc * 2;      // where the loaded row goes in an image
   float xv[16], pv[16];
-  auto load = [&](int64_t row) {
-    const bool ok = row < r1;
-    const int64_t rc = ok ? row : a.M - 1;
-    const float* xp = a.X + rc * a.K + k0 + lc;
-    const float* dp = a.dY + rc * a.N + n0 + lc;
-    const float rs = ok ? gS * (a.rowscale ? a.rowscale[rc] : 1.0f) : 0.0f;     // rows past the end contribute zero
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 x = *reinterpret_cast<const float4*>(xp + 4 * i);
-      float4 d = *reinterpret_cast<const float4*>(dp + 4 * i);
-      if (a.S) {
-        const float4 s = *reinterpret_cast<const float4*>(a.S + rc * a.N + n0 + lc + 4 * i);
-        d.x *= act_grad_from_out(a.act, s.x); d.y *= act_grad_from_out(a.act, s.y);
-        d.z *= act_grad_from_out(a.act, s.z); d.w *= act_grad_from_out(a.act, s.w);
-      }
-      xv[4 * i + 0] = x.x; xv[4 * i + 1] = x.y; xv[4 * i + 2] = x.z; xv[4 * i + 3] = x.w;
-      pv[4 * i + 0] = d.x * rs; pv[4 * i + 1] = d.y * rs; pv[4 * i + 2] = d.z * rs; pv[4 * i + 3] = d.w * rs;
-    }
-  };
+  auto load = [&](int64_t row) { gt_load_row(a, xv, pv, row, r1, k0 + lc, n0 + lc, gS); };
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -790,8 +767,8 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_dw_kernel(GtArgs a) {
 #pragma unroll 1
   for (int64_t rb = r0; rb < r1; rb += 32) {
     NG_LDS_BARRIER();
-    gt_store16(sXi, prow, lc, xv);
-    gt_store16(sPi, prow, lc, pv);
+    gx_split16<GT_PLANE>(sXi + simg, xv);
+    gx_split16<GT_PLANE>(sPi + simg, pv);
     NG_LDS_BARRIER();
     load(rb + 32 + lr);                   // next step (rows past r1 load row M-1 and are zeroed)
 #pragma unroll
@@ -801,38 +778,16 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_dw_kernel(GtArgs a) {
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
-          pa[j][p] = gt_tr_frag(sPi + p * GT_PLANE + 16 * ks * GT_ROWB + lane_off + 64 * (2 * nh + j));
-          xb[j][p] = gt_tr_frag(sXi + p * GT_PLANE + 16 * ks * GT_ROWB + lane_off + 64 * (2 * kh + j));
+          pa[j][p] = h2_tr_frag(sPi + p * GT_PLANE + 16 * ks * GT_ROWB + lane_off + 64 * (2 * nh + j), GT_ROWB);
+          xb[j][p] = h2_tr_frag(sXi + p * GT_PLANE + 16 * ks * GT_ROWB + lane_off + 64 * (2 * kh + j), GT_ROWB);
         }
 #pragma unroll
       for (int i = 0; i < 2; ++i) mma3_2a(pa[0], pa[1], xb[i], acc[0][i], acc[1][i]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  // D rows = n (from dP), D cols = k (from X): lane holds k = k0 + 32 (2 kh + i) + l31, n = n0 + 32 (2 nh + j) + 8q + 4 half + (0..3)
-  float* part = a.partial + (int64_t)blockIdx.z * a.K * a.N;
-  {
-    float chk = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) chk += fabsf(acc[j][i][t]);
-    range_guard_raise(a.guard, not_finite(chk * gI));
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int k = k0 + 32 * (2 * kh + i) + l31;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n = n0 + 32 * (2 * nh + j) + 8 * q + 4 * half;
-        *reinterpret_cast<float4*>(part + (int64_t)k * a.N + n) =
-            make_float4(gI * acc[j][i][4 * q + 0], gI * acc[j][i][4 * q + 1], gI * acc[j][i][4 * q + 2], gI * acc[j][i][4 * q + 3]);
-      }
-  }
+  // lane: k = k0 + 32 (2 kh + i) + l31, n = n0 + 32 (2 nh + j) + 8 q + 4 half + (0..3)
+  gt_epilogue<2>(a, acc, a.partial + (int64_t)blockIdx.z * a.K * a.N, k0 + 64 * kh + l31, n0 + 64 * nh + 4 * half, gI);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -843,24 +798,6 @@ __global__ __launch_bounds__(256, 2) void gemm_h2_dw_kernel(GtArgs a) {
 constexpr int GT8_ROWB = 528;                    // image row stride (bytes): 256 fp16 + 16, 132 dwords = 4 mod 64 banks
 constexpr int GT8_PLANE = 32 * GT8_ROWB;         // 16,896
 constexpr int GT8_LDS = 2 * 2 * 2 * GT8_PLANE;   // 135,168: two (X image, dP image) pairs
-
-__device__ __forceinline__ u32x4 gt8_tr_frag(const char* p) {
-  const gx_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) gx_s16x4*)p);
-  const gx_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) gx_s16x4*)(p + GT8_ROWB));
-  const u32x2 a = __builtin_bit_cast(u32x2, lo), b = __builtin_bit_cast(u32x2, hi);
-  return u32x4{a[0], a[1], b[0], b[1]};
-}
-
-__device__ __forceinline__ void gt8_store16(char* img, int prow, int col0, const float (&v)[16]) {
-  unsigned h[8], l[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) split2_pair(v[2 * j], v[2 * j + 1], h[j], l[j]);
-  char* d = img + prow * GT8_ROWB + col0 * 2;
-  *reinterpret_cast<u32x4*>(d) = u32x4{h[0], h[1], h[2], h[3]};
-  *reinterpret_cast<u32x4*>(d + 16) = u32x4{h[4], h[5], h[6], h[7]};
-  *reinterpret_cast<u32x4*>(d + GT8_PLANE) = u32x4{l[0], l[1], l[2], l[3]};
-  *reinterpret_cast<u32x4*>(d + GT8_PLANE + 16) = u32x4{l[4], l[5], l[6], l[7]};
-}
 
 __global__ __launch_bounds__(512, 1) void gemm_h2_dw8_kernel(GtArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_gt8[];
@@ -892,27 +829,12 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_dw8_kernel(GtArgs a) {
   const float gS = a.gscale[0], gI = a.gscale[1];       // dP is split as S * dP, the partial is written as acc / S
   // loader: thread -> row tid >> 4 of the 32-row step, 16 columns at 16 (tid & 15)
   const int lr = tid >> 4, lc = 16 * (tid & 15);
-  const int e16 = lr & 15;
-  const int prow = 16 * (lr >> 4) + 4 * (e16 & 3) + (e16 >> 2);   // see hx_prow_g in edge_bwd_h2.hip
+  const int simg = h2_prow(lr) * GT8_ROWB + lc * 2;     // where the loaded row goes in an image
   float xa[16], pa_[16], xb_[16], pb_[16];
-  auto load = [&](float (&xv)[16], float (&pv)[16], int64_t row) {
-    const bool ok = row < r1;
-    const int64_t rc = ok ? row : a.M - 1;
-    const float* xp = a.X + rc * a.K + k0 + lc;
-    const float* dp = a.dY + rc * a.N + n0 + lc;
-    const float rs = ok ? gS * (a.rowscale ? a.rowscale[rc] : 1.0f) : 0.0f;     // rows past the end contribute zero
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 x = *reinterpret_cast<const float4*>(xp + 4 * i);
-      float4 d = *reinterpret_cast<const float4*>(dp + 4 * i);
-      if (a.S) {
-        const float4 s = *reinterpret_cast<const float4*>(a.S + rc * a.N + n0 + lc + 4 * i);
-        d.x *= act_grad_from_out(a.act, s.x); d.y *= act_grad_from_out(a.act, s.y);
-        d.z *= act_grad_from_out(a.act, s.z); d.w *= act_grad_from_out(a.act, s.w);
-      }
-      xv[4 * i + 0] = x.x; xv[4 * i + 1] = x.y; xv[4 * i + 2] = x.z; xv[4 * i + 3] = x.w;
-      pv[4 * i + 0] = d.x * rs; pv[4 * i + 1] = d.y * rs; pv[4 * i + 2] = d.z * rs; pv[4 * i + 3] = d.w * rs;
-    }
+  auto load = [&](float (&xv)[16], float (&pv)[16], int64_t row) { gt_load_row(a, xv, pv, row, r1, k0 + lc, n0 + lc, gS); };
+  auto store = [&](char* img, const float (&xv)[16], const float (&pv)[16]) {     // X image | dP image
+    gx_split16<GT8_PLANE>(img + simg, xv);
+    gx_split16<GT8_PLANE>(img + 2 * GT8_PLANE + simg, pv);
   };
 
   f32x16 acc[4][2];
@@ -934,13 +856,13 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_dw8_kernel(GtArgs a) {
       for (int j = 0; j < 4; ++j)
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-          pa[j][p] = gt8_tr_frag(sPi + p * GT8_PLANE + 16 * ks * GT8_ROWB + lane_off + 64 * (4 * nh + j));
+          pa[j][p] = h2_tr_frag(sPi + p * GT8_PLANE + 16 * ks * GT8_ROWB + lane_off + 64 * (4 * nh + j), GT8_ROWB);
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         u32x4 xb[2];
 #pragma unroll
         for (int p = 0; p < 2; ++p)
-          xb[p] = gt8_tr_frag(sXi + p * GT8_PLANE + 16 * ks * GT8_ROWB + lane_off + 64 * (2 * kh + i));
+          xb[p] = h2_tr_frag(sXi + p * GT8_PLANE + 16 * ks * GT8_ROWB + lane_off + 64 * (2 * kh + i), GT8_ROWB);
         mma3_2a(pa[0], pa[1], xb, acc[0][i], acc[1][i]);
         mma3_2a(pa[2], pa[3], xb, acc[2][i], acc[3][i]);
       }
@@ -949,49 +871,24 @@ __global__ __launch_bounds__(512, 1) void gemm_h2_dw8_kernel(GtArgs a) {
   };
   load(xa, pa_, r0 + lr);
   load(xb_, pb_, r0 + 32 + lr);
-  gt8_store16(img0, prow, lc, xa);
-  gt8_store16(img0 + 2 * GT8_PLANE, prow, lc, pa_);
+  store(img0, xa, pa_);
   load(xa, pa_, r0 + 64 + lr);          // rows past r1 load row M-1 and are zeroed
   NG_LDS_BARRIER();
 #pragma unroll 1
   for (int64_t rb = r0; rb < r1; rb += 64) {
-    gt8_store16(img1, prow, lc, xb_);                       // rows rb + 32 (img1 was last read before the previous barrier)
-    gt8_store16(img1 + 2 * GT8_PLANE, prow, lc, pb_);
+    store(img1, xb_, pb_);                                  // rows rb + 32 (img1 was last read before the previous barrier)
     load(xb_, pb_, rb + 96 + lr);
     multiply(img0, img0 + 2 * GT8_PLANE);                   // rows rb
     NG_LDS_BARRIER();
     if (rb + 32 < r1) {                                     // uniform over the workgroup
-      gt8_store16(img0, prow, lc, xa);                      // rows rb + 64
-      gt8_store16(img0 + 2 * GT8_PLANE, prow, lc, pa_);
+      store(img0, xa, pa_);                                 // rows rb + 64
       load(xa, pa_, rb + 128 + lr);
       multiply(img1, img1 + 2 * GT8_PLANE);                 // rows rb + 32
       NG_LDS_BARRIER();
     }
   }
-  // D rows = n (from dP), D cols = k (from X): lane holds k = k0 + 32 (2 kh + i) + l31, n = n0 + 32 (4 nh + j) + 8q + 4 half + (0..3)
-  float* part = a.partial + (int64_t)zc * a.K * a.N;
-  {
-    float chk = 0.f;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) chk += fabsf(acc[j][i][t]);
-    range_guard_raise(a.guard, not_finite(chk * gI));
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int k = k0 + 32 * (2 * kh + i) + l31;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int n = n0 + 32 * (4 * nh + j) + 8 * q + 4 * half;
-        *reinterpret_cast<float4*>(part + (int64_t)k * a.N + n) =
-            make_float4(gI * acc[j][i][4 * q + 0], gI * acc[j][i][4 * q + 1], gI * acc[j][i][4 * q + 2], gI * acc[j][i][4 * q + 3]);
-      }
-  }
+  // lane: k = k0 + 32 (2 kh + i) + l31, n = n0 + 32 (4 nh + j) + 8 q + 4 half + (0..3)
+  gt_epilogue<4>(a, acc, a.partial + (int64_t)zc * a.K * a.N, k0 + 64 * kh + l31, n0 + 128 * nh + 4 * half, gI);
 }
 
 bool gemm_h2_dw8_ok(int64_t M, int Kin, int Nout) {
@@ -1025,192 +922,6 @@ int gemm_h2_dw(ng_ctx* ctx, hipStream_t st, int64_t M, int Kin, int Nout, int ac
                        st, a);
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
-}
-
-// ==================================================================================================================
-// Gather-GEMM (round 4): the MPLayer update and the node-side pull of its backward at the reference's default width
-// (atom_feature_size = 256, nmrgnn/model.py:22) WITHOUT the aggregate in HBM.  nmrgnn/layers.py:26-46:
-//     forward   h' = act(v * sum_n A_n W_n) + h,     A[i][(n, l)]  = sum_j   e[i,j,n] h[nlist[i,j]][l]
-//     backward  dh = dH + sum_n B_n Wn_n,            B[t][(n, m)]  = sum_in  e[i,j,n] dP[i][m]     (edges (i,j) with nlist[i,j] = t)
-// Until round 3 both ran as aggregate -> [N, 768] in HBM (402 MB written, then read) -> GEMM, and the backward pull read
-// 3 KB of dA per incoming edge through L2.  The kernel of this path is the window gather-GEMM of mp_gw.cuh (round 5: 256-row
-// tiles, one wave per SIMD, the gathered operand formed in registers out of an LDS window).  Round 4's producer / consumer
-// kernel (four producer waves walking the lists, four consumer waves multiplying; 375-450 us per launch against 300-330) was
-// removed in round 6 — DESIGN_HISTORY.md has its measurements.  The k-step order (slab-major, n inside) is the weight
-// image's (pack_bodies.cuh: PK_GG), built from w[l][m][n] directly — no Wp copy.
-// Ranges.  Forward operands are activations (split unscaled; an |A| >= 65504 raises the guard).  The pull's operand is a
-// gradient: the sums are multiplied by S * 2^-x before the split, S the power of two of dP (gemm_grad_scale) and 2^x >=
-// max_n sum_in |e_n| of the row, so no piece can overflow; the epilogue multiplies the row by 2^x / S.  A raised guard is
-// answered by mp_gg_repair_kernel: the same rows in plain fp32 on the vector ALU (slow, exact, an empty launch otherwise).
-enum { GG_PADDED = 0, GG_CSR = 1, GG_REC = 2 };
-
-struct GgArgs {
-  int64_t M;               // rows (atoms)
-  int F, Kpad;             // width of the gathered operand (= output width); slots per row of the padded form
-  const float* G;          // gathered operand [M][F]: h (forward) / dP (pull)
-  const int32_t* idx;      // GG_PADDED / GG_CSR: source row of an entry
-  const float* ew;         //                     its E weights, [entries][E]
-  const int32_t* ptr;      // GG_CSR / GG_REC: row extents [M + 1]
-  const float4* rec;       // GG_REC: {source (int bits), e_0, e_1, e_2} per entry
-  const char* Wimg;        // PK_GG image
-  const float* w;          // the layer's weight in the reference layout (repair kernel)
-  int mode;                // 0 forward, 1 pull (PK_GG)
-  const float* rowscale;   // [M] or nullptr
-  const float* R;          // residual / base [M][F] or nullptr
-  float* Y;                // [M][F]
-  float* S;                // activation output [M][F] or nullptr
-  int act;
-  float* A_out;            // forward, training: the aggregate [M][E*F] as a by-product (the backward's dw = A^T dP reads it), or nullptr
-  const float* gscale;     // GRAD: {S, 1/S} of the gathered operand
-  int no_window;           // mp_gw_kernel: take the memory path for every tile (NG_MP_GW=nowin)
-  RangeGuard guard;
-};
-
-template <int LK, int E>
-__device__ __forceinline__ float4 gg_entry(const GgArgs& a, int64_t t) {
-  if (LK == GG_REC) return a.rec[t];
-  float4 r;
-  r.x = __builtin_bit_cast(float, a.idx[t]);
-  r.y = a.ew[t * E];
-  r.z = E > 1 ? a.ew[t * E + 1] : 0.f;
-  r.w = E > 2 ? a.ew[t * E + 2] : 0.f;
-  return r;
-}
-
-// The rows of the same call in plain fp32 (one workgroup per row at a time, thread = column), executed only when the
-// kernel above raised the guard.  F == blockDim.x == 256.
-template <int LK, int E>
-__global__ __launch_bounds__(256) void mp_gg_repair_kernel(GgArgs a) {
-  if (!range_guard_raised(a.guard)) return;
-  __shared__ float sA[3 * 256];
-  const int c = threadIdx.x, F = a.F;
-  for (int64_t row = blockIdx.x; row < a.M; row += gridDim.x) {
-    int64_t p0, p1;
-    if (LK == GG_PADDED) { p0 = row * a.Kpad; p1 = p0 + a.Kpad; }
-    else { p0 = a.ptr[row]; p1 = a.ptr[row + 1]; }
-    float s[3] = {0.f, 0.f, 0.f};
-    for (int64_t t = p0; t < p1; ++t) {
-      const float4 e4 = gg_entry<LK, E>(a, t);
-      const float g = a.G[(int64_t)__builtin_bit_cast(int, e4.x) * F + c];
-      s[0] = fmaf(e4.y, g, s[0]); s[1] = fmaf(e4.z, g, s[1]); s[2] = fmaf(e4.w, g, s[2]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int n = 0; n < E; ++n) sA[n * 256 + c] = s[n];
-    __syncthreads();
-    float acc = 0.f;
-    for (int n = 0; n < E; ++n)
-      for (int k = 0; k < F; ++k) {
-        const float wv = a.mode == 0 ? a.w[((int64_t)k * F + c) * E + n] : a.w[((int64_t)c * F + k) * E + n];
-        acc = fmaf(sA[n * 256 + k], wv, acc);
-      }
-    float v = acc * (a.rowscale ? a.rowscale[row] : 1.0f);
-    v = act_apply(a.act, v);
-    if (a.S) a.S[row * F + c] = v;
-    a.Y[row * F + c] = v + (a.R ? a.R[row * F + c] : 0.f);
-  }
-}
-
-#include "mp_gw.cuh"
-
-// what the window gather-GEMM takes (everything else keeps the aggregate -> HBM -> GEMM path: mp_gg_supported)
-static bool gw_shape_ok(int64_t M, int F, int E, bool has_ptr, int Kpad) {
-  return E == 3 && F % 32 == 0 && M * (int64_t)F * 4 < ((int64_t)1 << 31) && (has_ptr || Kpad <= 16);
-}
-
-// DEFAULT for the forward of a call that does not keep the aggregate (inference: `A_save == nullptr`) on a batch of small
-// graphs (ng_ctx_set_graph_span: every row's sources lie inside the 320-row window): the window gather-GEMM (mp_gw.cuh).
-// Measured on MI355X at the bench batch (profiles/r05e_gw_ab.txt): 0.30-0.33 ms per layer against 0.134 + 0.227 for
-// aggregate -> HBM -> GEMM.  Training calls (the aggregate is written for dw = A^T dP: its row-per-lane stores cost the
-// kernel more than the round trip it saves) and the backward's pull (pull_win_kernel wins) keep their kernels unless
-// NG_MP_GG=1 asks for this one.
-bool mp_gw_infer_ok(ng_ctx* ctx, int64_t N, int K, int F, int E, bool csr, bool keeps_aggregate) {
-  return !sw().gemm_math_fp32 && !sw().mp_layered && !keeps_aggregate && F == 256 && E == 3 && (csr || K <= 16) &&
-         N >= sw().mp_gg_min_rows && N * (int64_t)F * 4 < ((int64_t)1 << 31) && ctx->graph_span > 0 && ctx->graph_span <= 256;
-}
-
-bool mp_gg_supported(int64_t N, int F, int E, int Kpad) {      // Kpad: slots per row of a padded list, 0 for CSR / record lists
-  // OPT-IN (NG_MP_GG=1): measured on MI355X the kernel does not beat aggregate -> HBM -> GEMM yet (375-450 us per launch
-  // against 134 + 240; the producer waves, four per CU, cannot keep enough gathers in flight — DESIGN section 4), so the
-  // default stays the two-kernel path.  Below NG_MP_GG_MIN_ROWS rows (default 8192 = 64 tiles) a call has too few
-  // 128-row tiles for 256 CUs either way.  Both are read with the other switches (ng_reload_env).
-  return sw().mp_gg_on && !sw().gemm_math_fp32 && !sw().mp_layered && F == 256 && N >= sw().mp_gg_min_rows &&
-         gw_shape_ok(N, F, E, Kpad == 0, Kpad);
-}
-
-// the PK_GG image of w for `mode` (cached / refreshed behind Adam when the image cache is on, else in the aux scratch)
-static char* gg_image(ng_ctx* ctx, hipStream_t st, int F, int E, int mode, const float* w, int* rc) {
-  const size_t bytes = (size_t)(F / 32) * E * gx_wchunk(4);
-  bool have = false;
-  char* img = (char*)cached_image(ctx, w, 15 + mode, bytes, &have);
-  const bool cached = img != nullptr;
-  if (!img) img = (char*)aux_workspace(ctx, bytes);
-  *rc = NG_OK;
-  if (!img) { *rc = NG_ERR_NOMEM; return nullptr; }
-  if (!have) {
-    PackJob j;
-    j.kind = PK_GG; j.i0 = E; j.i1 = F | (mode << 16); j.src[0] = w; j.dst[0] = img;
-    j.blocks = (int)cdiv((int64_t)(F / 32) * E * (F / 32) * 2 * 64, 256);
-    *rc = pack_launch(ctx, st, j);
-    if (*rc == NG_OK && cached) cache_set_job(ctx, w, 15 + mode, j);
-  }
-  return img;
-}
-
-template <int LK, bool GRAD>
-static int gg_launch(ng_ctx* ctx, hipStream_t st, GgArgs& a, int E, const char* tag) {
-  a.guard = range_guard_begin(ctx);
-  if (!a.guard.word) return NG_ERR_NOMEM;
-  if (!gw_shape_ok(a.M, a.F, E, a.ptr != nullptr, a.Kpad)) return fail(ctx, NG_ERR_INVALID, "gather-GEMM: shape outside the window form");
-  {
-    ProfScope ps(ctx, st, tag);
-    a.no_window = sw().mp_gw_nowin ? 1 : 0;
-    const unsigned wgrid = (unsigned)cdiv(a.M, GW_BM);
-    if (LK == GG_PADDED && a.Kpad <= 16)
-      hipLaunchKernelGGL((mp_gw_kernel<LK, 3, GRAD, 6>), dim3(wgrid), dim3(GW_THREADS), GW_LDS, st, a);
-    else
-      hipLaunchKernelGGL((mp_gw_kernel<LK, 3, GRAD, 8>), dim3(wgrid), dim3(GW_THREADS), GW_LDS, st, a);
-    NG_HIP(ctx, hipGetLastError());
-  }
-  ProfScope ps(ctx, st, "mp_gg_range_fallback");
-  const unsigned rgrid = (unsigned)std::min<int64_t>(a.M, (int64_t)ctx->num_cu * 8);
-  switch (E) {
-    case 1: hipLaunchKernelGGL((mp_gg_repair_kernel<LK, 1>), dim3(rgrid), dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((mp_gg_repair_kernel<LK, 2>), dim3(rgrid), dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((mp_gg_repair_kernel<LK, 3>), dim3(rgrid), dim3(256), 0, st, a); break;
-  }
-  NG_HIP(ctx, hipGetLastError());
-  return NG_OK;
-}
-
-// h_out = act(inv_degree * (A Wp)) + (residual ? h : 0),  A the neighbour aggregate of h over (row_ptr | K) lists
-int mp_gg_fwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, int act, int residual, const float* h,
-              const int32_t* row_ptr, const int32_t* col, const float* e, const float* inv_degree, const float* w,
-              float* h_out, float* s_save, float* A_out) {
-  int rc = NG_OK;
-  GgArgs a{};
-  a.A_out = A_out;
-  a.Wimg = gg_image(ctx, st, F, E, 0, w, &rc);
-  if (rc) return rc;
-  a.M = N; a.F = F; a.Kpad = K; a.G = h; a.idx = col; a.ew = e; a.ptr = row_ptr; a.w = w; a.mode = 0;
-  a.rowscale = inv_degree; a.R = residual ? h : nullptr; a.Y = h_out; a.S = s_save; a.act = act;
-  return row_ptr ? gg_launch<GG_CSR, false>(ctx, st, a, E, "mp_gg_fwd") : gg_launch<GG_PADDED, false>(ctx, st, a, E, "mp_gg_fwd");
-}
-
-// dh_in = dh_out + sum_n B_n Wn_n,  B the aggregate of dP over the incoming-edge records {source, e_0..e_2} (csc order)
-int mp_gg_pull(ng_ctx* ctx, hipStream_t st, int64_t N, int F, int E, const float* dP, const int32_t* csc_ptr,
-               const float* csc_rec, const float* w, const float* dh_out, float* dh_in, const float* gscale) {
-  int rc = NG_OK;
-  GgArgs a{};
-  a.Wimg = gg_image(ctx, st, F, E, 1, w, &rc);
-  if (rc) return rc;
-  if (!gscale) {
-    rc = gemm_grad_scale(ctx, st, dP, N, F, nullptr, &gscale);
-    if (rc) return rc;
-  }
-  a.M = N; a.F = F; a.Kpad = 0; a.G = dP; a.ptr = csc_ptr; a.rec = reinterpret_cast<const float4*>(csc_rec); a.w = w; a.mode = 1;
-  a.R = dh_out; a.Y = dh_in; a.act = NG_ACT_NONE; a.gscale = gscale;
-  return gg_launch<GG_REC, true>(ctx, st, a, E, "mp_gg_pull");
 }
 
 }  // namespace ng

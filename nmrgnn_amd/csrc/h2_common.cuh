@@ -73,6 +73,24 @@ __device__ __forceinline__ void mma3_2a(const u32x4 (&a0)[2], const u32x4 (&a1)[
   acc0 = mfma_f16(a0[0], b[0], acc0); acc1 = mfma_f16(a1[0], b[0], acc1);
 }
 
+// ---- fp16 piece images read as COLUMNS (the contraction runs over the image's rows: edge_bwd_h2.cuh, the dW kernels of
+// gemm_h2.hip).  Physical row of row e (0..63) of an image whose row stride is 16 B past a multiple of 256 B (272, 528):
+// a transposing read fetches 4 consecutive rows x 32 B per 16-lane group, and the permutation puts those four rows 16
+// banks apart (measurements: edge_bwd_h2.cuh, image geometry).
+__device__ __forceinline__ int h2_prow(int e) {
+  const int hi = e >> 4, a = (e >> 2) & 3, b = e & 3;
+  return 16 * hi + 4 * b + a;
+}
+
+// one MFMA operand (8 consecutive rows of this lane's column) = two transposing reads of 4 rows each; `step` is the
+// byte distance between the two quads' first rows
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x4 h2_tr_frag(const char* p, int step) {
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p + step));
+  const u32x2 a = __builtin_bit_cast(u32x2, lo), b = __builtin_bit_cast(u32x2, hi);
+  return u32x4{a[0], a[1], b[0], b[1]};
+}
 
 // ---- LDS-DMA through an asm statement (round 5).  For a `__builtin_amdgcn_raw_ptr_buffer_load_lds` in flight hipcc puts
 // `s_waitcnt vmcnt(N)` in front of every later LDS read it cannot prove disjoint from the copy's destination — the round

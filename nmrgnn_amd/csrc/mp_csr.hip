@@ -598,7 +598,7 @@ int mp_generic_fwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, 
                    const int32_t* row_ptr, const int32_t* col, const float* e, const float* inv_degree, const float* w,
                    float* h_out, float* A_save, float* s_save) {
   const int64_t KF = (int64_t)E * F;
-  if (E <= 3 && (mp_gg_supported(N, F, E, row_ptr ? 0 : K) || mp_gw_infer_ok(ctx, N, K, F, E, row_ptr != nullptr, A_save != nullptr)))     // gather-GEMM (gemm_h2.hip): the aggregate only as a by-product when asked for
+  if (E <= 3 && (mp_gg_supported(N, F, E, row_ptr ? 0 : K) || mp_gw_infer_ok(ctx, N, K, F, E, row_ptr != nullptr, A_save != nullptr)))     // gather-GEMM (mp_gg.hip): the aggregate only as a by-product when asked for
     return mp_gg_fwd(ctx, st, N, K, F, E, act, residual, h, row_ptr, col, e, inv_degree, w, h_out, s_save, A_save);
   float* ws = (float*)workspace(ctx, (size_t)(KF * F + (A_save ? 0 : N * KF)) * 4);
   if (!ws) return NG_ERR_NOMEM;
@@ -621,7 +621,7 @@ int mp_generic_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, 
   // dw == NULL: no weight gradient — no dw GEMM, no partials, and no rebuilt aggregate (its only reader is that GEMM)
   const size_t dw_scr = dw ? dense_dw_scratch_floats(ctx, N, (int)KF, F, false) : 0;
   const bool rebuild_A = dw && !A_save;
-  // node side as a gather-GEMM over dP rows (gemm_h2.hip) needs the incoming-edge records; built here when the caller has none
+  // node side as a gather-GEMM over dP rows (mp_gg.hip) needs the incoming-edge records; built here when the caller has none
   const bool gg = E <= 3 && N > 0 && mp_gg_supported(N, F, E, 0);
   const int64_t n_ent = row_ptr ? nnz : N * K;
   const size_t rec_floats = gg && !csc_rec ? (size_t)std::max<int64_t>(n_ent, 1) * 4 : 0;
@@ -665,7 +665,7 @@ int mp_generic_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, 
   rc = csr_edge_grad(ctx, st, N, K, F, E, h, row_ptr, col, dA, de, de_accum);
   if (rc) return rc;
   // node side: dh_in = dh_out + pull of dA over the incoming edges — at the default width as a gather-GEMM over dP rows
-  // (1 KB per incoming edge instead of 3 KB of dA; gemm_h2.hip)
+  // (1 KB per incoming edge instead of 3 KB of dA; mp_gg.hip)
   if (gg) {
     if (!csc_rec) {
       float* rec = scr + dw_scr + (rebuild_A ? N * KF : 0);

@@ -1,9 +1,14 @@
-// Window gather-GEMM (round 5): the MPLayer update and the node-side pull of its backward at the reference's default
-// width (atom_feature_size = 256, nmrgnn/model.py:22; semantics nmrgnn/layers.py:26-46) with NEITHER operand of the
-// product in HBM — included by gemm_h2.hip (GgArgs, the PK_GG weight image, the fp32 repair kernel and the epilogue are
-// mp_gg_kernel's).  What round 4's gather-GEMM measured (profiles/r04_gg_ab.txt, r05e_gw_ab.txt): four producer waves
-// per CU set the pace even with the L2 loads AND the matrix products compiled out (386 us per launch) — one wave per
-// SIMD issuing LDS record reads, index arithmetic, FMAs, splits and ring writes back to back.  This form has no roles:
+// Gather-GEMM: the MPLayer update and the node-side pull of its backward at the reference's default width
+// (atom_feature_size = 256, nmrgnn/model.py:22) WITHOUT the aggregate in HBM.  nmrgnn/layers.py:26-46:
+//     forward   h' = act(v * sum_n A_n W_n) + h,     A[i][(n, l)]  = sum_j   e[i,j,n] h[nlist[i,j]][l]
+//     backward  dh = dH + sum_n B_n Wn_n,            B[t][(n, m)]  = sum_in  e[i,j,n] dP[i][m]     (edges (i,j) with nlist[i,j] = t)
+// Until round 3 both ran as aggregate -> [N, 768] in HBM (402 MB written, then read) -> GEMM, and the backward pull read
+// 3 KB of dA per incoming edge through L2.  Round 4's producer / consumer kernel (four producer waves walking the lists,
+// four consumer waves multiplying; 375-450 us per launch against 300-330) was removed in round 6 — DESIGN_HISTORY.md has its
+// measurements (profiles/r04_gg_ab.txt, r05e_gw_ab.txt): four producer waves per CU set the pace even with the L2 loads AND
+// the matrix products compiled out (386 us per launch) — one wave per SIMD issuing LDS record reads, index arithmetic, FMAs,
+// splits and ring writes back to back.  The kernel here is round 5's WINDOW form, with neither operand of the product in
+// HBM and no roles:
 //   * tile = 256 rows x 256 output columns, 256 threads = ONE wave per SIMD with the whole 512-register file: lane
 //     (r = lane & 31, half = lane >> 5) of wave w OWNS rows m0 + 64 w + 32 b + r (b = 0, 1) for the whole kernel: the
 //     gathered sums of a 16-column k-step are formed in its registers and split in place into the B operand of
@@ -15,20 +20,97 @@
 //   * the gather reads an LDS WINDOW: the 64-byte column slice of the 320 source rows around the tile (molecule batches:
 //     a row's sources lie in its own graph), brought in by LDS-DMA one k-step ahead, double-buffered.  A tile whose
 //     sources span more rows (whole proteins, lists across graphs) takes the same code with buffer loads from L2;
-//   * the weight operand is the shared one: the 16 KB of piece fragments of a (k-step, n) pair (PK_GG image, L2-resident)
-//     come in by LDS-DMA two steps ahead into a three-slot ring (slot = n); every wave reads all of them (A operand:
-//     lane = output column) and uses each fragment for both of its row blocks; 786 KB per 256 rows = 402 MB per launch
-//     through the DMA path;
+//   * the weight operand is the shared one: the 16 KB of piece fragments of a (k-step, n) pair (PK_GG image, L2-resident,
+//     built from w[l][m][n] directly in the k-step order slab-major, n inside — pack_bodies.cuh) come in by LDS-DMA two
+//     steps ahead into a three-slot ring (slot = n); every wave reads all of them (A operand: lane = output column) and
+//     uses each fragment for both of its row blocks; 786 KB per 256 rows = 402 MB per launch through the DMA path;
 //   * one step = one n of one k-step, ONE barrier: 48 MFMAs per wave in eight groups of six, and after each group ONE
 //     list entry (of both rows) of the NEXT k-step's gather — the matrix pipe works on the group while the wave issues
 //     the entry's LDS reads and FMAs.
-// Ranges as in mp_gg_kernel: forward operands are split unscaled (|A| >= 65504 raises the guard); the pull's sums are
-// multiplied by S 2^-x (S of dP, 2^x >= max_n sum |e_n| of the row) and the epilogue multiplies the row by 2^x / S.  A
-// raised guard is answered by mp_gg_repair_kernel.
-// (LDS-DMA goes through h2_common.cuh's asm statement: lds_dma16)
-typedef dma_i4 gw_i4;
-__device__ __forceinline__ gw_i4 gw_rsrc(const void* p, unsigned bytes) { return dma_rsrc(p, bytes); }
-__device__ __forceinline__ void gw_dma(gw_i4 rs, const void* lds_dst, int voff, int soff) { lds_dma16(rs, lds_dst, voff, soff); }
+// (LDS-DMA goes through h2_common.cuh's asm statement: lds_dma16.)
+// Ranges.  Forward operands are activations (split unscaled; an |A| >= 65504 raises the guard).  The pull's operand is a
+// gradient: the sums are multiplied by S * 2^-x before the split, S the power of two of dP (gemm_grad_scale) and 2^x >=
+// max_n sum_in |e_n| of the row, so no piece can overflow; the epilogue multiplies the row by 2^x / S.  A raised guard is
+// answered by mp_gg_repair_kernel: the same rows in plain fp32 on the vector ALU (slow, exact, an empty launch otherwise).
+#include <algorithm>
+#include <type_traits>
+
+#include "edge_fused.h"     // NG_LDS_BARRIER
+#include "mfma_gemm.cuh"    // act_apply
+#include "ng_internal.h"
+#include "h2_common.cuh"
+#include "pack_bodies.cuh"  // the PK_GG image: pk::gxp_wchunk, pk::GXP_WINV
+
+namespace ng {
+
+enum { GG_PADDED = 0, GG_CSR = 1, GG_REC = 2 };
+
+struct GgArgs {
+  int64_t M;               // rows (atoms)
+  int F, Kpad;             // width of the gathered operand (= output width); slots per row of the padded form
+  const float* G;          // gathered operand [M][F]: h (forward) / dP (pull)
+  const int32_t* idx;      // GG_PADDED / GG_CSR: source row of an entry
+  const float* ew;         //                     its E weights, [entries][E]
+  const int32_t* ptr;      // GG_CSR / GG_REC: row extents [M + 1]
+  const float4* rec;       // GG_REC: {source (int bits), e_0, e_1, e_2} per entry
+  const char* Wimg;        // PK_GG image
+  const float* w;          // the layer's weight in the reference layout (repair kernel)
+  int mode;                // 0 forward, 1 pull (PK_GG)
+  const float* rowscale;   // [M] or nullptr
+  const float* R;          // residual / base [M][F] or nullptr
+  float* Y;                // [M][F]
+  float* S;                // activation output [M][F] or nullptr
+  int act;
+  float* A_out;            // forward, training: the aggregate [M][E*F] as a by-product (the backward's dw = A^T dP reads it), or nullptr
+  const float* gscale;     // GRAD: {S, 1/S} of the gathered operand
+  int no_window;           // mp_gw_kernel: take the memory path for every tile (NG_MP_GW=nowin)
+  RangeGuard guard;
+};
+
+template <int LK, int E>
+__device__ __forceinline__ float4 gg_entry(const GgArgs& a, int64_t t) {
+  if (LK == GG_REC) return a.rec[t];
+  float4 r;
+  r.x = __builtin_bit_cast(float, a.idx[t]);
+  r.y = a.ew[t * E];
+  r.z = E > 1 ? a.ew[t * E + 1] : 0.f;
+  r.w = E > 2 ? a.ew[t * E + 2] : 0.f;
+  return r;
+}
+
+// The rows of the same call in plain fp32 (one workgroup per row at a time, thread = column), executed only when the
+// kernel below raised the guard.  F == blockDim.x == 256.
+template <int LK, int E>
+__global__ __launch_bounds__(256) void mp_gg_repair_kernel(GgArgs a) {
+  if (!range_guard_raised(a.guard)) return;
+  __shared__ float sA[3 * 256];
+  const int c = threadIdx.x, F = a.F;
+  for (int64_t row = blockIdx.x; row < a.M; row += gridDim.x) {
+    int64_t p0, p1;
+    if (LK == GG_PADDED) { p0 = row * a.Kpad; p1 = p0 + a.Kpad; }
+    else { p0 = a.ptr[row]; p1 = a.ptr[row + 1]; }
+    float s[3] = {0.f, 0.f, 0.f};
+    for (int64_t t = p0; t < p1; ++t) {
+      const float4 e4 = gg_entry<LK, E>(a, t);
+      const float g = a.G[(int64_t)__builtin_bit_cast(int, e4.x) * F + c];
+      s[0] = fmaf(e4.y, g, s[0]); s[1] = fmaf(e4.z, g, s[1]); s[2] = fmaf(e4.w, g, s[2]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < E; ++n) sA[n * 256 + c] = s[n];
+    __syncthreads();
+    float acc = 0.f;
+    for (int n = 0; n < E; ++n)
+      for (int k = 0; k < F; ++k) {
+        const float wv = a.mode == 0 ? a.w[((int64_t)k * F + c) * E + n] : a.w[((int64_t)c * F + k) * E + n];
+        acc = fmaf(sA[n * 256 + k], wv, acc);
+      }
+    float v = acc * (a.rowscale ? a.rowscale[row] : 1.0f);
+    v = act_apply(a.act, v);
+    if (a.S) a.S[row * F + c] = v;
+    a.Y[row * F + c] = v + (a.R ? a.R[row * F + c] : 0.f);
+  }
+}
 
 typedef float gw_f4 __attribute__((ext_vector_type(4)));
 constexpr int GW_THREADS = 256, GW_BM = 256, GW_WROWS = 320;
@@ -52,7 +134,7 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
   char* const wring = smem_gw + 2 * GW_WINB;                             // [3][8 column blocks][2 pieces][1 KB]
   float4* const srec = reinterpret_cast<float4*>(smem_gw + 2 * GW_WINB + 3 * GW_WSLOT);   // [GW_ZERO + 1]
   int* const ctl = reinterpret_cast<int*>(srec + GW_ZERO + 1);          // per wave: [4] lowest, [4] highest source, [4] tail entries
-  constexpr int WCHUNK = gx_wchunk(4);                                   // bytes of the image per (32-column slab, n)
+  constexpr int WCHUNK = pk::gxp_wchunk(4);                                   // bytes of the image per (32-column slab, n)
   const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, half = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int F = a.F, NK = F / 16;
@@ -190,8 +272,8 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
 
   const __amdgpu_buffer_rsrc_t rsG =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.G), 0, (unsigned)(a.M * a.F * 4), 0x00020000);
-  const gw_i4 dmaG = gw_rsrc(a.G, (unsigned)(a.M * a.F * 4));
-  const gw_i4 dmaW = gw_rsrc(a.Wimg, (unsigned)((int64_t)(F / 32) * E * WCHUNK));
+  const dma_i4 dmaG = dma_rsrc(a.G, (unsigned)(a.M * a.F * 4));
+  const dma_i4 dmaW = dma_rsrc(a.Wimg, (unsigned)((int64_t)(F / 32) * E * WCHUNK));
 
   // W fragments of step (kk, n) -> ring slot n: 16 instructions of 1 KB, 4 per wave
   auto req_w = [&](int kk, int n) __attribute__((always_inline)) {
@@ -200,7 +282,7 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
     for (int q = 0; q < 4; ++q) {
       const int f = wave * 4 + q;                        // (nb, p) = (f >> 1, f & 1)
       const int goff = (u * E + n) * WCHUNK + (((f >> 1) * 2 + ks) * 2 + (f & 1)) * 1024;
-      gw_dma(dmaW, wring + n * GW_WSLOT + f * 1024, lane * 16, goff);
+      lds_dma16(dmaW, wring + n * GW_WSLOT + f * 1024, lane * 16, goff);
     }
   };
   // window of k-step kk -> win[kk & 1]: rows wlo .. wlo + 319, 64 bytes each; 20 instructions of 1 KB (16 rows), 5 per wave.
@@ -213,7 +295,7 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
       // 16-byte piece q of window row r sits at position q ^ ((r >> 2) & 3): rows 4 apart share their banks (64-byte rows), the
       // swizzle spreads the same piece of such rows over four positions (the gather's row reads: 8-way -> 2-way conflicts)
       const unsigned vo = (unsigned)(wlo + 16 * i + (lane >> 2)) * (unsigned)(F * 4) + (unsigned)((((lane & 3) ^ ((lane >> 4) & 3)) * 16) + kk * 64);
-      gw_dma(dmaG, dst + i * 1024, (int)vo, 0);
+      lds_dma16(dmaG, dst + i * 1024, (int)vo, 0);
     }
   };
   static_assert(GW_WROWS == 4 * 5 * 16, "req_win");
@@ -492,7 +574,7 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
         r[c][i] = gw_f4{0.f, 0.f, 0.f, 0.f};
         if (a.R && m < a.M) r[c][i] = *reinterpret_cast<const gw_f4*>(a.R + m * F + 64 * c + 4 * cc);
       }
-    const float rs = GX_WINV * (GRAD ? a.gscale[1] * sfac[b] : 1.0f) * ((a.rowscale && valid[b]) ? a.rowscale[mrow[b]] : 1.0f);
+    const float rs = pk::GXP_WINV * (GRAD ? a.gscale[1] * sfac[b] : 1.0f) * ((a.rowscale && valid[b]) ? a.rowscale[mrow[b]] : 1.0f);
     const int64_t mb = m0 + 64 * wave + 32 * b;
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -530,3 +612,105 @@ __global__ __launch_bounds__(GW_THREADS, 1) void mp_gw_kernel(GgArgs a) {
     }
   }
 }
+
+// what the window gather-GEMM takes (everything else keeps the aggregate -> HBM -> GEMM path: mp_gg_supported)
+static bool gw_shape_ok(int64_t M, int F, int E, bool has_ptr, int Kpad) {
+  return E == 3 && F % 32 == 0 && M * (int64_t)F * 4 < ((int64_t)1 << 31) && (has_ptr || Kpad <= 16);
+}
+
+// DEFAULT for the forward of a call that does not keep the aggregate (inference: `A_save == nullptr`) on a batch of small
+// graphs (ng_ctx_set_graph_span: every row's sources lie inside the 320-row window): the window gather-GEMM.
+// Measured on MI355X at the bench batch (profiles/r05e_gw_ab.txt): 0.30-0.33 ms per layer against 0.134 + 0.227 for
+// aggregate -> HBM -> GEMM.  Training calls (the aggregate is written for dw = A^T dP: its row-per-lane stores cost the
+// kernel more than the round trip it saves) and the backward's pull (pull_win_kernel wins) keep their kernels unless
+// NG_MP_GG=1 asks for this one.
+bool mp_gw_infer_ok(ng_ctx* ctx, int64_t N, int K, int F, int E, bool csr, bool keeps_aggregate) {
+  return !sw().gemm_math_fp32 && !sw().mp_layered && !keeps_aggregate && F == 256 && E == 3 && (csr || K <= 16) &&
+         N >= sw().mp_gg_min_rows && N * (int64_t)F * 4 < ((int64_t)1 << 31) && ctx->graph_span > 0 && ctx->graph_span <= 256;
+}
+
+bool mp_gg_supported(int64_t N, int F, int E, int Kpad) {      // Kpad: slots per row of a padded list, 0 for CSR / record lists
+  // OPT-IN (NG_MP_GG=1): measured on MI355X the kernel does not beat aggregate -> HBM -> GEMM yet (375-450 us per launch
+  // against 134 + 240; the producer waves, four per CU, cannot keep enough gathers in flight — DESIGN section 4), so the
+  // default stays the two-kernel path.  Below NG_MP_GG_MIN_ROWS rows (default 8192 = 64 tiles) a call has too few
+  // 128-row tiles for 256 CUs either way.  Both are read with the other switches (ng_reload_env).
+  return sw().mp_gg_on && !sw().gemm_math_fp32 && !sw().mp_layered && F == 256 && N >= sw().mp_gg_min_rows &&
+         gw_shape_ok(N, F, E, Kpad == 0, Kpad);
+}
+
+// the PK_GG image of w for `mode` (cached / refreshed behind Adam when the image cache is on, else in the aux scratch)
+static char* gg_image(ng_ctx* ctx, hipStream_t st, int F, int E, int mode, const float* w, int* rc) {
+  const size_t bytes = (size_t)(F / 32) * E * pk::gxp_wchunk(4);
+  bool have = false;
+  char* img = (char*)cached_image(ctx, w, 15 + mode, bytes, &have);
+  const bool cached = img != nullptr;
+  if (!img) img = (char*)aux_workspace(ctx, bytes);
+  *rc = NG_OK;
+  if (!img) { *rc = NG_ERR_NOMEM; return nullptr; }
+  if (!have) {
+    PackJob j;
+    j.kind = PK_GG; j.i0 = E; j.i1 = F | (mode << 16); j.src[0] = w; j.dst[0] = img;
+    j.blocks = (int)cdiv((int64_t)(F / 32) * E * (F / 32) * 2 * 64, 256);
+    *rc = pack_launch(ctx, st, j);
+    if (*rc == NG_OK && cached) cache_set_job(ctx, w, 15 + mode, j);
+  }
+  return img;
+}
+
+template <int LK, bool GRAD>
+static int gg_launch(ng_ctx* ctx, hipStream_t st, GgArgs& a, int E, const char* tag) {
+  a.guard = range_guard_begin(ctx);
+  if (!a.guard.word) return NG_ERR_NOMEM;
+  if (!gw_shape_ok(a.M, a.F, E, a.ptr != nullptr, a.Kpad)) return fail(ctx, NG_ERR_INVALID, "gather-GEMM: shape outside the window form");
+  {
+    ProfScope ps(ctx, st, tag);
+    a.no_window = sw().mp_gw_nowin ? 1 : 0;
+    const unsigned wgrid = (unsigned)cdiv(a.M, GW_BM);
+    if (LK == GG_PADDED && a.Kpad <= 16)
+      hipLaunchKernelGGL((mp_gw_kernel<LK, 3, GRAD, 6>), dim3(wgrid), dim3(GW_THREADS), GW_LDS, st, a);
+    else
+      hipLaunchKernelGGL((mp_gw_kernel<LK, 3, GRAD, 8>), dim3(wgrid), dim3(GW_THREADS), GW_LDS, st, a);
+    NG_HIP(ctx, hipGetLastError());
+  }
+  ProfScope ps(ctx, st, "mp_gg_range_fallback");
+  const unsigned rgrid = (unsigned)std::min<int64_t>(a.M, (int64_t)ctx->num_cu * 8);
+  switch (E) {
+    case 1: hipLaunchKernelGGL((mp_gg_repair_kernel<LK, 1>), dim3(rgrid), dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((mp_gg_repair_kernel<LK, 2>), dim3(rgrid), dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((mp_gg_repair_kernel<LK, 3>), dim3(rgrid), dim3(256), 0, st, a); break;
+  }
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}
+
+// h_out = act(inv_degree * (A Wp)) + (residual ? h : 0),  A the neighbour aggregate of h over (row_ptr | K) lists
+int mp_gg_fwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, int act, int residual, const float* h,
+              const int32_t* row_ptr, const int32_t* col, const float* e, const float* inv_degree, const float* w,
+              float* h_out, float* s_save, float* A_out) {
+  int rc = NG_OK;
+  GgArgs a{};
+  a.A_out = A_out;
+  a.Wimg = gg_image(ctx, st, F, E, 0, w, &rc);
+  if (rc) return rc;
+  a.M = N; a.F = F; a.Kpad = K; a.G = h; a.idx = col; a.ew = e; a.ptr = row_ptr; a.w = w; a.mode = 0;
+  a.rowscale = inv_degree; a.R = residual ? h : nullptr; a.Y = h_out; a.S = s_save; a.act = act;
+  return row_ptr ? gg_launch<GG_CSR, false>(ctx, st, a, E, "mp_gg_fwd") : gg_launch<GG_PADDED, false>(ctx, st, a, E, "mp_gg_fwd");
+}
+
+// dh_in = dh_out + sum_n B_n Wn_n,  B the aggregate of dP over the incoming-edge records {source, e_0..e_2} (csc order)
+int mp_gg_pull(ng_ctx* ctx, hipStream_t st, int64_t N, int F, int E, const float* dP, const int32_t* csc_ptr,
+               const float* csc_rec, const float* w, const float* dh_out, float* dh_in, const float* gscale) {
+  int rc = NG_OK;
+  GgArgs a{};
+  a.Wimg = gg_image(ctx, st, F, E, 1, w, &rc);
+  if (rc) return rc;
+  if (!gscale) {
+    rc = gemm_grad_scale(ctx, st, dP, N, F, nullptr, &gscale);
+    if (rc) return rc;
+  }
+  a.M = N; a.F = F; a.Kpad = 0; a.G = dP; a.ptr = csc_ptr; a.rec = reinterpret_cast<const float4*>(csc_rec); a.w = w; a.mode = 1;
+  a.R = dh_out; a.Y = dh_in; a.act = NG_ACT_NONE; a.gscale = gscale;
+  return gg_launch<GG_REC, true>(ctx, st, a, E, "mp_gg_pull");
+}
+
+}  // namespace ng

@@ -29,7 +29,7 @@ enum PackKind : int {
   PK_MPW_BWD = 5,    // window backward: dst[0] = T pieces, dst[1] = N pieces, dst[2] / dst[3] = f32 T / N (blocks 96) or none (48)
   PK_MPW_F32 = 6,    // one f32 fragment image: i1 = mode, dst[0]
   PK_FC = 7,         // FC block: src[0..L-1] = W_l, i0 = L, dst[0] = Wf, dst[1] = Wb
-  PK_GG = 8,         // gather-GEMM image of an MPLayer weight (gemm_h2.hip): src[0] = w, i0 = E, i1 = F | mode << 16, dst[0] = img
+  PK_GG = 8,         // gather-GEMM image of an MPLayer weight (mp_gg.hip): src[0] = w, i0 = E, i1 = F | mode << 16, dst[0] = img
   PK_GX = 9,         // piece image of a GEMM weight operand (gemm_h2.hip: gx_launch): src[0] = W (or an MPLayer weight w), i0 = K,
                      // i1 = N | mode << 20 | nbw << 24, dst[0] = img; mode: pack_bodies.cuh gx_img
   PK_MP_PLAIN = 10,  // MPLayer weight w[l][m][n] as the plain GEMM operand Wp[n F + l][m]: src[0] = w, i0 = F, i1 = E, dst[0] = Wp
@@ -123,7 +123,7 @@ namespace ng {
 //   NG_HEAD_PATH=generic   the first head / embedding-gradient kernels
 //   NG_KNN=serial / lanes  one lane / 8-16 lanes per query atom in the kNN graph kernel (default: one wave per query)
 //   NG_KNN=cells / brute   the cell-grid neighbour search for every frame size / for none (default: frames >= 16384 atoms)
-//   NG_MP_GG=1             default-width MPLayer as the window gather-GEMM (mp_gw.cuh) for every eligible call, training included (default: inference of molecule batches only)
+//   NG_MP_GG=1             default-width MPLayer as the window gather-GEMM (mp_gg.hip) for every eligible call, training included (default: inference of molecule batches only)
 //   NG_MP_GG_MIN_ROWS=n    smallest call (rows) that takes the gather-GEMM (default 8192)
 //   NG_MP_GW=nowin         the window gather-GEMM reads every tile's sources from memory (test: same bits as the window)
 //   NG_MP_W16=0            the eight-wave window kernels at F == 64 (default: sixteen waves, mp_win16*.hip)

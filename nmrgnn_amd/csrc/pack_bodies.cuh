@@ -244,7 +244,7 @@ __device__ __forceinline__ bool fc_h2(int bid, int nb, int tid, int L, const flo
   return bad;
 }
 
-// ---- PK_GG (gemm_h2.hip: mp_gg_kernel): fp16 piece fragments of an MPLayer weight w[l][m][n] in the k-step order of the
+// ---- PK_GG (mp_gg.hip: mp_gw_kernel): fp16 piece fragments of an MPLayer weight w[l][m][n] in the k-step order of the
 // gather-GEMM.  Step s = c32 * E + n covers the 32 gathered columns c = 32 c32 .. + 31 of edge feature n; output column o:
 //   mode 0 (forward update):  value(c, o) = w[l = c][m = o][n]        (A[i][(n, l)] = sum_j e_n h[nbr_j][l])
 //   mode 1 (pull, backward):  value(c, o) = w[l = o][m = c][n]        (B[i][(n, m)] = sum_in e_n dP[src][m])
@@ -278,7 +278,9 @@ __device__ __forceinline__ void gg_img(int bid, int nb_, int tid, int E, int F, 
 // mode 2 / 3: the same two with W = Wp[ne F + l][m] = w[l][m][ne], the GEMM form of an MPLayer weight (PK_MP_PLAIN), read from w
 // itself: the image does not wait for the plain copy, so both are rebuilt in the one launch behind the weight update
 constexpr int GXP_BK = 32;
-constexpr float GXP_WSCALE = 256.0f;
+constexpr float GXP_WSCALE = 256.0f, GXP_WINV = 1.0f / 256.0f;   // pieces of 2^8 W; the products' epilogues multiply by 2^-8
+// bytes of a PK_GX image per (column tile, k-step), of a PK_GG image (nbw = 4) per step: [2 nbw n-blocks][k-step of 16][piece][1 KB]
+constexpr int gxp_wchunk(int nbw) { return 2 * nbw * 2 * 2 * 1024; }
 __device__ __forceinline__ float gx_src(const float* __restrict__ W, int mode, int K, int N, int k, int n) {
   switch (mode) {
     case 0: return W[(int64_t)k * N + n];

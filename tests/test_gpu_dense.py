@@ -51,7 +51,10 @@ def rows(spec, cu, nout):
     return {"trip2": 2 * cu * 64 + 1,                           # tall kernels: first tile of the persistent grid's 2nd trip
             "tile-": 128 * 128 * cu // nout,                     # dense_fwd: M Nout <= 128 128 num_cu -> 64 x 64 tiles
             "tile+": 128 * 128 * cu // nout + 1,                 #            above -> 128 x 128 / 128 x 64 tiles
-            "big": 128 * 128 * cu // 64 + 1}[spec]               # above the 64 x 64 threshold for every Nout >= 64
+            "big": 128 * 128 * cu // 64 + 1,                     # above the 64 x 64 threshold for every Nout >= 64
+            # two 256-column tiles of a 128 x 256 kernel: a multiple of 8 row tiles above the short kernel's range
+            # (row tiles x 2 column tiles x 2 > cu) -> the permuted (row tile, column tile) mapping; one row more -> the plain one
+            "perm8": 128 * 8 * (cu // 32 + 1), "perm8+": 128 * 8 * (cu // 32 + 1) + 1}[spec]
 
 
 def dw8_plan(cu, M, Kin, Nout):
@@ -89,6 +92,12 @@ def _cases():
     for k, n in ((64, 128), (96, 384), (256, 256)):
         for m in (4095, 4096, 4097, 70001):
             c.append((f"h2long-{k}x{n}-M{m}", m, k, n, "h2"))
+    # two 256-column tiles: the forward (256 x 512) and dX (512 x 256) on the (row tile, column tile) mappings of the 128 x 256
+    # kernel; at 4096 / 4097 rows (32 / 33 row tiles) a 256-CU device still takes the short kernel
+    for m in (4096, 4097, "perm8", "perm8+"):
+        c.append((f"h2long-256x512-M{m}", m, 256, 512, "h2"))
+    for m in ("perm8", "perm8+"):
+        c.append((f"dw8-512x256-M{m}", m, 512, 256, "h2"))
     for m in (4097, 70001):                                     # 128-column tiles: dX split, dW on 128 x 128 tiles
         c.append((f"h2long-384x128-dw128-M{m}", m, 384, 128, "h2"))
     for k in (128, 768):                                         # split-operand, short (M >= 256, N % 256, K % 128)

@@ -2,7 +2,7 @@
 ng_mp_layer_bwd[_rec|_csr], ng_mp_aggregate[_csr] and ng_mp_edge_records, against the float64 statement of tests/mp_layer_ref.py.
 The kernels that serve no other width: the two-slab agg_win_kernel / egrad_win_kernel (mp_win.hip), pull_win_kernel<1|2|3>,
 csr_edge_grad_wide_kernel<E,16> / csr_scatter_pull_wide_kernel<E,16> and mp_dp_kernel (mp_csr.hip), and the window gather-GEMM
-mp_gw_kernel<PADDED|CSR|REC, 3, GRAD, 6|8> (mp_gw.cuh, gemm_h2.hip).
+mp_gw_kernel<PADDED|CSR|REC, 3, GRAD, 6|8> (mp_gg.hip).
 
 Every output is filled with NaN before the call; the graph span is announced per case and reset behind it.  Two families:
   exact   inputs on coarse binary grids (mp_layer_ref.exact_inputs): every output must equal the float64 statement BIT FOR BIT —

@@ -1,4 +1,4 @@
-"""Gather-GEMM form of the default-width MPLayer (csrc/mp_gw.cuh: mp_gw_kernel, round 5 — 256-row tiles, the gathered
+"""Gather-GEMM form of the default-width MPLayer (csrc/mp_gg.hip: mp_gw_kernel, round 5 — 256-row tiles, the gathered
 operand formed in registers from an LDS window; the neighbour aggregate never reaches HBM, the backward's node-side pull
 gathers dP rows the same way) against a float64 statement of nmrgnn/layers.py:26-46 + model.py:165-167 and against the
 aggregate -> HBM -> GEMM kernels it would replace.  (Round 4's producer / consumer kernel left the library in round 6; shapes

@@ -1,4 +1,4 @@
-"""which rows of the window gather-GEMM differ from the float64 reference (debug helper for mp_gw.cuh)"""
+"""which rows of the window gather-GEMM differ from the float64 reference (debug helper for mp_gg.hip)"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))

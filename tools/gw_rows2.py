@@ -1,4 +1,4 @@
-"""debug helper for mp_gw.cuh: only list entry J of every row carries weight; which J are wrong"""
+"""debug helper for mp_gg.hip: only list entry J of every row carries weight; which J are wrong"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))

@@ -1,4 +1,4 @@
-"""debug helper for mp_gw.cuh: which source row does entry J of each row actually gather"""
+"""debug helper for mp_gg.hip: which source row does entry J of each row actually gather"""
 import os, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))

@@ -1,6 +1,6 @@
 // LDS store THROUGHPUT by workgroup size and stores in flight per wait (round 5): how fast can the edge backward's piece
 // images be written?  One workgroup per CU; every wave writes `nw` stores, then s_waitcnt lgkmcnt(0); reports bytes per ns per CU.
-//   pat 0  ds_write_b64, G-image map (hx_prow_g, stride 272)      pat 1  ds_write_b64 contiguous
+//   pat 0  ds_write_b64, G-image map (h2_prow, stride 272)      pat 1  ds_write_b64 contiguous
 //   pat 2  ds_write_b128 contiguous                                pat 3  ds_write_b32 contiguous
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -83,8 +83,8 @@ __device__ __forceinline__ void rs_dw_gemm(f32x16 (&acc)[2], float* __restrict__
       b[p] = u32x4{(unsigned)lane, 1u, 2u, 3u}; a[p] = u32x4{(unsigned)lane, 5u, 6u, 7u};
       asm volatile("" : "+v"(b[p]), "+v"(a[p]));
 #else
-      b[p] = hx_tr_frag(zb + p * HX_PIECE_Z + ((ks & 1) + 32 * (ks >> 1)) * HX_ROWZ, 2 * HX_ROWZ);
-      a[p] = hx_tr_frag(g0 + p * HX_PIECE_G + 16 * ks * HX_ROWG, HX_ROWG);
+      b[p] = h2_tr_frag(zb + p * HX_PIECE_Z + ((ks & 1) + 32 * (ks >> 1)) * HX_ROWZ, 2 * HX_ROWZ);
+      a[p] = h2_tr_frag(g0 + p * HX_PIECE_G + 16 * ks * HX_ROWG, HX_ROWG);
 #endif
     }
     acc[0] = mma3(a, b, acc[0]);
@@ -96,7 +96,7 @@ __device__ __forceinline__ void rs_dw_gemm(f32x16 (&acc)[2], float* __restrict__
     asm volatile("" : "+v"(a[0]), "+v"(a[1]));
 #else
 #pragma unroll
-    for (int p = 0; p < 2; ++p) a[p] = hx_tr_frag(g0 + 64 + p * HX_PIECE_G + 16 * ks * HX_ROWG, HX_ROWG);
+    for (int p = 0; p < 2; ++p) a[p] = h2_tr_frag(g0 + 64 + p * HX_PIECE_G + 16 * ks * HX_ROWG, HX_ROWG);
 #endif
     acc[1] = mma3(a, b, acc[1]);
 #ifndef RS_NO_DB
@@ -208,7 +208,7 @@ __device__ __forceinline__ RsGeo rs_geo(int lane_in, int zk, int zrt) {
   g.half = g.lane >> 5; g.l31 = g.lane & 31;
   g.row = 32 * zrt + g.l31;
   g.col0 = 32 * zk + 4 * g.half;
-  g.prz = hx_prow_z(g.row); g.prg = hx_prow_g(g.row);
+  g.prz = hx_prow_z(g.row); g.prg = h2_prow(g.row);
   return g;
 }
 
