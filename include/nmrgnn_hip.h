@@ -377,12 +377,17 @@ int ng_fc_head_fwd(ng_ctx*, void* stream, int64_t N, int F, int L, int C, int ac
  * The reference hands the model a NEW graph tuple every step (nmrgnn/library.py:88-89, main.py:79); its backward is
  * TensorFlow's unsorted scatter-add behind tf.gather (layers.py:33).  The engine's backward pulls over incoming edges
  * instead, which needs, per batch, the transposed lists
- *   csc_ptr [N+1], csc_edge [<= n_entries]: the entries (eid = i*K + j for padded lists with K > 0 and slots
- *   edges[eid] == 0 dropped; eid = CSR entry index when K == 0, edges may be NULL = every entry live) whose neighbour
- *   is atom t, for t = 0..N-1, ascending eid inside a target (= a stable sort by target), csc_ptr[N] = number of
- *   live entries; and, for padded lists, nlist_c [N*K] (may be NULL): nlist with padded slots replaced by the atom's
- *   own index (their weight is exactly 0), the list the MP kernels gather through.
- * A deterministic counting sort in HIP; scratch comes from the context.  All pointers are device pointers. */
+ *   csc_ptr [N+1], csc_edge [<= n_entries]: the LIVE entries (eid = i*K + j for padded lists with K > 0; eid = CSR entry
+ *   index when K == 0) whose neighbour is atom t, for t = 0..N-1, ascending eid inside a target (= a stable sort by
+ *   target), csc_ptr[N] = number of live entries; and, for padded lists, nlist_c [N*K] (may be NULL): nlist with every
+ *   entry that is not live replaced by the atom's own index eid / K (its weight is exactly 0), the list the MP kernels
+ *   gather through.
+ *   An entry is live when edges[eid] > 0 AND 0 <= nlist[eid] < N.  Everything else is dropped like a padded slot: a
+ *   distance of 0, -0, a negative one, NaN (the same rule as ng_build_live_edges and every consumer's mask d_src > 0:
+ *   "not > 0", so +inf is live), and a target outside [0, N) whatever its distance.  edges may be NULL: every entry with
+ *   a target inside [0, N) is live.  csc_edge is written up to csc_ptr[N] and not beyond.
+ * A deterministic counting sort in HIP; scratch comes from the context.  All pointers are device pointers; nlist may be
+ * NULL only when n_entries == 0. */
 int ng_build_incoming_lists(ng_ctx*, void* stream, int64_t N, int K, int64_t n_entries, const int32_t* nlist,
                             const float* edges, int32_t* nlist_c, int32_t* csc_ptr, int32_t* csc_edge);
 size_t ng_incoming_lists_scratch_bytes(int64_t N, int64_t n_entries);

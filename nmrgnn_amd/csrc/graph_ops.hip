@@ -3,8 +3,9 @@
 // torch sort / bincount / cumsum launches.  The reference feeds a NEW graph every step (nmrgnn/library.py:88-89), so
 // this work is per step, not per data set.
 //
-//   entry id  eid = i*K + j (padded lists, slots with edges == 0 dropped: they carry e == 0 exactly, model.py:261)
-//             or the CSR entry index (row_ptr form: every entry is live)
+//   entry id  eid = i*K + j (padded lists; only LIVE slots are listed: edges > 0 and 0 <= target < N.  Every other slot
+//             carries e == 0 exactly, model.py:261, or has no atom to send to)
+//             or the CSR entry index (row_ptr form: every entry with a target in [0, N) is live)
 //   csc_ptr[t] .. csc_ptr[t+1]: the entries whose neighbour is atom t, in ASCENDING entry id — the order a stable sort by
 //   target gives, which every bit-for-bit test of the backward relies on.
 //
@@ -521,6 +522,8 @@ extern "C" size_t ng_incoming_lists_scratch_bytes(int64_t N, int64_t n_entries) 
 
 extern "C" int ng_build_incoming_lists(ng_ctx* ctx, void* stream, int64_t N, int K, int64_t n_entries, const int32_t* nlist,
                                        const float* edges, int32_t* nlist_c, int32_t* csc_ptr, int32_t* csc_edge) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, nlist || n_entries <= 0, "incoming lists: nlist required");
   NG_REQUIRE(ctx, N >= 0 && n_entries >= 0 && n_entries < ((int64_t)1 << 31), "incoming lists: sizes out of range");
   NG_REQUIRE(ctx, csc_ptr && csc_edge, "incoming lists: csc_ptr / csc_edge required");
   NG_REQUIRE(ctx, nlist_c == nullptr || K > 0, "incoming lists: nlist_c needs the padded form (K > 0)");
