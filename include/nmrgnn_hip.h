@@ -95,9 +95,15 @@ int ng_ctx_reserve(ng_ctx* ctx, uint64_t bytes);
  *   ng_replay_arm    on: arm before capturing (and leave armed while replaying: the captured nodes hold the block's address);
  *                    off: eager calls take their arguments again.
  *   ng_replay_stage  ONE eager launch per replayed step, before the graph launch: stores `seed` and Adam's rate for `step`
- *                    (the expression of ng_adam_step: same bits), clears the operand-range guard word, and copies up to 8
+ *                    (the expression of ng_adam_step: same bits) and a version of its own for the images the step's armed
+ *                    ng_adam_step rebuilds (a recorded launch would stamp every replay with the one version frozen into it,
+ *                    and an image once flagged "weights out of the fp16 piece range" could never lose the flag: the flag
+ *                    is lowered by a rebuild with ANOTHER version), clears the operand-range guard word, and copies up to 8
  *                    buffers (whole 32-bit words, device to device) — the step's inputs into the static buffers the captured
  *                    chain reads.  Inference replays need it only for the copies (seed / step are then ignored: pass step 1).
+ *                    EVERY armed ng_adam_step, eager (a warm-up step) or replayed, needs a staging of its own in front of
+ *                    it: it reads the staged rate, and two armed steps behind one staging would rebuild their images under
+ *                    one version.
  * A replayed TRAINING step changes the weights on the device while none of the library's host code runs: ng_adam_step's
  * bookkeeping of the packed-weight-image cache (the weight version, which images its launch rebuilt) happened once, at capture.
  *   ng_replay_token   after the capture: identifies the set of cached images the captured ng_adam_step rebuilds (0: none).

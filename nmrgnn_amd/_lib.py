@@ -197,6 +197,10 @@ class Context:
                           "(no HIP device? nmrgnn_amd needs an AMD GPU)")
         self.handle = h
         self.device_index = device_index
+        # which Engine last took the packed-weight-image cache (ng_weights_frozen owner; 0: none yet) and how often it changed
+        # hands between engines (Engine._own_images keeps both; replay.TrainStepReplay reads the count)
+        self.image_owner = 0
+        self.owner_switches = 0
 
     def check(self, rc: int, what: str):
         if rc != 0:

@@ -360,6 +360,7 @@ struct StageArgs {
   int n;
   uint64_t seed;
   float lr_t;
+  unsigned pack_ver;
   uint64_t* state;
   unsigned* guard_word;
 };
@@ -367,6 +368,7 @@ __global__ __launch_bounds__(256) void replay_stage_kernel(StageArgs a) {
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     a.state[0] = a.seed;
     reinterpret_cast<float*>(a.state)[2] = a.lr_t;
+    reinterpret_cast<unsigned*>(a.state)[ng::NG_REPLAY_VER_WORD] = a.pack_ver;
     *a.guard_word = 0;
   }
   for (int c = 0; c < a.n; ++c)
@@ -397,6 +399,9 @@ extern "C" int ng_replay_stage(ng_ctx* ctx, void* stream, uint64_t seed, float l
   a.n = n_copies; a.seed = seed;
   // the expression of ng_adam_step: the same bits reach the kernel
   a.lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)step)) / (1.0 - std::pow((double)beta1, (double)step)));
+  // the image version of this step's armed repack launch: one per staging, bit 31 clear (pack_flag_version sets it: never that
+  // of an eager launch), never 0
+  a.pack_ver = 0x40000000u | (++ctx->replay_serial & 0x3FFFFFFFu);
   a.state = reinterpret_cast<uint64_t*>(sm + ng::NG_REPLAY_STATE_OFFSET);
   a.guard_word = reinterpret_cast<unsigned*>(sm + ng::NG_SMALL_BYTES - 64);
   const int grid = (int)std::min<uint64_t>(256, std::max<uint64_t>(1, (most + 255) / 256));

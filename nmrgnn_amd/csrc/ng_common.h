@@ -40,8 +40,11 @@ struct PackJob {
   int i0 = 0, i1 = 0;
   const float* src[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   void* dst[4] = {nullptr, nullptr, nullptr, nullptr};
-  // weights out of the fp16 piece range (|2^8 w| >= 65504): the packer stores the image VERSION into *flag (a consumer
-  // compares with the version it was handed: nothing ever has to be cleared) and raises the per-call guard if there is one
+  // weights out of the fp16 piece range (|2^8 w| >= 65504): the packer stores the image VERSION into flag[0], and into flag[1]
+  // at every launch; a consumer compares the two words, so nothing has to be cleared — AS LONG AS no two launches on one image
+  // carry the same version.  Eager launches take it from the context's weight version; a launch recorded in a HIP graph has
+  // its argument frozen at capture and reads the word ng_replay_stage writes per step instead (repack.hip: ver_dev).  The
+  // packer also raises the per-call guard if there is one
   unsigned* flag = nullptr;
   RangeGuard guard = {nullptr, 0};
 };
@@ -107,6 +110,7 @@ struct ng_ctx {
   // the weights but runs no host bookkeeping, so every OTHER cached image kept reading as valid with weights of N steps ago)
   std::map<uint64_t, std::vector<WImage*>> wjobs_private_sel;
   uint64_t replay_token = 0;
+  uint32_t replay_serial = 0;      // stagings so far (ng_replay_stage): behind the per-step image version of armed repack launches
 };
 
 namespace ng {
@@ -178,9 +182,10 @@ void* workspace(ng_ctx* ctx, size_t bytes);
 void* aux_workspace(ng_ctx* ctx, size_t bytes);
 constexpr size_t NG_SMALL_BYTES = 64 * 1024;
 void* small_scratch(ng_ctx* ctx);      // NG_SMALL_BYTES, allocated once per context, address stable until ng_ctx_destroy
-// staged per-step state of a replayed training step: {u64 seed; f32 lr_t; ...} at a fixed place of the small scratch;
+// staged per-step state of a replayed training step: {u64 seed; f32 lr_t; -; u32 image version; ...} at a fixed place of the small scratch;
 // nullptr unless the context is armed (ng_replay_arm)
 constexpr size_t NG_REPLAY_STATE_OFFSET = NG_SMALL_BYTES - 256;
+constexpr int NG_REPLAY_VER_WORD = 4;      // 32-bit word of the block: the image version of the step's armed repack launch
 const uint64_t* replay_state(ng_ctx* ctx);
 // Frozen-weight image cache.  Returns nullptr when the cache is off (pack into scratch as before); otherwise a
 // persistent buffer of `bytes` for (src, kind) with *valid = true when it already holds the image of the current

@@ -18,8 +18,11 @@ __global__ __launch_bounds__(PKB) void pack_one_kernel(PackJob j, unsigned ver) 
 }
 
 // block0[k] = first block of job k (ascending), block0[njobs] = grid
+// `ver_dev` (armed launches: the word ng_replay_stage writes once per step, 0 = nothing staged): a recorded launch's `ver`
+// argument is frozen at capture, and with one version at every replay a flag raised once could never be lowered again
 __global__ __launch_bounds__(PKB) void repack_all_kernel(const PackJob* __restrict__ jobs, const unsigned* __restrict__ block0, int njobs,
-                                                         unsigned ver) {
+                                                         unsigned ver, const unsigned* __restrict__ ver_dev) {
+  if (ver_dev) { const unsigned staged = *ver_dev; ver = staged ? staged : ver; }
   int k = 0;
   for (int t = 1; t < njobs; ++t) k = blockIdx.x >= block0[t] ? t : k;      // uniform: scalar loads
   const PackJob j = jobs[k];
@@ -81,7 +84,9 @@ int repack_all(ng_ctx* ctx, hipStream_t st, const void* lo, const void* hi) {
   };
   const void* table = nullptr;
   int table_blocks = 0;
+  const unsigned* ver_dev = nullptr;
   if (ctx->replay_armed) {
+    if (const uint64_t* rs = replay_state(ctx)) ver_dev = reinterpret_cast<const unsigned*>(rs) + NG_REPLAY_VER_WORD;
     // a launch that may be captured (ng_replay_arm): its own immutable table.  The shared one below is rewritten whenever
     // another engine of the device updates its weights — a replayed step then rebuilt the OTHER engine's images (round 5:
     // two trainers on one device diverged at the second replayed step).  Uploaded by the warm-up steps, before any capture.
@@ -126,7 +131,7 @@ int repack_all(ng_ctx* ctx, hipStream_t st, const void* lo, const void* hi) {
     ProfScope ps(ctx, st, "repack_all");
     const size_t jb = ((size_t)n * sizeof(PackJob) + 255) / 256 * 256;
     hipLaunchKernelGGL(repack_all_kernel, dim3(table_blocks), dim3(PKB), 0, st, (const PackJob*)table,
-                       (const unsigned*)((const char*)table + jb), n, pack_flag_version(ctx));
+                       (const unsigned*)((const char*)table + jb), n, pack_flag_version(ctx), ver_dev);
     NG_HIP(ctx, hipGetLastError());
   }
   for (ng_ctx::WImage* w : sel) w->ver = ctx->wver;

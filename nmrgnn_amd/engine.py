@@ -142,6 +142,11 @@ class Engine:
         self._jgate = None                    # the gate words of the last backward's J check (edge_grad_table_report)
         self._wgen = 0                        # bumped whenever the weights change: a table kept over calls (frozen weights)
         self._table_cache = None
+        # announced weight changes (load_state_dict, weights_changed()): they leave every packed image invalid, and a captured
+        # chain — recorded while the images were valid — holds no pack launch.  ``_images_gen`` is the value of ``_announced``
+        # at the last adam_step that rebuilt the images (cache_images): replay.py refuses a chain in between
+        self._announced = 0
+        self._images_gen = 0
         # the row count of the table's own MLP launches (2T: the table and its midpoints), a device word the live kernels read
         self._rows_2t = torch.full((1,), 2 * self._table_points(), dtype=torch.int32, device=self.device)
         Engine._ids += 1
@@ -158,12 +163,26 @@ class Engine:
         if not on:
             self._ck(self.lib.ng_weights_frozen(self.ctx.handle, 0), "ng_weights_frozen")
 
+    def _own_images(self):
+        """ng_weights_frozen under this engine's id.  The context object counts how often the cache changed hands BETWEEN
+        ENGINES (the library then drops every registered rebuild job: an engine coming back re-registers only what its next
+        calls use); replay.py reads the count.  Only engines are counted: a caller that passes an owner id of its own to
+        ng_weights_frozen at the C ABI drops the jobs too, without the count moving — such a caller must not share a context
+        with a TrainStepReplay in use."""
+        ctx = self.ctx
+        if ctx.image_owner != self._id:
+            ctx.image_owner = self._id
+            ctx.owner_switches += 1
+        self._ck(self.lib.ng_weights_frozen(ctx.handle, self._id), "ng_weights_frozen")
+
     def weights_changed(self):
         self._wgen += 1
+        self._announced += 1
         self._ck(self.lib.ng_weights_changed(self.ctx.handle), "ng_weights_changed")
 
     def _on_params_changed(self):
         self._wgen += 1
+        self._announced += 1
         self.lib.ng_weights_changed(self.ctx.handle)
 
     # ------------------------------------------------------------------ helpers
@@ -209,7 +228,7 @@ class Engine:
                 raise ValueError("forward(loss=...) forms parameter gradients; keep_tape=\"inputs\" keeps no tape for them")
         if not (self._frozen or self.cache_images):
             return self._forward(batch, training, noise, dropout_mask, seed, keep_tape, loss)
-        self._ck(self.lib.ng_weights_frozen(self.ctx.handle, self._id), "ng_weights_frozen")
+        self._own_images()
         try:
             return self._forward(batch, training, noise, dropout_mask, seed, keep_tape, loss)
         finally:
@@ -518,7 +537,7 @@ class Engine:
         # and run as ONE launch before the node gradients are handed on (ng_defer_reductions: same bits, ~45 us less)
         self._ck(lib.ng_defer_reductions(h, st, 1 if self.defer_reductions and param_grad else 0), "ng_defer_reductions")
         if self.cache_images:
-            self._ck(lib.ng_weights_frozen(h, self._id), "ng_weights_frozen")
+            self._own_images()
         try:
             self._backward(tp, dpeaks, on_node_grads, lib, h, st, edge_grad, bool(param_grad))
         finally:
@@ -731,11 +750,13 @@ class Engine:
         self._wgen += 1
         P = self.params
         if self.cache_images:       # the update is followed by ONE launch that rebuilds this engine's packed weight images
-            self._ck(self.lib.ng_weights_frozen(self.ctx.handle, self._id), "ng_weights_frozen")
+            self._own_images()
         try:
             self._ck(self.lib.ng_adam_step(self.ctx.handle, self._st(), P.numel, ptr(P.flat), ptr(P.grad),
                                            ptr(self.adam_m), ptr(self.adam_v), lr, beta1, beta2, eps,
                                            self.adam_t, grad_scale), "ng_adam_step")
+            if self.cache_images:   # every registered image of this engine is that of the new weights
+                self._images_gen = self._announced
         finally:
             if self.cache_images:
                 self.lib.ng_weights_frozen(self.ctx.handle, 0)

@@ -57,6 +57,17 @@ class TrainStepReplay:
     Single process (the gradient all-reduce of a data-parallel world is not captured).  The loss tensor returned by
     ``step`` is a static buffer: read it before the next step.
 
+    After a weight change: the chain was recorded while every packed weight image was valid and holds no pack launch; its
+    own Adam launch is followed by the recorded rebuild of its images, so replayed steps may follow one another, and eager
+    ``Trainer.step`` calls of the same engine (any shape) may be mixed in, and steps of other engines of the device (where
+    another engine took the image cache over since the chain's images were last registered and an eager step moved the weights
+    since the last replayed one, one zero-rate eager step of the captured shape runs first: ``_refresh``).
+    An ANNOUNCED change — ``params.load_state_dict``,
+    ``engine.weights_changed()`` — leaves the images invalid: the next ``step`` raises ValueError until one eager
+    ``Trainer.step`` has run (it packs what it uses and rebuilds every other image behind its update), or a new replay
+    object is built.  A replayed step counts as a weight change of the engine like ``Engine.adam_step`` does (tables kept
+    for frozen weights, ``ShiftRestraint``, ``ForwardReplay``).
+
     ``names`` (int32 name ids [N]) captures the trainer's metric launch into the step (``Trainer(..., metrics=...)``);
     the ids become one more staged buffer, and a ``step`` without ``names`` keeps the previous step's ids."""
 
@@ -95,6 +106,26 @@ class TrainStepReplay:
         self._gb = gb
         return self.trainer.step(gb, self.s_y, self.s_w, names=self.s_names)
 
+    def _keep(self):
+        """the training state an eager step at a staged rate of ZERO still changes: Adam's moments, the host-side step
+        counters, the metric sums"""
+        eng, tr = self.eng, self.trainer
+        nm = tr.metrics if self.s_names is not None else None
+        keep_nm = (nm.moments.clone() if nm.moments is not None else None, nm.updates) if nm is not None else None
+        return (eng.adam_m.clone(), eng.adam_v.clone(), eng.adam_t, tr.step_count, nm, keep_nm)
+
+    def _restore(self, keep):
+        eng, tr = self.eng, self.trainer
+        eng.adam_m.copy_(keep[0]); eng.adam_v.copy_(keep[1])
+        eng.adam_t, tr.step_count = keep[2], keep[3]
+        nm, keep_nm = keep[4], keep[5]
+        if nm is not None:        # the warm-up steps' metric updates are not steps either
+            if keep_nm[0] is None:
+                nm.moments.zero_()
+            else:
+                nm.moments.copy_(keep_nm[0])
+            nm.updates = keep_nm[1]
+
     def _capture(self):
         eng, tr = self.eng, self.trainer
         P = eng.params
@@ -103,9 +134,7 @@ class TrainStepReplay:
         # them every packed image the captured chain will read — stay as they are bit for bit; Adam's moments, which the
         # warm-up does change, and the host-side step counters (the capture itself runs no kernel but counts steps) are
         # put back afterwards.
-        keep = (eng.adam_m.clone(), eng.adam_v.clone(), eng.adam_t, tr.step_count)
-        nm = tr.metrics if self.s_names is not None else None
-        keep_nm = (nm.moments.clone() if nm.moments is not None else None, nm.updates) if nm is not None else None
+        keep = self._keep()
         cur = torch.cuda.current_stream(eng.device)
         self._stream.wait_stream(cur)
         with torch.cuda.stream(self._stream):
@@ -122,18 +151,42 @@ class TrainStepReplay:
                 self._token = int(tok.value)
             finally:
                 eng.lib.ng_replay_arm(eng.ctx.handle, 0)
-            eng.adam_m.copy_(keep[0]); eng.adam_v.copy_(keep[1])
-            eng.adam_t, tr.step_count = keep[2], keep[3]
-            if nm is not None:        # the warm-up steps' metric updates are not steps either
-                if keep_nm[0] is None:
-                    nm.moments.zero_()
-                else:
-                    nm.moments.copy_(keep_nm[0])
-                nm.updates = keep_nm[1]
+            self._restore(keep)
         cur.wait_stream(self._stream)
+        # the weight generation as of this object's last step, and the count of changes of hands of the device's image cache
+        # as of the last time EVERY image of the chain was registered for a rebuild (here and in _refresh: a replayed step
+        # registers nothing, so a change of hands in front of it still counts afterwards)
+        self._wgen_seen, self._switches_seen = eng._wgen, eng.ctx.owner_switches
+
+    def _refresh(self):
+        """One eager step of the captured shape at a staged rate of ZERO, on the static buffers as they stand: its forward packs
+        and registers every image the chain reads that is not current, its update leaves the parameters bit for bit.  Needed
+        when the device's image cache changed hands since the chain's images were last registered, here or at the capture
+        (the library then forgets how to rebuild this engine's images, and neither a replayed step nor ng_replay_commit
+        registers any again) AND an eager step moved the weights since this object's last step: that step re-registered only
+        the images its own shape uses — a batch below 256 rows keeps none for the default-width GEMMs — and rebuilt only
+        those behind its update."""
+        eng = self.eng
+        keep, gb, wgen = self._keep(), self._gb, eng._wgen      # (the recorded chain reads the buffers of ITS batch: it stays)
+        eng._ck(eng.lib.ng_replay_arm(eng.ctx.handle, 1), "ng_replay_arm")
+        try:
+            _stage(eng, 1, 0.0, 1, [])
+            self._one_step()
+        finally:
+            eng.lib.ng_replay_arm(eng.ctx.handle, 0)
+            self._gb = gb
+        self._restore(keep)
+        eng._wgen = wgen            # the weights did not move: what is kept per weight generation stays valid
+        self._switches_seen = eng.ctx.owner_switches
 
     def step(self, graph_tuple, y, w, names=None):
         eng, tr = self.eng, self.trainer
+        if eng.cache_images and eng._images_gen != eng._announced:
+            raise ValueError("TrainStepReplay.step: the weights were changed by a load or weights_changed() and no step has "
+                             "rebuilt their packed images since; the captured chain holds no pack launch and would read the "
+                             "old ones.  Run one eager Trainer.step first, or build a new TrainStepReplay")
+        if eng.cache_images and self._wgen_seen != eng._wgen and self._switches_seen != eng.ctx.owner_switches:
+            self._refresh()
         atoms, nlist, edges, inv = graph_tuple
         # the seed sequence of Trainer.step (rank 0)
         seed = (0x9E3779B97F4A7C15 ^ (eng.adam_t * 1000003)) & ((1 << 63) - 1)
@@ -154,16 +207,22 @@ class TrainStepReplay:
         finally:
             eng.lib.ng_replay_arm(eng.ctx.handle, 0)
         eng.adam_t += 1
+        eng._wgen += 1          # Engine.adam_step's: whatever is kept per weight generation (the table of frozen weights) is stale
         tr.step_count += 1
         if self.s_names is not None:
             tr.metrics.updates += 1
+        self._wgen_seen = eng._wgen
         return self.loss
 
 
 class ForwardReplay:
     """``engine.forward(frames_to_batch(atoms, positions, K))`` for ONE frame shape — the kNN graph build on the GPU plus
     the model forward of a structure (``eval-struct``'s inner loop, nmrgnn/main.py:236-245) — replayed as a HIP graph.
-    ``__call__(positions[n,3])`` returns the static ``peaks[n]`` tensor (read it before the next call)."""
+    ``__call__(positions[n,3])`` returns the static ``peaks[n]`` tensor (read it before the next call).
+
+    After a weight change of any kind (a training step, eager or replayed, a load, ``weights_changed()``) the chain is
+    void: it holds no pack launch and, on a frozen engine, reads the edge-function table of the weights it was recorded
+    with.  A call then raises ValueError, as ``library.ShiftRestraint`` does: build a new ForwardReplay."""
 
     def __init__(self, engine, atoms, positions, neighbor_number=16):
         self.eng = engine
@@ -183,6 +242,7 @@ class ForwardReplay:
             with torch.cuda.graph(self._graph, stream=self._stream):
                 self.peaks = self._one()
         cur.wait_stream(self._stream)
+        self._wgen = engine._wgen
 
     def _one(self):
         self._gb = frames_to_batch(self.atoms, self.s_pos, self.K, device=self.eng.device)   # kept alive: the chain reads its buffers
@@ -191,6 +251,9 @@ class ForwardReplay:
         return out
 
     def __call__(self, positions):
+        if self.eng._wgen != self._wgen:
+            raise ValueError("ForwardReplay: the engine's weights changed since the chain was recorded (a training step or a "
+                             "load); build a new ForwardReplay")
         p = _like(self.s_pos, positions)
         if p.data_ptr() != self.s_pos.data_ptr():
             _stage(self.eng, 0, 1e-4, 1, [(p, self.s_pos)])
