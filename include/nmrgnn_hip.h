@@ -532,6 +532,28 @@ int ng_head_fwd(ng_ctx*, void* stream, int64_t N, int Fh, int C, const float* g,
 int ng_head_fwd_dropout(ng_ctx*, void* stream, int64_t N, int Fh, int C, const float* g, uint64_t seed, uint64_t offset,
                         float keep, float* mask_out, const float* Wout, const float* bout, const float* atoms,
                         const float* peak_std, const float* peak_avg, float* peaks);
+/* Head forward with the closed-form variance of the keras Dropout in front of out_layer (nmrgnn/model.py:216-219,266-273).
+ * The reference reaches that layer's randomness only by sampling model(x, training=True); dropout sits in front of the LAST
+ * linear layer only, so with independent masks m_f = Bernoulli(keep)/keep
+ *   delta_i = sum_f m_f g_if u_if + v_i,   u_if = sum_c atoms[i,c] std[c] Wout[f][c],   v_i = sum_c atoms[i,c] (std[c] b[c] + avg[c])
+ * has mean peaks[i] (the inference value) and variance exactly
+ *   var[i] = (1 - keep) / keep * sum_f (g_if u_if)^2          [ppm^2, float32]
+ * peaks [N] carries the bits of ng_head_fwd(drop_mask = NULL) on the same inputs (fast form for Fh in {32,64,128}, one thread
+ * per row otherwise and under NG_HEAD_PATH=generic); g is read once, one launch, no atomics, asynchronous and capturable, the
+ * same bits on every call.  keep == 1 gives var exactly 0.  No range handling: (g u)^2 overflows to inf where a float32
+ * square does.  C outside 1..32, keep outside (0,1], NULL peaks or var are refused before any launch; N = 0 returns NG_OK. */
+int ng_head_fwd_var(ng_ctx*, void* stream, int64_t N, int Fh, int C, const float* g, float keep,
+                    const float* Wout, const float* bout, const float* atoms,
+                    const float* peak_std, const float* peak_avg, float* peaks, float* var);
+/* Moments over S replicas of one structure (S noisy forwards of nmrgnn/model.py:253 GaussianNoise, or S perturbed coordinate
+ * sets): mu [S][N] predicted shifts, v [S][N] their dropout variances from ng_head_fwd_var (or NULL).  With d_s = mu_s - mu_0
+ *   mean[i] = mu_0 + sum d / S,   var_input[i] = max(0, (sum d^2 - (sum d)^2 / S) / (S - 1))  (unbiased; 0 for S = 1),
+ *   var_model[i] = sum_s v_s / S          (law of total variance: Var(delta_i) = var_model + var_input)
+ * One thread per atom, replicas in their order, float64 sums, each result rounded to float32 once; a column of equal values
+ * gives var_input exactly 0.  No atomics, deterministic, capturable.  Refused: S < 1; NULL mu, mean or var_input; one of
+ * v / var_model NULL without the other. */
+int ng_ensemble_moments(ng_ctx*, void* stream, int S, int64_t N, const float* mu, const float* v,
+                        float* mean, float* var_input, float* var_model);
 /* backward of ng_head_fwd: dg [N,Fh] (overwrite), dWout [Fh,C] and dbout [C] (overwrite).  dWout == dbout == NULL: dg only,
  * bit for bit that of the same call with them given; no weight-gradient sums, partials or reductions are formed (fast and
  * generic forms).  One of the two NULL is refused. */

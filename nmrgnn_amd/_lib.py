@@ -114,6 +114,8 @@ SIGNATURES = {
                             _vp]),
     "ng_head_fwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ng_head_fwd_dropout": (_int, [_vp, _vp, _i64, _int, _int, _vp, _u64, _u64, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ng_head_fwd_var": (_int, [_vp, _vp, _i64, _int, _int, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ng_ensemble_moments": (_int, [_vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ng_head_bwd": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ng_head_loss_blocks": (_int, [_vp, _int, _int, _int, _i64]),
     "ng_head_loss_bwd": (_int, [_vp, _vp, _i64, _int, _int, _int, _i64, _vp, _u64, _u64, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

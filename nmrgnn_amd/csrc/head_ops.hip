@@ -90,6 +90,56 @@ __global__ __launch_bounds__(256) void head_fwd_fast_kernel(int64_t N, int C, co
   }
 }
 
+// ---- head forward with the closed-form dropout variance (ng_head_fwd_var) ------------------------------------
+// Dropout sits only in front of the output layer, so with independent masks m_f = Bernoulli(keep) / keep the shift
+// delta_i = sum_f m_f g_if u_if + v_i has mean peaks_i (the inference value) and variance (1 - keep) / keep * sum_f (g_if u_if)^2.
+// Layout and peaks arithmetic are head_fwd_fast_kernel<LPR, false> with mask == NULL, so peaks carry its bits; the lane
+// already holds x and u0..u3, the variance is four more products, four squares and one more reduction: g is read once.
+// coef = (1 - keep) / keep formed on the host; 0 at keep == 1, where var is written as an exact 0 whatever the sum is.
+template <int LPR>
+__global__ __launch_bounds__(256) void head_fwd_var_fast_kernel(int64_t N, int C, const float* __restrict__ g,
+                                                                const float* __restrict__ Wout,
+                                                                const float* __restrict__ bout,
+                                                                const float* __restrict__ atoms,
+                                                                const float* __restrict__ pstd,
+                                                                const float* __restrict__ pavg, float coef,
+                                                                float* __restrict__ peaks, float* __restrict__ var) {
+  constexpr int Fh = LPR * 4;
+  __shared__ __attribute__((aligned(16))) float sWs[Fh * HC_MAX];     // [c][f]: std_c * Wout[f][c]
+  __shared__ float sV[HC_MAX];           // std_c * b_c + avg_c
+  for (int t = threadIdx.x; t < Fh * C; t += 256) sWs[(t % C) * Fh + t / C] = Wout[t] * pstd[t % C];
+  if (threadIdx.x < C) sV[threadIdx.x] = pstd[threadIdx.x] * bout[threadIdx.x] + pavg[threadIdx.x];
+  __syncthreads();
+  const int q = threadIdx.x % LPR;
+  const int64_t rows_per_pass = (int64_t)gridDim.x * (256 / LPR);
+  for (int64_t i = (int64_t)blockIdx.x * (256 / LPR) + threadIdx.x / LPR; i < N; i += rows_per_pass) {
+    const float4 x = *reinterpret_cast<const float4*>(g + i * Fh + 4 * q);
+    float u0 = 0.f, u1 = 0.f, u2 = 0.f, u3 = 0.f, v = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float a = atoms[i * C + c];
+      const float4 w4 = *reinterpret_cast<const float4*>(sWs + c * Fh + 4 * q);
+      u0 += a * w4.x; u1 += a * w4.y;
+      u2 += a * w4.z; u3 += a * w4.w;
+      v += a * sV[c];
+    }
+    // the peaks chain of head_fwd_fast_kernel, term for term (a differently contracted sum is 1 ulp off)
+    float p = fmaf(x.w, u3, fmaf(x.z, u2, fmaf(x.y, u1, x.x * u0)));
+    p = sum8(p);
+    if (LPR >= 16) p += __shfl_xor(p, 8, 64);
+    if (LPR == 32) p += __shfl_xor(p, 16, 64);
+    // the variance terms: rounded products of their own (not shared with the fused chain above), then their squares
+    const float t0 = x.x * u0, t1 = x.y * u1, t2 = x.z * u2, t3 = x.w * u3;
+    float s = fmaf(t3, t3, fmaf(t2, t2, fmaf(t1, t1, t0 * t0)));
+    s = sum8(s);
+    if (LPR >= 16) s += __shfl_xor(s, 8, 64);
+    if (LPR == 32) s += __shfl_xor(s, 16, 64);
+    if (q == 0) {
+      peaks[i] = p + v;
+      var[i] = coef == 0.f ? 0.f : coef * s;
+    }
+  }
+}
+
 // ---- head backward: dg + per-workgroup partials of [dWout ; dbout] ---------------------------------------
 // thread = (row lane r = tid / LPR, column lane q); accumulators acc[c][4] for its four f's, plus db[c] on q == 0.
 // DW = false: dg only (ng_head_bwd with dWout == dbout == NULL) — no weight-gradient sums, no partial
@@ -463,6 +513,25 @@ int head_fwd_fast(ng_ctx* ctx, hipStream_t st, int64_t N, int Fh, int C, const f
   else if (lpr == 32) NG_HF(32);     // the reference's default width: fc output 128 (the one-thread-per-atom kernel took 91 us for 2770 atoms)
   else NG_HF(16);
 #undef NG_HF
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}
+
+// the grid of head_fwd_fast (peaks of the two are compared bit for bit; the row arithmetic does not depend on it)
+int head_fwd_var_fast(ng_ctx* ctx, hipStream_t st, int64_t N, int Fh, int C, const float* g, const float* Wout,
+                      const float* bout, const float* atoms, const float* pstd, const float* pavg, float coef,
+                      float* peaks, float* var) {
+  const int lpr = Fh / 4;
+  const int64_t rpb = 256 / lpr;
+  const int grid = (int)std::min<int64_t>(cdiv(N, rpb), (int64_t)ctx->num_cu * 8);
+  ProfScope ps(ctx, st, "head_fwd_var");
+#define NG_HV(L)                                                                                                      \
+  hipLaunchKernelGGL((head_fwd_var_fast_kernel<L>), dim3(grid), dim3(256), 0, st, N, C, g, Wout, bout, atoms, pstd,   \
+                     pavg, coef, peaks, var)
+  if (lpr == 8) NG_HV(8);
+  else if (lpr == 32) NG_HV(32);
+  else NG_HV(16);
+#undef NG_HV
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
 }

@@ -246,6 +246,9 @@ int head_fwd_fast(ng_ctx* ctx, hipStream_t st, int64_t N, int Fh, int C, const f
                   const float* Wout, const float* bout, const float* atoms, const float* pstd,
                   const float* pavg, float* peaks,
                   uint64_t seed = 0, uint64_t offset = 0, float keep = 1.f, float* mask_out = nullptr);
+int head_fwd_var_fast(ng_ctx* ctx, hipStream_t st, int64_t N, int Fh, int C, const float* g, const float* Wout,
+                      const float* bout, const float* atoms, const float* pstd, const float* pavg, float coef,
+                      float* peaks, float* var);
 int head_bwd_fast(ng_ctx* ctx, hipStream_t st, int64_t N, int Fh, int C, const float* g, const float* mask,
                   const float* Wout, const float* atoms, const float* pstd, const float* dpeaks, float* dg,
                   float* dWout, float* dbout);

@@ -301,6 +301,52 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(int64_t N, int Fh, int C,
   peaks[i] = p;
 }
 
+// the same (mask == NULL) with the closed-form dropout variance var[i] = coef * sum_f (g[i,f] * u_if)^2,
+// u_if = sum_c atoms[i,c] std[c] Wout[f][c]: one thread per row; the peaks sums are those of head_fwd_kernel, in its order
+__global__ __launch_bounds__(256) void head_fwd_var_kernel(int64_t N, int Fh, int C,
+                                                           const float* __restrict__ g,
+                                                           const float* __restrict__ Wout,
+                                                           const float* __restrict__ bout,
+                                                           const float* __restrict__ atoms,
+                                                           const float* __restrict__ pstd,
+                                                           const float* __restrict__ pavg, float coef,
+                                                           float* __restrict__ peaks, float* __restrict__ var) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* sW = reinterpret_cast<float*>(smem_raw);  // [Fh*C]
+  for (int t = threadIdx.x; t < Fh * C; t += 256) sW[t] = Wout[t];
+  __syncthreads();
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  float full[MAX_C], as[MAX_C];
+#pragma unroll
+  for (int c = 0; c < MAX_C; ++c) {
+    full[c] = (c < C) ? bout[c] : 0.f;
+    as[c] = (c < C) ? atoms[i * C + c] * pstd[c] : 0.f;
+  }
+  float s = 0.f;
+  for (int f = 0; f < Fh; ++f) {
+    const float x = g[i * Fh + f];
+    float u = 0.f;
+#pragma unroll
+    for (int c = 0; c < MAX_C; ++c)
+      if (c < C) {
+        full[c] += x * sW[f * C + c];
+        u += as[c] * sW[f * C + c];
+      }
+    const float t = x * u;
+    s += t * t;
+  }
+  float p = 0.f;
+#pragma unroll
+  for (int c = 0; c < MAX_C; ++c)
+    if (c < C) {
+      const float a = atoms[i * C + c];
+      p += full[c] * a * pstd[c] + a * pavg[c];
+    }
+  peaks[i] = p;
+  var[i] = coef == 0.f ? 0.f : coef * s;
+}
+
 // dg[i][f] = mask[i][f] * sum_c dfull[i][c] Wout[f][c],  dfull[i][c] = dpeaks[i]*atoms[i][c]*std[c]
 __global__ __launch_bounds__(256) void head_bwd_dg_kernel(int64_t N, int Fh, int C,
                                                           const float* __restrict__ mask,
@@ -935,6 +981,25 @@ extern "C" int ng_head_fwd(ng_ctx* ctx, void* stream, int64_t N, int Fh, int C, 
   hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), (size_t)Fh * C * 4,
                      (hipStream_t)stream, N, Fh, C, g, drop_mask, Wout, bout, atoms, peak_std,
                      peak_avg, peaks);
+  NG_HIP(ctx, hipGetLastError());
+  return NG_OK;
+}
+
+extern "C" int ng_head_fwd_var(ng_ctx* ctx, void* stream, int64_t N, int Fh, int C, const float* g, float keep,
+                               const float* Wout, const float* bout, const float* atoms, const float* peak_std,
+                               const float* peak_avg, float* peaks, float* var) {
+  if (!ctx) return NG_ERR_INVALID;
+  NG_REQUIRE(ctx, C >= 1 && C <= MAX_C, "head_fwd_var: number of elements in 1..32");
+  NG_REQUIRE(ctx, keep > 0.f && keep <= 1.f, "head_fwd_var: dropout keep probability in (0,1]");
+  NG_REQUIRE(ctx, peaks && var, "head_fwd_var: peaks [N] and var [N] required");
+  if (N == 0) return NG_OK;
+  const float coef = (1.0f - keep) / keep;      // 0 exactly at keep == 1: the kernels then write var = 0
+  if (head_fwd_fast_supported(Fh, C))
+    return head_fwd_var_fast(ctx, (hipStream_t)stream, N, Fh, C, g, Wout, bout, atoms, peak_std, peak_avg, coef, peaks,
+                             var);
+  ProfScope ps(ctx, (hipStream_t)stream, "head_fwd_var");
+  hipLaunchKernelGGL(head_fwd_var_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), (size_t)Fh * C * 4,
+                     (hipStream_t)stream, N, Fh, C, g, Wout, bout, atoms, peak_std, peak_avg, coef, peaks, var);
   NG_HIP(ctx, hipGetLastError());
   return NG_OK;
 }

@@ -234,8 +234,46 @@ class Engine:
         finally:
             self.lib.ng_weights_frozen(self.ctx.handle, 0)
 
-    def _forward(self, batch, training, noise, dropout_mask, seed, keep_tape=None, loss=None):
-        tape = bool(training) if keep_tape is None else bool(keep_tape)
+    def forward_moments(self, batch: GraphBatch, seed=0, noise=True):
+        """(mu[N], var_drop[N]): the mean and the variance, over the Dropout in front of the output layer, of the shifts of a
+        training-mode forward — in closed form (``ng_head_fwd_var``), no mask is drawn and no tape is kept (``self.tape`` is
+        left as it is).  ``noise=True`` draws the GaussianNoise on the distances exactly as ``forward(training=True,
+        seed=seed)`` does (counter offset 0) — ``mu`` then carries the bits of that call with an all-ones dropout mask;
+        ``noise=False`` feeds the distances as they are; a tensor ``noise`` (xi, standard normal, one entry per list slot) is
+        added as ``forward(training=True, noise=xi)`` adds it.  The edge-path choice and every launch up to the FC block are
+        those of the training-mode forward; the fused FC + head tail is never taken (it produces no g).  A model without
+        dropout has keep = 1 and ``var_drop`` exactly 0.  ``var_drop`` is in ppm^2; no gradient of it is formed."""
+        xi = noise if isinstance(noise, torch.Tensor) else None
+        draw = xi is not None or bool(noise)
+        if not (self._frozen or self.cache_images):
+            return self._forward(batch, draw, xi, None, seed, moments=True)
+        self._own_images()
+        try:
+            return self._forward(batch, draw, xi, None, seed, moments=True)
+        finally:
+            self.lib.ng_weights_frozen(self.ctx.handle, 0)
+
+    def ensemble_moments(self, mu, v=None):
+        """(mean[N], var_input[N], var_model[N] or None) over the S rows of ``mu`` [S, N] — the shifts of S replicas — and of
+        their dropout variances ``v`` [S, N] (``ng_ensemble_moments``: float64 sums in replica order, the unbiased variance,
+        0 for S = 1).  The total variance of a shift is var_model + var_input."""
+        if mu.dim() != 2 or mu.shape[0] < 1:
+            raise ValueError("ensemble_moments: mu must be [S, N] with S >= 1")
+        if v is not None and tuple(v.shape) != tuple(mu.shape):
+            raise ValueError("ensemble_moments: v must have the shape of mu")
+        S, N = int(mu.shape[0]), int(mu.shape[1])
+        mu = mu.to(device=self.device, dtype=torch.float32).contiguous()
+        v = None if v is None else v.to(device=self.device, dtype=torch.float32).contiguous()
+        mean, var_in = self._new(N), self._new(N)
+        var_model = None if v is None else self._new(N)
+        self._ck(self.lib.ng_ensemble_moments(self.ctx.handle, self._st(), S, N, ptr(mu), ptr(v), ptr(mean), ptr(var_in),
+                                              ptr(var_model)), "ng_ensemble_moments")
+        return mean, var_in, var_model
+
+    def _forward(self, batch, training, noise, dropout_mask, seed, keep_tape=None, loss=None, moments=False):
+        # moments (forward_moments): the launches of a taped training-mode call without its tape; ``training`` says only
+        # whether the distance noise is drawn, and the head is ng_head_fwd_var
+        tape = False if moments else (bool(training) if keep_tape is None else bool(keep_tape))
         inputs_only = isinstance(keep_tape, str)      # "inputs": the node side keeps its tape, the edge MLP none
         edge_tape = tape and not inputs_only
         lib, h, st = self.lib, self.ctx.handle, self._st()
@@ -274,7 +312,7 @@ class Engine:
                          "ng_add_scaled")
         # the table of the edge function and the guard's verdict — before the per-edge launch, which on the "table" path runs
         # over gate[1] rows: none unless the guard is up
-        table = self._edge_table_build(batch, live, d_eff, edge_tape, training) if path in ("table", "table_host") else None
+        table = self._edge_table_build(batch, live, d_eff, edge_tape, training or moments) if path in ("table", "table_host") else None
         if path == "table_host" and table is None:      # the guard, read on the host, is up
             path = "slots"
         if path == "table":
@@ -291,27 +329,38 @@ class Engine:
         self._ck(lib.ng_embed_fwd(h, st, N, self.C, F, ptr(batch.atoms), ptr(P["embed/kernel"]),
                                   ptr(h0)), "ng_embed_fwd")
         hs, As, Ss = [h0], [], []
+        # moments: the layer launches of the taped call (which kernel runs depends on whether A / S are asked for), their
+        # by-products written to one scratch pair that every layer overwrites
+        scratch = {}
+
+        def taped(*shape):
+            if tape:
+                return self._new(*shape)
+            if shape not in scratch:
+                scratch[shape] = self._new(*shape)
+            return scratch[shape]
+        like_tape = tape or moments
         for l in range(self.L):
             hn = self._new(N, F)
-            S = self._new(N, F) if (tape and self.mp_act != 0) else None
-            if batch.is_csr and not tape and N <= FUSED_TAIL_MAX_ATOMS and lib.ng_mp_layer_short_ok(N, 1, F, E):
+            S = taped(N, F) if (like_tape and self.mp_act != 0) else None
+            if batch.is_csr and not tape and not moments and N <= FUSED_TAIL_MAX_ATOMS and lib.ng_mp_layer_short_ok(N, 1, F, E):
                 A = None        # molecule-sized inference over CSR lists: one launch per layer
                 self._ck(lib.ng_mp_layer_fwd_short_csr(h, st, N, F, E, self.mp_act, 1, ptr(hs[-1]), ptr(batch.row_ptr),
                                                        ptr(batch.nlist), ptr(e), ptr(batch.inv_degree), ptr(P[f"mp/{l}/w"]),
                                                        ptr(hn)), "ng_mp_layer_fwd_short_csr")
             elif batch.is_csr:        # variable-degree lists: row_ptr / col instead of [N,K]
-                A = self._new(N, E, F) if tape else None
+                A = taped(N, E, F) if like_tape else None
                 self._ck(lib.ng_mp_layer_fwd_csr(h, st, N, ne, F, E, self.mp_act, 1, ptr(hs[-1]),
                                                  ptr(batch.row_ptr), ptr(batch.nlist), ptr(e),
                                                  ptr(batch.inv_degree), ptr(P[f"mp/{l}/w"]), ptr(hn), ptr(A),
                                                  ptr(S)), "ng_mp_layer_fwd_csr")
-            elif not tape and N <= FUSED_TAIL_MAX_ATOMS and lib.ng_mp_layer_short_ok(N, K, F, E):
+            elif not tape and not moments and N <= FUSED_TAIL_MAX_ATOMS and lib.ng_mp_layer_short_ok(N, K, F, E):
                 # molecule-sized inference: aggregate + update of the layer in ONE launch (csrc/frame_fused.hip)
                 A = None
                 self._ck(lib.ng_mp_layer_fwd_short(h, st, N, K, F, E, self.mp_act, 1, ptr(hs[-1]), ptr(batch.nlist_c), ptr(e),
                                                    ptr(batch.inv_degree), ptr(P[f"mp/{l}/w"]), ptr(hn)), "ng_mp_layer_fwd_short")
             else:
-                A = self._new(N, E, F) if (tape and lib.ng_mp_layer_wants_aggregate(F, E, K)) else None
+                A = taped(N, E, F) if (like_tape and lib.ng_mp_layer_wants_aggregate(F, E, K)) else None
                 self._ck(lib.ng_mp_layer_fwd(h, st, N, K, F, E, self.mp_act, 1, ptr(hs[-1]),
                                              ptr(batch.nlist_c), ptr(e), ptr(batch.inv_degree),
                                              ptr(P[f"mp/{l}/w"]), ptr(hn), ptr(A), ptr(S)),
@@ -323,7 +372,7 @@ class Engine:
         Bfc = [P[f"fc/{t}/bias"] for t in range(self.Lf)]
         # molecule-sized inference: FC block + head in ONE launch (csrc/frame_fused.hip)
         # (not for a training-mode forward without a tape: the fused tail has no dropout, the layered path applies it)
-        if not tape and not (training and self.use_dropout) and N <= FUSED_TAIL_MAX_ATOMS \
+        if not tape and not moments and not (training and self.use_dropout) and N <= FUSED_TAIL_MAX_ATOMS \
                 and lib.ng_fc_head_ok(N, F, self.Lf, self.C, self.fc_act):
             peaks = self._new(N)
             self._ck(lib.ng_fc_head_fwd(h, st, N, F, self.Lf, self.C, self.fc_act, ptr(hs[-1]), ptr_array(Wfc), ptr_array(Bfc),
@@ -340,6 +389,13 @@ class Engine:
                                      ptr_array(Bfc), ptr_array(fx[1:]), ptr(g)), "ng_fc_block_fwd")
         mask = None
         peaks = self._new(N)
+        if moments:
+            var = self._new(N)
+            keep = (1.0 - DROPOUT_RATE) if self.use_dropout else 1.0
+            self._ck(lib.ng_head_fwd_var(h, st, N, Fh, self.C, ptr(g), keep, ptr(P["out/kernel"]), ptr(P["out/bias"]),
+                                         ptr(batch.atoms), ptr(self.peak_std), ptr(self.peak_avg), ptr(peaks), ptr(var)),
+                     "ng_head_fwd_var")
+            return peaks, var
         loss_t = dpeaks = dg = head_partial = None
         nb = 0
         if loss is not None and self.fuse_head_loss and dropout_mask is None:

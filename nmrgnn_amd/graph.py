@@ -179,6 +179,37 @@ class GraphBatch:
         return GraphBatch.from_csr(self.atoms, row_ptr.to(torch.int32), self.nlist[keep], self.edges[keep],
                                    self.inv_degree, graph_ptr=self.graph_ptr_host, device=self.device, validate=False)
 
+    def replicate(self, S):
+        """This batch ``S`` times in ONE batch of S * N atoms (replica s owns the atoms [s * N, (s + 1) * N)): the input of
+        a replica ensemble (``Engine.forward_moments``, ``GNNModel.predict_uncertainty``).  ``atoms``, ``edges`` and
+        ``inv_degree`` are tiled; ``nlist`` / ``col`` get ``+ s * N`` in EVERY slot, so a padded slot of replica s points
+        into replica s; ``row_ptr`` is offset by ``s * nnz`` and ``graph_ptr`` by ``s * N``.  Torch ops on the device, no
+        host read.  The replicas keep no positions or box (their lists are fixed: ``positions_grad`` is not for them)."""
+        S = int(S)
+        if S < 1:
+            raise ValueError(f"replicate: at least one replica, got {S}")
+        N = self.N
+        if S * max(N, 1) >= 2 ** 31 or S * self.n_edges >= 2 ** 31:
+            raise ValueError("replicate: more than 2^31 - 1 atoms or list entries in one batch")
+        gp = self.graph_ptr_host.astype(np.int64)
+        graph_ptr = np.concatenate([gp[:1]] + [gp[1:] + s * N for s in range(S)])
+        off = torch.arange(S, dtype=torch.int32, device=self.device) * N
+        atoms = self.atoms.repeat(S, 1)
+        inv = self.inv_degree.repeat(S)
+        if self.is_csr:
+            nnz = self.nnz
+            col = (self.nlist[None, :] + off[:, None]).reshape(-1)
+            row_of = (self.row_of[None, :] + off[:, None]).reshape(-1)
+            roff = torch.arange(S, dtype=torch.int32, device=self.device) * nnz
+            row_ptr = torch.cat([(self.row_ptr[None, :-1] + roff[:, None]).reshape(-1),
+                                 torch.full((1,), S * nnz, dtype=torch.int32, device=self.device)])
+            return GraphBatch.from_csr(atoms, row_ptr, col, self.edges.detach().repeat(S), inv, graph_ptr=graph_ptr,
+                                       device=self.device, validate=False, row_of=row_of)
+        nlist = (self.nlist[None] + off[:, None, None]).reshape(S * N, self.K)
+        # lists without a padded slot stay their own compute-side lists
+        return GraphBatch(atoms, nlist, self.edges.detach().repeat(S, 1), inv, graph_ptr=graph_ptr, device=self.device,
+                          validate=False, nlist_c=nlist if self.nlist_c is self.nlist else None, ctx=self._ctx)
+
     @property
     def max_graph_atoms(self):
         """atoms of the largest member graph (a hint for the engine: ng_ctx_set_graph_span)"""

@@ -179,6 +179,66 @@ def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_num
     return energy, forces
 
 
+def _position_sigma(position_sigma, n):
+    """host check of a coordinate error (a scalar or [n] Angstrom, finite, >= 0): float32 [n]"""
+    try:
+        s = _host64(position_sigma)
+    except (TypeError, ValueError):
+        raise ValueError(f"shift_uncertainty: position_sigma must be a number or an [{n}] array, got {position_sigma!r}")
+    if s.ndim == 0:
+        s = np.full(n, float(s))
+    if s.shape != (n,):
+        raise ValueError(f"shift_uncertainty: position_sigma must be a scalar or [{n}], got {s.shape}")
+    if not np.isfinite(s).all() or (s < 0).any():
+        raise ValueError("shift_uncertainty: position_sigma must be finite and >= 0")
+    return s.astype(np.float32)
+
+
+def shift_uncertainty(model, atoms, positions, samples=32, position_sigma=None, neighbor_number=16, box=None, seed=0):
+    """``(mean, std_model, std_input)`` [n] in ppm, on the device: the predicted shifts of one structure with an error bar
+    per atom.  ``std_model`` is the closed-form spread of the model's Dropout, ``std_input`` the sampled spread over
+    ``samples`` perturbed inputs (``GNNModel.predict_uncertainty``); the two parts add in variance:
+
+        total_std = sqrt(std_model**2 + std_input**2)
+        restraint = ShiftRestraint(model, atoms, targets, tolerance=k * total_std)     # a flat bottom of k error bars
+
+    ``atoms`` [n, C] one-hot, ``positions`` [n, 3] in Angstrom; the graph is the kNN graph of ``frames_to_batch`` with
+    ``neighbor_number`` neighbours, in the periodic ``box`` if one is given.
+
+    ``position_sigma=None``: the input part comes from the model's own GaussianNoise on the distances, at fixed neighbour
+    lists — ``model.predict_uncertainty(frames_to_batch(atoms, positions), samples, seed)``.
+
+    ``position_sigma``: a scalar or [n] coordinate error in Angstrom, finite and >= 0 (from a crystallographic B-factor:
+    sqrt(B / (8 pi^2))).  The input part then comes from coordinate error instead: the S replicas are
+    ``positions + sigma_i * xi`` with xi standard normal (``ng_randn(seed, offset 0)`` over [S, n, 3]), their neighbour lists
+    are rebuilt per replica, and the model's distance noise is off.  A bad sigma raises ValueError before any device work."""
+    import torch
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError(f"shift_uncertainty: samples must be >= 1, got {samples}")
+    shape = tuple(positions.shape) if hasattr(positions, "shape") else np.shape(positions)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"shift_uncertainty: one structure, positions [n, 3]; got {shape}")
+    n = shape[0]
+    sigma = None if position_sigma is None else _position_sigma(position_sigma, n)
+    from .graph import frames_to_batch
+    if model.engine is None:
+        model.build(int(atoms.shape[-1]) if isinstance(atoms, torch.Tensor) else int(np.asarray(atoms).shape[-1]))
+    eng = model.engine
+    pos = positions.detach() if isinstance(positions, torch.Tensor) else torch.from_numpy(np.asarray(positions, np.float32))
+    pos = pos.to(device=eng.device, dtype=torch.float32)
+    box = box.detach() if isinstance(box, torch.Tensor) else box
+    if sigma is None:
+        batch = frames_to_batch(atoms, pos, neighbor_number=neighbor_number, device=eng.device, box=box)
+        return model.predict_uncertainty(batch, samples=samples, seed=seed)
+    xi = eng.randn(samples * n * 3, seed, 0).view(samples, n, 3)
+    frames = pos[None] + torch.from_numpy(sigma).to(eng.device)[None, :, None] * xi
+    batch = frames_to_batch(atoms, frames, neighbor_number=neighbor_number, device=eng.device, box=box)
+    mu, var = eng.forward_moments(batch, seed=seed, noise=False)
+    mean, var_in, var_model = eng.ensemble_moments(mu.view(samples, n), var.view(samples, n))
+    return mean, torch.sqrt(var_model), torch.sqrt(var_in)
+
+
 def _restraint_positions(positions, R, n):
     """host check of a call's positions: [R, n, 3] (or [n, 3] when R == 1); returns the torch view [R, n, 3] (not yet on the
     device) and whether the caller gave [n, 3]"""

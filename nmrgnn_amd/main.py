@@ -36,14 +36,33 @@ def _open_structure(struct_files):
 
 
 def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16, stride=1,
-                   frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False, separate=False, boxes=False):
+                   frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False, separate=False, boxes=False,
+                   uncertainty=0, position_sigma=None, average=False):
     """Predict shifts for every ``stride``-th frame and write the reference's CSV.  Returns the timing
     buckets in seconds.  ``pbc``: neighbour lists under the minimum-image convention in each frame's box (its CRYST1
     record); a frame without one is an error.  ``separate``: every file is a structure of its own (see
     :func:`_eval_separate`); with ``boxes`` every (file, frame) structure uses its own CRYST1 box when it has one and open
-    boundaries otherwise."""
+    boundaries otherwise.
+
+    ``uncertainty`` = S > 0: two more columns behind ``frame``, ``std_model`` and ``std_input`` in ppm, rounded like
+    ``peaks``: the error bar of every shift from S replicas of its frame (library.shift_uncertainty, seeded with the frame
+    number; total = sqrt(std_model^2 + std_input^2)).  ``position_sigma`` (Angstrom): the input part from a coordinate error
+    of that size instead of the model's distance noise.  ``average``: ONE row per atom over the frames read — ``index,
+    residues, resids, names, peaks`` (the mean over the frames), ``peaks_std`` (the sample standard deviation over the
+    frames, n - 1 in the denominator; 0 for one frame), ``confident`` (of the mean), ``frames`` (how many were read); the
+    moments are taken on the device (ng_ensemble_moments).  Without these options the CSV is what it always was."""
     if len(struct_files) == 0:
         raise ValueError('Must pass at least on structure file')
+    uncertainty = int(uncertainty or 0)
+    if uncertainty < 0:
+        raise ValueError('--uncertainty takes a number of replicas >= 1')
+    if separate and (uncertainty or average):
+        raise ValueError('--separate cannot be combined with --uncertainty or --average: the files are different topologies, '
+                         'and both options work on the frames of one')
+    if position_sigma is not None and not uncertainty:
+        raise ValueError('--position-sigma goes with --uncertainty S')
+    if average and uncertainty:
+        raise ValueError('--average and --uncertainty cannot be combined: run them one after the other')
     if separate and pbc:
         raise ValueError('--separate and --pbc cannot be combined: --pbc wants a box on every frame of one topology; '
                          'use --separate --boxes for one box, or none, per structure')
@@ -54,7 +73,7 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
                               device, echo, boxes)
     import torch
     from .graph import frames_to_batch
-    from .library import check_peaks, load_model
+    from .library import check_peaks, load_model, shift_uncertainty
     from .structure import atoms_onehot
 
     model = load_model(model_file, device=device)
@@ -70,6 +89,7 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     model.freeze()          # inference only: the engine keeps its packed weight images across the per-frame calls
     timing = {'Structure': 0.0, 'Model Inference (MI355X)': 0.0, 'Parsing': 0.0}
     rows = []
+    kept = []               # --average: the [frames, n] peaks stay on the device
     for b0 in range(0, len(frame_ids), max(1, frames_per_batch)):
         chunk = frame_ids[b0:b0 + max(1, frames_per_batch)]
         t = time.perf_counter()
@@ -80,8 +100,19 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         torch.cuda.synchronize(dev)
         timing['Structure'] += time.perf_counter() - t
         t = time.perf_counter()
-        peaks = model(batch).cpu().numpy()
+        peaks = model(batch)
+        if average:
+            kept.append(peaks.reshape(len(chunk), n))
+            timing['Model Inference (MI355X)'] += time.perf_counter() - t
+            echo('|'.join(f'{k}:{v:5.2f}s' for k, v in timing.items()))
+            continue
+        peaks = peaks.cpu().numpy()
         peaks = peaks.reshape(len(chunk), n)
+        stds = []
+        for fr in (chunk if uncertainty else ()):
+            _, sm, si = shift_uncertainty(model, atoms, u.frames[fr], samples=uncertainty, position_sigma=position_sigma,
+                                          neighbor_number=neighbor_number, box=u.dimensions[fr] if pbc else None, seed=fr)
+            stds.append((np.round(sm.cpu().numpy().astype(np.float64), 2), np.round(si.cpu().numpy().astype(np.float64), 2)))
         conf = []
         for k in range(len(chunk)):
             try:
@@ -96,14 +127,32 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         for k, fr in enumerate(chunk):
             pk = np.round(peaks[k].astype(np.float64), 2)
             for i in range(n):
-                rows.append((i, u.resnames[i], int(u.resids[i]), u.names[i], pk[i], bool(conf[k][i]),
-                             float(fr), fr))
+                row = (i, u.resnames[i], int(u.resids[i]), u.names[i], pk[i], bool(conf[k][i]), float(fr), fr)
+                rows.append(row + (stds[k][0][i], stds[k][1][i]) if uncertainty else row)
         timing['Parsing'] += time.perf_counter() - t
         echo('|'.join(f'{k}:{v:5.2f}s' for k, v in timing.items()))
+    header = ['index', 'residues', 'resids', 'names', 'peaks', 'confident', 'time', 'frame']
+    if uncertainty:
+        header += ['std_model', 'std_input']
+    if average:
+        t = time.perf_counter()
+        mean, var, _ = model.engine.ensemble_moments(torch.cat(kept))
+        pk = np.round(mean.cpu().numpy().astype(np.float64), 2)
+        sd = np.round(torch.sqrt(var).cpu().numpy().astype(np.float64), 2)
+        try:
+            conf = check_peaks(atoms, mean.cpu().numpy())
+        except Warning as w:
+            if not keep_going:
+                raise
+            echo(f'mean over {len(frame_ids)} frames: {w}')
+            conf = np.zeros(n, dtype=bool)
+        rows = [(i, u.resnames[i], int(u.resids[i]), u.names[i], pk[i], sd[i], bool(conf[i]), len(frame_ids)) for i in range(n)]
+        header = ['index', 'residues', 'resids', 'names', 'peaks', 'peaks_std', 'confident', 'frames']
+        timing['Parsing'] += time.perf_counter() - t
     os.makedirs(os.path.dirname(os.path.abspath(output_csv)), exist_ok=True)
     with open(output_csv, 'w', newline='') as f:
         wr = csv.writer(f)
-        wr.writerow(['index', 'residues', 'resids', 'names', 'peaks', 'confident', 'time', 'frame'])
+        wr.writerow(header)
         wr.writerows(rows)
     echo(f'You can now find your result in {output_csv}')
     return timing
@@ -185,16 +234,34 @@ def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride
 @click.option('--boxes', is_flag=True,
               help='With --separate: minimum-image neighbour lists in each structure\'s own box (CRYST1), open boundaries '
                    'for structures without one')
+@click.option('--uncertainty', default=0, metavar='S',
+              help='Append std_model and std_input (ppm) per atom and frame: the closed-form dropout spread and the spread '
+                   'over S noisy replicas of the frame')
+@click.option('--position-sigma', default=None, type=float, metavar='X',
+              help='With --uncertainty: the input spread from a coordinate error of X Angstrom instead of the model\'s '
+                   'distance noise')
+@click.option('--average', is_flag=True,
+              help='One row per atom: mean and standard deviation of the shifts over the frames read')
 def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, pbc, separate,
-                boxes):
+                boxes, uncertainty, position_sigma, average):
     '''Predict NMR chemical shifts with specific file'''
+    if separate and (uncertainty or average):
+        raise click.UsageError('--separate cannot be combined with --uncertainty or --average: the files are different '
+                               'topologies, and both options work on the frames of one')
+    if uncertainty < 0:
+        raise click.UsageError('--uncertainty takes a number of replicas >= 1')
+    if position_sigma is not None and not uncertainty:
+        raise click.UsageError('--position-sigma goes with --uncertainty S')
+    if average and uncertainty:
+        raise click.UsageError('--average and --uncertainty cannot be combined: run them one after the other')
     if separate and pbc:
         raise click.UsageError('--separate and --pbc cannot be combined; use --separate --boxes for one box, or none, per '
                                'structure')
     if boxes and not separate:
         raise click.UsageError('--boxes goes with --separate; use --pbc for frames of one topology')
     eval_structure(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch,
-                   keep_going, echo=click.echo, pbc=pbc, separate=separate, boxes=boxes)
+                   keep_going, echo=click.echo, pbc=pbc, separate=separate, boxes=boxes, uncertainty=uncertainty,
+                   position_sigma=position_sigma, average=average)
 
 
 if __name__ == '__main__':

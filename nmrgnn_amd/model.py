@@ -93,8 +93,7 @@ class GNNModel:
         if self.engine is None:
             self.build(batch.C)
         if training and seed is None:
-            seed = ((int(self._seed) * 0x9E3779B97F4A7C15) ^ (self._train_calls * 1000003 + 0x632BE5AB)) & ((1 << 63) - 1)
-            self._train_calls += 1
+            seed = self._train_seed()
         leaf = self._flat_leaf
         if torch.is_grad_enabled() and batch.edges.requires_grad:
             # gradients with respect to the inputs (a watched ``edges``, or positions through frames_to_batch): the edges
@@ -114,6 +113,64 @@ class GNNModel:
 
     call = __call__
     predict = __call__
+
+    def _train_seed(self):
+        """the Philox key of the next training-mode call (``__call__(training=True)`` without ``seed=``)"""
+        seed = ((int(self._seed) * 0x9E3779B97F4A7C15) ^ (self._train_calls * 1000003 + 0x632BE5AB)) & ((1 << 63) - 1)
+        self._train_calls += 1
+        return seed
+
+    def predict_uncertainty(self, inputs, samples=32, seed=None, chunk_atoms=1 << 20):
+        """``(mean, std_model, std_input)``, each [N] in ppm: an error bar for every predicted shift from the model's own two
+        random layers (nmrgnn/model.py:253,266-267), which the reference reaches only through ``model(x, training=True)``.
+
+        ``std_model``: the Dropout in front of the output layer, in CLOSED FORM — Var = (1 - keep) / keep * sum_f (g_f u_f)^2
+        per replica (``ng_head_fwd_var``), averaged over the replicas; no mask is drawn.  ``std_input``: the GaussianNoise on
+        the distances, SAMPLED — the spread of the dropout-mean shift over ``samples`` noisy replicas of the input, which run
+        as one batch (``GraphBatch.replicate``) in chunks of at most ``chunk_atoms`` atoms (always at least one replica per
+        chunk).  ``mean`` is the mean over the replicas.  By the law of total variance the two parts add:
+        ``total_std = sqrt(std_model**2 + std_input**2)``.
+
+        A model with ``noise == 0`` runs one replica and returns ``std_input`` exactly 0; a model without dropout returns
+        ``std_model`` exactly 0.  ``seed=None`` derives the seed as ``__call__(training=True)`` does (a fresh draw per call).
+        The noise of all replicas is ONE draw, ``ng_randn(seed, offset 0)`` over [samples, edges] — what the unchunked call
+        draws inside its launch; a chunk takes its slice of it, so the result does not depend on ``chunk_atoms`` beyond
+        float32 rounding (a seed per chunk would make it depend on the chunking).  Device inputs give device tensors, host inputs NumPy, as ``__call__``."""
+        samples = int(samples)
+        if samples < 1:
+            raise ValueError(f"predict_uncertainty: samples must be >= 1, got {samples}")
+        if int(chunk_atoms) < 1:
+            raise ValueError(f"predict_uncertainty: chunk_atoms must be >= 1, got {chunk_atoms}")
+        batch, on_device = self._as_batch(inputs)
+        if self.engine is None:
+            self.build(batch.C)
+        eng = self.engine
+        if seed is None:
+            seed = self._train_seed()
+        S = samples if eng.sigma > 0 else 1
+        N = batch.N
+        per = max(1, min(S, int(chunk_atoms) // max(N, 1)))
+        mu = torch.empty(S, N, dtype=torch.float32, device=eng.device)
+        var = torch.empty(S, N, dtype=torch.float32, device=eng.device)
+        ne = batch.n_edges
+        for s0 in range(0, S, per):
+            n = min(per, S - s0)
+            noise = True            # one chunk: the draw inside the launch, as forward(training=True, seed=seed)
+            if per < S and eng.sigma > 0:
+                # the chunk's slice of that same draw: elements [s0 * ne, (s0 + n) * ne) of ng_randn(seed, offset 0)
+                # (a Philox counter holds four elements; a slice that starts inside one is copied to an aligned buffer)
+                lead = (s0 * ne) % 4
+                noise = eng.randn(lead + n * ne, int(seed), (s0 * ne) // 4)
+                if lead:
+                    noise = noise[lead:].clone()
+            m, v = eng.forward_moments(batch.replicate(n), seed=int(seed), noise=noise)
+            mu[s0:s0 + n] = m.view(n, N)
+            var[s0:s0 + n] = v.view(n, N)
+        mean, var_in, var_model = eng.ensemble_moments(mu, var)
+        out = (mean, torch.sqrt(var_model), torch.sqrt(var_in))
+        if on_device:
+            return out
+        return tuple(t.cpu().numpy().view(Peaks) for t in out)
 
     def evaluate(self, data, metrics=None):
         """Validation pass (keras ``evaluate`` / the ``validation_data`` of nmrgnn/main.py:79-80).  ``data`` yields
