@@ -291,7 +291,8 @@ int ng_embed_bwd(ng_ctx*, void* stream, int64_t N, int C, int F, const float* at
                  const float* dh0, float* dWemb);
 
 /* MPLayer aggregation, nmrgnn/layers.py:33 + the (i,j)-contraction of layers.py:39-40:
- *   A[i,n,l] = sum_j e[i,j,n] * h[nlist[i,j], l]        A is [N,E,F] */
+ *   A[i,n,l] = sum_j e[i,j,n] * h[nlist[i,j], l]        A is [N,E,F]
+ *   F a multiple of 4 in [16, 1024] for E <= 8; F in {16,32,64,128,256} for 8 < E <= 64 */
 int ng_mp_aggregate(ng_ctx*, void* stream, int64_t N, int K, int F, int E, const float* h,
                     const int32_t* nlist, const float* e, float* A);
 

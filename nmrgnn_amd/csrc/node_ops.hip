@@ -193,8 +193,8 @@ __global__ __launch_bounds__(256) void aggregate_kernel(int64_t N, int K, int F,
 
 static int aggregate(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int F, int E, const float* h,
                      const int32_t* nlist, const float* e, float* A) {
-  NG_REQUIRE(ctx, F % 4 == 0 && F >= 16 && F <= 1024 && (256 % (F / 4)) == 0,
-             "aggregate: F in {16,32,64,128,256,512,1024}");
+  // F / 4 lanes per atom, 256 / (F / 4) atoms per block (the lanes past the last whole atom idle): any multiple of 4
+  NG_REQUIRE(ctx, F % 4 == 0 && F >= 16 && F <= 1024, "aggregate: F % 4 == 0, 16 <= F <= 1024");
   NG_REQUIRE(ctx, E >= 1 && E <= 64, "aggregate: edge_feature_size <= 64");
   if (N == 0) return NG_OK;
   if (E > MAX_E) return csr_aggregate(ctx, st, N, K, F, E, h, nullptr, nlist, e, A);

@@ -48,6 +48,22 @@ def _glorot(shape, dev, gen):
     return ((torch.rand(*shape, generator=gen) * 2 - 1) * lim).to(dev)
 
 
+def _shape(x):
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def check_built_shapes(layer, built, wanted):
+    """A built layer (or one whose weights were set by hand) called with inputs of another shape would hand the
+    kernels a weight buffer of the wrong size; Keras raises there, and so does this.  ``built`` and ``wanted``
+    are sequences of ``(weight name, shape)``: the shapes the layer holds and the ones the call's inputs imply
+    (``None`` in a wanted shape leaves that dimension open).  Plain tuples only: nothing here touches a device."""
+    built, wanted = [(n, tuple(s)) for n, s in built], [(n, tuple(s)) for n, s in wanted]
+    for (name, have), (_, want) in zip(built, wanted):
+        if len(have) != len(want) or any(w is not None and h != w for h, w in zip(have, want)):
+            raise ValueError(f"{layer}: weights were built as {dict(built)}, but this call's inputs need "
+                             f"{dict(wanted)} (mismatch at {name!r}: {have} != {want})")
+
+
 def get_regularizer(spec):
     """tf.keras.regularizers.get for the cases a weight regulariser can take without Keras: None, a callable
     (w -> scalar), 'l1' / 'l2' / 'l1_l2' (Keras default factor 0.01), or a Keras-style config dict
@@ -141,6 +157,9 @@ class MPLayer(_Layer):
 
     def __call__(self, inputs, residual=False):
         nodes, nlist, edges, inv_degree = inputs
+        if self.built:                                # also a w set by hand after the first call
+            F, E = _shape(nodes)[-1], _shape(edges)[-1]
+            check_built_shapes(self.name, [("w", _shape(self.w))], [("w", (F, F, E))])
         dev = _device()
         nodes, nlist = _f32(nodes, dev), _i32(nlist, dev)
         edges, inv = _f32(edges, dev), _f32(inv_degree, dev).reshape(-1)
@@ -161,12 +180,17 @@ class MPLayer(_Layer):
 
 class _DenseStack(_Layer):
     """sequence of keras Dense layers evaluated with ng_dense_fwd (shapes padded to the kernel's
-    granularity: contraction % 8, outputs % 4 — zero padding does not change the product)."""
+    granularity: contraction % 8, outputs % 4, both to the same multiple of 8 under a residual — zero padding does not
+    change the product, and the padded output columns are sliced off)."""
 
     def _dense(self, x, W, b, act, residual, dev):
         M, Kin = x.shape
         Nout = W.shape[1]
+        if residual and Kin != Nout:
+            raise ValueError(f"_dense: a residual needs as many outputs as inputs, got {Kin} -> {Nout}")
         Kp, Np = (Kin + 7) // 8 * 8, (Nout + 3) // 4 * 4
+        if residual:
+            Np = Kp        # the kernel adds its (padded) input: one common size, the padded columns are sliced off
         if Kp != Kin:
             x = torch.nn.functional.pad(x, (0, Kp - Kin))
             W = torch.nn.functional.pad(W, (0, 0, 0, Kp - Kin))
@@ -177,7 +201,7 @@ class _DenseStack(_Layer):
         y = torch.empty(M, Np, dtype=torch.float32, device=dev)
         ctx = self._ctx(dev)
         ctx.check(ctx.lib.ng_dense_fwd(ctx.handle, self._st(dev), M, Kp, Np, ACT[act],
-                                       1 if (residual and Kp == Np) else 0, ptr(x), ptr(W), ptr(b),
+                                       1 if residual else 0, ptr(x), ptr(W), ptr(b),
                                        ptr(y), None), "ng_dense_fwd")
         return y[:, :Nout].contiguous() if Np != Nout else y
 
@@ -208,6 +232,9 @@ class EdgeFCBlock(_DenseStack):
         self.weights = None
 
     def __call__(self, edge_input):
+        if self.built:
+            check_built_shapes(self.name, [("dense_0/kernel", _shape(self.weights[0][0]))],
+                               [("dense_0/kernel", (_shape(edge_input)[-1], None))])
         dev = _device()
         x = _f32(edge_input, dev)
         lead, D = x.shape[:-1], x.shape[-1]
@@ -300,6 +327,10 @@ class AMPLayer(_DenseStack):
 
     def __call__(self, inputs):
         nodes, nlist, edges, inv_degree = inputs
+        if self.built:
+            F, E = _shape(nodes)[-1], _shape(edges)[-1]
+            check_built_shapes(self.name, [("wq", _shape(self.wq)), ("wk", _shape(self.wk)), ("wv", _shape(self.wv))],
+                               [("wq", (F, E)), ("wk", (E, E)), ("wv", (F, F))])
         dev = _device()
         nodes, nlist = _f32(nodes, dev), _i32(nlist, dev)
         edges, inv = _f32(edges, dev), _f32(inv_degree, dev).reshape(-1)
