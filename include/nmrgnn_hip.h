@@ -229,7 +229,11 @@ int ng_edge_mlp_bwd_live(ng_ctx*, void* stream, int64_t n_slots, int H, int E, i
  *   dd * scale * (r_i - r_j) / |r_i - r_j| on atom i and its negative on atom j, the gradient of a function of the edges
  *   (edges = |r_i - r_j| * scale, ng_knn_graph / ng_cutoff_fill) with respect to the positions pos [N][3] at fixed lists.
  *   Padded form: nlist / edges / dd [N][K] (a slot is live when edges > 0); CSR form: row_ptr [N+1], col / row_of / dd [nnz].
- *   csc_ptr / csc_edge: the incoming-edge lists (ng_build_incoming_lists).  A gather, no atomics: bitwise deterministic. */
+ *   csc_ptr / csc_edge: the incoming-edge lists (ng_build_incoming_lists).  A gather, no atomics: bitwise deterministic.
+ *   Entries that contribute nothing, here and in every ng_positions_grad* / ng_box_grad* below: dd == 0 (skipped on both
+ *   ends, whatever the geometry), and an entry whose two ends coincide after the displacement policy, |u| == 0 (the cutoff
+ *   builders list coincident atoms in the CSR form): the gradient of |r| at 0 is taken as 0, as the padded live rule
+ *   (edges > 0) already has it.  dpos, strain and dvec stay finite for any finite dd. */
 int ng_edge_mlp_dinput(ng_ctx*, void* stream, int64_t n_slots, int H, int E, int Le, int act, const float* d_src,
                        const float* d_eff, const int32_t* perm, const int32_t* n_live, const float* centers, float gap,
                        const float* const* W, const float* const* b, const float* de, float* J_out, float* dd_out);

@@ -116,7 +116,8 @@ __global__ __launch_bounds__(BG_ROWS) void box_grad_chunk_kernel(int64_t N, int 
       float ux, uy, uz;
       D(qx, qy, qz, px, py, pz, ux, uy, uz);
       const double x = ux, y = uy, z = uz;
-      const double w = (double)ge * (double)scale / sqrt(x * x + y * y + z * z);   // p = w u
+      const double len = sqrt(x * x + y * y + z * z);
+      const double w = len > 0.0 ? (double)ge * (double)scale / len : 0.0;   // p = w u; a slot of length zero adds nothing
       const double wx = w * x, wy = w * y, wz = w * z;
       v[0] += x * wx; v[1] += y * wy; v[2] += z * wz;
       v[3] += x * wy; v[4] += x * wz; v[5] += y * wz;

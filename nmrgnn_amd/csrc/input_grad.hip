@@ -209,13 +209,16 @@ __global__ __launch_bounds__(DI_THREADS) void edge_dinput_kernel(
 
 // the term of slot (i -> j): f * (r_i - r_j), f = g * scale / |r_i - r_j|; both ends call it with (i, j) in this order.
 // r_i - r_j is minus the displacement D(r_i, r_j) the list builders computed for the edge (pbc.cuh; for DispOpen the same
-// bits as r_i - r_j: a negated difference is exact)
+// bits as r_i - r_j: a negated difference is exact).  A slot of length zero (coincident ends, which the cutoff builders
+// list) contributes nothing: the gradient of |r| at 0 is taken as 0, a select on the finished factor, so that the length
+// expression stays what it was
 template <class Disp>
 __device__ __forceinline__ float3 pg_term(const Disp& D, const float* __restrict__ pos, int64_t i, int64_t j, float g, float scale) {
   float ux, uy, uz;
   D(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], pos[3 * j], pos[3 * j + 1], pos[3 * j + 2], ux, uy, uz);
   const float vx = -ux, vy = -uy, vz = -uz;
-  const float f = g * scale / sqrtf(vx * vx + vy * vy + vz * vz);
+  const float len = sqrtf(vx * vx + vy * vy + vz * vz);
+  const float f = len > 0.f ? g * scale / len : 0.f;
   return make_float3(f * vx, f * vy, f * vz);
 }
 

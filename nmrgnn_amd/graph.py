@@ -307,7 +307,8 @@ class GraphBatch:
     def positions_grad(self, dedges):
         """dL/d(positions) [G, n, 3] from dL/d(edges) ``dedges`` (shaped like ``edges``), at fixed neighbour lists: the
         chain rule through edges = |r_i - r_j| * scale (include/nmrgnn_hip.h: ng_positions_grad).  Needs the positions the
-        lists were built from (frames_to_batch / frames_to_batch_cutoff)."""
+        lists were built from (frames_to_batch / frames_to_batch_cutoff).  An edge between coincident atoms (a cutoff list
+        holds them) contributes nothing whatever its ``dedges``, here and in ``box_grad``."""
         if self.positions is None:
             raise ValueError("positions_grad: this batch was not built from positions (frames_to_batch / frames_to_batch_cutoff)")
         return _positions_grad(self._positions_state(), dedges)
