@@ -40,7 +40,7 @@ __global__ void rbf_kernel(int64_t n_edges, int H, const float* __restrict__ d_s
   }
 }
 
-// last (linear) edge layer with tiny output width E:  e[r][n] = m_r * (Z[r][:] @ W[:, n] + b[n])
+// last (linear) edge layer with tiny output width E:  e[r][n] = m_r ? Z[r][:] @ W[:, n] + b[n] : +0
 // 4 lanes per row, each covering a quarter of every 16-float chunk; shuffle-reduce over the 4.
 template <int E>
 __global__ __launch_bounds__(256) void edge_out_fwd_kernel(int64_t n_edges, int H,
@@ -74,9 +74,9 @@ __global__ __launch_bounds__(256) void edge_out_fwd_kernel(int64_t n_edges, int 
     acc[n] += __shfl_xor(acc[n], 2, 64);
   }
   if (live && q == 0) {
-    const float m = d_src[r] > 0.f ? 1.f : 0.f;
+    const bool live_slot = d_src[r] > 0.f;   // a dead slot is +0, as on the fused and the wide path (not -0 under a negative sum)
 #pragma unroll
-    for (int n = 0; n < E; ++n) e_out[r * E + n] = m * (acc[n] + b[n]);
+    for (int n = 0; n < E; ++n) e_out[r * E + n] = live_slot ? acc[n] + b[n] : 0.f;
   }
 }
 
