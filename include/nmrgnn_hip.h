@@ -424,6 +424,56 @@ int ng_cutoff_fill_rows_pbc(ng_ctx*, void* stream, int G, int n, float cutoff, f
 /* out[0..n] = exclusive prefix sums of in[0..n-1], out[n] = total (row_ptr from ng_cutoff_count's degrees) */
 int ng_exclusive_scan_i32(ng_ctx*, void* stream, int64_t n, const int32_t* in, int32_t* out);
 
+/* ---- receptive-field pruning (csrc/prune.hip; additive in ABI 9) -------------------------------------------------
+ * The model is strictly local: the shift of an atom depends on the atoms within mp_layers list steps of it.  These
+ * calls restrict a batch to what can reach the SELECTED atoms and expand results back to the parent's shape.  Lists
+ * are padded (K > 0: nlist / edges [N*K]) or CSR (K == 0: row_ptr [N+1], row_of [n_entries], nlist = col, edges =
+ * dist); an entry is live by ng_build_incoming_lists' rule (edges > 0 AND 0 <= target < N; edges == NULL: the target
+ * alone), so a padded slot (0, 0.0) never pulls atom 0 in.  Integer work and copies, no atomics on values: the same
+ * inputs give the same bits.  No host synchronisation; every refusal (NG_ERR_INVALID: NULL context, hops outside
+ * [0, 64], K > 64, N * K >= 2^31, NULL lists with n_entries > 0) comes before any write.
+ *
+ * ng_receptive_hops: seed [N] (nonzero = selected) -> hop [N]: the smallest d <= hops such that the atom is reached
+ *   from a selected atom in d steps i -> nlist[i, k] along live entries (row i names the atoms whose features i
+ *   reads), -1 when there is none.  One frontier round per hop, one thread per entry.  N == 0 or no seed is legal.
+ * ng_prune_keep_flags: flag [N] = hop >= 0.  The caller's ng_exclusive_scan_i32 of it is idx [N+1]: the new index of
+ *   every kept atom, idx[N] = M atoms kept, idx[graph_ptr[g]] = kept atoms in front of graph g.
+ * ng_prune_lists (padded): for every kept atom i, r = idx[i]: keep[r] = i, hop_p[r] = hop[i], atoms_p[r, :C] and
+ *   inv_degree_p[r] copied from the parent (inv_degree is NOT recomputed from the pruned row); nlist_p[r, k] =
+ *   idx[nlist[i, k]], edges_p[r, k] = edges[i, k] where the slot is live and hop[i] < hops — its target is then kept by
+ *   construction — and otherwise a dead slot (idx[graph_ptr[g]], 0.0), g the row's graph: the builders' (0, 0.0)
+ *   shifted to the batch.  Rows at hop == hops contribute their embedding only.  Outputs are [M]-shaped.
+ * ng_prune_degrees_csr: deg [N] = the parent degree of a kept row with hop < hops, else 0.  Its exclusive scan
+ *   rp_full [N+1] places the kept entries; rp_full[N] = nnz_p, read in the same synchronisation as M.
+ * ng_prune_lists_csr: the row outputs as above, row_ptr_p [M+1] (row_ptr_p[r] = rp_full[keep[r]], [M] = nnz_p) and
+ *   col_p / dist_p / row_of_p [nnz_p]: the entries of the rows with hop < hops at the same position inside the row
+ *   (NULL when nnz_p == 0).  An entry that is not live becomes (the row itself, 0.0).
+ * ng_prune_expand_edge_grad: writes EVERY entry of the parent-shaped de [n_entries]: de_p of the pruned batch where the
+ *   entry was kept (live, row with 0 <= hop < hops; same slot, or same position in the row through row_ptr_p), +0.0
+ *   everywhere else.
+ * ng_prune_expand_rows: out [N] = fill, then out[keep[r]] = v[r] for r < M (peaks, per-atom uncertainties). */
+int ng_receptive_hops(ng_ctx*, void* stream, int64_t N, int K, int64_t n_entries, const int32_t* row_ptr,
+                      const int32_t* row_of, const int32_t* nlist, const float* edges, const int32_t* seed, int hops,
+                      int32_t* hop);
+int ng_prune_keep_flags(ng_ctx*, void* stream, int64_t N, const int32_t* hop, int32_t* flag);
+int ng_prune_degrees_csr(ng_ctx*, void* stream, int64_t N, int hops, const int32_t* row_ptr, const int32_t* hop,
+                         int32_t* deg);
+int ng_prune_lists(ng_ctx*, void* stream, int64_t N, int K, int C, int G, int hops, const int32_t* graph_ptr,
+                   const int32_t* nlist, const float* edges, const float* atoms, const float* inv_degree,
+                   const int32_t* hop, const int32_t* idx, int32_t* keep, int32_t* hop_p, float* atoms_p,
+                   float* inv_degree_p, int32_t* nlist_p, float* edges_p);
+int ng_prune_lists_csr(ng_ctx*, void* stream, int64_t N, int64_t n_entries, int C, int hops, const int32_t* row_ptr,
+                       const int32_t* row_of, const int32_t* col, const float* dist, const float* atoms,
+                       const float* inv_degree, const int32_t* hop, const int32_t* idx, const int32_t* rp_full,
+                       int32_t* keep, int32_t* hop_p, float* atoms_p, float* inv_degree_p, int32_t* row_ptr_p,
+                       int32_t* col_p, float* dist_p, int32_t* row_of_p);
+int ng_prune_expand_edge_grad(ng_ctx*, void* stream, int64_t N, int K, int64_t n_entries, int hops,
+                              const int32_t* row_ptr, const int32_t* row_of, const int32_t* nlist, const float* edges,
+                              const int32_t* hop, const int32_t* idx, const int32_t* row_ptr_p, const float* de_p,
+                              float* de);
+int ng_prune_expand_rows(ng_ctx*, void* stream, int64_t N, int64_t M, const int32_t* keep, const float* v, float fill,
+                         float* out);
+
 /* ---- graph front end: K nearest neighbours per atom, per frame --------------------------------
  * Replaces the neighbour search behind nmrgnn.universe2graph (nmrgnn/library.py:106-117, external
  * nmrdata.parse_universe) and the per-frame graph construction of eval-struct (main.py:236-243).

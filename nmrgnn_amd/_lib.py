@@ -109,6 +109,13 @@ SIGNATURES = {
     "ng_cutoff_count_pbc": (_int, [_vp, _vp, _int, _int, _f, _vp, _vp, _int, _vp]),
     "ng_cutoff_fill_rows_pbc": (_int, [_vp, _vp, _int, _int, _f, _f, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "ng_exclusive_scan_i32": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "ng_receptive_hops": (_int, [_vp, _vp, _i64, _int, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
+    "ng_prune_keep_flags": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "ng_prune_degrees_csr": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp]),
+    "ng_prune_lists": (_int, [_vp, _vp, _i64, _int, _int, _int, _int] + [_vp] * 13),
+    "ng_prune_lists_csr": (_int, [_vp, _vp, _i64, _i64, _int, _int] + [_vp] * 17),
+    "ng_prune_expand_edge_grad": (_int, [_vp, _vp, _i64, _int, _i64, _int] + [_vp] * 9),
+    "ng_prune_expand_rows": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _f, _vp]),
     "ng_dense_fwd": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "ng_dense_bwd": (_int, [_vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                             _vp]),

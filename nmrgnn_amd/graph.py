@@ -347,6 +347,154 @@ class GraphBatch:
             raise ValueError("a CSR batch has no (atoms, nlist, edges, inv_degree) tuple; see row_ptr / nlist / edges")
         return self.atoms, self.nlist, self.edges, self.inv_degree
 
+    # ------------------------------------------------------------------ receptive-field pruning (csrc/prune.hip)
+    parent = None        # set on the result of restrict(): the batch it was cut from
+    keep = None          # [M] int32: parent index of every row
+    hop = None           # [M] int32: list steps from the nearest selected atom (0 = selected)
+    graph_index = None   # [G'] host int32: parent graph of every graph (graphs without a kept atom are dropped)
+    _prune = None        # (hops, hop [N], idx [N+1], row_ptr_p) of the parent's shape, for the expansions
+    _selected = None
+
+    def restrict(self, select, hops):
+        """This batch cut down to the receptive field of the ``select``-ed atoms: every atom within ``hops`` steps
+        i -> nlist[i, k] along live entries, and the live entries of the rows closer than ``hops``.  With
+        ``hops = mp_layers`` the model's output at the selected atoms, and every gradient of a loss that reads only them, is
+        that of the whole batch.
+
+        ``select``: a mask [N] (bool, or floating point holding only 0.0 and 1.0) or an integer index array, on the host or
+        the device; the dtype decides, so every integer array is read as INDICES (``selection_mask``).  A wrong length,
+        indices out of range or twice, nothing selected, or ``hops`` outside [0, 64] raise ValueError.  Host inputs are
+        checked before any device work.  A device bool mask is not read back: when it selects nothing, that shows only in
+        the call's one host synchronisation, after the pruning launches.  A device index array is copied to the host to be
+        checked, a host synchronisation of its own: pass a mask, or host indices, where that matters.
+
+        Returns a GraphBatch of M <= N atoms in the parent's order and list form, with ``parent``, ``keep`` [M], ``hop`` [M],
+        ``selected`` [S] (its rows that hold the selected atoms, ascending parent index), ``graph_ptr`` without the graphs
+        that lost every atom, ``graph_index`` [G'], ``expand`` and ``expand_edge_grad``.  It keeps no positions: geometry
+        gradients go through the parent, ``parent.positions_grad(pruned.expand_edge_grad(de))``.  Where the parent's
+        ``edges`` require grad the pruned ``edges`` carry a grad_fn back to them.  Values at rows with ``hop > 0`` are NOT
+        the model's values of those atoms."""
+        import ctypes as C
+        from . import _lib
+        from ._lib import ptr
+        hops = int(hops)
+        if not 0 <= hops <= 64:
+            raise ValueError(f"restrict: hops must be in [0, 64], got {hops}")
+        if self.device.type != "cuda":
+            raise ValueError("restrict: a device batch is needed")
+        seed, sel_host = _select_seed(select, self.N, self.device)
+        N, K, dev = self.N, self.K, self.device
+        if not self.is_csr and N * K >= 2 ** 31:
+            raise ValueError("restrict: N * K exceeds 2^31 - 1 slots")
+        ctx = self._ctx or _lib.get_context(dev.index)
+        csr = self.is_csr
+        ne = self.n_edges
+        edges = self.edges.detach()
+        row_ptr, row_of = (self.row_ptr, self.row_of) if csr else (None, None)
+        hop = torch.empty(N, dtype=torch.int32, device=dev)
+        flag = torch.empty(N, dtype=torch.int32, device=dev)
+        idx = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        gp_long = torch.as_tensor(self.graph_ptr_host.astype(np.int64), device=dev)
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            ctx.check(ctx.lib.ng_receptive_hops(ctx.handle, st, N, K, ne, ptr(row_ptr), ptr(row_of), ptr(self.nlist), ptr(edges),
+                                                ptr(seed), hops, ptr(hop)), "ng_receptive_hops")
+            ctx.check(ctx.lib.ng_prune_keep_flags(ctx.handle, st, N, ptr(hop), ptr(flag)), "ng_prune_keep_flags")
+            ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, N, ptr(flag), ptr(idx)), "ng_exclusive_scan_i32")
+            sizes = [idx[gp_long]]
+            if csr:
+                rp_full = torch.empty(N + 1, dtype=torch.int32, device=dev)
+                ctx.check(ctx.lib.ng_prune_degrees_csr(ctx.handle, st, N, hops, ptr(row_ptr), ptr(hop), ptr(flag)),
+                          "ng_prune_degrees_csr")
+                ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, N, ptr(flag), ptr(rp_full)), "ng_exclusive_scan_i32")
+                sizes.append(rp_full[N:])
+            # the one host synchronisation: kept atoms in front of every graph (the last is M) and, for CSR, the kept entries
+            sizes = torch.cat(sizes).cpu().numpy().astype(np.int64)
+            before, M = sizes[:self.G + 1], int(sizes[self.G])
+            if M == 0:
+                raise ValueError("restrict: nothing selected")
+            counts = np.diff(before)
+            graph_index = np.nonzero(counts > 0)[0].astype(np.int32)
+            gp_p = np.concatenate([[0], np.cumsum(counts[graph_index])]).astype(np.int32)
+            keep = torch.empty(M, dtype=torch.int32, device=dev)
+            hop_p = torch.empty(M, dtype=torch.int32, device=dev)
+            atoms_p = torch.empty(M, self.C, dtype=torch.float32, device=dev)
+            inv_p = torch.empty(M, dtype=torch.float32, device=dev)
+            if csr:
+                nnz_p = int(sizes[self.G + 1])
+                row_ptr_p = torch.empty(M + 1, dtype=torch.int32, device=dev)
+                col_p = torch.empty(nnz_p, dtype=torch.int32, device=dev)
+                dist_p = torch.empty(nnz_p, dtype=torch.float32, device=dev)
+                row_of_p = torch.empty(nnz_p, dtype=torch.int32, device=dev)
+                ctx.check(ctx.lib.ng_prune_lists_csr(ctx.handle, st, N, ne, self.C, hops, ptr(row_ptr), ptr(row_of), ptr(self.nlist),
+                                                     ptr(edges), ptr(self.atoms), ptr(self.inv_degree), ptr(hop), ptr(idx),
+                                                     ptr(rp_full), ptr(keep), ptr(hop_p), ptr(atoms_p), ptr(inv_p), ptr(row_ptr_p),
+                                                     ptr(col_p) if nnz_p else None, ptr(dist_p) if nnz_p else None,
+                                                     ptr(row_of_p) if nnz_p else None), "ng_prune_lists_csr")
+                b = GraphBatch.from_csr(atoms_p, row_ptr_p, col_p, dist_p, inv_p, graph_ptr=gp_p, device=dev, validate=False,
+                                        row_of=row_of_p)
+                b._ctx = self._ctx
+            else:
+                row_ptr_p = None
+                nlist_p = torch.empty(M, K, dtype=torch.int32, device=dev)
+                edges_p = torch.empty(M, K, dtype=torch.float32, device=dev)
+                ctx.check(ctx.lib.ng_prune_lists(ctx.handle, st, N, K, self.C, self.G, hops, ptr(self.graph_ptr), ptr(self.nlist),
+                                                 ptr(edges), ptr(self.atoms), ptr(self.inv_degree), ptr(hop), ptr(idx), ptr(keep),
+                                                 ptr(hop_p), ptr(atoms_p), ptr(inv_p), ptr(nlist_p), ptr(edges_p)), "ng_prune_lists")
+                b = GraphBatch(atoms_p, nlist_p, edges_p, inv_p, graph_ptr=gp_p, device=dev, validate=False, nlist_c=None,
+                               ctx=self._ctx)
+        b.parent, b.keep, b.hop, b.graph_index = self, keep, hop_p, graph_index
+        b._prune = (hops, hop, idx, row_ptr_p)
+        if sel_host is not None:           # indices known on the host: their rows without a data-dependent torch op
+            b._selected = idx[torch.as_tensor(sel_host, device=dev)].to(torch.int64)
+        if self.edges.requires_grad and torch.is_grad_enabled():
+            b.edges = _PrunedEdges.apply(self.edges, b._expand_state(), {"edges": b.edges})
+        return b
+
+    @property
+    def selected(self):
+        """[S] int64: the rows of a restricted batch that hold the selected atoms, in ascending parent index"""
+        if self._selected is None and self.hop is not None:
+            self._selected = torch.nonzero(self.hop == 0).reshape(-1)
+        return self._selected
+
+    def _expand_state(self):
+        """what expand_edge_grad reads, without the pruned batch itself (an autograd node keeps this)"""
+        p = self.parent
+        hops, hop, idx, row_ptr_p = self._prune
+        return (p._ctx, p.device, p.N, p.K, p.n_edges, hops, p.row_ptr, getattr(p, "row_of", None), p.nlist, p.edges.detach(), hop,
+                idx, row_ptr_p, tuple(p.edges.shape), self.n_edges)
+
+    def expand_edge_grad(self, dedges):
+        """dL/d(edges) of a restricted batch in the PARENT's shape: its value where the entry was kept, +0.0 elsewhere
+        (ng_prune_expand_edge_grad); the input of ``parent.positions_grad`` / ``parent.box_grad``"""
+        if self.parent is None:
+            raise ValueError("expand_edge_grad: not a restricted batch (GraphBatch.restrict)")
+        return _expand_edge_grad(self._expand_state(), dedges)
+
+    def expand(self, values, fill=float("nan"), selected=False):
+        """per-atom values of a restricted batch in the PARENT's shape [N], ``fill`` on the other atoms
+        (ng_prune_expand_rows).  ``values`` is [M], one per row of this batch; with ``selected=True`` it is [S], one per
+        selected atom (the order of ``self.selected``), and every atom that is not selected gets ``fill``."""
+        if self.parent is None:
+            raise ValueError("expand: not a restricted batch (GraphBatch.restrict)")
+        import ctypes as C
+        from . import _lib
+        from ._lib import ptr
+        p = self.parent
+        v = torch.as_tensor(values).detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        keep = self.keep[self.selected].contiguous() if selected else self.keep
+        if v.shape[0] != keep.shape[0]:
+            raise ValueError(f"expand: values has {v.shape[0]} entries for {keep.shape[0]} "
+                             f"{'selected atoms' if selected else 'rows'}")
+        ctx = p._ctx or _lib.get_context(self.device.index)
+        out = torch.empty(p.N, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            ctx.check(ctx.lib.ng_prune_expand_rows(ctx.handle, st, p.N, v.shape[0], ptr(keep), ptr(v), float(fill), ptr(out)),
+                      "ng_prune_expand_rows")
+        return out
+
 
 def concat_graphs(graphs, device=None):
     """Concatenate per-graph tuples into one batch, offsetting neighbour indices.
@@ -521,6 +669,80 @@ def _box_grad(state, dedges, want_dvec=True):
             ctx.check(ctx.lib.ng_box_grad(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale, G,
                                           ptr(graph_ptr), ptr(box), tric, ptr(strain), ptr(dvec)), "ng_box_grad")
     return strain, dvec
+
+
+def selection_mask(select, N, device):
+    """The int32 0/1 mask [N] on ``device`` of a selection as ``GraphBatch.restrict`` reads it (validated the same way):
+    for callers that repeat or combine selections before restricting, e.g. one selection in every replica."""
+    return _select_seed(select, N, device)[0]
+
+
+def _select_seed(select, N, device):
+    """(seed [N] int32 on the device, sorted host indices or None) of a selection.  The dtype decides the reading, never the
+    values: bool [N], or floating point [N] holding only 0.0 and 1.0, is a mask; every integer array is a list of INDICES
+    (so an integer 0-1 array is not a mask: convert it with ``.astype(bool)``).  Host inputs are validated on the host;
+    a device bool mask is only shape-checked (no read-back); any other device tensor is copied to the host first."""
+    if isinstance(select, torch.Tensor) and select.is_cuda:
+        if select.dtype == torch.bool:
+            if select.dim() != 1 or select.shape[0] != N:
+                raise ValueError(f"restrict: a mask needs {N} entries, got {tuple(select.shape)}")
+            return select.to(device=device, dtype=torch.int32).contiguous(), None
+        select = select.cpu()              # index arrays are checked on the host: a host synchronisation of its own
+    s = select.numpy() if isinstance(select, torch.Tensor) else np.asarray(select)
+    if s.ndim != 1:
+        raise ValueError(f"restrict: select must be a mask [N] or an index array, got shape {s.shape}")
+    if s.dtype == np.bool_:
+        if s.shape[0] != N:
+            raise ValueError(f"restrict: a mask needs {N} entries, got {s.shape[0]}")
+        idx = np.nonzero(s)[0]
+    elif np.issubdtype(s.dtype, np.integer):
+        idx = s.astype(np.int64)
+        if len(idx) and (idx.min() < 0 or idx.max() >= N):
+            raise ValueError(f"restrict: indices must lie in [0, {N})")
+        idx = np.sort(idx)
+        if (np.diff(idx) == 0).any():
+            raise ValueError("restrict: an index is given twice")
+    elif np.issubdtype(s.dtype, np.floating) and s.shape[0] == N and np.isin(s, (0.0, 1.0)).all():
+        idx = np.nonzero(s)[0]
+    else:
+        raise ValueError("restrict: select must be a bool / 0-1 mask [N] or an integer index array")
+    if len(idx) == 0:
+        raise ValueError("restrict: nothing selected")
+    seed = np.zeros(N, dtype=np.int32)
+    seed[idx] = 1
+    return torch.from_numpy(seed).to(device), idx.astype(np.int64)
+
+
+def _expand_edge_grad(state, dedges):
+    import ctypes as C
+    from . import _lib
+    from ._lib import ptr
+    ctx, device, N, K, ne, hops, row_ptr, row_of, nlist, edges, hop, idx, row_ptr_p, shape, ne_p = state
+    ctx = ctx or _lib.get_context(device.index)
+    dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
+    if dd.numel() != ne_p:
+        raise ValueError(f"expand_edge_grad: dedges has {dd.numel()} entries for {ne_p} edges")
+    de = torch.empty(shape, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        ctx.check(ctx.lib.ng_prune_expand_edge_grad(ctx.handle, st, N, K, ne, hops, ptr(row_ptr), ptr(row_of), ptr(nlist),
+                                                    ptr(edges), ptr(hop), ptr(idx), ptr(row_ptr_p), ptr(dd), ptr(de)),
+                  "ng_prune_expand_edge_grad")
+    return de
+
+
+class _PrunedEdges(torch.autograd.Function):
+    """the edges of a restricted batch as a function of the parent's (the pruned batch's own tensor, not a copy); the
+    backward is ng_prune_expand_edge_grad"""
+
+    @staticmethod
+    def forward(ctx, parent_edges, state, holder):
+        ctx.state = state
+        return holder.pop("edges")
+
+    @staticmethod
+    def backward(ctx, dedges):
+        return _expand_edge_grad(ctx.state, dedges), None, None
 
 
 def _box_dims_grad(dims, dvec):

@@ -125,7 +125,7 @@ def check_peaks(atoms, peaks, cutoff_sigma=4, warn_sigma=2.5):
     return confident
 
 
-def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_number=16, box=None, virial=False):
+def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_number=16, box=None, virial=False, prune=False):
     """Chemical-shift restraint of one structure: ``(energy, forces)`` with
 
         energy = sum_i w_i (delta_pred_i - delta_exp_i)^2          ppm^2, a 0-d device tensor
@@ -148,7 +148,14 @@ def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_num
     ``GraphBatch.box_grad`` for the same edge gradient, the negative derivative of the energy with respect to a homogeneous
     strain of positions and box together, at fixed lists and images (its pressure contribution is trace / (3 V)).  One more
     library call, no torch autograd; energy and forces are bitwise those of ``virial=False``.  Without a box it is the
-    same sum over the open-boundary edges."""
+    same sum over the open-boundary edges.
+
+    ``prune=True``: the forward and the backward run on the receptive field of the atoms with ``weights != 0`` alone
+    (``GraphBatch.restrict``, DESIGN.md §7.17: the atoms within ``mp_layers`` list steps of them) and the edge gradient is
+    expanded to the whole structure before the positions kernel.  The lists are still built for every atom.  Same
+    shapes; energy, forces and virial are those of ``prune=False`` up to float32 summation order, the forces exactly 0.0
+    on atoms outside the field.  One host synchronisation (the size of the field); all weights 0 raises ValueError.  The
+    call to use when a few percent of the atoms carry a measured shift (a solute in explicit solvent)."""
     import torch
     from .graph import frames_to_batch
     if model.engine is None:
@@ -166,12 +173,19 @@ def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_num
         dtype=torch.float32, device=eng.device).reshape(-1)
     if y.shape[0] != batch.N or w.shape[0] != batch.N:
         raise ValueError(f"shift_restraint: targets / weights need {batch.N} entries")
-    peaks = eng.forward(batch, training=False, keep_tape=True)
+    run = batch
+    if prune:
+        run = batch.restrict(w != 0, model.receptive_hops)
+        keep = run.keep.to(torch.int64)
+        y, w = y[keep], w[keep]
+    peaks = eng.forward(run, training=False, keep_tape=True)
     diff = peaks - y
     energy = (diff * diff * w).sum()
     dpeaks = w * (2.0 * diff)              # d energy / d peaks, the bits torch autograd gives for the same expression
-    dedges = torch.empty(batch.edges.shape, dtype=torch.float32, device=eng.device)
+    dedges = torch.empty(run.edges.shape, dtype=torch.float32, device=eng.device)
     eng.backward(dpeaks, edge_grad=dedges)
+    if prune:
+        dedges = run.expand_edge_grad(dedges)
     forces = -batch.positions_grad(dedges)[0]
     if virial:
         from .graph import _box_grad
@@ -194,7 +208,8 @@ def _position_sigma(position_sigma, n):
     return s.astype(np.float32)
 
 
-def shift_uncertainty(model, atoms, positions, samples=32, position_sigma=None, neighbor_number=16, box=None, seed=0):
+def shift_uncertainty(model, atoms, positions, samples=32, position_sigma=None, neighbor_number=16, box=None, seed=0,
+                      select=None):
     """``(mean, std_model, std_input)`` [n] in ppm, on the device: the predicted shifts of one structure with an error bar
     per atom.  ``std_model`` is the closed-form spread of the model's Dropout, ``std_input`` the sampled spread over
     ``samples`` perturbed inputs (``GNNModel.predict_uncertainty``); the two parts add in variance:
@@ -211,7 +226,12 @@ def shift_uncertainty(model, atoms, positions, samples=32, position_sigma=None, 
     ``position_sigma``: a scalar or [n] coordinate error in Angstrom, finite and >= 0 (from a crystallographic B-factor:
     sqrt(B / (8 pi^2))).  The input part then comes from coordinate error instead: the S replicas are
     ``positions + sigma_i * xi`` with xi standard normal (``ng_randn(seed, offset 0)`` over [S, n, 3]), their neighbour lists
-    are rebuilt per replica, and the model's distance noise is off.  A bad sigma raises ValueError before any device work."""
+    are rebuilt per replica, and the model's distance noise is off.  A bad sigma raises ValueError before any device work.
+
+    ``select``: a mask [n] or an index array — error bars for these atoms only.  The batch (or the batch of replicas) is
+    restricted to their receptive field before the forward (``GraphBatch.restrict``); the outputs stay [n], NaN outside
+    the selection.  The model's distance noise is then drawn over the restricted lists: the same distribution, not the
+    same draws, as without ``select``."""
     import torch
     samples = int(samples)
     if samples < 1:
@@ -230,10 +250,27 @@ def shift_uncertainty(model, atoms, positions, samples=32, position_sigma=None, 
     box = box.detach() if isinstance(box, torch.Tensor) else box
     if sigma is None:
         batch = frames_to_batch(atoms, pos, neighbor_number=neighbor_number, device=eng.device, box=box)
-        return model.predict_uncertainty(batch, samples=samples, seed=seed)
+        if select is None:
+            return model.predict_uncertainty(batch, samples=samples, seed=seed)
+        pruned = batch.restrict(select, model.receptive_hops)
+        sel = pruned.selected
+        return tuple(pruned.expand(t[sel], selected=True) for t in model.predict_uncertainty(pruned, samples=samples, seed=seed))
     xi = eng.randn(samples * n * 3, seed, 0).view(samples, n, 3)
     frames = pos[None] + torch.from_numpy(sigma).to(eng.device)[None, :, None] * xi
     batch = frames_to_batch(atoms, frames, neighbor_number=neighbor_number, device=eng.device, box=box)
+    if select is not None:
+        # the same atoms in every replica; each replica has a receptive field of its own (its lists were rebuilt)
+        from .graph import selection_mask
+        one = selection_mask(select, n, eng.device)
+        pruned = batch.restrict(one.bool().repeat(samples), model.receptive_hops)
+        sel = pruned.selected
+        S_ = sel.shape[0] // samples
+        mu, var = eng.forward_moments(pruned, seed=seed, noise=False)
+        mean, var_in, var_model = eng.ensemble_moments(mu[sel].view(samples, S_).contiguous(), var[sel].view(samples, S_).contiguous())
+        at = torch.nonzero(one).reshape(-1)
+        out = torch.full((3, n), float("nan"), dtype=torch.float32, device=eng.device)
+        out[:, at] = torch.stack([mean, torch.sqrt(var_model), torch.sqrt(var_in)])
+        return out[0], out[1], out[2]
     mu, var = eng.forward_moments(batch, seed=seed, noise=False)
     mean, var_in, var_model = eng.ensemble_moments(mu.view(samples, n), var.view(samples, n))
     return mean, torch.sqrt(var_model), torch.sqrt(var_in)

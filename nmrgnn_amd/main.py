@@ -37,7 +37,7 @@ def _open_structure(struct_files):
 
 def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16, stride=1,
                    frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False, separate=False, boxes=False,
-                   uncertainty=0, position_sigma=None, average=False):
+                   uncertainty=0, position_sigma=None, average=False, atom_names=None):
     """Predict shifts for every ``stride``-th frame and write the reference's CSV.  Returns the timing
     buckets in seconds.  ``pbc``: neighbour lists under the minimum-image convention in each frame's box (its CRYST1
     record); a frame without one is an error.  ``separate``: every file is a structure of its own (see
@@ -50,7 +50,11 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     of that size instead of the model's distance noise.  ``average``: ONE row per atom over the frames read — ``index,
     residues, resids, names, peaks`` (the mean over the frames), ``peaks_std`` (the sample standard deviation over the
     frames, n - 1 in the denominator; 0 for one frame), ``confident`` (of the mean), ``frames`` (how many were read); the
-    moments are taken on the device (ng_ensemble_moments).  Without these options the CSV is what it always was."""
+    moments are taken on the device (ng_ensemble_moments).  Without these options the CSV is what it always was.
+
+    ``atom_names``: a sequence of PDB atom names (exact match) — rows for these atoms only, with their original ``index``;
+    the model runs on their receptive field alone (GNNModel.predict_selected) and ``check_peaks`` on them.  Names that match
+    no atom raise AtomNamesError."""
     if len(struct_files) == 0:
         raise ValueError('Must pass at least on structure file')
     uncertainty = int(uncertainty or 0)
@@ -70,7 +74,7 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         raise ValueError('--boxes goes with --separate (one box, or none, per structure); use --pbc for frames of one topology')
     if separate:
         return _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going,
-                              device, echo, boxes)
+                              device, echo, boxes, atom_names)
     import torch
     from .graph import frames_to_batch
     from .library import check_peaks, load_model, shift_uncertainty
@@ -85,6 +89,14 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
             raise ValueError(f"--pbc: frame {missing[0]} has no box (no CRYST1 record, or the 1 Angstrom placeholder)")
     atoms = atoms_onehot(u.elements)
     n = atoms.shape[0]
+    select = _name_mask(u.names, atom_names)        # None: every atom
+    idx = np.arange(n) if select is None else np.nonzero(select)[0]
+    if select is not None:
+        if len(idx) == 0:
+            raise AtomNamesError(f"--atom-names {','.join(atom_names)}: no atom of {', '.join(struct_files)} has one of these names")
+        atoms_all, atoms, n = atoms, atoms[idx], len(idx)      # what follows the model call sees the selected atoms only
+    else:
+        atoms_all = atoms
     model.build(atoms.shape[1])
     model.freeze()          # inference only: the engine keeps its packed weight images across the per-frame calls
     timing = {'Structure': 0.0, 'Model Inference (MI355X)': 0.0, 'Parsing': 0.0}
@@ -96,11 +108,11 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         model.build(atoms.shape[1])
         dev = model.engine.device
         box = np.stack([u.dimensions[fr] for fr in chunk]) if pbc else None
-        batch = frames_to_batch(atoms, np.stack([u.frames[fr] for fr in chunk]), neighbor_number, device=dev, box=box)
+        batch = frames_to_batch(atoms_all, np.stack([u.frames[fr] for fr in chunk]), neighbor_number, device=dev, box=box)
         torch.cuda.synchronize(dev)
         timing['Structure'] += time.perf_counter() - t
         t = time.perf_counter()
-        peaks = model(batch)
+        peaks = model(batch) if select is None else model.predict_selected(batch, np.tile(select, len(chunk)))
         if average:
             kept.append(peaks.reshape(len(chunk), n))
             timing['Model Inference (MI355X)'] += time.perf_counter() - t
@@ -110,8 +122,11 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         peaks = peaks.reshape(len(chunk), n)
         stds = []
         for fr in (chunk if uncertainty else ()):
-            _, sm, si = shift_uncertainty(model, atoms, u.frames[fr], samples=uncertainty, position_sigma=position_sigma,
-                                          neighbor_number=neighbor_number, box=u.dimensions[fr] if pbc else None, seed=fr)
+            _, sm, si = shift_uncertainty(model, atoms_all, u.frames[fr], samples=uncertainty, position_sigma=position_sigma,
+                                          neighbor_number=neighbor_number, box=u.dimensions[fr] if pbc else None, seed=fr,
+                                          select=select)
+            if select is not None:
+                sm, si = sm[idx], si[idx]
             stds.append((np.round(sm.cpu().numpy().astype(np.float64), 2), np.round(si.cpu().numpy().astype(np.float64), 2)))
         conf = []
         for k in range(len(chunk)):
@@ -126,9 +141,9 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         t = time.perf_counter()
         for k, fr in enumerate(chunk):
             pk = np.round(peaks[k].astype(np.float64), 2)
-            for i in range(n):
-                row = (i, u.resnames[i], int(u.resids[i]), u.names[i], pk[i], bool(conf[k][i]), float(fr), fr)
-                rows.append(row + (stds[k][0][i], stds[k][1][i]) if uncertainty else row)
+            for j, i in enumerate(idx):
+                row = (int(i), u.resnames[i], int(u.resids[i]), u.names[i], pk[j], bool(conf[k][j]), float(fr), fr)
+                rows.append(row + (stds[k][0][j], stds[k][1][j]) if uncertainty else row)
         timing['Parsing'] += time.perf_counter() - t
         echo('|'.join(f'{k}:{v:5.2f}s' for k, v in timing.items()))
     header = ['index', 'residues', 'resids', 'names', 'peaks', 'confident', 'time', 'frame']
@@ -146,7 +161,8 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
                 raise
             echo(f'mean over {len(frame_ids)} frames: {w}')
             conf = np.zeros(n, dtype=bool)
-        rows = [(i, u.resnames[i], int(u.resids[i]), u.names[i], pk[i], sd[i], bool(conf[i]), len(frame_ids)) for i in range(n)]
+        rows = [(int(i), u.resnames[i], int(u.resids[i]), u.names[i], pk[j], sd[j], bool(conf[j]), len(frame_ids))
+                for j, i in enumerate(idx)]
         header = ['index', 'residues', 'resids', 'names', 'peaks', 'peaks_std', 'confident', 'frames']
         timing['Parsing'] += time.perf_counter() - t
     os.makedirs(os.path.dirname(os.path.abspath(output_csv)), exist_ok=True)
@@ -158,8 +174,20 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     return timing
 
 
+class AtomNamesError(ValueError):
+    """--atom-names matched no atom: the command line reports it as a message"""
+
+
+def _name_mask(names, atom_names):
+    """bool [n]: the atoms whose PDB name is one of ``atom_names`` (exact match); None without a name list"""
+    if atom_names is None:
+        return None
+    want = {a.strip() for a in atom_names if a.strip()}
+    return np.array([str(nm).strip() in want for nm in names], dtype=bool)
+
+
 def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, device, echo,
-                   boxes=False):
+                   boxes=False, atom_names=None):
     """``eval-struct --separate``: every file is a structure of its own, with all of its MODEL frames (every ``stride``-th,
     counted per file).  The structure-frames of all files go ``frames_per_batch`` at a time into one ragged device batch
     (graph.structures_to_batch); the CSV has a leading ``file`` column (the path as given), then the reference's.  ``boxes``:
@@ -175,6 +203,12 @@ def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride
     structs = [read_pdb(f) for f in struct_files]
     atoms = [atoms_onehot(s.elements) for s in structs]
     items = [(k, fr) for k, s in enumerate(structs) for fr in range(0, len(s), stride)]     # (file, frame)
+    masks = [_name_mask(s.names, atom_names) for s in structs]      # None: every atom
+    if atom_names is not None:
+        if not any(m.any() for m in masks):
+            raise AtomNamesError(f"--atom-names {','.join(atom_names)}: no atom of {', '.join(struct_files)} has one of these names")
+        items = [(k, fr) for k, fr in items if masks[k].any()]      # a structure without a match gives no rows
+    index = [np.arange(s.n_atoms) if m is None else np.nonzero(m)[0] for s, m in zip(structs, masks)]
     timing['Structure'] += time.perf_counter() - t
     model.build(atoms[0].shape[1])
     model.freeze()
@@ -189,12 +223,16 @@ def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride
         torch.cuda.synchronize(dev)
         timing['Structure'] += time.perf_counter() - t
         t = time.perf_counter()
-        peaks = model(batch).cpu().numpy().reshape(-1)
-        gp = batch.graph_ptr_host
+        if atom_names is None:
+            peaks = model(batch).cpu().numpy().reshape(-1)
+            gp = batch.graph_ptr_host
+        else:       # the selected atoms of every structure-frame, on their receptive fields alone
+            peaks = model.predict_selected(batch, np.concatenate([masks[k] for k, _ in chunk])).cpu().numpy().reshape(-1)
+            gp = np.concatenate([[0], np.cumsum([len(index[k]) for k, _ in chunk])])
         conf = []
         for m, (k, fr) in enumerate(chunk):
             try:
-                conf.append(check_peaks(atoms[k], peaks[gp[m]:gp[m + 1]]))
+                conf.append(check_peaks(atoms[k][index[k]], peaks[gp[m]:gp[m + 1]]))
             except Warning as w:
                 if not keep_going:
                     raise
@@ -205,8 +243,8 @@ def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride
         for m, (k, fr) in enumerate(chunk):
             s = structs[k]
             pk = np.round(peaks[gp[m]:gp[m + 1]].astype(np.float64), 2)
-            for i in range(s.n_atoms):
-                rows.append((struct_files[k], i, s.resnames[i], int(s.resids[i]), s.names[i], pk[i], bool(conf[m][i]),
+            for j, i in enumerate(index[k]):
+                rows.append((struct_files[k], int(i), s.resnames[i], int(s.resids[i]), s.names[i], pk[j], bool(conf[m][j]),
                              float(fr), fr))
         timing['Parsing'] += time.perf_counter() - t
         echo('|'.join(f'{k}:{v:5.2f}s' for k, v in timing.items()))
@@ -242,8 +280,11 @@ def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride
                    'distance noise')
 @click.option('--average', is_flag=True,
               help='One row per atom: mean and standard deviation of the shifts over the frames read')
+@click.option('--atom-names', default=None, metavar='A,B,...',
+              help='Only the atoms with one of these PDB names (exact match, comma separated, e.g. H,N,CA,CB,C): the model runs '
+                   'on the atoms that can reach them; rows keep their original index')
 def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, pbc, separate,
-                boxes, uncertainty, position_sigma, average):
+                boxes, uncertainty, position_sigma, average, atom_names):
     '''Predict NMR chemical shifts with specific file'''
     if separate and (uncertainty or average):
         raise click.UsageError('--separate cannot be combined with --uncertainty or --average: the files are different '
@@ -259,9 +300,17 @@ def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, f
                                'structure')
     if boxes and not separate:
         raise click.UsageError('--boxes goes with --separate; use --pbc for frames of one topology')
-    eval_structure(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch,
-                   keep_going, echo=click.echo, pbc=pbc, separate=separate, boxes=boxes, uncertainty=uncertainty,
-                   position_sigma=position_sigma, average=average)
+    names = None
+    if atom_names is not None:
+        names = [a.strip() for a in atom_names.split(',') if a.strip()]
+        if not names:
+            raise click.UsageError('--atom-names takes a comma-separated list of PDB atom names')
+    try:
+        eval_structure(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch,
+                       keep_going, echo=click.echo, pbc=pbc, separate=separate, boxes=boxes, uncertainty=uncertainty,
+                       position_sigma=position_sigma, average=average, atom_names=names)
+    except AtomNamesError as e:
+        raise click.ClickException(str(e))
 
 
 if __name__ == '__main__':

@@ -114,6 +114,27 @@ class GNNModel:
     call = __call__
     predict = __call__
 
+    @property
+    def receptive_hops(self):
+        """list steps a predicted shift can see: one per message-passing layer (the FC and head layers are per atom, the
+        model has no global term) — the ``hops`` of ``GraphBatch.restrict`` that leave the selected shifts exact"""
+        return int(self.hypers.get('mp_layers'))
+
+    def predict_selected(self, inputs, select):
+        """the [S] shifts of the ``select``-ed atoms (a mask [N] or an index array; ascending atom index), from an inference
+        forward on their receptive field alone (``GraphBatch.restrict(select, receptive_hops)``): the
+        values ``self(inputs)[select]`` holds, at the cost of the atoms and edges that can reach them.  ``inputs`` as
+        ``__call__``; device inputs give a device tensor, host inputs NumPy."""
+        batch, on_device = self._as_batch(inputs)
+        if self.engine is None:
+            self.build(batch.C)
+        pruned = batch.restrict(select, self.receptive_hops)
+        with torch.no_grad():
+            peaks = self.engine.forward(pruned, training=False)[pruned.selected]
+        if on_device:
+            return peaks
+        return peaks.cpu().numpy().view(Peaks)
+
     def _train_seed(self):
         """the Philox key of the next training-mode call (``__call__(training=True)`` without ``seed=``)"""
         seed = ((int(self._seed) * 0x9E3779B97F4A7C15) ^ (self._train_calls * 1000003 + 0x632BE5AB)) & ((1 << 63) - 1)
