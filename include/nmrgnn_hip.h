@@ -748,6 +748,29 @@ int ng_loss_name(ng_ctx*, void* stream, int64_t N, int G, const int32_t* graph_p
 int ng_name_metrics(ng_ctx*, void* stream, int64_t N, const float* y, const float* w, const int32_t* names, const float* pred,
                     int n_names, const uint32_t* member, int K, int accumulate, double* moments);
 
+/* Mini-batch collation from a device-resident record store (nmrgnn_amd/dataset.py: ShiftDataset.batch; csrc/collate.hip).
+ * The store holds R records back to back, record r in the rows [rec_ptr[r], rec_ptr[r+1]) of
+ *   s_atoms [Ntot,C] f32, s_nlist [Ntot,K] i32 (record-LOCAL indices), s_edges [Ntot,K] f32, s_inv_degree [Ntot] f32,
+ *   s_y [Ntot,3] f32 (shift, name id, mask), s_w [Ntot] f32;  rec_ptr [R+1] int64 on the device.
+ * The batch is the records ids[0..G) (int32, any order, repeats allowed) in that order; graph_ptr [G+1] int32 holds their
+ * batch offsets (graph_ptr[0] = 0, graph_ptr[G] = N, graph_ptr[g+1] - graph_ptr[g] = the size of record ids[g]; the caller
+ * knows the sizes on the host).  Outputs, for batch row i of graph g with source row s = rec_ptr[ids[g]] + i - graph_ptr[g]:
+ *   atoms[i,:] = s_atoms[s,:], nlist[i,:] = s_nlist[s,:] + graph_ptr[g] (EVERY slot, padded ones included),
+ *   edges[i,:] = s_edges[s,:], inv_degree[i], w[i], y0[i] = s_y[s,0], names[i] = (int32) s_y[s,1] (truncation),
+ *   y_true[i,:] = s_y[s,:] (y_true may be NULL).
+ * These are the arrays of a host concatenation with offset neighbour indices, bit for bit.  One launch on `stream`,
+ * asynchronous, no allocation, no atomics: a second call writes the same bits.  Source offsets are 64-bit (Ntot * K may
+ * pass 2^31).  ids and graph_ptr live on the device and are not read by the host: a row whose id lies outside [0, R) or
+ * whose source row lies outside its record is skipped (its outputs keep what they held), never read out of bounds.
+ * Refused (NG_ERR_INVALID, before any launch): NULL context; K or C outside [1, 4096]; N < 0 or N >= 2^31 - 256; G < 1 with
+ * N > 0, or G > N; R < 1 with N > 0, or Ntot < R; with N > 0 a NULL store array, ids, graph_ptr or output other than y_true.
+ * N == 0 returns NG_OK and launches nothing. */
+int ng_collate_batch(ng_ctx*, void* stream, int64_t R, int64_t Ntot, const float* s_atoms, const int32_t* s_nlist,
+                     const float* s_edges, const float* s_inv_degree, const float* s_y, const float* s_w,
+                     const int64_t* rec_ptr, const int32_t* ids, const int32_t* graph_ptr, int64_t N, int K, int C, int G,
+                     float* atoms, int32_t* nlist, float* edges, float* inv_degree, float* y0, float* w, int32_t* names,
+                     float* y_true);
+
 /* Keras Adam (nmrgnn/model.py:44-45): one fused pass over the flat parameter buffer.
  *   g is first multiplied by grad_scale (1/world_size after a summing all-reduce). */
 int ng_adam_step(ng_ctx*, void* stream, int64_t n, float* p, const float* g, float* m, float* v,

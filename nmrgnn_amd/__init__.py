@@ -17,7 +17,8 @@ _LAZY = {
     "MPLayer": "layers", "AMPLayer": "layers", "RBFExpansion": "layers", "EdgeFCBlock": "layers", "MPBlock": "layers",
     "FCBlock": "layers", "GNNModel": "model", "build_GNNModel": "model",
     "load_model": "library", "universe2graph": "library", "check_peaks": "library",
-    "save_model": "library", "NameLoss": "losses", "Trainer": "train",
+    "save_model": "library", "NameLoss": "losses", "Trainer": "train", "ShiftDataset": "dataset",
+    "ReduceLROnPlateau": "callbacks", "ModelCheckpoint": "callbacks", "EarlyStopping": "callbacks",
     "type_mask": "metrics", "NameRMSD": "metrics", "NameCorr": "metrics", "NameCount": "metrics", "NameMetrics": "metrics",
 }
 # nmrgnn/__init__.py:26-29: the reference's custom Keras objects, keyed by class name

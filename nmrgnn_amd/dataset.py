@@ -1,0 +1,299 @@
+"""``ShiftDataset`` — a ragged record store in device memory, and mini-batches from it in one launch.
+
+A record is what the reference's ``nmrdata.dataset(..., label_info=True)`` yields (nmrgnn/library.py:50-89):
+``x = (atoms[n, C], nlist[n, K], edges[n, K], inv_degree[n])``, ``y[n, 3]`` = [shift, name id, mask], ``w[n]``.  ``nlist`` is
+record-local; padded slots hold ``nlist == 0`` and ``edges == 0``.  The store keeps R records back to back:
+
+    atoms [Ntot, C] f32 (rows as given)     nlist [Ntot, K] i32 (record-local)     edges [Ntot, K] f32
+    inv_degree [Ntot] f32 (as given)        y [Ntot, 3] f32                        w [Ntot] f32
+    rec_ptr [R + 1] int64 (device and host)  file_ptr [S + 1] int64 (host: the records of source s)
+
+A whole training set fits on the device (100 000 records of up to 256 atoms at K = 16 are about 5 GB), so a mini-batch is
+``ng_collate_batch`` (csrc/collate.hip) away: the host knows every record's size, forms ``graph_ptr`` by a NumPy cumsum,
+sends it with the record ids in ONE small copy, and one launch writes the batch — the arrays of ``graph.concat_graphs``
+over the same records in the same order, bit for bit.  Everything is validated once, when the store is built; a batch
+checks nothing and never reads the device.
+
+On a CPU device ``batch`` does the same with torch indexing (host tests, shard bookkeeping)."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .graph import BatchPrefetcher, GraphBatch, _norm_device
+
+FORMAT_VERSION = 1
+_ARRAYS = ("atoms", "nlist", "edges", "inv_degree", "y", "w")
+_DTYPES = {"atoms": np.float32, "nlist": np.int32, "edges": np.float32, "inv_degree": np.float32, "y": np.float32,
+           "w": np.float32}
+_MAX_BATCH_ATOMS = 2 ** 31 - 256          # ng_collate_batch's limit on N
+
+
+def _check_record(r, rec, C, K):
+    """one ``(x, y, w)`` tuple -> its six host arrays, or ValueError naming record ``r``"""
+    try:
+        x, y, w = rec
+        atoms, nlist, edges, inv = x
+    except (TypeError, ValueError):
+        raise ValueError(f"record {r}: expected ((atoms, nlist, edges, inv_degree), y, w)") from None
+    atoms, nlist_raw, edges = np.asarray(atoms), np.asarray(nlist), np.asarray(edges)
+    inv, y, w = np.asarray(inv).reshape(-1), np.asarray(y), np.asarray(w).reshape(-1)
+    if atoms.ndim != 2 or nlist_raw.ndim != 2 or edges.ndim != 2 or y.ndim != 2 or y.shape[1] != 3:
+        raise ValueError(f"record {r}: atoms must be [n, C], nlist and edges [n, K], y [n, 3]")
+    n = atoms.shape[0]
+    if n == 0:
+        raise ValueError(f"record {r}: no atoms")
+    if atoms.shape[1] < 1 or nlist_raw.shape[1] < 1:
+        raise ValueError(f"record {r}: C and K must be at least 1")
+    if C is not None and (atoms.shape[1] != C or nlist_raw.shape[1] != K):
+        raise ValueError(f"record {r}: C = {atoms.shape[1]}, K = {nlist_raw.shape[1]}, but the records before it have "
+                         f"C = {C}, K = {K}")
+    if nlist_raw.shape[0] != n or tuple(edges.shape) != tuple(nlist_raw.shape) or inv.shape[0] != n or y.shape[0] != n \
+            or w.shape[0] != n:
+        raise ValueError(f"record {r}: {n} atom rows, but nlist {nlist_raw.shape}, edges {edges.shape}, inv_degree "
+                         f"{inv.shape}, y {y.shape}, w {w.shape}")
+    nl = nlist_raw.astype(np.int64)
+    if not np.array_equal(nl, nlist_raw):
+        raise ValueError(f"record {r}: nlist holds values that are no integers")
+    if nl.min() < 0 or nl.max() >= n:
+        raise ValueError(f"record {r}: nlist entries must lie in [0, {n}); got [{nl.min()}, {nl.max()}]")
+    edges = edges.astype(np.float32)
+    if not np.isfinite(edges).all() or (edges < 0).any():
+        raise ValueError(f"record {r}: edges must be finite and >= 0")
+    return (atoms.astype(np.float32), nl.astype(np.int32), edges, inv.astype(np.float32), y.astype(np.float32),
+            w.astype(np.float32))
+
+
+class _StorePrefetcher(BatchPrefetcher):
+    """BatchPrefetcher over lists of record ids: batch t + 1 is collated on the side stream, with the side context, while
+    step t runs; the label tensors are handed over like the batch's own"""
+
+    def __init__(self, dataset, id_lists):
+        super().__init__(id_lists, device=dataset.device)
+        self.dataset = dataset
+        self._first = True
+        if self.device.type == "cuda":
+            # one side stream and library context per store, shared by its views and kept across epochs
+            side = dataset._side
+            if not side:
+                from . import _lib
+                side["stream"] = torch.cuda.Stream(device=self.device)
+                side["ctx"] = _lib.Context(self.device.index)
+            self._stream, self._ctx = side["stream"], side["ctx"]
+
+    def _construct(self, ids, ctx):
+        return self.dataset._collate(ids, False, ctx)[:4]
+
+    def _device_inputs(self, ids):
+        # the store was written long before; only the first batch waits for whatever built it on the consumer's stream
+        first, self._first = self._first, False
+        return first
+
+    def _hand_over(self, out, ready):
+        gb = super()._hand_over(out[0], ready)
+        if ready is not None:
+            consumer = torch.cuda.current_stream(self.device)
+            for t in out[1:]:
+                t.record_stream(consumer)
+        return (gb,) + tuple(out[1:])
+
+
+class ShiftDataset:
+    """A record store, or a view of one by a list of record ids (``split``); see the module docstring.  ``len()`` is the
+    number of records of the view, and every record id a method takes counts within the view."""
+
+    def __init__(self, arrays, rec_ptr, file_ptr, device=None, _ids=None, _parent=None):
+        if _parent is not None:                       # a view: shares every array
+            self.__dict__.update(_parent.__dict__)
+            self.record_ids = np.asarray(_ids, np.int64)
+            return
+        self.device = _norm_device(device)
+        self.rec_ptr_host = np.ascontiguousarray(rec_ptr, dtype=np.int64)
+        self.file_ptr = np.ascontiguousarray(file_ptr, dtype=np.int64)
+        self.R = len(self.rec_ptr_host) - 1
+        self.Ntot = int(self.rec_ptr_host[-1])
+        for k in _ARRAYS:
+            a = np.ascontiguousarray(arrays[k], dtype=_DTYPES[k])
+            if a.shape[0] != self.Ntot:
+                raise ValueError(f"{k} has {a.shape[0]} rows, rec_ptr ends at {self.Ntot}")
+            setattr(self, k, torch.from_numpy(a).to(self.device))
+        self.C, self.K = int(self.atoms.shape[1]), int(self.nlist.shape[1])
+        self.rec_ptr = torch.from_numpy(self.rec_ptr_host).to(self.device)
+        self._sizes = np.diff(self.rec_ptr_host)
+        self._side = {}                               # the prefetcher's stream and context (made at the first epoch)
+        self.record_ids = np.arange(self.R, dtype=np.int64)
+
+    # ------------------------------------------------------------------ building, files
+    @classmethod
+    def from_records(cls, records, device=None):
+        """The store of an iterable of the reference's ``(x, y, w)`` tuples (anything with ``__array__``: a user with
+        TensorFlow and nmrdata converts once).  Validated here, once: ``ValueError`` naming the record for C or K that
+        differ between records, ``nlist`` outside [0, n), negative or non-finite ``edges``, a row-count mismatch, n == 0."""
+        parts, C, K = [], None, None
+        for r, rec in enumerate(records):
+            arrs = _check_record(r, rec, C, K)
+            C, K = arrs[0].shape[1], arrs[1].shape[1]
+            parts.append(arrs)
+        if not parts:
+            raise ValueError("from_records: no records")
+        arrays = {k: np.concatenate([p[i] for p in parts]) for i, k in enumerate(_ARRAYS)}
+        rec_ptr = np.concatenate([[0], np.cumsum([p[0].shape[0] for p in parts])])
+        return cls(arrays, rec_ptr, [0, len(parts)], device=device)
+
+    def _host_arrays(self):
+        """(arrays, rec_ptr) of this view's records in view order, on the host"""
+        ids = self.record_ids
+        sizes = self._sizes[ids]
+        gp = np.concatenate([[0], np.cumsum(sizes)])
+        rows = torch.from_numpy(np.repeat(self.rec_ptr_host[ids] - gp[:-1], sizes) + np.arange(gp[-1]))
+        return {k: getattr(self, k).cpu()[rows].numpy() for k in _ARRAYS}, gp
+
+    def save(self, path):
+        """one ``.npz``: the six arrays, ``rec_ptr``, ``file_ptr`` and ``format_version``.  A view saves its own records,
+        in its order, as one source."""
+        whole = len(self.record_ids) == self.R and np.array_equal(self.record_ids, np.arange(self.R))
+        arrays, rec_ptr = self._host_arrays()
+        file_ptr = self.file_ptr if whole else np.asarray([0, len(self.record_ids)], np.int64)
+        with open(path, "wb") as f:
+            np.savez(f, rec_ptr=rec_ptr.astype(np.int64), file_ptr=file_ptr, format_version=np.asarray(FORMAT_VERSION, np.int64),
+                     **arrays)
+
+    @classmethod
+    def load(cls, paths, device=None):
+        """the store of one file or of several, concatenated in the order given; ``file_ptr`` keeps the sources apart
+        (``split`` takes its validation share from every source).  The arrays were validated when they were built; here
+        only their shapes and the version are checked."""
+        if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+            paths = [paths]
+        parts, rec_ptrs, file_ptrs, base_r, base_n = [], [np.zeros(1, np.int64)], [np.zeros(1, np.int64)], 0, 0
+        for p in paths:
+            with np.load(p) as z:
+                if "format_version" not in z.files or int(z["format_version"]) != FORMAT_VERSION:
+                    raise ValueError(f"{p}: not a ShiftDataset file of format version {FORMAT_VERSION}")
+                arrs = {k: z[k] for k in _ARRAYS}
+                rp, fp = z["rec_ptr"].astype(np.int64), z["file_ptr"].astype(np.int64)
+            if parts and (arrs["atoms"].shape[1] != parts[0]["atoms"].shape[1]
+                          or arrs["nlist"].shape[1] != parts[0]["nlist"].shape[1]):
+                raise ValueError(f"{p}: C or K differ from those of {paths[0]}")
+            if rp[0] != 0 or (np.diff(rp) < 1).any() or fp[0] != 0 or fp[-1] != len(rp) - 1 or (np.diff(fp) < 0).any():
+                raise ValueError(f"{p}: inconsistent rec_ptr / file_ptr")
+            parts.append(arrs)
+            rec_ptrs.append(rp[1:] + base_n)
+            file_ptrs.append(fp[1:] + base_r)
+            base_r += len(rp) - 1
+            base_n += int(rp[-1])
+        if not parts:
+            raise ValueError("load: no files")
+        arrays = {k: np.concatenate([a[k] for a in parts]) for k in _ARRAYS}
+        return cls(arrays, np.concatenate(rec_ptrs), np.concatenate(file_ptrs), device=device)
+
+    def __len__(self):
+        return len(self.record_ids)
+
+    def record_sizes(self):
+        """atoms of every record of the view (host)"""
+        return self._sizes[self.record_ids]
+
+    def _view(self, ids):
+        return ShiftDataset(None, None, None, _ids=ids, _parent=self)
+
+    def split(self, validation):
+        """``(train, val)`` views: of every source's records (within this view, in its order) the first
+        ``int(validation * count)`` go to validation, the rest to train (nmrgnn/library.py:60-70 takes the same share of
+        every file).  No data is copied."""
+        validation = float(validation)
+        if not 0.0 <= validation <= 1.0:
+            raise ValueError(f"split: validation must lie in [0, 1], got {validation}")
+        src = np.searchsorted(self.file_ptr, self.record_ids, side="right") - 1
+        train, val = [], []
+        for s in range(len(self.file_ptr) - 1):
+            mine = self.record_ids[src == s]
+            k = int(validation * len(mine))
+            val.append(mine[:k])
+            train.append(mine[k:])
+        return self._view(np.concatenate(train)), self._view(np.concatenate(val))
+
+    # ------------------------------------------------------------------ batches
+    def _collate(self, ids, want_y_true, ctx=None):
+        """(GraphBatch, y, w, names, y_true or None) of the view's records ``ids``"""
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        if len(ids) == 0:
+            raise ValueError("batch: no record ids")
+        if ids.min() < 0 or ids.max() >= len(self.record_ids):
+            raise ValueError(f"batch: record ids must lie in [0, {len(self.record_ids)})")
+        store_ids = self.record_ids[ids]
+        sizes = self._sizes[store_ids]
+        G = len(store_ids)
+        gp = np.zeros(G + 1, np.int64)
+        np.cumsum(sizes, out=gp[1:])
+        N = int(gp[-1])
+        if N >= _MAX_BATCH_ATOMS:
+            raise ValueError(f"batch: {N} atoms in one batch")
+        dev = self.device
+        if dev.type != "cuda":
+            rows = torch.from_numpy(np.repeat(self.rec_ptr_host[store_ids] - gp[:-1], sizes) + np.arange(N))
+            off = torch.from_numpy(np.repeat(gp[:-1], sizes).astype(np.int32))
+            yt = self.y[rows]
+            gb = GraphBatch(self.atoms[rows], self.nlist[rows] + off[:, None], self.edges[rows], self.inv_degree[rows],
+                            graph_ptr=gp, device=dev, validate=False)
+            return gb, yt[:, 0].contiguous(), self.w[rows], yt[:, 1].to(torch.int32), (yt if want_y_true else None)
+        import ctypes as C
+        from . import _lib
+        from ._lib import ptr
+        lib_ctx = ctx or _lib.get_context(dev.index)
+        # graph_ptr first, so that the batch's graph_ptr starts its allocation; the ids behind it: one copy
+        meta = torch.from_numpy(np.concatenate([gp, store_ids]).astype(np.int32)).to(dev)
+        gp_dev, ids_dev = meta[:G + 1], meta[G + 1:]
+        atoms = torch.empty(N, self.C, dtype=torch.float32, device=dev)
+        nlist = torch.empty(N, self.K, dtype=torch.int32, device=dev)
+        edges = torch.empty(N, self.K, dtype=torch.float32, device=dev)
+        inv = torch.empty(N, dtype=torch.float32, device=dev)
+        y0 = torch.empty(N, dtype=torch.float32, device=dev)
+        w = torch.empty(N, dtype=torch.float32, device=dev)
+        names = torch.empty(N, dtype=torch.int32, device=dev)
+        y_true = torch.empty(N, 3, dtype=torch.float32, device=dev) if want_y_true else None
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            lib_ctx.check(lib_ctx.lib.ng_collate_batch(
+                lib_ctx.handle, st, self.R, self.Ntot, ptr(self.atoms), ptr(self.nlist), ptr(self.edges), ptr(self.inv_degree),
+                ptr(self.y), ptr(self.w), ptr(self.rec_ptr), ptr(ids_dev), ptr(gp_dev), N, self.K, self.C, G, ptr(atoms),
+                ptr(nlist), ptr(edges), ptr(inv), ptr(y0), ptr(w), ptr(names), ptr(y_true)), "ng_collate_batch")
+        gb = GraphBatch(atoms, nlist, edges, inv, graph_ptr=gp, device=dev, validate=False, ctx=ctx, graph_ptr_dev=gp_dev)
+        return gb, y0, w, names, y_true
+
+    def batch(self, ids):
+        """``(GraphBatch, y[N], w[N], names[N] int32)`` of the records ``ids`` (any order, repeats allowed): the arrays of
+        ``concat_graphs`` over these records in this order, padded slots offset like the rest; ``y`` is the shift column,
+        ``names`` the int32 truncation of the name column (``metrics._split_y_true``).  No host synchronisation."""
+        return self._collate(ids, False)[:4]
+
+    def _epoch_order(self, shuffle, seed, epoch):
+        n = len(self.record_ids)
+        if not shuffle:
+            return np.arange(n, dtype=np.int64)
+        return np.random.default_rng([int(seed), int(epoch)]).permutation(n).astype(np.int64)
+
+    def epoch_ids(self, batch_graphs, shuffle=True, seed=0, epoch=0, drop_remainder=False):
+        """the id lists of an epoch's batches (what ``batches`` collates)"""
+        batch_graphs = int(batch_graphs)
+        if batch_graphs < 1:
+            raise ValueError(f"batch_graphs must be >= 1, got {batch_graphs}")
+        order = self._epoch_order(shuffle, seed, epoch)
+        out = [order[i:i + batch_graphs] for i in range(0, len(order), batch_graphs)]
+        if drop_remainder and out and len(out[-1]) < batch_graphs:
+            out.pop()
+        return out
+
+    def batches(self, batch_graphs, shuffle=True, seed=0, epoch=0, drop_remainder=False):
+        """Iterate over one epoch: ``(GraphBatch, y, w, names)`` per batch of ``batch_graphs`` records.  The order is
+        ``np.random.default_rng([seed, epoch]).permutation(len(self))`` — a FULL permutation, where the reference shuffles
+        through a 500-record buffer (nmrgnn/library.py:73); store order with ``shuffle=False``.  The last, shorter batch is
+        kept unless ``drop_remainder``.  On the GPU batch t + 1 is collated on a side stream with its own library context
+        while the caller's step t runs (``graph.BatchPrefetcher``); the bits are those of ``batch(ids)``."""
+        return iter(_StorePrefetcher(self, self.epoch_ids(batch_graphs, shuffle, seed, epoch, drop_remainder)))
+
+    def eval_batches(self, batch_graphs):
+        """``(GraphBatch, y_true[N, 3])`` in store order: what ``GNNModel.evaluate`` takes"""
+        for ids in self.epoch_ids(batch_graphs, shuffle=False):
+            out = self._collate(ids, True)
+            yield out[0], out[4]

@@ -75,7 +75,7 @@ class GraphBatch:
     _ctx = None        # library context for the list builders; None = the device's shared one (BatchPrefetcher sets its own)
 
     def __init__(self, atoms, nlist, edges, inv_degree, graph_ptr=None, device=None,
-                 validate=True, nlist_c=None, ctx=None):
+                 validate=True, nlist_c=None, ctx=None, graph_ptr_dev=None):
         self.device = _norm_device(device)
         self._ctx = ctx
         self.atoms = _to_dev(atoms, torch.float32, self.device)
@@ -97,7 +97,9 @@ class GraphBatch:
         if graph_ptr is None:
             graph_ptr = [0, self.N]
         self.graph_ptr_host = np.asarray(graph_ptr, dtype=np.int32)
-        self.graph_ptr = _graph_ptr_dev(self.graph_ptr_host, self.device)
+        # graph_ptr_dev: the caller already holds this partition on the device (dataset.ShiftDataset.batch sends it with the
+        # record ids in one copy)
+        self.graph_ptr = graph_ptr_dev if graph_ptr_dev is not None else _graph_ptr_dev(self.graph_ptr_host, self.device)
         self.G = len(self.graph_ptr_host) - 1
         self._csc = None
         self._live = None
@@ -535,29 +537,39 @@ class BatchPrefetcher:
         self._stream = None
         self._ctx = None
 
-    def _build(self, item):
+    def _construct(self, item, ctx):
+        """the batch of one source item (a subclass may return a tuple whose first element is the batch)"""
         if len(item) == 2 and not hasattr(item[0], "shape"):
             raw, graph_ptr = item
         else:
             raw, graph_ptr = item, None
+        return GraphBatch(*raw, graph_ptr=graph_ptr, device=self.device, ctx=ctx, **self.batch_kw)
+
+    def _device_inputs(self, item):
+        """does the item hold device tensors that the consumer's stream may still be writing?"""
+        raw = item[0] if len(item) == 2 and not hasattr(item[0], "shape") else item
+        return any(isinstance(x, torch.Tensor) and x.is_cuda for x in raw)
+
+    def _build(self, item):
         if self.device.type != "cuda":
-            return GraphBatch(*raw, graph_ptr=graph_ptr, device=self.device, **self.batch_kw), None
+            return self._construct(item, None), None
         from . import _lib
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=self.device)
             self._ctx = _lib.Context(self.device.index)
-        if any(isinstance(x, torch.Tensor) and x.is_cuda for x in raw):
+        if self._device_inputs(item):
             # device inputs may have been produced on the consumer's stream: wait for what is enqueued there (at most the
             # previous step).  Host arrays need no such wait — and must not have one: a pageable copy holds the host until it
             # has run, and behind that wait it would run only after the previous step, with the next step not yet enqueued
             self._stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(self._stream):
-            gb = GraphBatch(*raw, graph_ptr=graph_ptr, device=self.device, ctx=self._ctx, **self.batch_kw)
+            out = self._construct(item, self._ctx)
+            gb = out[0] if isinstance(out, tuple) else out
             gb.csc()
             gb.live_edges()
             ready = torch.cuda.Event()
             ready.record(self._stream)
-        return gb, ready
+        return out, ready
 
     def _hand_over(self, gb, ready):
         if ready is None:

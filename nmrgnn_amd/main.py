@@ -1,11 +1,15 @@
-"""Command line of the hot path's caller: ``eval-struct`` (nmrgnn/main.py:192-278).
+"""Command line of the hot path's caller: ``eval-struct`` (nmrgnn/main.py:192-278) and ``train`` (nmrgnn/main.py:36-90).
 
 Same arguments, options, CSV columns and per-phase timing line as the reference command.  Frames
 of a trajectory are independent graphs, so they are concatenated ``--frames-per-batch`` at a time into
 one device batch (one launch sequence per batch instead of one per frame) and their neighbour lists
 are built on the GPU (ng_knn_graph); the reference evaluates frame by frame with a CPU neighbour search.  With
-``--separate`` every file is a structure of its own, batched as a ragged batch (graph.structures_to_batch).  The training / hyper-parameter-search commands of the reference are out of scope
-(control plane)."""
+``--separate`` every file is a structure of its own, batched as a ragged batch (graph.structures_to_batch).
+
+``train RECORDS... NAME [EPOCHS]`` is the reference's training command on ``dataset.ShiftDataset`` files (``.npz``, written by
+``ShiftDataset.save``; the package reads no TFRecords): ``GNNModel.fit`` with the reference's callbacks, the model saved to
+NAME and the history pickled beside it.  Out of scope: ``--tensorboard``, ``hyper`` (the hyper-parameter search) and
+``eval-tfrecords`` (its table needs nmrdata's residue-name list, which the package does not ship)."""
 from __future__ import annotations
 
 import csv
@@ -311,6 +315,75 @@ def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, f
                        position_sigma=position_sigma, average=average, atom_names=names)
     except AtomNamesError as e:
         raise click.ClickException(str(e))
+
+
+def _load_embeddings(path):
+    """nmrdata's embeddings dict ({'atom': ..., 'nlist': ..., 'name': {name: id}}) from a JSON or a pickle file"""
+    import json
+    import pickle
+    with open(path, 'rb') as f:
+        raw = f.read()
+    try:
+        emb = json.loads(raw.decode('utf-8'))
+    except (UnicodeDecodeError, ValueError):
+        emb = pickle.loads(raw)
+    if not isinstance(emb, dict) or 'name' not in emb:
+        raise ValueError(f"{path}: no embeddings dict with a 'name' table")
+    return emb
+
+
+def train_model(records, name, epochs=3, checkpoint_path='/tmp/checkpoint', embeddings=None, validation=0.1, load=False,
+                loss_balance=1.0, batch_graphs=1, seed=0, device=None, echo=print):
+    """The reference's ``train`` (nmrgnn/main.py:36-90) on ``ShiftDataset`` files: build the model, optionally load the
+    checkpoint, fit with ReduceLROnPlateau(val_loss, 0.99, patience 4, min_lr 1e-4) and a checkpoint every epoch, save the
+    model to ``name`` and pickle the history to the first free ``name-history-<i>.pb``.  Returns ``(model, history)``."""
+    import pickle
+    from .callbacks import ModelCheckpoint, ReduceLROnPlateau, history_path
+    from .dataset import ShiftDataset
+    from .model import build_GNNModel
+    if len(records) == 0:
+        raise ValueError('Must give input record files')
+    emb = _load_embeddings(embeddings) if embeddings is not None else None
+    model = build_GNNModel(loss_balance=loss_balance, device=device, embeddings=emb)
+    if load:
+        model.load_weights(checkpoint_path)
+    data = ShiftDataset.load(list(records), device=device)
+    train_data, validation_data = data.split(validation)
+    callbacks = []
+    if len(validation_data):              # the plateau rule watches val_loss
+        callbacks.append(ReduceLROnPlateau(monitor='val_loss', factor=0.99, patience=4, min_lr=1e-4, verbose=1))
+    callbacks.append(ModelCheckpoint(checkpoint_path))
+    results = model.fit(train_data, epochs=epochs, callbacks=callbacks, batch_graphs=batch_graphs, seed=seed,
+                        validation_data=validation_data if len(validation_data) else None, verbose=0)
+    for e, i in enumerate(results.epoch):
+        echo(f"Epoch {i + 1}: " + " - ".join(f"{k}: {v[e]:.6g}" for k, v in results.history.items()))
+    model.save(name)
+    pfile = history_path(name)
+    with open(pfile, 'wb') as f:
+        pickle.dump(results.history, file=f)
+    echo(f'Model saved to {name}, history to {pfile}')
+    return model, results
+
+
+@main.command(name='train')
+@click.argument('records', nargs=-1, type=click.Path(exists=True))
+@click.argument('name')
+@click.argument('epochs', default=3)
+@click.option('--checkpoint-path', default='/tmp/checkpoint', type=click.Path(), help='where to save model')
+@click.option('--embeddings', default=None, type=click.Path(exists=True),
+              help='JSON or pickle file with the nmrdata embeddings dict (enables the per-name metrics)')
+@click.option('--validation', default=0.1, help='relative size of validation')
+@click.option('--load/--noload', default=False, help='Load saved model at checkpoint path?')
+@click.option('--loss-balance', default=1.0, help='Balance between L2 (max @ 1.0) and corr loss (max @ 0.0)')
+@click.option('--batch-graphs', default=1, help='Records per optimiser step (1: the reference; more changes the optimisation)')
+@click.option('--seed', default=0, help='Seed of the per-epoch shuffle')
+@click.option('--device', default=None, help='Device, e.g. cuda:0')
+def train(records, name, epochs, checkpoint_path, embeddings, validation, load, loss_balance, batch_graphs, seed, device):
+    '''Train the model on ShiftDataset record files (.npz)'''
+    if len(records) == 0:
+        raise click.UsageError('Must give input record files')
+    train_model(records, name, epochs, checkpoint_path=checkpoint_path, embeddings=embeddings, validation=validation,
+                load=load, loss_balance=loss_balance, batch_graphs=batch_graphs, seed=seed, device=device, echo=click.echo)
 
 
 if __name__ == '__main__':

@@ -25,6 +25,14 @@ class Peaks(np.ndarray):
         return np.asarray(self)
 
 
+class History:
+    """what ``GNNModel.fit`` returns: ``history`` {name: one value per epoch} and ``epoch``, the epoch numbers"""
+
+    def __init__(self):
+        self.history = {}
+        self.epoch = []
+
+
 class GNNModel:
     def __init__(self, hypers, peak_standards, name='gnn-model', device=None, seed=1234, **kwargs):
         self.hypers = hypers
@@ -242,6 +250,84 @@ class GNNModel:
         if nm is not None:
             out.update(nm.results())
         return out
+
+    def fit(self, train, epochs=1, validation_data=None, batch_graphs=1, callbacks=(), shuffle=True, seed=0,
+            initial_epoch=0, verbose=1):
+        """Train on a ``dataset.ShiftDataset`` (keras ``model.fit`` as nmrgnn/main.py:79-80 calls it).  Runs ``epochs``
+        epochs, numbered ``initial_epoch, initial_epoch + 1, ...`` (the number seeds the shuffle and is what callbacks see;
+        unlike keras, ``epochs`` counts the epochs RUN, so ``fit(epochs=1, initial_epoch=1)`` after ``load_weights`` is the
+        second epoch of ``fit(epochs=2)``).  Returns an object whose ``.history`` is a ``dict[str, list[float]]`` with the
+        keys ``loss``, the metric names, ``val_loss`` / ``val_<metric>`` (with ``validation_data``) and ``lr``.
+
+        ``batch_graphs=1`` is the reference's one record per step.  Larger values are this package's batched step and CHANGE
+        THE OPTIMISATION: the loss is a mean over the batch's graphs, so G records make one step on their mean gradient
+        instead of G steps.  Single process: a ``torch.distributed`` world larger than 1 is refused (``Trainer`` with
+        ``parallel.GradBuckets`` is the data-parallel path).
+
+        Per epoch: ``Trainer.step`` over ``train.batches(batch_graphs, shuffle, seed, epoch)`` (a full permutation keyed on
+        ``[seed, epoch]``; batches collated on the device one ahead of the step).  The trainer is built once per ``fit`` from
+        ``self.loss.s``, ``self.optimizer['learning_rate']`` and ``self.metrics`` and closed at the end; the step's weight
+        column is the records' ``w``, times the membership of ``self.loss.label_idx`` where that is set (as ``evaluate``).
+        ``loss`` is the mean of the step losses (summed on the device in float64, read once per epoch), as keras reports it;
+        the training metrics are those of the epoch's LAST step (the reference's overwrite semantics,
+        ``Trainer.metric_results``).  ``val_*`` come from ``self.evaluate(validation_data.eval_batches(...))``: metrics
+        accumulated over the whole set, and ``val_loss`` the L2 loss whatever ``loss_balance`` is.  ``lr`` is the rate the
+        epoch ran with (callbacks change it afterwards).  Noise and dropout draws are keyed on the optimiser step, which
+        checkpoints carry, so a resumed run continues the sequence."""
+        from .dataset import ShiftDataset
+        from .losses import NameLoss
+        from .train import Trainer
+        if not isinstance(train, ShiftDataset) or not (validation_data is None or isinstance(validation_data, ShiftDataset)):
+            raise TypeError("fit: train and validation_data are dataset.ShiftDataset objects (ShiftDataset.from_records)")
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            raise RuntimeError("fit is single process; in a torch.distributed world larger than 1 drive Trainer.step yourself")
+        if len(train) == 0:
+            raise ValueError("fit: the training set holds no record")
+        epochs, batch_graphs, initial_epoch = int(epochs), int(batch_graphs), int(initial_epoch)
+        self.build(train.C)
+        eng = self.engine
+        if train.device != eng.device:
+            raise ValueError(f"fit: the data lives on {train.device}, the model on {eng.device}")
+        loss_fn = getattr(self, 'loss', None)
+        label_idx = loss_fn.label_idx if isinstance(loss_fn, NameLoss) else None
+        ln = None if label_idx is None else torch.as_tensor(np.atleast_1d(np.asarray(label_idx, np.int32)), device=eng.device)
+        opt = getattr(self, 'optimizer', None) or {}
+        metrics = getattr(self, 'metrics', None) or None
+        trainer = Trainer(eng, lr=float(opt.get('learning_rate', self.hypers.get('learning_rate'))),
+                          loss_balance=float(getattr(loss_fn, 's', 1.0)), metrics=metrics)
+        history = History()
+        self.stop_training = False
+        try:
+            for cb in callbacks:
+                if hasattr(cb, 'on_train_begin'):
+                    cb.on_train_begin(self, trainer)
+            for epoch in range(initial_epoch, initial_epoch + epochs):
+                total = torch.zeros((), dtype=torch.float64, device=eng.device)
+                steps = 0
+                for batch, y, w, names in train.batches(batch_graphs, shuffle=shuffle, seed=seed, epoch=epoch):
+                    lw = w if ln is None else w * torch.isin(names, ln).to(torch.float32)
+                    loss = trainer.step(batch, y, lw, names=names if metrics else None)
+                    total += loss.reshape(()).to(torch.float64)
+                    steps += 1
+                logs = {'loss': float(total.item()) / steps}
+                if metrics:
+                    logs.update(trainer.metric_results())
+                if validation_data is not None and len(validation_data):
+                    val = self.evaluate(validation_data.eval_batches(batch_graphs))
+                    logs.update({f'val_{k}': v for k, v in val.items()})
+                logs['lr'] = float(trainer.lr)
+                for k, v in logs.items():
+                    history.history.setdefault(k, []).append(float(v))
+                history.epoch.append(epoch)
+                if verbose:
+                    print(f"Epoch {epoch + 1}: " + " - ".join(f"{k}: {v:.6g}" for k, v in logs.items()))
+                for cb in callbacks:
+                    cb.on_epoch_end(epoch, logs, self, trainer)
+                if self.stop_training:
+                    break
+        finally:
+            trainer.close()
+        return history
 
     # -- torch.autograd surface (SURVEY 8b: the outer autograd shell)
     def parameters(self):
