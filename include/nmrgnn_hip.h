@@ -771,6 +771,41 @@ int ng_collate_batch(ng_ctx*, void* stream, int64_t R, int64_t Ntot, const float
                      float* atoms, int32_t* nlist, float* edges, float* inv_degree, float* y0, float* w, int32_t* names,
                      float* y_true);
 
+/* A ragged kNN batch written into a record store: the inverse of ng_collate_batch (nmrgnn_amd/dataset.py:
+ * ShiftDataset.from_structures; csrc/records.hip).  The batch is what structures_to_batch builds: G structures back to back,
+ * graph_ptr [G+1] int32 on the device (graph_ptr[0] = 0, graph_ptr[G] = N), b_atoms [N,C] f32, b_nlist [N,K] i32 with
+ * BATCH-GLOBAL indices, b_edges [N,K] f32; per atom a label shift [N] f32 (a non-finite value: no label) and name_id [N] i32.
+ * Batch row i of structure g (n_g atoms) becomes row s = row0 + i of the six store arrays (layout as ng_collate_batch, Ncap rows):
+ *   slot k is live iff b_edges[i,k] > 0 (false for -0.0 and NaN): s_nlist[s,k] = b_nlist[i,k] - graph_ptr[g],
+ *   s_edges[s,k] = b_edges[i,k]; every other slot holds (0, +0.0f).  A live slot whose local index lies outside [0, n_g) is
+ *   written as (0, +0.0f) and counters[0] is incremented; no neighbour row is ever read.
+ *   s_inv_degree[s] = 1.0f / (float)#(s_nlist[s,:] > 0), 0 when that count is 0: from the local list just written, so local
+ *   index 0 never counts (nmrgnn/library.py:115-116).
+ *   s_atoms[s,:] = b_atoms[i,:];  s_y[s,:] = (finite(shift[i]) ? shift[i] : 0, (float)name_id[i], mask), s_w[s] = mask,
+ *   mask = finite(shift[i]) ? 1 : 0;  counters[1] gains the number of rows with mask 1.
+ * counters [2] int32 on the device are added to and never reset by the call (integer adds: the totals do not depend on the
+ * order).  One launch on `stream`, asynchronous, no allocation, no scratch; everything but the counters is a function of the
+ * inputs alone, so a second call writes the same bits.  graph_ptr is not read by the host: whatever it holds, nothing is read or
+ * written outside the N batch rows and the N store rows.
+ * Refused (NG_ERR_INVALID, before any launch): NULL context; K or C outside [1, 4096]; N < 0 or N >= 2^31 - 256; G < 1 with
+ * N > 0, or G > N; row0 < 0 or row0 + N > Ncap; with N > 0 any NULL pointer.  N == 0 returns NG_OK and launches nothing. */
+int ng_store_from_batch(ng_ctx*, void* stream, int64_t N, int K, int C, int G, const int32_t* graph_ptr, const float* b_atoms,
+                        const int32_t* b_nlist, const float* b_edges, const float* shift, const int32_t* name_id, int64_t row0,
+                        int64_t Ncap, float* s_atoms, int32_t* s_nlist, float* s_edges, float* s_inv_degree, float* s_y,
+                        float* s_w, int32_t* counters);
+
+/* Per-element label statistics of a record store, or of a view of it (ShiftDataset.standards; csrc/records.hip).  Over the
+ * rows of the records ids[0..Rv) (int32 on the device; an id outside [0, R) and a record whose rows do not lie in [0, Ntot]
+ * are skipped) with y[row,2] > 0, the element of a row being the index of its first non-zero column of atoms [Ntot,C] (a row
+ * without one is skipped):
+ *   out[c][3] = (count, sum y0, sum y0^2) in float64, y0 = (double) y[row,0] converted BEFORE it is squared.
+ * Two launches as ng_name_metrics (per-workgroup partials in the context's scratch, then a fixed-order sum): asynchronous,
+ * no atomics, bitwise deterministic.  rec_ptr [R+1] int64 on the device.  Rv == 0 writes zeros.
+ * Refused (NG_ERR_INVALID, before any launch): NULL context; C outside [1, 4096]; R < 0, Ntot < R; Rv < 0 or Rv >= 2^31; out
+ * NULL; with Rv > 0 a NULL atoms, y, rec_ptr or ids. */
+int ng_label_moments(ng_ctx*, void* stream, int64_t R, int64_t Ntot, int C, const float* atoms, const float* y,
+                     const int64_t* rec_ptr, const int32_t* ids, int64_t Rv, double* out);
+
 /* Keras Adam (nmrgnn/model.py:44-45): one fused pass over the flat parameter buffer.
  *   g is first multiplied by grad_scale (1/world_size after a summing all-reduce). */
 int ng_adam_step(ng_ctx*, void* stream, int64_t n, float* p, const float* g, float* m, float* v,

@@ -14,7 +14,11 @@ sends it with the record ids in ONE small copy, and one launch writes the batch 
 over the same records in the same order, bit for bit.  Everything is validated once, when the store is built; a batch
 checks nothing and never reads the device.
 
-On a CPU device ``batch`` does the same with torch indexing (host tests, shard bookkeeping)."""
+On a CPU device ``batch`` does the same with torch indexing (host tests, shard bookkeeping).
+
+``from_structures`` fills a store from structures and shift tables, the lists built on the GPU and written into the store by
+``ng_store_from_batch`` (csrc/records.hip); ``standards()`` gives the per-element label statistics of a view
+(``ng_label_moments``) for ``build_GNNModel(peak_standards=)``."""
 from __future__ import annotations
 
 import numpy as np
@@ -26,6 +30,7 @@ FORMAT_VERSION = 1
 _ARRAYS = ("atoms", "nlist", "edges", "inv_degree", "y", "w")
 _DTYPES = {"atoms": np.float32, "nlist": np.int32, "edges": np.float32, "inv_degree": np.float32, "y": np.float32,
            "w": np.float32}
+_TORCH_DTYPES = {k: (torch.int32 if v is np.int32 else torch.float32) for k, v in _DTYPES.items()}
 _MAX_BATCH_ATOMS = 2 ** 31 - 256          # ng_collate_batch's limit on N
 
 
@@ -62,6 +67,22 @@ def _check_record(r, rec, C, K):
         raise ValueError(f"record {r}: edges must be finite and >= 0")
     return (atoms.astype(np.float32), nl.astype(np.int32), edges, inv.astype(np.float32), y.astype(np.float32),
             w.astype(np.float32))
+
+
+def label_moments_host(atoms, y):
+    """float64 [C, 3]: (count, sum y0, sum y0^2) per element over the rows with ``y[:, 2] > 0``; the element of a row is its
+    first non-zero atom column, a row without one is skipped (what ``ng_label_moments`` sums on the device)"""
+    atoms, y = np.asarray(atoms), np.asarray(y)
+    C = atoms.shape[1]
+    nz = atoms != 0
+    use = (y[:, 2] > 0) & nz.any(axis=1)
+    el = np.argmax(nz, axis=1)[use]
+    y0 = y[use, 0].astype(np.float64)
+    out = np.zeros((C, 3), np.float64)
+    out[:, 0] = np.bincount(el, minlength=C)
+    out[:, 1] = np.bincount(el, weights=y0, minlength=C)
+    out[:, 2] = np.bincount(el, weights=y0 * y0, minlength=C)
+    return out
 
 
 class _StorePrefetcher(BatchPrefetcher):
@@ -102,6 +123,9 @@ class ShiftDataset:
     """A record store, or a view of one by a list of record ids (``split``); see the module docstring.  ``len()`` is the
     number of records of the view, and every record id a method takes counts within the view."""
 
+    name_table = None      # {'RES-NAME': id} of a store built by from_structures
+    join_report = None     # its label-join counts (structure.JOIN_COUNTS, 'rows', 'labelled', 'structures')
+
     def __init__(self, arrays, rec_ptr, file_ptr, device=None, _ids=None, _parent=None):
         if _parent is not None:                       # a view: shares every array
             self.__dict__.update(_parent.__dict__)
@@ -113,10 +137,15 @@ class ShiftDataset:
         self.R = len(self.rec_ptr_host) - 1
         self.Ntot = int(self.rec_ptr_host[-1])
         for k in _ARRAYS:
-            a = np.ascontiguousarray(arrays[k], dtype=_DTYPES[k])
+            a = arrays[k]
+            if isinstance(a, torch.Tensor):           # built on the device (from_structures): taken as it is
+                if a.device != self.device or a.dtype != _TORCH_DTYPES[k] or not a.is_contiguous():
+                    raise ValueError(f"{k}: a contiguous {_TORCH_DTYPES[k]} tensor on {self.device} expected")
+            else:
+                a = np.ascontiguousarray(a, dtype=_DTYPES[k])
             if a.shape[0] != self.Ntot:
                 raise ValueError(f"{k} has {a.shape[0]} rows, rec_ptr ends at {self.Ntot}")
-            setattr(self, k, torch.from_numpy(a).to(self.device))
+            setattr(self, k, a if isinstance(a, torch.Tensor) else torch.from_numpy(a).to(self.device))
         self.C, self.K = int(self.atoms.shape[1]), int(self.nlist.shape[1])
         self.rec_ptr = torch.from_numpy(self.rec_ptr_host).to(self.device)
         self._sizes = np.diff(self.rec_ptr_host)
@@ -139,6 +168,163 @@ class ShiftDataset:
         arrays = {k: np.concatenate([p[i] for p in parts]) for i, k in enumerate(_ARRAYS)}
         rec_ptr = np.concatenate([[0], np.cumsum([p[0].shape[0] for p in parts])])
         return cls(arrays, rec_ptr, [0, len(parts)], device=device)
+
+    @classmethod
+    def from_structures(cls, structures, shifts, neighbor_number=16, frames='first', names=None, boxes=False, strict=True,
+                        chunk_atoms=1 << 20, device=None):
+        """The store of structures with assigned shifts: one record per structure (``frames='first'``) or
+        per frame of it (``frames='all'``, every frame with the structure's labels), kNN lists of ``neighbor_number``
+        neighbours, one source (``file_ptr = [0, R]``).
+
+        ``structures``: ``structure.Structure`` objects or PDB paths.  ``shifts``: per structure a table (the dict of
+        ``structure.read_shift_table``), a path to one, or ``None`` (no labels).  Labels are joined on the host by ``(resid,
+        atom name)`` (``structure.join_shifts``): with ``strict`` a table row that matches no atom, two atoms, another
+        residue name or an atom already labelled raises ``ValueError`` naming the structure and the row; otherwise such rows
+        are dropped and counted in ``join_report`` on the returned store.  ``names``: a ``{'RES-NAME': id}`` table (default
+        ``structure.name_table(structures)``; kept as ``name_table``); an atom whose key it lacks gets id 0.  A labelled atom
+        has ``y = (shift, id, 1)`` and ``w = 1``, every other ``y = (0, id, 0)`` and ``w = 0``.
+
+        On the GPU the structures go through ``graph.structures_to_batch`` in chunks of at most ``chunk_atoms`` atoms (a
+        larger structure is a chunk of its own), each chunk written by one ``ng_store_from_batch`` launch into store arrays
+        allocated once at their final size; the launch's two counters are read once, at the end.  ``boxes=True``: every
+        frame's ``Structure.dimensions`` goes to ``structures_to_batch(boxes=)``.  On a CPU device the same arrays come
+        from ``structure.knn_graph`` per record and NumPy (host tests; no periodic boxes).  A slot whose distance is not
+        > 0 (padding, coincident atoms) holds ``nlist = 0, edges = 0``; ``inv_degree`` is ``structure.inv_degree_of`` of the
+        stored list."""
+        import os
+        from .structure import (Structure, atoms_onehot, inv_degree_of, join_shifts, knn_graph, name_ids, name_keys,
+                                name_table, read_pdb, read_shift_table)
+        if frames not in ('first', 'all'):
+            raise ValueError(f"from_structures: frames is 'first' or 'all', got {frames!r}")
+        structures = list(structures)
+        shifts = list(shifts) if shifts is not None else [None] * len(structures)
+        if not structures:
+            raise ValueError("from_structures: no structures")
+        if len(shifts) != len(structures):
+            raise ValueError(f"from_structures: {len(structures)} structures but {len(shifts)} shift tables")
+        K, chunk_atoms = int(neighbor_number), int(chunk_atoms)
+        if not 1 <= K <= 64:
+            raise ValueError(f"from_structures: neighbor_number must be in [1, 64], got {neighbor_number}")
+        if chunk_atoms < 1:
+            raise ValueError(f"from_structures: chunk_atoms must be >= 1, got {chunk_atoms}")
+        device = _norm_device(device)
+        labels = [str(s) if isinstance(s, (str, os.PathLike)) else f"structure {k}" for k, s in enumerate(structures)]
+        structs = [read_pdb(s) if isinstance(s, (str, os.PathLike)) else s for s in structures]
+        for k, s in enumerate(structs):
+            if not isinstance(s, Structure) or s.n_atoms == 0 or len(s) == 0:
+                raise ValueError(f"from_structures: {labels[k]}: a Structure with atoms and at least one frame expected")
+        keys = [name_keys(s) for s in structs]
+        table = dict(names) if names is not None else name_table(structs, keys)
+        report = {"structures": len(structs), "rows": 0}
+        per = []                                      # per structure: (atoms one-hot, shift or NaN, name id)
+        for k, (s, t) in enumerate(zip(structs, shifts)):
+            if isinstance(t, (str, os.PathLike)):
+                t = read_shift_table(t)
+            sh, rep = join_shifts(s, t, strict=strict, label=labels[k])
+            report["rows"] += 0 if t is None else len(t["shift"])
+            for key, v in rep.items():
+                report[key] = report.get(key, 0) + v
+            per.append((atoms_onehot(s.elements), sh, name_ids(s, table, keys[k])))
+        items = [(k, fr) for k, s in enumerate(structs) for fr in (range(len(s)) if frames == 'all' else (0,))]
+        sizes = np.asarray([structs[k].n_atoms for k, _ in items], np.int64)
+        rec_ptr = np.zeros(len(items) + 1, np.int64)
+        np.cumsum(sizes, out=rec_ptr[1:])
+        Ntot, C = int(rec_ptr[-1]), per[0][0].shape[1]
+        if device.type != "cuda":
+            if boxes:
+                raise ValueError("from_structures: periodic boxes need the GPU list builder")
+            parts = {k: [] for k in _ARRAYS}
+            for k, fr in items:
+                atoms, sh, ids = per[k]
+                nlist, edges = knn_graph(structs[k].frames[fr], K)
+                live = edges > 0
+                nlist, edges = np.where(live, nlist, 0).astype(np.int32), np.where(live, edges, 0).astype(np.float32)
+                has = np.isfinite(sh)
+                mask = has.astype(np.float32)
+                parts["atoms"].append(atoms)
+                parts["nlist"].append(nlist)
+                parts["edges"].append(edges)
+                parts["inv_degree"].append(inv_degree_of(nlist))
+                parts["y"].append(np.stack([np.where(has, sh, 0).astype(np.float32), ids.astype(np.float32), mask], axis=1))
+                parts["w"].append(mask)
+            ds = cls({k: np.concatenate(v) for k, v in parts.items()}, rec_ptr, [0, len(items)], device=device)
+            report["labelled"] = int(ds.w.sum().item())
+        else:
+            import ctypes as C_
+            from . import _lib
+            from ._lib import ptr
+            from .graph import structures_to_batch
+            ctx = _lib.get_context(device.index)
+            shape = {"atoms": (Ntot, C), "nlist": (Ntot, K), "edges": (Ntot, K), "inv_degree": (Ntot,), "y": (Ntot, 3),
+                     "w": (Ntot,)}
+            arrays = {k: torch.empty(shape[k], dtype=_TORCH_DTYPES[k], device=device) for k in _ARRAYS}
+            counters = torch.zeros(2, dtype=torch.int32, device=device)
+            a = 0
+            while a < len(items):                     # items [a, b): as many as fit chunk_atoms, at least one
+                b, n = a + 1, int(sizes[a])
+                while b < len(items) and n + int(sizes[b]) <= chunk_atoms:
+                    n += int(sizes[b])
+                    b += 1
+                if n >= _MAX_BATCH_ATOMS:
+                    raise ValueError(f"from_structures: {n} atoms in one chunk")
+                chunk = items[a:b]
+                gb = structures_to_batch([per[k][0] for k, _ in chunk], [structs[k].frames[fr] for k, fr in chunk], K,
+                                         device=device,
+                                         boxes=[structs[k].dimensions[fr] for k, fr in chunk] if boxes else None)
+                # labels and name ids of the chunk in ONE copy: the shifts' bits ride as int32
+                meta = torch.from_numpy(np.concatenate([np.concatenate([per[k][1] for k, _ in chunk]).view(np.int32),
+                                                        np.concatenate([per[k][2] for k, _ in chunk])])).to(device)
+                with torch.cuda.device(device):
+                    st = C_.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+                    ctx.check(ctx.lib.ng_store_from_batch(
+                        ctx.handle, st, n, K, C, len(chunk), ptr(gb.graph_ptr), ptr(gb.atoms), ptr(gb.nlist), ptr(gb.edges),
+                        ptr(meta[:n]), ptr(meta[n:]), int(rec_ptr[a]), Ntot, ptr(arrays["atoms"]), ptr(arrays["nlist"]),
+                        ptr(arrays["edges"]), ptr(arrays["inv_degree"]), ptr(arrays["y"]), ptr(arrays["w"]), ptr(counters)),
+                        "ng_store_from_batch")
+                a = b
+            bad, labelled = (int(v) for v in counters.cpu())      # the one read of the device
+            if bad:
+                raise ValueError(f"from_structures: {bad} neighbour-list slot(s) point outside their structure")
+            ds = cls(arrays, rec_ptr, [0, len(items)], device=device)
+            report["labelled"] = labelled
+        ds.name_table = table
+        ds.join_report = report
+        return ds
+
+    def standards(self):
+        """``{element index: (symbol, avg, std)}`` of this view's labelled rows, in the shape of
+        ``standards.load_standards()``: take it from the TRAIN view and hand it to ``build_GNNModel(peak_standards=)``.  The
+        element of a row is its first non-zero atom column; a row counts when ``y[:, 2] > 0``.  ``avg = sum(y) / n``, ``std =
+        sqrt(max(sum(y^2) / n - avg^2, 0))`` in float64: the POPULATION form (this package's convention; nmrdata's is not
+        pinned).  An element with fewer than 2 labels gets ``(symbol, 0.0, 0.0)``.  ``ng_label_moments`` on the GPU (one
+        read of 3 C doubles), NumPy on a CPU device."""
+        from .standards import ELEMENTS
+        ids = self.record_ids
+        if self.device.type == "cuda":
+            import ctypes as C_
+            from . import _lib
+            from ._lib import ptr
+            ctx = _lib.get_context(self.device.index)
+            ids_dev = torch.from_numpy(ids.astype(np.int32)).to(self.device)
+            out = torch.empty(self.C, 3, dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                st = C_.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+                ctx.check(ctx.lib.ng_label_moments(ctx.handle, st, self.R, self.Ntot, self.C, ptr(self.atoms), ptr(self.y),
+                                                   ptr(self.rec_ptr), ptr(ids_dev), len(ids), ptr(out)), "ng_label_moments")
+            mom = out.cpu().numpy()
+        else:
+            arrays, _ = self._host_arrays()
+            mom = label_moments_host(arrays["atoms"], arrays["y"])
+        res = {}
+        for c in range(self.C):
+            sym = ELEMENTS[c] if c < len(ELEMENTS) else 'X'
+            n, s1, s2 = (float(v) for v in mom[c])
+            if n < 2:
+                res[c] = (sym, 0.0, 0.0)
+            else:
+                avg = s1 / n
+                res[c] = (sym, avg, float(np.sqrt(max(s2 / n - avg * avg, 0.0))))
+        return res
 
     def _host_arrays(self):
         """(arrays, rec_ptr) of this view's records in view order, on the host"""

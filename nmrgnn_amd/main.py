@@ -8,7 +8,8 @@ are built on the GPU (ng_knn_graph); the reference evaluates frame by frame with
 
 ``train RECORDS... NAME [EPOCHS]`` is the reference's training command on ``dataset.ShiftDataset`` files (``.npz``, written by
 ``ShiftDataset.save``; the package reads no TFRecords): ``GNNModel.fit`` with the reference's callbacks, the model saved to
-NAME and the history pickled beside it.  Out of scope: ``--tensorboard``, ``hyper`` (the hyper-parameter search) and
+NAME and the history pickled beside it.  ``make-records OUT.npz --pair STRUCT SHIFTS ...`` writes such a file from structures
+and CSV tables of assigned shifts (``ShiftDataset.from_structures``).  Out of scope: ``--tensorboard``, ``hyper`` (the hyper-parameter search) and
 ``eval-tfrecords`` (its table needs nmrdata's residue-name list, which the package does not ship)."""
 from __future__ import annotations
 
@@ -333,22 +334,27 @@ def _load_embeddings(path):
 
 
 def train_model(records, name, epochs=3, checkpoint_path='/tmp/checkpoint', embeddings=None, validation=0.1, load=False,
-                loss_balance=1.0, batch_graphs=1, seed=0, device=None, echo=print):
+                loss_balance=1.0, batch_graphs=1, seed=0, device=None, echo=print, standards='default'):
     """The reference's ``train`` (nmrgnn/main.py:36-90) on ``ShiftDataset`` files: build the model, optionally load the
     checkpoint, fit with ReduceLROnPlateau(val_loss, 0.99, patience 4, min_lr 1e-4) and a checkpoint every epoch, save the
-    model to ``name`` and pickle the history to the first free ``name-history-<i>.pb``.  Returns ``(model, history)``."""
+    model to ``name`` and pickle the history to the first free ``name-history-<i>.pb``.  Returns ``(model, history)``.
+    ``standards``: ``'default'`` (the bundled ``standards.load_standards()``) or ``'data'`` (``standards()`` of the train
+    view: the per-element mean and spread of the labels the model is trained on)."""
     import pickle
     from .callbacks import ModelCheckpoint, ReduceLROnPlateau, history_path
     from .dataset import ShiftDataset
     from .model import build_GNNModel
     if len(records) == 0:
         raise ValueError('Must give input record files')
+    if standards not in ('default', 'data'):
+        raise ValueError(f"standards is 'default' or 'data', got {standards!r}")
     emb = _load_embeddings(embeddings) if embeddings is not None else None
-    model = build_GNNModel(loss_balance=loss_balance, device=device, embeddings=emb)
-    if load:
-        model.load_weights(checkpoint_path)
     data = ShiftDataset.load(list(records), device=device)
     train_data, validation_data = data.split(validation)
+    model = build_GNNModel(loss_balance=loss_balance, device=device, embeddings=emb,
+                           peak_standards=train_data.standards() if standards == 'data' else None)
+    if load:
+        model.load_weights(checkpoint_path)
     callbacks = []
     if len(validation_data):              # the plateau rule watches val_loss
         callbacks.append(ReduceLROnPlateau(monitor='val_loss', factor=0.99, patience=4, min_lr=1e-4, verbose=1))
@@ -378,12 +384,74 @@ def train_model(records, name, epochs=3, checkpoint_path='/tmp/checkpoint', embe
 @click.option('--batch-graphs', default=1, help='Records per optimiser step (1: the reference; more changes the optimisation)')
 @click.option('--seed', default=0, help='Seed of the per-epoch shuffle')
 @click.option('--device', default=None, help='Device, e.g. cuda:0')
-def train(records, name, epochs, checkpoint_path, embeddings, validation, load, loss_balance, batch_graphs, seed, device):
+@click.option('--standards', default='default', type=click.Choice(['default', 'data']),
+              help='Peak standards of the model: the bundled ones, or the per-element mean and spread of the training labels')
+def train(records, name, epochs, checkpoint_path, embeddings, validation, load, loss_balance, batch_graphs, seed, device,
+          standards):
     '''Train the model on ShiftDataset record files (.npz)'''
     if len(records) == 0:
         raise click.UsageError('Must give input record files')
     train_model(records, name, epochs, checkpoint_path=checkpoint_path, embeddings=embeddings, validation=validation,
-                load=load, loss_balance=loss_balance, batch_graphs=batch_graphs, seed=seed, device=device, echo=click.echo)
+                load=load, loss_balance=loss_balance, batch_graphs=batch_graphs, seed=seed, device=device, echo=click.echo,
+                standards=standards)
+
+
+def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None, embeddings_out=None, pbc=False,
+                 keep_going=False, device=None, echo=print):
+    """``make-records``: structures with assigned shifts -> one ``ShiftDataset`` file.  ``pairs``: ``(structure file, shift
+    table CSV)`` per structure.  ``embeddings``: take the name ids from this file's ``'name'`` table (keys it lacks get id 0);
+    otherwise the table is ``structure.name_table`` of the structures, and ``embeddings_out`` writes it as the JSON
+    ``{'atom': ..., 'name': ...}`` that ``train --embeddings`` reads.  ``pbc``: minimum-image lists in every frame's CRYST1
+    box.  ``keep_going``: drop and count shift-table rows that do not join instead of stopping.  Returns the store."""
+    import json
+    from .dataset import ShiftDataset
+    from .standards import load_embeddings
+    if len(pairs) == 0:
+        raise ValueError('Must give at least one --pair STRUCT SHIFTS')
+    if embeddings is not None and embeddings_out is not None:
+        raise ValueError('--embeddings and --embeddings-out cannot be combined')
+    names = _load_embeddings(embeddings)['name'] if embeddings is not None else None
+    ds = ShiftDataset.from_structures([p[0] for p in pairs], [p[1] for p in pairs], neighbor_number=neighbor_number,
+                                      frames=frames, names=names, boxes=pbc, strict=not keep_going, device=device)
+    ds.save(out)
+    rep = ds.join_report
+    echo(f"{ds.R} records, {ds.Ntot} atoms, {rep['labelled']} labelled rows from {rep['rows']} table rows of "
+         f"{rep['structures']} structures written to {out}")
+    dropped = {k: v for k, v in rep.items() if k not in ('rows', 'labelled', 'structures') and v}
+    if dropped:
+        echo('table rows dropped: ' + ', '.join(f'{k}: {v}' for k, v in dropped.items()))
+    if embeddings_out is not None:
+        with open(embeddings_out, 'w') as f:
+            json.dump({'atom': load_embeddings()['atom'], 'name': ds.name_table}, f, indent=1)
+        echo(f'Embeddings written to {embeddings_out}')
+    return ds
+
+
+@main.command(name='make-records')
+@click.argument('out', type=click.Path())
+@click.option('--pair', 'pairs', nargs=2, multiple=True, type=click.Path(exists=True), metavar='STRUCT SHIFTS',
+              help='A structure file (PDB) and the CSV of its assigned shifts (resid,name,shift[,resname]); repeat per structure')
+@click.option('--frames', default='first', type=click.Choice(['first', 'all']),
+              help='One record per structure, or one per frame (MODEL) with the same labels')
+@click.option('--neighbor-number', default=16, help='The model specific size of neighbor lists')
+@click.option('--embeddings', default=None, type=click.Path(exists=True),
+              help='JSON or pickle file with an embeddings dict: name ids come from its name table')
+@click.option('--embeddings-out', default=None, type=click.Path(),
+              help='Write the name table built from the structures as a JSON embeddings file for train --embeddings')
+@click.option('--pbc', is_flag=True, help='Minimum-image neighbour lists in each frame\'s periodic box (CRYST1)')
+@click.option('--keep-going', is_flag=True, help='Drop and count shift-table rows that match no atom instead of stopping')
+@click.option('--device', default=None, help='Device, e.g. cuda:0')
+def make_records_cmd(out, pairs, frames, neighbor_number, embeddings, embeddings_out, pbc, keep_going, device):
+    '''Build a ShiftDataset record file (.npz) from structures and shift tables'''
+    if len(pairs) == 0:
+        raise click.UsageError('Must give at least one --pair STRUCT SHIFTS')
+    if embeddings is not None and embeddings_out is not None:
+        raise click.UsageError('--embeddings and --embeddings-out cannot be combined')
+    try:
+        make_records(out, pairs, frames=frames, neighbor_number=neighbor_number, embeddings=embeddings,
+                     embeddings_out=embeddings_out, pbc=pbc, keep_going=keep_going, device=device, echo=click.echo)
+    except ValueError as e:
+        raise click.ClickException(str(e))
 
 
 if __name__ == '__main__':

@@ -432,19 +432,21 @@ class GNNModel:
         self._restore_adam()
 
 
-def build_GNNModel(hp=None, metrics=True, loss_balance=1.0, device=None, embeddings=None):
+def build_GNNModel(hp=None, metrics=True, loss_balance=1.0, device=None, embeddings=None, peak_standards=None):
     """nmrgnn/model.py:12-105.  Declares the hyper-parameter space on ``hp`` (same names/defaults),
     loads the peak standards and returns a GNNModel with ``optimizer`` / ``loss`` attributes set
     (Adam at hp['learning_rate'], NameLoss(s=loss_balance)).
     ``metrics=True`` with an ``embeddings`` dict that has ``'name'`` (nmrdata.load_embeddings(), not shipped here: the
     package has no residue-name table) sets ``model.metrics`` to the reference's 15 metrics (model.py:56-103,
     ``metrics.reference_metrics``; ``ValueError`` when a regular expression matches no name); otherwise
-    ``model.metrics = []``.  ``Trainer(..., metrics=model.metrics)`` and ``model.evaluate`` report them."""
+    ``model.metrics = []``.  ``Trainer(..., metrics=model.metrics)`` and ``model.evaluate`` report them.
+    ``peak_standards``: ``{element index: (symbol, avg, std)}`` of the training data (``ShiftDataset.standards()`` of the
+    train view) in place of the bundled ``standards.load_standards()``; ``save`` / ``load_model`` carry them."""
     from .losses import NameLoss
     from .metrics import reference_metrics
     hp = HyperParameters() if hp is None else hp
     declare_gnn_space(hp)
-    model = GNNModel(hp, load_standards(), device=device)
+    model = GNNModel(hp, load_standards() if peak_standards is None else peak_standards, device=device)
     model.metrics = reference_metrics(embeddings) if (metrics and embeddings is not None and 'name' in embeddings) else []
     model.loss = NameLoss(label_idx=None, s=loss_balance)
     model.optimizer = {"name": "Adam", "learning_rate": hp.get('learning_rate'),

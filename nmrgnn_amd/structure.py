@@ -143,6 +143,118 @@ def atoms_onehot(elements):
     return out
 
 
+MAX_NAME_IDS = 2 ** 24          # a name id travels as a float32 in y[:, 1]: every integer below 2^24 is exact
+
+
+def name_keys(structure):
+    """'RES-NAME' per atom: the key shape the reference's class masks split on '-' (nmrgnn/main.py:124-135)"""
+    res, names = np.asarray(structure.resnames).astype(str).tolist(), np.asarray(structure.names).astype(str).tolist()
+    return [f"{r.strip()}-{n.strip()}" for r, n in zip(res, names)]
+
+
+def name_table(structures, keys_of=None):
+    """{'RES-NAME': id} over the atoms of ``structures``: id 0 is the key 'X' (what an atom gets whose key a given table
+    lacks), the other keys count from 1 in sorted order.  ``ValueError`` for more than 2^24 ids.  ``keys_of``: the
+    structures' ``name_keys``, where the caller holds them already."""
+    keys = set()
+    for k in (keys_of if keys_of is not None else map(name_keys, structures)):
+        keys.update(k)
+    keys.discard('X')
+    if len(keys) + 1 > MAX_NAME_IDS:
+        raise ValueError(f"name_table: {len(keys) + 1} name ids, but an id must stay below 2^24 to travel as a float32")
+    table = {'X': 0}
+    for i, k in enumerate(sorted(keys)):
+        table[k] = i + 1
+    return table
+
+
+def name_ids(structure, table, keys=None):
+    """int32 [n]: the id of every atom's key in ``table``, 0 ('X') where the table lacks it (``keys``: the structure's
+    ``name_keys``, where the caller holds them already)"""
+    ids = np.array([table.get(k, 0) for k in (name_keys(structure) if keys is None else keys)], np.int64)
+    if len(ids) and (ids.min() < 0 or ids.max() >= MAX_NAME_IDS):
+        raise ValueError("name ids must lie in [0, 2^24)")
+    return ids.astype(np.int32)
+
+
+def read_shift_table(path):
+    """A CSV of assigned shifts with a header row: the columns ``resid``, ``name``, ``shift`` and optionally ``resname``
+    (any order, other columns ignored).  Returns ``{'resid': int64 [m], 'name': str [m], 'shift': float32 [m], 'resname':
+    str [m] or None}``; a blank or non-numeric ``shift`` gives NaN: a row without a label."""
+    import csv
+    opener = gzip.open if str(path).endswith(".gz") else open
+    with opener(path, "rt", newline="") as f:
+        rd = csv.reader(f)
+        try:
+            header = [h.strip().lower() for h in next(rd)]
+        except StopIteration:
+            raise ValueError(f"{path}: empty shift table") from None
+        missing = [c for c in ("resid", "name", "shift") if c not in header]
+        if missing:
+            raise ValueError(f"{path}: the header lacks the column(s) {', '.join(missing)} (got {', '.join(header)})")
+        col = {c: header.index(c) for c in ("resid", "name", "shift", "resname") if c in header}
+        resid, name, shift, resname = [], [], [], []
+        for ln, row in enumerate(rd, start=2):
+            if not row or all(not c.strip() for c in row):
+                continue
+            if len(row) <= max(col.values()):
+                raise ValueError(f"{path}: line {ln} has {len(row)} fields, the header {len(header)}")
+            try:
+                resid.append(int(row[col["resid"]]))
+            except ValueError:
+                raise ValueError(f"{path}: line {ln}: resid {row[col['resid']]!r} is no integer") from None
+            name.append(row[col["name"]].strip())
+            try:
+                v = float(row[col["shift"]])
+            except ValueError:
+                v = float("nan")
+            shift.append(v if np.isfinite(v) else float("nan"))
+            if "resname" in col:
+                resname.append(row[col["resname"]].strip())
+    return {"resid": np.asarray(resid, np.int64), "name": np.asarray(name, dtype=str).reshape(-1),
+            "shift": np.asarray(shift, np.float32), "resname": np.asarray(resname, dtype=str).reshape(-1) if "resname" in col else None}
+
+
+JOIN_COUNTS = ("unmatched", "ambiguous", "duplicate", "resname_mismatch")
+
+
+def join_shifts(structure, table, strict=True, label="structure"):
+    """``(shift float32 [n], report)``: the table's shifts laid on the structure's atoms by ``(resid, atom name)``, NaN where an
+    atom has no label.  A table row that matches no atom, that matches two atoms, whose ``resname`` differs from its atom's,
+    or whose atom an earlier row has labelled already: ``ValueError`` naming ``label`` and the row with ``strict``; otherwise
+    the row is dropped and counted in ``report`` (keys JOIN_COUNTS)."""
+    n = structure.n_atoms
+    out = np.full(n, np.nan, np.float32)
+    report = {k: 0 for k in JOIN_COUNTS}
+    if table is None:
+        return out, report
+    where = {}
+    atom_names = [a.strip() for a in np.asarray(structure.names).astype(str).tolist()]
+    for i, key in enumerate(zip(np.asarray(structure.resids).astype(np.int64).tolist(), atom_names)):
+        where.setdefault(key, []).append(i)
+    taken = np.zeros(n, bool)
+    resname = table.get("resname")
+    for j, (rid, nm, sh) in enumerate(zip(table["resid"], table["name"], table["shift"])):
+        row = f"row {j} (resid {int(rid)}, name {nm})"
+        hits = where.get((int(rid), str(nm).strip()), [])
+        if len(hits) == 0:
+            why, msg = "unmatched", "matches no atom"
+        elif len(hits) > 1:
+            why, msg = "ambiguous", f"matches {len(hits)} atoms"
+        elif resname is not None and str(resname[j]).strip() != str(structure.resnames[hits[0]]).strip():
+            why, msg = "resname_mismatch", f"names residue {resname[j]}, the structure has {structure.resnames[hits[0]]}"
+        elif taken[hits[0]]:
+            why, msg = "duplicate", "labels an atom that an earlier row labelled"
+        else:
+            taken[hits[0]] = True
+            out[hits[0]] = sh
+            continue
+        if strict:
+            raise ValueError(f"{label}: shift table {row} {msg}")
+        report[why] += 1
+    return out, report
+
+
 def inv_degree_of(nlist):
     """nmrgnn/library.py:115-116: 1 / #(nlist > 0), 0 when that count is 0 (index 0 never counts)."""
     deg = (np.asarray(nlist) > 0).sum(axis=1).astype(np.float32)
