@@ -121,32 +121,6 @@ void* small_scratch(ng_ctx* ctx) {
   return p;
 }
 
-void* cached_image(ng_ctx* ctx, const void* src, int kind, size_t bytes, bool* valid) {
-  *valid = false;
-  if (!ctx->wcache) return nullptr;
-  // A source inside the context's own scratch is a temporary (a weight matrix repacked for THIS call: the same address
-  // holds another layer's weights on the next call) — never a cache key.  Round-2 advisor finding: with the cache keyed
-  // by such an address a frozen window around a multi-layer backward multiplied with the previous layer's image.
-  auto inside = [&](const void* base, size_t n) {
-    return base && (const char*)src >= (const char*)base && (const char*)src < (const char*)base + n;
-  };
-  if (inside(ctx->ws, ctx->ws_bytes) || inside(ctx->aux, ctx->aux_bytes)) return nullptr;
-  ng_ctx::WImage& w = ctx->wimg[std::make_pair(src, kind)];
-  if (w.bytes < bytes) {
-    DeviceGuard dg(ctx->device);
-    if (w.buf) { (void)hipDeviceSynchronize(); (void)hipFree(w.buf); w.buf = nullptr; w.bytes = 0; }
-    if (hipMalloc(&w.buf, bytes) != hipSuccess) { w.buf = nullptr; return nullptr; }
-    (void)hipMemset(w.buf, 0, bytes);      // (flag words inside an image start out equal to no version)
-    w.bytes = bytes;
-    w.ver = 0;
-    w.has_job = false;                     // a registered job points into the old buffer
-    ctx->wjobs_dirty = true;
-  }
-  *valid = w.ver == ctx->wver;
-  w.ver = ctx->wver;
-  return w.buf;
-}
-
 // ---- deferred second-stage reductions (reduce.cuh) ------------------------------------------------------------------
 constexpr int RB_MAX_JOBS = 24;
 struct ReduceBatch {
@@ -307,27 +281,9 @@ ProfScope::~ProfScope() {
 
 extern "C" int ng_abi_version(void) { return NG_ABI_VERSION; }
 
-extern "C" int ng_weights_frozen(ng_ctx* ctx, int owner) {
-  if (!ctx) return NG_ERR_INVALID;
-  if (owner != 0 && owner != ctx->wowner) {   // another model takes the cache over: nothing in it is its own
-    ctx->wver++;
-    ctx->wowner = owner;
-    for (auto& kv : ctx->wimg) kv.second.has_job = false;     // (its weights may be gone: nothing of it is refreshed)
-    ctx->wjobs_dirty = true;
-  }
-  ctx->wcache = owner != 0;
-  return NG_OK;
-}
-
 extern "C" int ng_ctx_set_graph_span(ng_ctx* ctx, int64_t max_graph_atoms) {
   if (!ctx) return NG_ERR_INVALID;
   ctx->graph_span = max_graph_atoms > 0 ? max_graph_atoms : 0;
-  return NG_OK;
-}
-
-extern "C" int ng_weights_changed(ng_ctx* ctx) {
-  if (!ctx) return NG_ERR_INVALID;
-  ctx->wver++;
   return NG_OK;
 }
 
@@ -410,23 +366,6 @@ extern "C" int ng_replay_stage(ng_ctx* ctx, void* stream, uint64_t seed, float l
   return NG_OK;
 }
 
-extern "C" int ng_replay_token(ng_ctx* ctx, uint64_t* token) {
-  if (!ctx || !token) return NG_ERR_INVALID;
-  *token = ctx->replay_token;
-  return NG_OK;
-}
-
-// host bookkeeping of ONE replayed ng_adam_step: the weights moved, the captured repack launch rebuilt the images of `token`
-extern "C" int ng_replay_commit(ng_ctx* ctx, uint64_t token) {
-  if (!ctx) return NG_ERR_INVALID;
-  ctx->wver++;
-  auto it = ctx->wjobs_private_sel.find(token);
-  if (token != 0 && it != ctx->wjobs_private_sel.end())
-    for (ng_ctx::WImage* w : it->second)
-      if (w->buf && w->has_job) w->ver = ctx->wver;
-  return NG_OK;
-}
-
 extern "C" int ng_reload_env(void) {
   ng::load_switches();
   return NG_OK;
@@ -457,10 +396,7 @@ extern "C" void ng_ctx_destroy(ng_ctx* ctx) {
   if (ctx->ws) (void)hipFree(ctx->ws);
   if (ctx->aux) (void)hipFree(ctx->aux);
   if (ctx->small) (void)hipFree(ctx->small);
-  for (auto& kv : ctx->wimg)
-    if (kv.second.buf) (void)hipFree(kv.second.buf);
-  if (ctx->wjobs_dev) (void)hipFree(ctx->wjobs_dev);
-  for (auto& kv : ctx->wjobs_private) (void)hipFree(kv.second);
+  ng::image_cache_free(ctx);
   for (auto& r : ctx->recs) {
     (void)hipEventDestroy(r.start);
     (void)hipEventDestroy(r.stop);

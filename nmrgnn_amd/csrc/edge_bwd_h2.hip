@@ -442,18 +442,13 @@ int edge_bwd_h2_launch(ng_ctx* ctx, hipStream_t st, int64_t n_edges, int E, cons
   float* blockmax = reinterpret_cast<float*>(wt_img + HX_WT_BYTES + 16);
   // the W^T image: cached while the weights are frozen / refreshed behind Adam, else in the caller's scratch
   int nb_max = 0;
-  bool have_wt = false;
-  char* wimg = (char*)cached_image(ctx, W[1], 13, HX_WT_BYTES + 16, &have_wt);
-  const bool cached_wt = wimg != nullptr;
-  if (!wimg) wimg = wt_img;
+  const ImageSlot s = image_slot(ctx, W[1], IK_EDGE_WT, HX_WT_BYTES + 16, IMG_NONE, wt_img);
+  char* wimg = (char*)s.buf;
   {
     ProfScope ps(ctx, st, "edge_bwd_h2_prep");
-    if (!have_wt) {
-      PackJob j;
-      j.kind = PK_EDGE_WT; j.blocks = 17; j.src[0] = W[1]; j.src[1] = W[2]; j.src[2] = W[3]; j.i0 = E; j.dst[0] = wimg;
-      if (int rc = pack_launch(ctx, st, j)) return rc;
-      if (cached_wt) cache_set_job(ctx, W[1], 13, j);
-    }
+    PackJob j;
+    j.kind = PK_EDGE_WT; j.blocks = 17; j.src[0] = W[1]; j.src[1] = W[2]; j.src[2] = W[3]; j.i0 = E; j.dst[0] = wimg;
+    if (int rc = image_pack(ctx, st, s, j)) return rc;
     if (n_edges * E <= HX_DIRECT_MAX && (reinterpret_cast<uintptr_t>(de) & 15) == 0) {
       // one graph per call: the few workgroups read the 48 KB of de themselves instead of waiting for a launch that does
       nb_max = -(int)(n_edges * E);

@@ -329,16 +329,10 @@ int edge_fused_fwd_f32(ng_ctx* ctx, hipStream_t st, int64_t n_edges, int E, cons
   // scratch: fragment-ordered copy of the three hidden weight matrices
   const size_t pk_floats = (size_t)3 * FH * FH;
   // (frozen weights: the fragment copy is kept like every other packed image — one launch less per call)
-  bool have = false;
-  float* Wpk = (float*)cached_image(ctx, W[0], 11, (pk_floats + FH) * 4, &have);
-  const bool cached = Wpk != nullptr;
-  if (!Wpk) Wpk = (float*)(guard ? aux_workspace(ctx, (pk_floats + FH) * 4) : workspace(ctx, (pk_floats + FH) * 4));
+  const ImageSlot s = image_slot(ctx, W[0], IK_EDGE_F32, (pk_floats + FH) * 4, guard ? IMG_AUX : IMG_WS);
+  float* Wpk = (float*)s.buf;
   if (!Wpk) return NG_ERR_NOMEM;
-  if (!have) {
-    const PackJob j = edge_fused_pack_job(W, Wpk, nullptr);
-    if (int rc = pack_launch(ctx, st, j)) return rc;
-    if (cached) cache_set_job(ctx, W[0], 11, j);
-  }
+  if (int rc = image_pack(ctx, st, s, edge_fused_pack_job(W, Wpk, nullptr))) return rc;
   EdgeFwdArgs a;
   a.tape_blocked = tape_blocked ? 1 : 0;
   a.guard = guard ? *guard : RangeGuard{nullptr, 0};

@@ -416,18 +416,13 @@ int edge_fused_bwd(ng_ctx* ctx, hipStream_t st, int64_t n_edges, int E, const fl
   const int nseg = edge_bwd_h2_segments(n_edges);      // launches of the split-operand kernel (1 below 8.4 M edges)
   // W^T fragments of the f32-input kernel (the strict-fp32 path, or the range fallback of the split-operand kernel): a
   // cached image while the weights are frozen / refreshed behind Adam (pack_bodies.cuh), else packed into the scratch
-  bool haveT = false;
-  float* WpkT = (float*)cached_image(ctx, W[0], 12, pk_floats * 4, &haveT);
-  const bool cachedT = WpkT != nullptr;
+  ImageSlot s = image_slot(ctx, W[0], IK_EDGE_F32_T, pk_floats * 4, IMG_NONE);
   float* ws = (float*)workspace(ctx, (pk_floats + (size_t)nseg * grid * stride) * 4 + edge_bwd_h2_ws_bytes());
   if (!ws) return NG_ERR_NOMEM;
-  if (!cachedT) WpkT = ws;
+  if (!s.cached) s.buf = ws;
+  float* WpkT = (float*)s.buf;
   float* partial = ws + pk_floats;
-  if (!haveT) {
-    const PackJob j = edge_fused_pack_job(W, nullptr, WpkT);
-    if (int rc = pack_launch(ctx, st, j)) return rc;
-    if (cachedT) cache_set_job(ctx, W[0], 12, j);
-  }
+  if (int rc = image_pack(ctx, st, s, edge_fused_pack_job(W, nullptr, WpkT))) return rc;
   EdgeBwdArgs a;
   a.n_edges = n_edges; a.d_src = d_src; a.d_eff = d_eff; a.centers = centers;
   a.neg_inv_gap = (float)(-1.0 / (double)gap);

@@ -444,18 +444,13 @@ int edge_h2_fwd(ng_ctx* ctx, hipStream_t st, int64_t n_edges, int E, const float
                 const float* centers, float gap, const float* const* W, const float* const* b, float* e_out,
                 float* z_save, LiveEdges live) {
   const size_t img_bytes = (size_t)H2_NCHUNK * H2_CHUNK;
-  bool have = false;
-  char* img = (char*)cached_image(ctx, W[0], 6, img_bytes + FH * 4, &have);
-  const bool cached = img != nullptr;
-  if (!img) img = (char*)workspace(ctx, img_bytes + FH * 4);
+  const ImageSlot s = image_slot(ctx, W[0], IK_EDGE_H2, img_bytes + FH * 4, IMG_WS);
+  char* img = (char*)s.buf;
   if (!img) return NG_ERR_NOMEM;
-  if (!have) {
-    PackJob j;
-    j.kind = PK_EDGE_H2; j.blocks = (int)cdiv(H2_NCHUNK * 16 * 64, PKB); j.i0 = E;
-    j.src[0] = W[0]; j.src[1] = W[1]; j.src[2] = W[2]; j.src[3] = W[3]; j.dst[0] = img;
-    if (int rc = pack_launch(ctx, st, j)) return rc;
-    if (cached) cache_set_job(ctx, W[0], 6, j);
-  }
+  PackJob j;
+  j.kind = PK_EDGE_H2; j.blocks = (int)cdiv(H2_NCHUNK * 16 * 64, PKB); j.i0 = E;
+  j.src[0] = W[0]; j.src[1] = W[1]; j.src[2] = W[2]; j.src[3] = W[3]; j.dst[0] = img;
+  if (int rc = image_pack(ctx, st, s, j)) return rc;
   EdgeH2Args a;
   a.n_edges = n_edges; a.d_src = d_src; a.d_eff = d_eff; a.centers = centers;
   a.neg_inv_gap_log2e = (float)(-1.4426950408889634 / (double)gap);

@@ -831,30 +831,23 @@ struct FcImage {
 };
 
 // the block's packed weights: the cached image of the weights when the cache is on (shared by the forward and the backward of
-// a step, refreshed behind Adam), else `scratch`.  A guarded call's pack launch checks the weights against the piece range.
-static bool fc_packed(ng_ctx* ctx, hipStream_t st, int L, const float* const* W, float* scratch, RangeGuard guard, FcImage* im,
-                      int* rc) {
-  bool have = false;
-  float* ws = (float*)cached_image(ctx, W[0], 5, fc_fused_pack_floats(L) * 4, &have);
-  const bool cached = ws != nullptr;
-  if (!ws) ws = scratch;
-  *rc = NG_OK;
-  if (!ws) return false;      // not cacheable and the caller brought no scratch: it calls again with one
+// a step, refreshed behind Adam), else `scratch`, or the main workspace when the caller brings none.  A guarded call's pack
+// launch checks the weights against the piece range.
+static int fc_packed(ng_ctx* ctx, hipStream_t st, int L, const float* const* W, float* scratch, RangeGuard guard, FcImage* im) {
+  const ImageSlot s = image_slot(ctx, W[0], IK_FC, fc_fused_pack_floats(L) * 4, IMG_WS, scratch);
+  float* ws = (float*)s.buf;
+  if (!ws) return NG_ERR_NOMEM;
   const size_t LF = (size_t)L * FC_F * FC_F;
   im->Wf = ws; im->Wb = ws + LF; im->dummy = ws + 2 * LF;
   unsigned* flag = reinterpret_cast<unsigned*>(ws + 2 * LF + 64);
   im->WfH = reinterpret_cast<unsigned*>(ws + 2 * LF + 80); im->WbH = im->WfH + LF;
-  im->wflag = cached ? flag : nullptr;
-  if (!have) {
-    PackJob j;
-    j.kind = PK_FC; j.blocks = 32; j.i0 = L;
-    for (int l = 0; l < L; ++l) j.src[l] = W[l];
-    j.dst[0] = im->Wf; j.dst[1] = im->Wb; j.dst[2] = (float*)im->WfH; j.dst[3] = (float*)im->WbH;
-    j.flag = cached ? flag : nullptr; j.guard = guard;
-    *rc = pack_launch(ctx, st, j);
-    if (*rc == NG_OK && cached) cache_set_job(ctx, W[0], 5, j);
-  }
-  return true;
+  im->wflag = s.cached ? flag : nullptr;
+  PackJob j;
+  j.kind = PK_FC; j.blocks = 32; j.i0 = L;
+  for (int l = 0; l < L; ++l) j.src[l] = W[l];
+  j.dst[0] = im->Wf; j.dst[1] = im->Wb; j.dst[2] = (float*)im->WfH; j.dst[3] = (float*)im->WbH;
+  j.flag = s.cached ? flag : nullptr; j.guard = guard;
+  return image_pack(ctx, st, s, j);
 }
 
 int fc_fused_fwd(ng_ctx* ctx, hipStream_t st, int64_t N, int L, int act, const float* x, const float* const* W,
@@ -866,15 +859,8 @@ int fc_fused_fwd(ng_ctx* ctx, hipStream_t st, int64_t N, int L, int act, const f
     guard = range_guard_begin(ctx);
     if (!guard.word) return NG_ERR_NOMEM;
   }
-  float* scratch = ctx->wcache ? nullptr : (float*)workspace(ctx, fc_fused_pack_floats(L) * 4);
-  int rc = NG_OK;
   FcImage im{};
-  if (!fc_packed(ctx, st, L, W, scratch, guard, &im, &rc)) {      // (cache on, but this source is not cacheable)
-    scratch = (float*)workspace(ctx, fc_fused_pack_floats(L) * 4);
-    if (!scratch) return NG_ERR_NOMEM;
-    (void)fc_packed(ctx, st, L, W, scratch, guard, &im, &rc);
-  }
-  if (rc) return rc;
+  if (int rc = fc_packed(ctx, st, L, W, nullptr, guard, &im)) return rc;
   FcFwdArgs a{};
   a.N = N; a.act = act; a.x = x; a.Wf = im.Wf; a.g = g; a.dummy = im.dummy;
   a.WfH = im.WfH; a.guard = guard; a.wflag = im.wflag; a.wflag_ver = pack_flag_version(ctx);
@@ -920,10 +906,8 @@ int fc_fused_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int L, int act, const f
     guard = range_guard_begin(ctx);
     if (!guard.word) return NG_ERR_NOMEM;
   }
-  int rc = NG_OK;
   FcImage im{};
-  (void)fc_packed(ctx, st, L, W, ws, guard, &im, &rc);
-  if (rc) return rc;
+  if (int rc = fc_packed(ctx, st, L, W, ws, guard, &im)) return rc;
   FcBwdArgs a{};
   a.N = N; a.act = act; a.g = g; a.dg = dg; a.Wb = im.Wb; a.dx = dx; a.partial = partial; a.part_stride = part;
   a.dummy = im.dummy;

@@ -523,14 +523,14 @@ extern "C" int ng_fc_head_fwd(ng_ctx* ctx, void* stream, int64_t N, int F, int L
   char* scratch = nullptr;
   for (int l = 0; l < 4; ++l) {
     a.W[l] = W[l]; a.b[l] = b[l];
-    bool have = false;
-    char* img = (char*)cached_image(ctx, W[l], 9, img_bytes, &have);
-    if (!img) {                     // weights not frozen: images into the aux scratch, packed on every call
+    const ImageSlot s = image_slot(ctx, W[l], IK_FF_FC, img_bytes, IMG_NONE);
+    char* img = (char*)s.buf;
+    if (!s.cached) {                // weights not frozen: the four images into one block of the aux scratch, packed on every call
       if (!scratch) scratch = (char*)aux_workspace(ctx, 4 * img_bytes);
       if (!scratch) return NG_ERR_NOMEM;
       img = scratch + l * img_bytes;
     }
-    if (!have) {
+    if (!s.fresh) {
       hipLaunchKernelGGL(ff_pack_kernel, dim3((FFW / 32) * 8 * 2 * 64 / 256), dim3(256), 0, st, FFW, l < 3 ? FFW : FFW / 2, W[l],
                          (unsigned*)img);
       NG_HIP(ctx, hipGetLastError());
@@ -554,11 +554,10 @@ static int mp_layer_short_launch(ng_ctx* ctx, void* stream, int64_t N, int K, in
   DeviceGuard dg(ctx->device);
   const int KF = E * FFW;
   const size_t img_bytes = (size_t)(KF / 32) * FF_WCHUNK;
-  bool have = false;
-  char* img = (char*)cached_image(ctx, w, 10, img_bytes, &have);
-  if (!img) img = (char*)aux_workspace(ctx, img_bytes);
+  const ImageSlot s = image_slot(ctx, w, IK_FF_MP, img_bytes, IMG_AUX);
+  char* img = (char*)s.buf;
   if (!img) return NG_ERR_NOMEM;
-  if (!have) {
+  if (!s.fresh) {
     hipLaunchKernelGGL(ff_pack_mp_kernel, dim3((KF / 32) * 8 * 2 * 64 / 256), dim3(256), 0, st, E, w, (unsigned*)img);
     NG_HIP(ctx, hipGetLastError());
   }

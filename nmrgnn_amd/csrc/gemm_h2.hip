@@ -50,7 +50,6 @@ constexpr int GX_XPLANE = GX_BM * GX_XROW;        // 10,240
 using pk::gxp_wchunk;                             // bytes per (column tile, k-step)
 static_assert(GX_BK == pk::GXP_BK, "pack_bodies.cuh");
 constexpr int GX_LDS = 2 * GX_XPLANE + gxp_wchunk(2);   // gemm_h2_fwd_kernel: 36,864, two workgroups per CU
-static int gx_image_kind(int trans, int nbw) { return 3 + 16 * trans + 32 * nbw; }       // cache kind of the image
 static PackJob gx_pack_job(int K, int N, int mode, int nbw, const float* W, void* img) {
   PackJob j;
   j.kind = PK_GX; j.i0 = K; j.i1 = N | (mode << 20) | (nbw << 24); j.src[0] = W; j.dst[0] = img;
@@ -582,20 +581,12 @@ static int gx_launch(ng_ctx* ctx, hipStream_t st, GxArgs& a, const float* W, int
   const int nbw = a.N % 256 == 0 ? 4 : 2;          // 256-column tiles when N allows
   const int BN = 64 * nbw;
   const size_t img_bytes = (size_t)a.N * a.K * 4;  // two fp16 pieces per weight
-  bool have = false;
-  char* img = (char*)cached_image(ctx, W, gx_image_kind(trans, nbw), img_bytes, &have);
-  const bool cached = img != nullptr;
-  if (!img) img = (char*)aux_workspace(ctx, img_bytes);   // callers hold pointers into the main workspace
-  if (!img) return NG_ERR_NOMEM;
-  if (!have) {
-    // (an image whose source is a weight tensor itself is rebuilt behind ng_adam_step from here on; one registered by
-    // gemm_h2_prepack_mp arrives valid and never comes here)
-    const PackJob j = gx_pack_job(a.K, a.N, trans, nbw, W, img);
-    const int rc = pack_launch(ctx, st, j);
-    if (rc) return rc;
-    if (cached) cache_set_job(ctx, W, gx_image_kind(trans, nbw), j);
-  }
-  a.Wimg = img;
+  const ImageSlot s = image_slot(ctx, W, gx_image_kind(trans, nbw), img_bytes, IMG_AUX);   // (aux: callers hold pointers into the main workspace)
+  if (!s.buf) return NG_ERR_NOMEM;
+  // (an image whose source is a weight tensor itself is rebuilt behind ng_adam_step from here on; one registered by
+  // gemm_h2_prepack_mp arrives fresh and is not packed here)
+  if (int rc = image_pack(ctx, st, s, gx_pack_job(a.K, a.N, trans, nbw, W, s.buf))) return rc;
+  a.Wimg = (char*)s.buf;
   ProfScope ps(ctx, st, tag);
   const dim3 grid((unsigned)cdiv(a.M, GX_BM), (unsigned)(a.N / BN));
   if (gx_short_ok(a.K, a.N) && cdiv(a.M, GX_BM) * (a.N / BN) * 2 <= ctx->num_cu) {
@@ -645,16 +636,11 @@ int gemm_h2_dx(ng_ctx* ctx, hipStream_t st, int64_t M, int Kin, int Nout, int ac
 // the plain copy, and gx_launch finds them valid.  No-op when the image cache is off or the product will not take this path.
 int gemm_h2_prepack_mp(ng_ctx* ctx, hipStream_t st, int64_t M, int F, int E, const float* w, const float* Wp, int trans) {
   const int K = trans ? F : E * F, N = trans ? E * F : F;
-  if (!ctx->wcache || !gemm_h2_fwd_ok(M, K, N)) return NG_OK;
+  if (!gemm_h2_fwd_ok(M, K, N)) return NG_OK;
   const int nbw = N % 256 == 0 ? 4 : 2;
-  bool have = false;
-  char* img = (char*)cached_image(ctx, Wp, gx_image_kind(trans, nbw), (size_t)N * K * 4, &have);
-  if (!img || have) return NG_OK;
-  const PackJob j = gx_pack_job(K, N, 2 + trans, nbw, w, img);
-  const int rc = pack_launch(ctx, st, j);
-  if (rc) return rc;
-  cache_set_job(ctx, Wp, gx_image_kind(trans, nbw), j);
-  return NG_OK;
+  const ImageSlot s = image_slot(ctx, Wp, gx_image_kind(trans, nbw), (size_t)N * K * 4, IMG_NONE);
+  if (!s.cached) return NG_OK;
+  return image_pack(ctx, st, s, gx_pack_job(K, N, 2 + trans, nbw, w, s.buf));
 }
 
 // ------------------------------------------------------------------------------------------------------------------

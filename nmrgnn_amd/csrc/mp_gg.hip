@@ -641,20 +641,13 @@ bool mp_gg_supported(int64_t N, int F, int E, int Kpad) {      // Kpad: slots pe
 // the PK_GG image of w for `mode` (cached / refreshed behind Adam when the image cache is on, else in the aux scratch)
 static char* gg_image(ng_ctx* ctx, hipStream_t st, int F, int E, int mode, const float* w, int* rc) {
   const size_t bytes = (size_t)(F / 32) * E * pk::gxp_wchunk(4);
-  bool have = false;
-  char* img = (char*)cached_image(ctx, w, 15 + mode, bytes, &have);
-  const bool cached = img != nullptr;
-  if (!img) img = (char*)aux_workspace(ctx, bytes);
-  *rc = NG_OK;
-  if (!img) { *rc = NG_ERR_NOMEM; return nullptr; }
-  if (!have) {
-    PackJob j;
-    j.kind = PK_GG; j.i0 = E; j.i1 = F | (mode << 16); j.src[0] = w; j.dst[0] = img;
-    j.blocks = (int)cdiv((int64_t)(F / 32) * E * (F / 32) * 2 * 64, 256);
-    *rc = pack_launch(ctx, st, j);
-    if (*rc == NG_OK && cached) cache_set_job(ctx, w, 15 + mode, j);
-  }
-  return img;
+  const ImageSlot s = image_slot(ctx, w, gg_image_kind(mode), bytes, IMG_AUX);
+  if (!s.buf) { *rc = NG_ERR_NOMEM; return nullptr; }
+  PackJob j;
+  j.kind = PK_GG; j.i0 = E; j.i1 = F | (mode << 16); j.src[0] = w; j.dst[0] = s.buf;
+  j.blocks = (int)cdiv((int64_t)(F / 32) * E * (F / 32) * 2 * 64, 256);
+  *rc = image_pack(ctx, st, s, j);
+  return (char*)s.buf;
 }
 
 template <int LK, bool GRAD>

@@ -916,27 +916,19 @@ int mp_win_fwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int act, in
   // the f32 image of the same weights behind it (one cached buffer, one pack job)
   const size_t img_floats = (size_t)KF * WF + 64 + 16;
   const size_t tot_floats = guarded ? 2 * img_floats : img_floats;
-  bool have = false;
-  float* Wfrag = (float*)cached_image(ctx, w, h2 ? 7 : 4, tot_floats * 4, &have);
-  const bool cached = Wfrag != nullptr;
-  if (!cached) {
-    Wfrag = (float*)workspace(ctx, tot_floats * 4);
-    if (!Wfrag) return NG_ERR_NOMEM;
-    have = false;
-  }
+  const ImageSlot s = image_slot(ctx, w, h2 ? IK_MPW_FWD : IK_MPW_F32, tot_floats * 4, IMG_WS);
+  if (!s.buf) return NG_ERR_NOMEM;
+  float* Wfrag = (float*)s.buf;
   float* Wf32 = guarded ? Wfrag + img_floats : nullptr;
-  unsigned* wflag = cached && guarded ? reinterpret_cast<unsigned*>(Wfrag + KF * WF + 64) : nullptr;
-  if (!have) {
-    PackJob j;
-    if (h2) {
-      j.kind = PK_MPW_FWD; j.blocks = guarded ? 48 : 24; j.i0 = E; j.src[0] = w; j.dst[0] = Wfrag; j.dst[1] = Wf32;
-      j.flag = wflag; j.guard = guard;
-    } else {
-      j.kind = PK_MPW_F32; j.blocks = 24; j.i0 = E; j.i1 = 0; j.src[0] = w; j.dst[0] = Wfrag;
-    }
-    if (int rc = pack_launch(ctx, st, j)) return rc;
-    if (cached) cache_set_job(ctx, w, h2 ? 7 : 4, j);
+  unsigned* wflag = s.cached && guarded ? reinterpret_cast<unsigned*>(Wfrag + KF * WF + 64) : nullptr;
+  PackJob j;
+  if (h2) {
+    j.kind = PK_MPW_FWD; j.blocks = guarded ? 48 : 24; j.i0 = E; j.src[0] = w; j.dst[0] = Wfrag; j.dst[1] = Wf32;
+    j.flag = wflag; j.guard = guard;
+  } else {
+    j.kind = PK_MPW_F32; j.blocks = 24; j.i0 = E; j.i1 = 0; j.src[0] = w; j.dst[0] = Wfrag;
   }
+  if (int rc = image_pack(ctx, st, s, j)) return rc;
   if (h2 && sw().mp_w16 && mp_wave_wanted(ctx, N, E, K))
     return mp_wave_launch(ctx, st, N, K, act, residual, h, nlist, e, inv_degree, Wfrag, Wf32, wflag, guard, h_out, s_save);
   if (h2 && sw().mp_w16 && mp_win16_supported(E, K))

@@ -970,18 +970,16 @@ int mp_win_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int act, co
   // refreshed behind Adam (pack_bodies.cuh), else the head of the scratch.
   // scratch: [images] | dP [N,64] | records [N*K,4] (when the caller has none) | dw partials
   const size_t img_floats = (size_t)4 * KF * WF + 16;
-  bool have = false;
-  float* imgs = (float*)cached_image(ctx, w, h2 ? 8 : 14, img_floats * 4, &have);
-  const bool cached = imgs != nullptr;
+  ImageSlot s = image_slot(ctx, w, h2 ? IK_MPW_BWD : IK_MPW_BWD_F32, img_floats * 4, IMG_NONE);
   const size_t rec_floats = csc_rec ? 0 : (size_t)N * K * 4;
-  float* ws = (float*)workspace(ctx, (size_t)((cached ? 0 : img_floats) + N * WF + rec_floats + dw_scr + 64) * 4);
+  float* ws = (float*)workspace(ctx, (size_t)((s.cached ? 0 : img_floats) + N * WF + rec_floats + dw_scr + 64) * 4);
   if (!ws) return NG_ERR_NOMEM;
-  if (!cached) { imgs = ws; ws += img_floats; have = false; }
-  float* WfragT = imgs;
+  if (!s.cached) { s.buf = ws; ws += img_floats; }
+  float* WfragT = (float*)s.buf;
   float* WfragN = WfragT + KF * WF;
   float* WfragT32 = WfragN + KF * WF;
   float* WfragN32 = WfragT32 + KF * WF;
-  unsigned* wflag = cached && guarded ? reinterpret_cast<unsigned*>(WfragN32 + KF * WF) : nullptr;
+  unsigned* wflag = s.cached && guarded ? reinterpret_cast<unsigned*>(WfragN32 + KF * WF) : nullptr;
   float* dP = ws;
   float* rec = dP + N * WF;
   float* scr = rec + rec_floats;
@@ -990,16 +988,10 @@ int mp_win_bwd(ng_ctx* ctx, hipStream_t st, int64_t N, int K, int E, int act, co
   if (dw)
     if (float* dscr = deferred_partials(ctx, dw_scr)) scr = dscr;
   int rc = NG_OK;
-  if (!have) {
-    if (h2) {
-      const PackJob j = mpw_bwd_job(E, w, WfragT, WfragN, guarded ? WfragT32 : nullptr, guarded ? WfragN32 : nullptr, wflag, guard);
-      rc = pack_launch(ctx, st, j);
-      if (rc == NG_OK && cached) cache_set_job(ctx, w, 8, j);
-    } else {
-      rc = mpw_pack2(ctx, st, E, w, 2, WfragT, 1, WfragN);       // (strict-fp32 mode: two small launches, not registered)
-      if (cached) have = false;
-    }
-  }
+  if (h2)
+    rc = image_pack(ctx, st, s, mpw_bwd_job(E, w, WfragT, WfragN, guarded ? WfragT32 : nullptr, guarded ? WfragN32 : nullptr, wflag, guard));
+  else if (!s.fresh)
+    rc = mpw_pack2(ctx, st, E, w, 2, WfragT, 1, WfragN);       // (strict-fp32 mode: two small launches, not registered)
   if (rc) return rc;
   const unsigned wver = pack_flag_version(ctx);
   rc = mp_win_bwd_edge(ctx, st, N, K, E, act, h, nlist, inv_degree, WfragT, s_save, dh_out, dP, de, de_accum, dummy, guard,

@@ -48,6 +48,37 @@ struct PackJob {
   unsigned* flag = nullptr;
   RangeGuard guard = {nullptr, 0};
 };
+
+// The images the context keeps (repack.hip), as the second half of their key (source pointer, kind).  The numbers are fixed:
+// the map order of the cache decides the job order of repack_all.  Per kind: the weights it is keyed by (and packed from),
+// its PackKind or "own pack kernel, no job" (never registered: rebuilt at its next use), and whether it holds a flag-word pair
+enum ImageKind : int {
+  IK_MP_PLAIN = 1,      // node_ops.hip: key w; PK_MP_PLAIN
+  IK_MPW_F32 = 4,       // mp_win.hip, strict fp32: key w; PK_MPW_F32
+  IK_FC = 5,            // fc_fused.hip: key W[0], from W[0..L-1]; PK_FC; flag pair
+  IK_EDGE_H2 = 6,       // edge_fwd_h2.hip: key W[0], from W[0..3]; PK_EDGE_H2
+  IK_MPW_FWD = 7,       // mp_win.hip: key w; PK_MPW_FWD; flag pair (guarded calls)
+  IK_MPW_BWD = 8,       // mp_win_bwd.hip: key w; PK_MPW_BWD; flag pair (guarded calls)
+  IK_FF_FC = 9,         // frame_fused.hip: key W[l], one image per layer; own pack kernel (ff_pack_kernel), no job
+  IK_FF_MP = 10,        // frame_fused.hip: key w; own pack kernel (ff_pack_mp_kernel), no job
+  IK_EDGE_F32 = 11,     // edge_fused.hip: key W[0], from W[0..2]; PK_EDGE_F32 (dst[0])
+  IK_EDGE_F32_T = 12,   // edge_fused_bwd.hip: key W[0], from W[0..2]; PK_EDGE_F32 (dst[1]: transposed)
+  IK_EDGE_WT = 13,      // edge_bwd_h2.hip: key W[1], from W[1..3]; PK_EDGE_WT
+  IK_MPW_BWD_F32 = 14,  // mp_win_bwd.hip, strict fp32: key w; own pack kernels (mpw_pack2), no job
+  // mp_gg.hip, gg_image_kind(mode): key w; PK_GG
+  IK_GG_FWD = 15, IK_GG_PULL = 16,
+  // gemm_h2.hip, gx_image_kind(trans, nbw): key W, or the cached plain copy Wp of an MPLayer weight w (gemm_h2_prepack_mp:
+  // packed from w); PK_GX
+  IK_GX_N2 = 67, IK_GX_T2 = 83, IK_GX_N4 = 131, IK_GX_T4 = 147,
+};
+constexpr ImageKind gg_image_kind(int mode) { return (ImageKind)(15 + mode); }                            // mode 0, 1
+constexpr ImageKind gx_image_kind(int trans, int nbw) { return (ImageKind)(3 + 16 * trans + 32 * nbw); }  // trans 0, 1; nbw 2, 4
+static_assert(gg_image_kind(0) == IK_GG_FWD && gg_image_kind(1) == IK_GG_PULL && gx_image_kind(0, 2) == IK_GX_N2 &&
+              gx_image_kind(1, 2) == IK_GX_T2 && gx_image_kind(0, 4) == IK_GX_N4 && gx_image_kind(1, 4) == IK_GX_T4,
+              "the two families are the enumerators above");
+static_assert(IK_MP_PLAIN < IK_MPW_F32 && IK_MPW_BWD_F32 < gg_image_kind(0) && gg_image_kind(1) < gx_image_kind(0, 2) &&
+              gx_image_kind(1, 2) < gx_image_kind(0, 4),
+              "single kinds, the gather-GEMM family and the GEMM family: pairwise disjoint ranges");
 }  // namespace ng
 
 struct ng_prof_rec {
@@ -187,17 +218,31 @@ void* small_scratch(ng_ctx* ctx);      // NG_SMALL_BYTES, allocated once per con
 constexpr size_t NG_REPLAY_STATE_OFFSET = NG_SMALL_BYTES - 256;
 constexpr int NG_REPLAY_VER_WORD = 4;      // 32-bit word of the block: the image version of the step's armed repack launch
 const uint64_t* replay_state(ng_ctx* ctx);
-// Frozen-weight image cache.  Returns nullptr when the cache is off (pack into scratch as before); otherwise a
-// persistent buffer of `bytes` for (src, kind) with *valid = true when it already holds the image of the current
-// weights (skip the pack launch).  kinds: 1 MPLayer Wp, 3 GEMM fp16-piece image, 4 window fragments, 5 FC fragments, 6 edge fp16-piece image
-void* cached_image(ng_ctx* ctx, const void* src, int kind, size_t bytes, bool* valid);
-// after packing a cached image: remember how (pack_bodies.cuh), so that ng_adam_step can refresh it
-void cache_set_job(ng_ctx* ctx, const void* src, int kind, const PackJob& job);
-// one image now (first use / cache off); the version a flag word is compared with
+// ---- Frozen-weight image cache (repack.hip: the only file that touches the w* fields of ng_ctx) ----------------------------
+// Where the image of (src, kind) lives for this call.  Cache on (ng_weights_frozen) and src cacheable: the context's buffer
+// of `bytes` for the key, `cached`, and `fresh` when it already holds the image of the current weights.  Otherwise the
+// scratch the caller names — `own` if given, else the main / aux workspace of `bytes`, asked for only now (growing a
+// workspace synchronises and allocates: a call served from the cache must not), else nullptr (IMG_NONE: the caller carves
+// the image out of a block of its own and sets `buf`) — and `fresh` is false: it is packed on every call.
+//  - scratch is never a key: a source inside the context's own workspaces is not cacheable (repack.hip has the why)
+//  - a flag-word pair means something only in a cached image: hand its pointer to the job and the kernel only when `cached`
+//  - a buffer that grows drops its registered job (the job points into the old one)
+enum ImageScratch { IMG_NONE, IMG_WS, IMG_AUX };
+struct ImageSlot { void* buf; bool cached; bool fresh; ng_ctx::WImage* entry; };      // entry: the cache's own, nullptr unless cached
+ImageSlot image_slot(ng_ctx* ctx, const void* src, ImageKind kind, size_t bytes, ImageScratch where, void* own = nullptr);
+// Runs `job` (pack_bodies.cuh) unless the slot is fresh, and keeps it with a cached image so that ng_adam_step can refresh it
+// (repack_all) — without its per-call guard, which means nothing to a later refresh.  An image with a pack kernel of its own
+// is launched by its site on !fresh and keeps no job: it is rebuilt at its next use.
+int image_pack(ng_ctx* ctx, hipStream_t st, const ImageSlot& slot, const PackJob& job);
+// one image now, nothing kept; the version a flag word is compared with
 int pack_launch(ng_ctx* ctx, hipStream_t st, const PackJob& job);
 unsigned pack_flag_version(const ng_ctx* ctx);
+// the weights moved (ng_adam_step): every image is stale from here on
+void weights_bump(ng_ctx* ctx);
 // every registered image whose sources all lie in [lo, hi): one launch on `st`; the images then carry the current version
 int repack_all(ng_ctx* ctx, hipStream_t st, const void* lo, const void* hi);
+// ng_ctx_destroy: the images and the job tables
+void image_cache_free(ng_ctx* ctx);
 
 // RAII-less profiling bracket: call begin before the launch(es), end after.
 struct ProfScope {

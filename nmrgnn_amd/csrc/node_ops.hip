@@ -246,21 +246,14 @@ int mp_repack_w(ng_ctx* ctx, hipStream_t st, int F, int E, const float* w, float
 // ng_adam_step together with the piece image of the product — gemm_h2_prepack_mp — so that a training step packs nothing), or
 // `scratch` filled here when the image cache is off.  trans: 0 = the update product, 1 = the dA product.
 int mp_plain_weights(ng_ctx* ctx, hipStream_t st, int64_t M, int F, int E, const float* w, float* scratch, int trans, const float** Wp) {
-  bool have = false;
-  float* Wc = (float*)cached_image(ctx, w, 1, (size_t)E * F * F * 4, &have);
-  if (!Wc) {
-    *Wp = scratch;
-    return mp_repack_w(ctx, st, F, E, w, scratch);
-  }
+  const ImageSlot s = image_slot(ctx, w, IK_MP_PLAIN, (size_t)E * F * F * 4, IMG_NONE, scratch);
+  float* Wc = (float*)s.buf;
   *Wp = Wc;
-  if (!have) {
-    PackJob j;
-    j.kind = PK_MP_PLAIN; j.i0 = F; j.i1 = E; j.src[0] = w; j.dst[0] = Wc;
-    j.blocks = (int)std::min<int64_t>(cdiv((int64_t)E * F * F, 256), 1024);
-    const int rc = pack_launch(ctx, st, j);
-    if (rc) return rc;
-    cache_set_job(ctx, w, 1, j);
-  }
+  if (!s.cached) return mp_repack_w(ctx, st, F, E, w, Wc);
+  PackJob j;
+  j.kind = PK_MP_PLAIN; j.i0 = F; j.i1 = E; j.src[0] = w; j.dst[0] = Wc;
+  j.blocks = (int)std::min<int64_t>(cdiv((int64_t)E * F * F, 256), 1024);
+  if (int rc = image_pack(ctx, st, s, j)) return rc;
   return gemm_h2_prepack_mp(ctx, st, M, F, E, w, Wc, trans);
 }
 
@@ -1194,7 +1187,7 @@ extern "C" int ng_adam_step(ng_ctx* ctx, void* stream, int64_t n, float* p, cons
                             float grad_scale) {
   if (!ctx) return NG_ERR_INVALID;
   NG_REQUIRE(ctx, step >= 1, "adam: step counts from 1");
-  ctx->wver++;                       // packed weight images of a frozen-weight cache are stale from here on
+  weights_bump(ctx);                 // packed weight images of a frozen-weight cache are stale from here on
   if (n == 0) return NG_OK;
   const double lr_t = (double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)step)) /
                       (1.0 - std::pow((double)beta1, (double)step));

@@ -1,4 +1,6 @@
-// One kernel for every weight image of the step (round 4; pack_bodies.cuh has the bodies and the why).
+// The frozen-weight image cache — the only file that reads or writes the cache's fields of ng_ctx (wimg, wver, wcache, wowner,
+// wjobs_*, replay_token; ng_common.h states the contract of image_slot / image_pack) — and one kernel for every weight image
+// of the step (round 4; pack_bodies.cuh has the bodies and the why).
 //   pack_launch : ONE image now — first use of a cached image, or the cache is off (the job travels as a kernel argument)
 //   repack_all  : every job registered in the context's image cache whose source weights lie inside the block Adam has
 //                 just updated, in ONE launch behind the Adam kernel; the images then carry the new weight version and no
@@ -38,13 +40,59 @@ int pack_launch(ng_ctx* ctx, hipStream_t st, const PackJob& job) {
   return NG_OK;
 }
 
-void cache_set_job(ng_ctx* ctx, const void* src, int kind, const PackJob& job) {
-  auto it = ctx->wimg.find(std::make_pair(src, kind));
-  if (it == ctx->wimg.end()) return;
-  it->second.job = job;
-  it->second.job.guard = RangeGuard{nullptr, 0};      // a per-call guard means nothing to a later refresh
-  it->second.has_job = true;
+// the context's entry for (src, kind) with a buffer of `bytes`, *valid when it holds the image of the current weights;
+// nullptr: not cacheable
+static ng_ctx::WImage* cached_image(ng_ctx* ctx, const void* src, int kind, size_t bytes, bool* valid) {
+  *valid = false;
+  if (!ctx->wcache) return nullptr;
+  // A source inside the context's own scratch is a temporary (a weight matrix repacked for THIS call: the same address
+  // holds another layer's weights on the next call) — never a cache key.  Round-2 advisor finding: with the cache keyed
+  // by such an address a frozen window around a multi-layer backward multiplied with the previous layer's image.
+  auto inside = [&](const void* base, size_t n) {
+    return base && (const char*)src >= (const char*)base && (const char*)src < (const char*)base + n;
+  };
+  if (inside(ctx->ws, ctx->ws_bytes) || inside(ctx->aux, ctx->aux_bytes)) return nullptr;
+  ng_ctx::WImage& w = ctx->wimg[std::make_pair(src, kind)];
+  if (w.bytes < bytes) {
+    DeviceGuard dg(ctx->device);
+    if (w.buf) { (void)hipDeviceSynchronize(); (void)hipFree(w.buf); w.buf = nullptr; w.bytes = 0; }
+    if (hipMalloc(&w.buf, bytes) != hipSuccess) { w.buf = nullptr; return nullptr; }
+    (void)hipMemset(w.buf, 0, bytes);      // (flag words inside an image start out equal to no version)
+    w.bytes = bytes;
+    w.ver = 0;
+    w.has_job = false;                     // a registered job points into the old buffer
+    ctx->wjobs_dirty = true;
+  }
+  *valid = w.ver == ctx->wver;
+  w.ver = ctx->wver;
+  return &w;
+}
+
+ImageSlot image_slot(ng_ctx* ctx, const void* src, ImageKind kind, size_t bytes, ImageScratch where, void* own) {
+  bool fresh = false;
+  if (ng_ctx::WImage* w = cached_image(ctx, src, kind, bytes, &fresh)) return ImageSlot{w->buf, true, fresh, w};
+  if (!own && where != IMG_NONE) own = where == IMG_WS ? workspace(ctx, bytes) : aux_workspace(ctx, bytes);
+  return ImageSlot{own, false, false, nullptr};
+}
+
+int image_pack(ng_ctx* ctx, hipStream_t st, const ImageSlot& slot, const PackJob& job) {
+  if (slot.fresh) return NG_OK;
+  if (int rc = pack_launch(ctx, st, job)) return rc;
+  if (!slot.cached) return NG_OK;
+  slot.entry->job = job;
+  slot.entry->job.guard = RangeGuard{nullptr, 0};      // a per-call guard means nothing to a later refresh
+  slot.entry->has_job = true;
   ctx->wjobs_dirty = true;
+  return NG_OK;
+}
+
+void weights_bump(ng_ctx* ctx) { ctx->wver++; }
+
+void image_cache_free(ng_ctx* ctx) {
+  for (auto& kv : ctx->wimg)
+    if (kv.second.buf) (void)hipFree(kv.second.buf);
+  if (ctx->wjobs_dev) (void)hipFree(ctx->wjobs_dev);
+  for (auto& kv : ctx->wjobs_private) (void)hipFree(kv.second);
 }
 
 int repack_all(ng_ctx* ctx, hipStream_t st, const void* lo, const void* hi) {
@@ -139,3 +187,38 @@ int repack_all(ng_ctx* ctx, hipStream_t st, const void* lo, const void* hi) {
 }
 
 }  // namespace ng
+
+extern "C" int ng_weights_frozen(ng_ctx* ctx, int owner) {
+  if (!ctx) return NG_ERR_INVALID;
+  if (owner != 0 && owner != ctx->wowner) {   // another model takes the cache over: nothing in it is its own
+    ctx->wver++;
+    ctx->wowner = owner;
+    for (auto& kv : ctx->wimg) kv.second.has_job = false;     // (its weights may be gone: nothing of it is refreshed)
+    ctx->wjobs_dirty = true;
+  }
+  ctx->wcache = owner != 0;
+  return NG_OK;
+}
+
+extern "C" int ng_weights_changed(ng_ctx* ctx) {
+  if (!ctx) return NG_ERR_INVALID;
+  ctx->wver++;
+  return NG_OK;
+}
+
+extern "C" int ng_replay_token(ng_ctx* ctx, uint64_t* token) {
+  if (!ctx || !token) return NG_ERR_INVALID;
+  *token = ctx->replay_token;
+  return NG_OK;
+}
+
+// host bookkeeping of ONE replayed ng_adam_step: the weights moved, the captured repack launch rebuilt the images of `token`
+extern "C" int ng_replay_commit(ng_ctx* ctx, uint64_t token) {
+  if (!ctx) return NG_ERR_INVALID;
+  ctx->wver++;
+  auto it = ctx->wjobs_private_sel.find(token);
+  if (token != 0 && it != ctx->wjobs_private_sel.end())
+    for (ng_ctx::WImage* w : it->second)
+      if (w->buf && w->has_job) w->ver = ctx->wver;
+  return NG_OK;
+}

@@ -1,10 +1,10 @@
-"""Every packed weight image the context keeps (ng_ctx::wimg, csrc/capi.hip cached_image) through its life, at the C ABI: after
+"""Every packed weight image the context keeps (ng_ctx::wimg, csrc/repack.hip image_slot) through its life, at the C ABI: after
 each step the consumer's outputs must be, bit for bit, those of the same call with the cache off (ng_weights_frozen(ctx, 0):
 the image is packed in front of the use) on the weights as they are now.  "The images are the same bits whichever launch
 builds them", so no tolerance is involved.  Every output is filled with NaN before the call and compared as bit patterns, and
 no element of an output may still hold the prefill (de of the MPLayer: the live slots).
 
-Cases (tests/weight_cache_cases.py: CASES; one row per `cached_image(` call of csrc/, "#n" = the n-th call of the file):
+Cases (tests/weight_cache_cases.py: CASES; one row per `image_slot(` call of csrc/, "#n" = the n-th call of the file):
 
   site                    kind(s)      PackKind                  entry point                      reached by               cases
   mp_win.hip#0            7            PK_MPW_FWD   (flag pair)  ng_mp_layer_fwd, F = 64          default                  win_e3_k16, win_e1_k8, win_w8_e3_k16

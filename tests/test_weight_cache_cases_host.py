@@ -1,4 +1,7 @@
 """Conditions on the inputs of the weight-cache tests (tests/weight_cache_cases.py): no GPU, nothing measured."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -6,7 +9,7 @@ import weight_cache_cases as wc
 
 
 def test_every_cached_image_call_site_has_a_case():
-    """a search of csrc/*.hip for `cached_image(`: 13 calls (and the definition in capi.hip, which is not one).  A site added
+    """a search of csrc/*.hip for `image_slot(`: 13 calls (and the definition in repack.hip, which is not one).  A site added
     later fails here until a case names it; a case naming a site that is gone fails too"""
     found = wc.sites()
     assert len(found) == 13, sorted(found)
@@ -22,6 +25,54 @@ def test_case_names_are_unique_and_kinds_are_stated():
     kinds = {k for c in wc.CASES for k in c["kinds"]}
     gx = {wc.gx_kind(t, n) for t in (0, 1) for n in (2, 4)}
     assert kinds >= {1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16} | gx, sorted(kinds)
+
+
+def _csrc(name):
+    with open(os.path.join(wc.CSRC, name)) as f:
+        return f.read()
+
+
+def test_image_kind_enum_names_exactly_the_kinds_of_the_cases():
+    """`enum ImageKind` of ng_common.h and the formulas of its two family functions, read from the text: together they give the
+    kinds the cases name, no more and no fewer, and every member of a family is an enumerator too"""
+    text = _csrc("ng_common.h")
+    body = re.search(r"enum ImageKind : int \{(.*?)\n\};", text, re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    enum = {name: int(val) for name, val in re.findall(r"(IK_\w+)\s*=\s*(\d+)", body)}
+    assert len(set(enum.values())) == len(enum) and len(enum) == len(re.findall(r"IK_\w+", body)), enum
+    gg = re.search(r"constexpr ImageKind gg_image_kind\(int mode\) \{ return \(ImageKind\)\(([^;]*)\); \}", text).group(1)
+    gx = re.search(r"constexpr ImageKind gx_image_kind\(int trans, int nbw\) \{ return \(ImageKind\)\(([^;]*)\); \}", text).group(1)
+    assert re.fullmatch(r"[\d\s+*a-z]+", gg) and re.fullmatch(r"[\d\s+*a-z]+", gx), (gg, gx)
+    gg_kinds = {eval(gg, {"__builtins__": {}}, {"mode": m}) for m in (0, 1)}
+    gx_kinds = {eval(gx, {"__builtins__": {}}, {"trans": t, "nbw": n}) for t in (0, 1) for n in (2, 4)}
+    assert gx_kinds == {wc.gx_kind(t, n) for t in (0, 1) for n in (2, 4)}
+    assert len(gg_kinds) == 2 and len(gx_kinds) == 4 and not gg_kinds & gx_kinds
+    assert gg_kinds | gx_kinds <= set(enum.values())
+    singles = set(enum.values()) - gg_kinds - gx_kinds
+    assert singles == {1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14}, sorted(singles)
+    assert set(enum.values()) == {k for c in wc.CASES for k in c["kinds"]}, sorted(enum.items(), key=lambda kv: kv[1])
+
+
+def test_cache_fields_are_used_in_the_cache_module_alone():
+    """member uses (`->name`) of the image cache's fields of ng_ctx, in every source and header of csrc/: only ng_common.h (the
+    struct) and repack.hip may hold one.  Local variables of the same names (wimg, wver) are no member uses"""
+    member = re.compile(r"(?:->|\.)\s*(wimg|wver|wcache|wowner|wjobs_\w*|replay_token)\b")
+    names = sorted(n for n in os.listdir(wc.CSRC) if n.endswith((".hip", ".cuh", ".h")))
+    assert "repack.hip" in names and "ng_common.h" in names and len(names) > 40
+    found = {}
+    for name in names:
+        hits = [m.group(0) for m in member.finditer(_csrc(name))]
+        if hits:
+            found[name] = hits
+    assert member.search("ctx->wver++") and member.search("c -> wjobs_dirty") and not member.search("const unsigned wver = f(ctx);")
+    assert "repack.hip" in found                     # the search finds the uses that are there
+    assert set(found) <= {"repack.hip", "ng_common.h"}, {k: v for k, v in found.items() if k != "repack.hip"}
+    # and no call site passes a number for a kind: the third argument of image_slot names an enumerator or a family function
+    calls = [(name, m.group(1)) for name in names if name not in ("repack.hip", "ng_common.h")
+             for m in re.finditer(r"image_slot\(ctx, [^,]+, ([^,]+),", _csrc(name))]
+    assert len(calls) == 13
+    for name, kind in calls:
+        assert re.match(r"(h2 \? )?(IK_\w+|g[gx]_image_kind\()", kind) and not re.search(r"\b\d", kind), (name, kind)
 
 
 def test_flagged_and_multi_source_cases_run_their_extra_steps():

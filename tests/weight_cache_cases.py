@@ -1,9 +1,10 @@
 """The inputs of the weight-cache tests (test_gpu_weight_images.py, test_gpu_weight_state.py), host side only: the table of
-cases per `cached_image(` call site of csrc/, the flat weight layouts with their Adam blocks, and the seeded operation
+cases per `image_slot(` call site of csrc/, the flat weight layouts with their Adam blocks, and the seeded operation
 sequences.  test_weight_cache_cases_host.py asserts the conditions these inputs have to meet.
 
-A site is "<file>#<n>": the n-th `cached_image(` call of csrc/<file> in source order (sites() finds them; the definition in
-capi.hip is not a call).  Kinds are the cache-kind numbers passed there; PackKind names are those of csrc/ng_common.h."""
+A site is "<file>#<n>": the n-th `image_slot(` call of csrc/<file> in source order (sites() finds them; the definition in
+repack.hip is not a call).  Kinds are the values of the ImageKind passed there; ImageKind and PackKind are those of
+csrc/ng_common.h."""
 import os
 import re
 
@@ -13,20 +14,20 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def sites():
-    """{"mp_win.hip#0", ...}: every call of cached_image( in csrc/*.hip"""
+    """{"mp_win.hip#0", ...}: every call of image_slot( in csrc/*.hip"""
     out = set()
     for name in sorted(os.listdir(CSRC)):
         if not name.endswith(".hip"):
             continue
         with open(os.path.join(CSRC, name)) as f:
             text = f.read()
-        calls = [m for m in re.finditer(r"cached_image\(", text) if not text[:m.start()].endswith("void* ")]
+        calls = [m for m in re.finditer(r"image_slot\(", text) if not text[:m.start()].endswith("ImageSlot ")]
         out.update(f"{name}#{k}" for k in range(len(calls)))
     return out
 
 
 def gx_kind(trans, nbw):
-    """gx_image_kind of csrc/gemm_h2.hip"""
+    """gx_image_kind of csrc/ng_common.h"""
     return 3 + 16 * trans + 32 * nbw
 
 
