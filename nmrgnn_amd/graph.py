@@ -15,12 +15,24 @@ A GraphBatch additionally carries
   * ``graph_ptr`` [G+1]: atom ranges of the member graphs (loss is per graph, losses.py:37-39);
   * the transposed incoming-edge lists ``csc_ptr`` [N+1] / ``csc_edge`` [nnz] used by the
     deterministic backward scatter (edge id = i*K + j, grouped by target nlist[i,j]); slots with
-    ``edges == 0`` are dropped — they carry e == 0 exactly because of the edge mask (model.py:261).
+    ``edges == 0`` are dropped — they carry e == 0 exactly because of the edge mask (model.py:261);
+  * where it was built from positions, those, the distance scale and the boundary conditions (``set_geometry``).  The
+    records behind ``positions_grad`` / ``box_grad`` and the choice of a library entry point live in geometry.py.
 """
 from __future__ import annotations
 
+from collections import namedtuple
+from dataclasses import dataclass
+from functools import partial
+
 import numpy as np
 import torch
+
+from . import _lib
+from ._lib import ptr
+from .geometry import OPEN_BOUNDARY, Boundary, Geometry, Layout, ListView, cutoff_count_call, cutoff_fill_call, edge_grad_input, \
+    knn_call, library_calls
+from .pbc import prepare, prepare_ragged, triclinic_vectors_torch
 
 
 def _norm_device(device):
@@ -65,12 +77,20 @@ def _to_dev(x, dtype, device):
 class GraphBatch:
     is_csr = False
     row_ptr = None
-    positions = None   # [G, n, 3] Angstrom, and the distance scale: set by frames_to_batch / frames_to_batch_cutoff
-    scale = None
-    box = None         # [G, 9] lattice vectors on the device (nmrgnn_amd.pbc) when the lists were built in periodic boxes
-    box_triclinic = False
-    box_kind = None    # [G] int32 on the device (-1 open, 0 orthorhombic, 1 reduced triclinic): a ragged batch whose structures
-    box_kind_host = None   # have boundary kinds of their own (structures_to_batch(boxes=)); then ``box`` holds zeros for open ones
+    positions = None   # [G, n, 3] (ragged: [N, 3]) Angstrom, the distance scale and the boundary conditions the lists were
+    scale = None       # built with: set_geometry, called by the builders from positions
+    boundary = OPEN_BOUNDARY
+
+    def set_geometry(self, positions, scale, boundary):
+        """the one place that attaches the geometry the lists were built from (geometry.Boundary)"""
+        self.positions, self.scale, self.boundary = positions, float(scale), boundary
+
+    # the boundary, field by field (geometry.Boundary): None / False without periodic boxes, the kinds None unless the
+    # structures have kinds of their own (structures_to_batch(boxes=))
+    box = property(lambda self: self.boundary.box)
+    box_triclinic = property(lambda self: self.boundary.triclinic)
+    box_kind = property(lambda self: self.boundary.kind)
+    box_kind_host = property(lambda self: self.boundary.kind_host)
 
     _ctx = None        # library context for the list builders; None = the device's shared one (BatchPrefetcher sets its own)
 
@@ -228,35 +248,27 @@ class GraphBatch:
         ng_build_incoming_lists; the reference sees a new graph every step, nmrgnn/library.py:88-89)."""
         if self.device.type != "cuda":
             return self._build_lists_host(nlist_c)
-        import ctypes as C
-        from . import _lib
-        from ._lib import ptr
-        ctx = self._ctx or _lib.get_context(self.device.index)
         n_entries = self.n_edges
         csc_ptr = torch.empty(self.N + 1, dtype=torch.int32, device=self.device)
         csc_edge = torch.empty(max(n_entries, 1), dtype=torch.int32, device=self.device)
-        if nlist_c is not None and not self.is_csr and self._live is None \
-                and ctx.lib.ng_graph_lists_one_launch(self.N, self.K):
-            # molecule-sized call: the live-edge view in the same launch (ng_build_graph_lists)
-            perm = torch.empty(n_entries, dtype=torch.int32, device=self.device)
-            pos = torch.empty(n_entries, dtype=torch.int32, device=self.device)
-            d_c = torch.empty(n_entries, dtype=torch.float32, device=self.device)
-            n_live = torch.empty(1, dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-                ctx.check(ctx.lib.ng_build_graph_lists(ctx.handle, st, self.N, self.K, ptr(self.nlist), ptr(self.edges),
-                                                       ptr(nlist_c), ptr(csc_ptr), ptr(csc_edge), ptr(perm), ptr(pos),
-                                                       ptr(d_c), ptr(n_live)), "ng_build_graph_lists")
-            self._csc = (csc_ptr, csc_edge)
-            self._live = (perm, pos, d_c, n_live)
-            return
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            ctx.check(ctx.lib.ng_build_incoming_lists(ctx.handle, st, self.N, 0 if self.is_csr else self.K, n_entries,
-                                                      ptr(self.nlist), None if self.is_csr else ptr(self.edges),
-                                                      ptr(nlist_c), ptr(csc_ptr), ptr(csc_edge)),
-                      "ng_build_incoming_lists")
+        with library_calls(self._ctx, self.device) as call:
+            if nlist_c is not None and not self.is_csr and self._live is None \
+                    and _lib.load().ng_graph_lists_one_launch(self.N, self.K):
+                # molecule-sized call: the live-edge view in the same launch (ng_build_graph_lists)
+                live = self._live_buffers()
+                call("ng_build_graph_lists", (self.N, self.K, ptr(self.nlist), ptr(self.edges), ptr(nlist_c), ptr(csc_ptr),
+                                              ptr(csc_edge), *map(ptr, live)))
+                self._live = live
+            else:
+                call("ng_build_incoming_lists", (self.N, 0 if self.is_csr else self.K, n_entries, ptr(self.nlist),
+                                                 None if self.is_csr else ptr(self.edges), ptr(nlist_c), ptr(csc_ptr),
+                                                 ptr(csc_edge)))
         self._csc = (csc_ptr, csc_edge)
+
+    def _live_buffers(self):
+        """(perm, pos, d_c, n_live), to be written"""
+        new = partial(torch.empty, dtype=torch.int32, device=self.device)
+        return new(self.n_edges), new(self.n_edges), new(self.n_edges, dtype=torch.float32), new(1)
 
     def _build_lists_host(self, nlist_c=None):
         """the same lists with torch ops, for batches held in HOST memory (shard bookkeeping in the multi-process CPU
@@ -268,9 +280,9 @@ class GraphBatch:
         eid = torch.arange(flat.shape[0]) if self.is_csr else torch.nonzero((self.edges > 0).reshape(-1)).reshape(-1)
         tgt = flat[eid].to(torch.int64)
         order = torch.argsort(tgt, stable=True)
-        ptr = torch.zeros(self.N + 1, dtype=torch.int64)
-        ptr[1:] = torch.cumsum(torch.bincount(tgt, minlength=self.N), 0)
-        self._csc = (ptr.to(torch.int32).contiguous(), eid[order].to(torch.int32).contiguous())
+        cptr = torch.zeros(self.N + 1, dtype=torch.int64)
+        cptr[1:] = torch.cumsum(torch.bincount(tgt, minlength=self.N), 0)
+        self._csc = (cptr.to(torch.int32).contiguous(), eid[order].to(torch.int32).contiguous())
 
     def live_edges(self, force=False):
         """(perm, pos, d_c, n_live) of the padded lists (include/nmrgnn_hip.h: ng_build_live_edges) — the row order of
@@ -283,20 +295,10 @@ class GraphBatch:
         if not force and (self.is_csr or self.nlist_c is self.nlist):
             return None
         if self._live is None:
-            import ctypes as C
-            from . import _lib
-            from ._lib import ptr
-            ctx = self._ctx or _lib.get_context(self.device.index)
-            ne = self.n_edges
-            perm = torch.empty(ne, dtype=torch.int32, device=self.device)
-            pos = torch.empty(ne, dtype=torch.int32, device=self.device)
-            d_c = torch.empty(ne, dtype=torch.float32, device=self.device)
-            n_live = torch.empty(1, dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-                ctx.check(ctx.lib.ng_build_live_edges(ctx.handle, st, ne, ptr(self.edges), ptr(perm), ptr(pos), ptr(d_c),
-                                                      ptr(n_live)), "ng_build_live_edges")
-            self._live = (perm, pos, d_c, n_live)
+            live = self._live_buffers()
+            with library_calls(self._ctx, self.device) as call:
+                call("ng_build_live_edges", (self.n_edges, ptr(self.edges), *map(ptr, live)))
+            self._live = live
         return self._live
 
     def csc(self):
@@ -313,36 +315,31 @@ class GraphBatch:
         holds them) contributes nothing whatever its ``dedges``, here and in ``box_grad``."""
         if self.positions is None:
             raise ValueError("positions_grad: this batch was not built from positions (frames_to_batch / frames_to_batch_cutoff)")
-        return _positions_grad(self._positions_state(), dedges)
+        return self.geometry(incoming=True).positions_grad(dedges)
 
-    def box_grad(self, dedges):
+    def box_grad(self, dedges, want_dvec=True):
         """``(strain, dvec)``, both [G, 3, 3] float64 on the device, from dL/d(edges) ``dedges`` in one library call
         (include/nmrgnn_hip.h: ng_box_grad), at fixed lists and images.  Per frame, over its live edges u (the displacement
         that built the edge), p = dL/du and n the image triple with u = r_j - r_i + n h:
         ``strain`` = sum u (x) p, the derivative with respect to a homogeneous strain of positions and box together (the
         virial is ``-strain``); ``dvec`` = sum n (x) p = dL/d(lattice vectors) [rows a, b, c] at fixed positions, zero without
-        a box.  Works on batches built from positions (frames_to_batch, frames_to_batch_cutoff, structures_to_batch)."""
+        a box; ``want_dvec=False`` skips it (``dvec`` is None).  Works on batches built from positions (frames_to_batch,
+        frames_to_batch_cutoff, structures_to_batch)."""
         if self.positions is None:
             raise ValueError("box_grad: this batch was not built from positions (frames_to_batch / frames_to_batch_cutoff / "
                              "structures_to_batch)")
-        return _box_grad(self._box_state(), dedges)
+        return self.geometry().box_grad(dedges, want_dvec)
 
-    def _box_state(self):
-        """what box_grad reads, without the batch itself (as _positions_state; no incoming-edge lists needed)"""
-        state = (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
-                 self.edges.detach(), self.row_ptr, self.box, int(self.box_triclinic), self.G, self.graph_ptr)
-        # a boxed ragged batch appends its kinds: _box_grad then calls the per-structure entry points
-        return state if self.box_kind is None else state + (self.box_kind, self.box_kind_host)
+    def _list_view(self):
+        return ListView(self.is_csr, self.N, self.K, self.nlist, self.edges.detach(), self.row_ptr, getattr(self, "row_of", None))
 
-    def _positions_state(self):
-        """what positions_grad reads, without the batch itself (an autograd node keeps this, not the batch whose edges are
-        its output: no reference cycle)"""
-        csc_ptr, csc_edge = self.csc()
-        state = (self._ctx, self.device, self.positions, float(self.scale), self.is_csr, self.N, self.K, self.nlist,
-                 self.edges.detach(), self.row_ptr, getattr(self, "row_of", None), csc_ptr, csc_edge, self.box,
-                 int(self.box_triclinic))
-        # a boxed ragged batch appends what finds a row's structure and its kind (_positions_grad)
-        return state if self.box_kind is None else state + (self.G, self.graph_ptr, self.box_kind, self.box_kind_host)
+    def geometry(self, incoming=False):
+        """what positions_grad and box_grad read as of now, without the batch itself (an autograd node keeps this, not the
+        batch whose edges are its output: no reference cycle).  ``incoming``: with the incoming-edge lists, which
+        positions_grad alone needs."""
+        csc_ptr, csc_edge = self.csc() if incoming else (None, None)
+        return Geometry(self._ctx, self.device, self.positions, float(self.scale), self.boundary, self._list_view(), self.G,
+                        self.graph_ptr, csc_ptr, csc_edge)
 
     def as_tuple(self):
         if self.is_csr:
@@ -354,7 +351,8 @@ class GraphBatch:
     keep = None          # [M] int32: parent index of every row
     hop = None           # [M] int32: list steps from the nearest selected atom (0 = selected)
     graph_index = None   # [G'] host int32: parent graph of every graph (graphs without a kept atom are dropped)
-    _prune = None        # (hops, hop [N], idx [N+1], row_ptr_p) of the parent's shape, for the expansions
+    _Cut = namedtuple("_Cut", "hops hop idx row_ptr_p")
+    _prune = None        # _Cut(hops, hop [N], idx [N+1], row_ptr_p) of the parent's shape, for the expansions
     _selected = None
 
     def restrict(self, select, hops):
@@ -376,9 +374,6 @@ class GraphBatch:
         gradients go through the parent, ``parent.positions_grad(pruned.expand_edge_grad(de))``.  Where the parent's
         ``edges`` require grad the pruned ``edges`` carry a grad_fn back to them.  Values at rows with ``hop > 0`` are NOT
         the model's values of those atoms."""
-        import ctypes as C
-        from . import _lib
-        from ._lib import ptr
         hops = int(hops)
         if not 0 <= hops <= 64:
             raise ValueError(f"restrict: hops must be in [0, 64], got {hops}")
@@ -388,27 +383,21 @@ class GraphBatch:
         N, K, dev = self.N, self.K, self.device
         if not self.is_csr and N * K >= 2 ** 31:
             raise ValueError("restrict: N * K exceeds 2^31 - 1 slots")
-        ctx = self._ctx or _lib.get_context(dev.index)
-        csr = self.is_csr
-        ne = self.n_edges
-        edges = self.edges.detach()
-        row_ptr, row_of = (self.row_ptr, self.row_of) if csr else (None, None)
-        hop = torch.empty(N, dtype=torch.int32, device=dev)
-        flag = torch.empty(N, dtype=torch.int32, device=dev)
-        idx = torch.empty(N + 1, dtype=torch.int32, device=dev)
+        csr, ne, view = self.is_csr, self.n_edges, self._list_view()
+        edges, row_ptr, row_of = view.edges, view.row_ptr, view.row_of
+        new = partial(torch.empty, dtype=torch.int32, device=dev)
+        hop, flag, idx = new(N), new(N), new(N + 1)
         gp_long = torch.as_tensor(self.graph_ptr_host.astype(np.int64), device=dev)
-        with torch.cuda.device(dev):
-            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            ctx.check(ctx.lib.ng_receptive_hops(ctx.handle, st, N, K, ne, ptr(row_ptr), ptr(row_of), ptr(self.nlist), ptr(edges),
-                                                ptr(seed), hops, ptr(hop)), "ng_receptive_hops")
-            ctx.check(ctx.lib.ng_prune_keep_flags(ctx.handle, st, N, ptr(hop), ptr(flag)), "ng_prune_keep_flags")
-            ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, N, ptr(flag), ptr(idx)), "ng_exclusive_scan_i32")
+        with library_calls(self._ctx, dev) as call:
+            call("ng_receptive_hops", (N, K, ne, ptr(row_ptr), ptr(row_of), ptr(self.nlist), ptr(edges), ptr(seed), hops,
+                                       ptr(hop)))
+            call("ng_prune_keep_flags", (N, ptr(hop), ptr(flag)))
+            call("ng_exclusive_scan_i32", (N, ptr(flag), ptr(idx)))
             sizes = [idx[gp_long]]
             if csr:
-                rp_full = torch.empty(N + 1, dtype=torch.int32, device=dev)
-                ctx.check(ctx.lib.ng_prune_degrees_csr(ctx.handle, st, N, hops, ptr(row_ptr), ptr(hop), ptr(flag)),
-                          "ng_prune_degrees_csr")
-                ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, N, ptr(flag), ptr(rp_full)), "ng_exclusive_scan_i32")
+                rp_full = new(N + 1)
+                call("ng_prune_degrees_csr", (N, hops, ptr(row_ptr), ptr(hop), ptr(flag)))
+                call("ng_exclusive_scan_i32", (N, ptr(flag), ptr(rp_full)))
                 sizes.append(rp_full[N:])
             # the one host synchronisation: kept atoms in front of every graph (the last is M) and, for CSR, the kept entries
             sizes = torch.cat(sizes).cpu().numpy().astype(np.int64)
@@ -418,39 +407,33 @@ class GraphBatch:
             counts = np.diff(before)
             graph_index = np.nonzero(counts > 0)[0].astype(np.int32)
             gp_p = np.concatenate([[0], np.cumsum(counts[graph_index])]).astype(np.int32)
-            keep = torch.empty(M, dtype=torch.int32, device=dev)
-            hop_p = torch.empty(M, dtype=torch.int32, device=dev)
-            atoms_p = torch.empty(M, self.C, dtype=torch.float32, device=dev)
-            inv_p = torch.empty(M, dtype=torch.float32, device=dev)
+            keep, hop_p = new(M), new(M)
+            atoms_p, inv_p = new(M, self.C, dtype=torch.float32), new(M, dtype=torch.float32)
             if csr:
                 nnz_p = int(sizes[self.G + 1])
-                row_ptr_p = torch.empty(M + 1, dtype=torch.int32, device=dev)
-                col_p = torch.empty(nnz_p, dtype=torch.int32, device=dev)
-                dist_p = torch.empty(nnz_p, dtype=torch.float32, device=dev)
-                row_of_p = torch.empty(nnz_p, dtype=torch.int32, device=dev)
-                ctx.check(ctx.lib.ng_prune_lists_csr(ctx.handle, st, N, ne, self.C, hops, ptr(row_ptr), ptr(row_of), ptr(self.nlist),
-                                                     ptr(edges), ptr(self.atoms), ptr(self.inv_degree), ptr(hop), ptr(idx),
-                                                     ptr(rp_full), ptr(keep), ptr(hop_p), ptr(atoms_p), ptr(inv_p), ptr(row_ptr_p),
-                                                     ptr(col_p) if nnz_p else None, ptr(dist_p) if nnz_p else None,
-                                                     ptr(row_of_p) if nnz_p else None), "ng_prune_lists_csr")
+                row_ptr_p, col_p, row_of_p = new(M + 1), new(nnz_p), new(nnz_p)
+                dist_p = new(nnz_p, dtype=torch.float32)
+                call("ng_prune_lists_csr", (N, ne, self.C, hops, ptr(row_ptr), ptr(row_of), ptr(self.nlist), ptr(edges),
+                                            ptr(self.atoms), ptr(self.inv_degree), ptr(hop), ptr(idx), ptr(rp_full), ptr(keep),
+                                            ptr(hop_p), ptr(atoms_p), ptr(inv_p), ptr(row_ptr_p), ptr(col_p) if nnz_p else None,
+                                            ptr(dist_p) if nnz_p else None, ptr(row_of_p) if nnz_p else None))
                 b = GraphBatch.from_csr(atoms_p, row_ptr_p, col_p, dist_p, inv_p, graph_ptr=gp_p, device=dev, validate=False,
                                         row_of=row_of_p)
                 b._ctx = self._ctx
             else:
                 row_ptr_p = None
-                nlist_p = torch.empty(M, K, dtype=torch.int32, device=dev)
-                edges_p = torch.empty(M, K, dtype=torch.float32, device=dev)
-                ctx.check(ctx.lib.ng_prune_lists(ctx.handle, st, N, K, self.C, self.G, hops, ptr(self.graph_ptr), ptr(self.nlist),
-                                                 ptr(edges), ptr(self.atoms), ptr(self.inv_degree), ptr(hop), ptr(idx), ptr(keep),
-                                                 ptr(hop_p), ptr(atoms_p), ptr(inv_p), ptr(nlist_p), ptr(edges_p)), "ng_prune_lists")
+                nlist_p, edges_p = new(M, K), new(M, K, dtype=torch.float32)
+                call("ng_prune_lists", (N, K, self.C, self.G, hops, ptr(self.graph_ptr), ptr(self.nlist), ptr(edges),
+                                        ptr(self.atoms), ptr(self.inv_degree), ptr(hop), ptr(idx), ptr(keep), ptr(hop_p),
+                                        ptr(atoms_p), ptr(inv_p), ptr(nlist_p), ptr(edges_p)))
                 b = GraphBatch(atoms_p, nlist_p, edges_p, inv_p, graph_ptr=gp_p, device=dev, validate=False, nlist_c=None,
                                ctx=self._ctx)
         b.parent, b.keep, b.hop, b.graph_index = self, keep, hop_p, graph_index
-        b._prune = (hops, hop, idx, row_ptr_p)
+        b._prune = self._Cut(hops, hop, idx, row_ptr_p)
         if sel_host is not None:           # indices known on the host: their rows without a data-dependent torch op
             b._selected = idx[torch.as_tensor(sel_host, device=dev)].to(torch.int64)
         if self.edges.requires_grad and torch.is_grad_enabled():
-            b.edges = _PrunedEdges.apply(self.edges, b._expand_state(), {"edges": b.edges})
+            b.edges = _PrunedEdges.apply(self.edges, b._expansion(), {"edges": b.edges})
         return b
 
     @property
@@ -460,19 +443,17 @@ class GraphBatch:
             self._selected = torch.nonzero(self.hop == 0).reshape(-1)
         return self._selected
 
-    def _expand_state(self):
+    def _expansion(self):
         """what expand_edge_grad reads, without the pruned batch itself (an autograd node keeps this)"""
         p = self.parent
-        hops, hop, idx, row_ptr_p = self._prune
-        return (p._ctx, p.device, p.N, p.K, p.n_edges, hops, p.row_ptr, getattr(p, "row_of", None), p.nlist, p.edges.detach(), hop,
-                idx, row_ptr_p, tuple(p.edges.shape), self.n_edges)
+        return _Expansion(p._ctx, p.device, p._list_view(), n_pruned=self.n_edges, **self._prune._asdict())
 
     def expand_edge_grad(self, dedges):
         """dL/d(edges) of a restricted batch in the PARENT's shape: its value where the entry was kept, +0.0 elsewhere
         (ng_prune_expand_edge_grad); the input of ``parent.positions_grad`` / ``parent.box_grad``"""
         if self.parent is None:
             raise ValueError("expand_edge_grad: not a restricted batch (GraphBatch.restrict)")
-        return _expand_edge_grad(self._expand_state(), dedges)
+        return self._expansion().edge_grad(dedges)
 
     def expand(self, values, fill=float("nan"), selected=False):
         """per-atom values of a restricted batch in the PARENT's shape [N], ``fill`` on the other atoms
@@ -480,22 +461,38 @@ class GraphBatch:
         selected atom (the order of ``self.selected``), and every atom that is not selected gets ``fill``."""
         if self.parent is None:
             raise ValueError("expand: not a restricted batch (GraphBatch.restrict)")
-        import ctypes as C
-        from . import _lib
-        from ._lib import ptr
         p = self.parent
         v = torch.as_tensor(values).detach().to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
         keep = self.keep[self.selected].contiguous() if selected else self.keep
         if v.shape[0] != keep.shape[0]:
             raise ValueError(f"expand: values has {v.shape[0]} entries for {keep.shape[0]} "
                              f"{'selected atoms' if selected else 'rows'}")
-        ctx = p._ctx or _lib.get_context(self.device.index)
         out = torch.empty(p.N, dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            ctx.check(ctx.lib.ng_prune_expand_rows(ctx.handle, st, p.N, v.shape[0], ptr(keep), ptr(v), float(fill), ptr(out)),
-                      "ng_prune_expand_rows")
+        with library_calls(p._ctx, self.device) as call:
+            call("ng_prune_expand_rows", (p.N, v.shape[0], ptr(keep), ptr(v), float(fill), ptr(out)))
         return out
+
+
+@dataclass(frozen=True, eq=False)
+class _Expansion:
+    """what leads from a restricted batch back to its parent: the parent's lists, and ``hops``, ``hop`` [N], ``idx`` [N+1]
+    and the pruned ``row_ptr`` (CSR) of the cut; ``n_pruned`` entries in the pruned lists"""
+    ctx: object
+    device: torch.device
+    lists: ListView
+    hops: int
+    hop: torch.Tensor
+    idx: torch.Tensor
+    row_ptr_p: torch.Tensor
+    n_pruned: int
+
+    def edge_grad(self, dedges):
+        v, dd = self.lists, edge_grad_input(dedges, self.device, self.n_pruned, "expand_edge_grad")
+        de = torch.empty(v.edges.shape, dtype=torch.float32, device=self.device)
+        with library_calls(self.ctx, self.device) as call:
+            call("ng_prune_expand_edge_grad", (v.N, v.K, v.edges.numel(), self.hops, ptr(v.row_ptr), ptr(v.row_of), ptr(v.nlist),
+                                               ptr(v.edges), ptr(self.hop), ptr(self.idx), ptr(self.row_ptr_p), ptr(dd), ptr(de)))
+        return de
 
 
 def concat_graphs(graphs, device=None):
@@ -553,7 +550,6 @@ class BatchPrefetcher:
     def _build(self, item):
         if self.device.type != "cuda":
             return self._construct(item, None), None
-        from . import _lib
         if self._stream is None:
             self._stream = torch.cuda.Stream(device=self.device)
             self._ctx = _lib.Context(self.device.index)
@@ -602,87 +598,6 @@ class BatchPrefetcher:
             yield self._hand_over(*cur)
 
 
-def _positions_grad(state, dedges):
-    import ctypes as C
-    from . import _lib
-    from ._lib import ptr
-    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, row_of, csc_ptr, csc_edge, box, tric = state[:15]
-    ragged = state[15:]                  # (G, graph_ptr, kind, kind_host) of a boxed ragged batch
-    ctx = ctx or _lib.get_context(device.index)
-    dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
-    if dd.numel() != edges.numel():
-        raise ValueError(f"positions_grad: dedges has {dd.numel()} entries for {edges.numel()} edges")
-    dpos = torch.empty_like(pos)
-    with torch.cuda.device(device):
-        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        if ragged:                      # every structure by its own boundary kind (csrc/pbc.cuh: DispPer)
-            G, graph_ptr, kind, kind_host = ragged
-            kh = C.c_void_p(kind_host.ctypes.data)
-            if is_csr:
-                ctx.check(ctx.lib.ng_positions_grad_csr_ragged_pbc(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr),
-                                                                   ptr(nlist), ptr(row_of), ptr(dd), scale, ptr(csc_ptr),
-                                                                   ptr(csc_edge), G, ptr(graph_ptr), ptr(box), ptr(kind), kh,
-                                                                   ptr(dpos)), "ng_positions_grad_csr_ragged_pbc")
-            else:
-                ctx.check(ctx.lib.ng_positions_grad_ragged_pbc(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd),
-                                                               scale, ptr(csc_ptr), ptr(csc_edge), G, ptr(graph_ptr), ptr(box),
-                                                               ptr(kind), kh, ptr(dpos)), "ng_positions_grad_ragged_pbc")
-        elif box is not None:           # minimum-image vectors along the edges (csrc/pbc.cuh)
-            n = pos.shape[-2]
-            if is_csr:
-                ctx.check(ctx.lib.ng_positions_grad_csr_pbc(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist),
-                                                            ptr(row_of), ptr(dd), scale, ptr(csc_ptr), ptr(csc_edge), n,
-                                                            ptr(box), tric, ptr(dpos)), "ng_positions_grad_csr_pbc")
-            else:
-                ctx.check(ctx.lib.ng_positions_grad_pbc(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale,
-                                                        ptr(csc_ptr), ptr(csc_edge), n, ptr(box), tric, ptr(dpos)),
-                          "ng_positions_grad_pbc")
-        elif is_csr:
-            ctx.check(ctx.lib.ng_positions_grad_csr(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist),
-                                                    ptr(row_of), ptr(dd), scale, ptr(csc_ptr), ptr(csc_edge), ptr(dpos)),
-                      "ng_positions_grad_csr")
-        else:
-            ctx.check(ctx.lib.ng_positions_grad(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale,
-                                                ptr(csc_ptr), ptr(csc_edge), ptr(dpos)), "ng_positions_grad")
-    return dpos
-
-
-def _box_grad(state, dedges, want_dvec=True):
-    import ctypes as C
-    from . import _lib
-    from ._lib import ptr
-    ctx, device, pos, scale, is_csr, N, K, nlist, edges, row_ptr, box, tric, G, graph_ptr = state[:14]
-    ragged = state[14:]                  # (kind, kind_host) of a boxed ragged batch
-    ctx = ctx or _lib.get_context(device.index)
-    dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
-    if dd.numel() != edges.numel():
-        raise ValueError(f"box_grad: dedges has {dd.numel()} entries for {edges.numel()} edges")
-    strain = torch.empty(G, 3, 3, dtype=torch.float64, device=device)
-    dvec = torch.empty(G, 3, 3, dtype=torch.float64, device=device) if want_dvec else None
-    tric = tric if box is not None else -1          # -1: open boundaries, dvec = 0
-    with torch.cuda.device(device):
-        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        if ragged:
-            kind, kind_host = ragged
-            kh = C.c_void_p(kind_host.ctypes.data)
-            if is_csr:
-                ctx.check(ctx.lib.ng_box_grad_csr_ragged(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist),
-                                                         ptr(dd), scale, G, ptr(graph_ptr), ptr(box), ptr(kind), kh,
-                                                         ptr(strain), ptr(dvec)), "ng_box_grad_csr_ragged")
-            else:
-                ctx.check(ctx.lib.ng_box_grad_ragged(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale, G,
-                                                     ptr(graph_ptr), ptr(box), ptr(kind), kh, ptr(strain), ptr(dvec)),
-                          "ng_box_grad_ragged")
-        elif is_csr:
-            ctx.check(ctx.lib.ng_box_grad_csr(ctx.handle, st, N, edges.numel(), ptr(pos), ptr(row_ptr), ptr(nlist), ptr(dd),
-                                              scale, G, ptr(graph_ptr), ptr(box), tric, ptr(strain), ptr(dvec)),
-                      "ng_box_grad_csr")
-        else:
-            ctx.check(ctx.lib.ng_box_grad(ctx.handle, st, N, K, ptr(pos), ptr(nlist), ptr(edges), ptr(dd), scale, G,
-                                          ptr(graph_ptr), ptr(box), tric, ptr(strain), ptr(dvec)), "ng_box_grad")
-    return strain, dvec
-
-
 def selection_mask(select, N, device):
     """The int32 0/1 mask [N] on ``device`` of a selection as ``GraphBatch.restrict`` reads it (validated the same way):
     for callers that repeat or combine selections before restricting, e.g. one selection in every replica."""
@@ -725,42 +640,23 @@ def _select_seed(select, N, device):
     return torch.from_numpy(seed).to(device), idx.astype(np.int64)
 
 
-def _expand_edge_grad(state, dedges):
-    import ctypes as C
-    from . import _lib
-    from ._lib import ptr
-    ctx, device, N, K, ne, hops, row_ptr, row_of, nlist, edges, hop, idx, row_ptr_p, shape, ne_p = state
-    ctx = ctx or _lib.get_context(device.index)
-    dd = dedges.detach().to(device=device, dtype=torch.float32).contiguous()
-    if dd.numel() != ne_p:
-        raise ValueError(f"expand_edge_grad: dedges has {dd.numel()} entries for {ne_p} edges")
-    de = torch.empty(shape, dtype=torch.float32, device=device)
-    with torch.cuda.device(device):
-        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        ctx.check(ctx.lib.ng_prune_expand_edge_grad(ctx.handle, st, N, K, ne, hops, ptr(row_ptr), ptr(row_of), ptr(nlist),
-                                                    ptr(edges), ptr(hop), ptr(idx), ptr(row_ptr_p), ptr(dd), ptr(de)),
-                  "ng_prune_expand_edge_grad")
-    return de
-
-
 class _PrunedEdges(torch.autograd.Function):
     """the edges of a restricted batch as a function of the parent's (the pruned batch's own tensor, not a copy); the
     backward is ng_prune_expand_edge_grad"""
 
     @staticmethod
-    def forward(ctx, parent_edges, state, holder):
-        ctx.state = state
+    def forward(ctx, parent_edges, expansion, holder):
+        ctx.expansion = expansion
         return holder.pop("edges")
 
     @staticmethod
     def backward(ctx, dedges):
-        return _expand_edge_grad(ctx.state, dedges), None, None
+        return ctx.expansion.edge_grad(dedges), None, None
 
 
 def _box_dims_grad(dims, dvec):
     """d(loss)/d(a, b, c, alpha, beta, gamma) from dvec = d(loss)/d(lattice vectors) [G, 3, 3]: the chain rule through the
     float64 restatement of the conversion (pbc.triclinic_vectors_torch); a shared [6] box sums over the frames"""
-    from .pbc import triclinic_vectors_torch
     with torch.enable_grad():
         d = dims.detach().to(dtype=torch.float64).requires_grad_(True)
         h = triclinic_vectors_torch(d.expand(dvec.shape[0], 6) if d.dim() == 1 else d)
@@ -774,11 +670,10 @@ class _EdgesOfPositions(torch.autograd.Function):
     chained through the box conversion"""
 
     @staticmethod
-    def forward(ctx, frames, box, build):
+    def forward(ctx, frames, box, build, holder):
         # a copy of the positions: an in-place update of ``frames`` before the backward must not move the lists' atoms
-        batch = build(frames.detach().clone() if isinstance(frames, torch.Tensor) else frames)
-        ctx.state = batch._positions_state() if ctx.needs_input_grad[0] else None
-        ctx.box_state = batch._box_state() if ctx.needs_input_grad[1] else None
+        batch = holder["batch"] = build(frames.detach().clone() if isinstance(frames, torch.Tensor) else frames)
+        ctx.geometry = batch.geometry(incoming=ctx.needs_input_grad[0])
         ctx.box_dims = box.detach().clone() if ctx.needs_input_grad[1] else None
         if ctx.needs_input_grad[0]:
             ctx.frames_shape, ctx.frames_device = frames.shape, frames.device
@@ -788,10 +683,10 @@ class _EdgesOfPositions(torch.autograd.Function):
     def backward(ctx, dedges):
         dpos = dbox = None
         if ctx.needs_input_grad[0]:
-            dpos = _positions_grad(ctx.state, dedges).reshape(ctx.frames_shape).to(ctx.frames_device)
+            dpos = ctx.geometry.positions_grad(dedges).reshape(ctx.frames_shape).to(ctx.frames_device)
         if ctx.needs_input_grad[1]:
-            dbox = _box_dims_grad(ctx.box_dims, _box_grad(ctx.box_state, dedges)[1])
-        return dpos, dbox, None
+            dbox = _box_dims_grad(ctx.box_dims, ctx.geometry.box_grad(dedges)[1])
+        return dpos, dbox, None, None
 
 
 def _positions_batch(frames, build, box=None):
@@ -801,19 +696,41 @@ def _positions_batch(frames, build, box=None):
     if not ((isinstance(frames, torch.Tensor) and frames.requires_grad or box_grad) and torch.is_grad_enabled()):
         return build(frames)
     holder = {}
-
-    def make(f):
-        holder["batch"] = build(f)
-        return holder["batch"]
-    edges = _EdgesOfPositions.apply(frames, box if box_grad else None, make)
+    edges = _EdgesOfPositions.apply(frames, box if box_grad else None, build, holder)
     batch = holder.pop("batch")
     batch.edges = edges         # the same storage the kernels read, now with a grad_fn
     return batch
 
 
-def _frame_count(frames):
-    shape = tuple(frames.shape) if hasattr(frames, "shape") else np.shape(frames)
-    return 1 if len(shape) == 2 else int(shape[0])
+def batch_from_positions(atoms, pos, layout, scale, boundary, K=None, cutoff=None, out=None):
+    """The one list-build path: the batch of device ``atoms`` [N, C] and device positions ``pos`` under ``layout`` and
+    ``boundary``, with its geometry attached.  ``cutoff`` None: padded kNN lists with ``K`` neighbours, one library call
+    and no host synchronisation; ``out``: (nlist [N, K], edges [N, K], inv_degree [N]) allocated by the caller (a captured
+    chain writes into static buffers).  Else the CSR lists of the cutoff: count, scan, size the buffers, fill."""
+    N, dev = layout.N, pos.device
+    new = partial(torch.empty, dtype=torch.int32, device=dev)
+    with library_calls(None, dev) as call:
+        if cutoff is None:
+            nlist, edges, inv = out or (new(N, K), new(N, K, dtype=torch.float32), new(N, dtype=torch.float32))
+            call(*knn_call(layout, boundary, K, scale, pos, nlist, edges, inv))
+            # every graph larger than K: every atom has K real neighbours, no padded slot -> the compute-side list IS the list
+            b = GraphBatch(atoms, nlist, edges, inv, graph_ptr=layout.graph_ptr_host, device=dev, validate=False,
+                           nlist_c=nlist if layout.min_n > K else None)
+        else:
+            deg, row_ptr = new(N), new(N + 1)
+            call(*cutoff_count_call(layout, boundary, cutoff, pos, deg))
+            call("ng_exclusive_scan_i32", (N, ptr(deg), ptr(row_ptr)))
+            # the one host synchronisation: the list length sizes the buffers.  Summed in int64 — the device scan is int32
+            # and a total of 2^32 or more would wrap back to a plausible positive number
+            nnz = int(deg.sum(dtype=torch.int64))
+            if nnz >= 2 ** 31:
+                raise ValueError("cutoff graph: more than 2^31 edges in one batch")
+            col, dist, row_of, inv = new(nnz), new(nnz, dtype=torch.float32), new(nnz), new(N, dtype=torch.float32)
+            call(*cutoff_fill_call(layout, boundary, cutoff, scale, pos, row_ptr, col, dist, inv, row_of))
+            b = GraphBatch.from_csr(atoms, row_ptr, col, dist, inv, graph_ptr=layout.graph_ptr_host, device=dev,
+                                    validate=False, row_of=row_of)
+    b.set_geometry(pos, scale, boundary)
+    return b
 
 
 def _host_box(box, frames):
@@ -821,14 +738,10 @@ def _host_box(box, frames):
     ``box`` gives what its detached host copy gives."""
     if box is None:
         return None
-    from .pbc import prepare
     if isinstance(box, torch.Tensor):
         box = box.detach().cpu().numpy()
-    return prepare(box, _frame_count(frames))
-
-
-def _device_box(pbc, device):
-    return torch.from_numpy(pbc[0]).to(device) if pbc is not None else None
+    shape = tuple(frames.shape) if hasattr(frames, "shape") else np.shape(frames)
+    return prepare(box, 1 if len(shape) == 2 else int(shape[0]))
 
 
 def frames_to_batch(atoms, frames, neighbor_number=16, scale=0.1, device=None, box=None):
@@ -847,43 +760,22 @@ def frames_to_batch(atoms, frames, neighbor_number=16, scale=0.1, device=None, b
     box conversion (nmrgnn_amd.pbc.triclinic_vectors_torch), at fixed lists and images, summed over the frames of a
     shared [6] box; the lists are those of ``box.detach().cpu().numpy()``."""
     pbc = _host_box(box, frames)
-    return _positions_batch(frames, lambda f: _frames_to_batch(atoms, f, neighbor_number, scale, device, pbc), box)
+    return _positions_batch(frames, lambda f: _frames_batch(atoms, f, scale, device, pbc, K=int(neighbor_number)), box)
 
 
-def _frames_to_batch(atoms, frames, neighbor_number, scale, device, pbc=None):
-    import ctypes as C
-    from . import _lib
-    from ._lib import ptr
+def _frames_batch(atoms, frames, scale, device, pbc, K=None, cutoff=None):
+    """the positions and atoms of G frames on the device, then the one list-build path"""
     device = _norm_device(device)
     pos = _to_dev(np.asarray(frames, dtype=np.float32) if not isinstance(frames, torch.Tensor) else frames,
                   torch.float32, device)
     if pos.dim() == 2:
         pos = pos[None]
     G, n, _ = pos.shape
-    K = int(neighbor_number)
     at = _to_dev(atoms, torch.float32, device)
     if at.shape[0] != n:
         raise ValueError(f"atoms has {at.shape[0]} rows but frames have {n} atoms")
-    nlist = torch.empty(G * n, K, dtype=torch.int32, device=device)
-    edges = torch.empty(G * n, K, dtype=torch.float32, device=device)
-    inv = torch.empty(G * n, dtype=torch.float32, device=device)
-    ctx = _lib.get_context(device.index)
-    st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-    box = _device_box(pbc, device)
-    if box is None:
-        ctx.check(ctx.lib.ng_knn_graph(ctx.handle, st, G, n, K, float(scale), ptr(pos), ptr(nlist), ptr(edges),
-                                       ptr(inv)), "ng_knn_graph")
-    else:
-        ctx.check(ctx.lib.ng_knn_graph_pbc(ctx.handle, st, G, n, K, float(scale), ptr(pos), ptr(box), int(pbc[1]),
-                                           ptr(nlist), ptr(edges), ptr(inv)), "ng_knn_graph_pbc")
-    ptrs = np.arange(G + 1, dtype=np.int64) * n
-    # n > K: every atom has K real neighbours, no padded slot -> the compute-side list IS the list
-    b = GraphBatch(at.repeat(G, 1) if G > 1 else at, nlist, edges, inv, graph_ptr=ptrs, device=device, validate=False,
-                   nlist_c=nlist if n > K else None)
-    b.positions, b.scale = pos, float(scale)
-    if box is not None:
-        b.box, b.box_triclinic = box, bool(pbc[1])
-    return b
+    return batch_from_positions(at.repeat(G, 1) if G > 1 else at, pos, Layout.frames(G, n), scale,
+                                Boundary.from_host(pbc, device), K, cutoff)
 
 
 def frames_to_batch_cutoff(atoms, frames, cutoff=4.0, scale=0.1, device=None, box=None):
@@ -896,57 +788,7 @@ def frames_to_batch_cutoff(atoms, frames, cutoff=4.0, scale=0.1, device=None, bo
     pbc = _host_box(box, frames)
     if pbc is not None and len(pbc[2]) and not float(cutoff) < 0.5 * float(pbc[2].min()):
         raise ValueError(f"cutoff {cutoff} must be below half the smallest box width ({0.5 * float(pbc[2].min()):.6g})")
-    return _positions_batch(frames, lambda f: _frames_to_batch_cutoff(atoms, f, cutoff, scale, device, pbc), box)
-
-
-def _frames_to_batch_cutoff(atoms, frames, cutoff, scale, device, pbc=None):
-    import ctypes as C
-    from . import _lib
-    from ._lib import ptr
-    device = _norm_device(device)
-    pos = _to_dev(np.asarray(frames, dtype=np.float32) if not isinstance(frames, torch.Tensor) else frames,
-                  torch.float32, device)
-    if pos.dim() == 2:
-        pos = pos[None]
-    G, n, _ = pos.shape
-    at = _to_dev(atoms, torch.float32, device)
-    if at.shape[0] != n:
-        raise ValueError(f"atoms has {at.shape[0]} rows but frames have {n} atoms")
-    ctx = _lib.get_context(device.index)
-    with torch.cuda.device(device):
-        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        deg = torch.empty(G * n, dtype=torch.int32, device=device)
-        box = _device_box(pbc, device)
-        if box is None:
-            ctx.check(ctx.lib.ng_cutoff_count(ctx.handle, st, G, n, float(cutoff), ptr(pos), ptr(deg)), "ng_cutoff_count")
-        else:
-            ctx.check(ctx.lib.ng_cutoff_count_pbc(ctx.handle, st, G, n, float(cutoff), ptr(pos), ptr(box), int(pbc[1]),
-                                                  ptr(deg)), "ng_cutoff_count_pbc")
-        row_ptr = torch.empty(G * n + 1, dtype=torch.int32, device=device)
-        ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, G * n, ptr(deg), ptr(row_ptr)), "ng_exclusive_scan_i32")
-        # the one host synchronisation: the list length sizes the buffers.  Summed in int64 — the device scan is int32
-        # and a total of 2^32 or more would wrap back to a plausible positive number
-        nnz = int(deg.sum(dtype=torch.int64))
-        if nnz >= 2 ** 31:
-            raise ValueError("cutoff graph: more than 2^31 edges in one batch")
-        col = torch.empty(nnz, dtype=torch.int32, device=device)
-        dist = torch.empty(nnz, dtype=torch.float32, device=device)
-        row_of = torch.empty(nnz, dtype=torch.int32, device=device)
-        inv = torch.empty(G * n, dtype=torch.float32, device=device)
-        if box is None:
-            ctx.check(ctx.lib.ng_cutoff_fill_rows(ctx.handle, st, G, n, float(cutoff), float(scale), ptr(pos), ptr(row_ptr),
-                                                  ptr(col), ptr(dist), ptr(inv), ptr(row_of)), "ng_cutoff_fill_rows")
-        else:
-            ctx.check(ctx.lib.ng_cutoff_fill_rows_pbc(ctx.handle, st, G, n, float(cutoff), float(scale), ptr(pos), ptr(box),
-                                                      int(pbc[1]), ptr(row_ptr), ptr(col), ptr(dist), ptr(inv), ptr(row_of)),
-                      "ng_cutoff_fill_rows_pbc")
-    ptrs = np.arange(G + 1, dtype=np.int64) * n
-    b = GraphBatch.from_csr(at.repeat(G, 1) if G > 1 else at, row_ptr, col, dist, inv, graph_ptr=ptrs, device=device,
-                            validate=False, row_of=row_of)
-    b.positions, b.scale = pos, float(scale)
-    if box is not None:
-        b.box, b.box_triclinic = box, bool(pbc[1])
-    return b
+    return _positions_batch(frames, lambda f: _frames_batch(atoms, f, scale, device, pbc, cutoff=cutoff), box)
 
 
 def _cat_rows(parts, device):
@@ -1022,7 +864,6 @@ def _host_boxes(boxes, G, cutoff):
     """None (every structure open), or pbc.prepare_ragged's (vectors, kinds, widths) for G structures, validated on the host"""
     if boxes is None:
         return None
-    from .pbc import prepare_ragged
     pr = prepare_ragged(boxes, G)
     if not (pr[1] >= 0).any():
         return None
@@ -1077,70 +918,14 @@ def structures_to_batch(atoms, positions, neighbor_number=16, cutoff=None, scale
         pr = _host_boxes(boxes, len(gp) - 1, cutoff)
     if cutoff is None and int(gp[-1]) * K >= 2 ** 31:
         raise ValueError("structures_to_batch: N * neighbor_number exceeds 2^31 - 1 slots")
-    return _positions_batch(pos, lambda f: _structures_to_batch(atoms, f, gp, K, cutoff, scale, device, pr),
+    return _positions_batch(pos, lambda f: _structures_batch(atoms, f, gp, K, cutoff, scale, device, pr),
                             boxes if pr is not None and isinstance(boxes, torch.Tensor) else None)
 
 
-def _structures_to_batch(atoms, positions, gp, K, cutoff, scale, device, pr=None):
-    import ctypes as C
-    from . import _lib
-    from ._lib import ptr
+def _structures_batch(atoms, positions, gp, K, cutoff, scale, device, pr=None):
+    """the concatenated positions and atoms and the partition on the device, then the one list-build path"""
     pos = _to_dev(positions, torch.float32, device).reshape(-1, 3)
     at = _to_dev(atoms, torch.float32, device)
-    N, G = int(gp[-1]), len(gp) - 1
-    max_n = int(np.max(np.diff(gp)))
     gp_host = gp.astype(np.int32)
-    gp_dev = _graph_ptr_dev(gp_host, device)
-    ctx = _lib.get_context(device.index)
-    if pr is not None:          # boxes [G, 9] and kinds [G] on the device, the kinds on the host as well
-        box, kind_host = torch.from_numpy(pr[0]).to(device), np.ascontiguousarray(pr[1], dtype=np.int32)
-        kind, kh = torch.from_numpy(kind_host).to(device), C.c_void_p(kind_host.ctypes.data)
-    with torch.cuda.device(device):
-        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        if cutoff is None:
-            nlist = torch.empty(N, K, dtype=torch.int32, device=device)
-            edges = torch.empty(N, K, dtype=torch.float32, device=device)
-            inv = torch.empty(N, dtype=torch.float32, device=device)
-            if pr is None:
-                ctx.check(ctx.lib.ng_knn_graph_ragged(ctx.handle, st, G, N, K, float(scale), ptr(pos), ptr(gp_dev),
-                                                      C.c_void_p(gp_host.ctypes.data), max_n, ptr(nlist), ptr(edges),
-                                                      ptr(inv)), "ng_knn_graph_ragged")
-            else:
-                ctx.check(ctx.lib.ng_knn_graph_ragged_pbc(ctx.handle, st, G, N, K, float(scale), ptr(pos), ptr(gp_dev),
-                                                          C.c_void_p(gp_host.ctypes.data), max_n, ptr(box), ptr(kind), kh,
-                                                          ptr(nlist), ptr(edges), ptr(inv)), "ng_knn_graph_ragged_pbc")
-            # every structure larger than K: no padded slot, the compute-side list IS the list (as _frames_to_batch)
-            b = GraphBatch(at, nlist, edges, inv, graph_ptr=gp_host, device=device, validate=False,
-                           nlist_c=nlist if int(np.min(np.diff(gp))) > K else None)
-        else:
-            deg = torch.empty(N, dtype=torch.int32, device=device)
-            if pr is None:
-                ctx.check(ctx.lib.ng_cutoff_count_ragged(ctx.handle, st, G, N, float(cutoff), ptr(pos), ptr(gp_dev), max_n,
-                                                         ptr(deg)), "ng_cutoff_count_ragged")
-            else:
-                ctx.check(ctx.lib.ng_cutoff_count_ragged_pbc(ctx.handle, st, G, N, float(cutoff), ptr(pos), ptr(gp_dev), max_n,
-                                                             ptr(box), ptr(kind), kh, ptr(deg)), "ng_cutoff_count_ragged_pbc")
-            row_ptr = torch.empty(N + 1, dtype=torch.int32, device=device)
-            ctx.check(ctx.lib.ng_exclusive_scan_i32(ctx.handle, st, N, ptr(deg), ptr(row_ptr)), "ng_exclusive_scan_i32")
-            nnz = int(deg.sum(dtype=torch.int64))      # the one host synchronisation, as in _frames_to_batch_cutoff
-            if nnz >= 2 ** 31:
-                raise ValueError("cutoff graph: more than 2^31 edges in one batch")
-            col = torch.empty(nnz, dtype=torch.int32, device=device)
-            dist = torch.empty(nnz, dtype=torch.float32, device=device)
-            row_of = torch.empty(nnz, dtype=torch.int32, device=device)
-            inv = torch.empty(N, dtype=torch.float32, device=device)
-            if pr is None:
-                ctx.check(ctx.lib.ng_cutoff_fill_rows_ragged(ctx.handle, st, G, N, float(cutoff), float(scale), ptr(pos),
-                                                             ptr(gp_dev), max_n, ptr(row_ptr), ptr(col), ptr(dist), ptr(inv),
-                                                             ptr(row_of)), "ng_cutoff_fill_rows_ragged")
-            else:
-                ctx.check(ctx.lib.ng_cutoff_fill_rows_ragged_pbc(ctx.handle, st, G, N, float(cutoff), float(scale), ptr(pos),
-                                                                 ptr(gp_dev), max_n, ptr(box), ptr(kind), kh, ptr(row_ptr),
-                                                                 ptr(col), ptr(dist), ptr(inv), ptr(row_of)),
-                          "ng_cutoff_fill_rows_ragged_pbc")
-            b = GraphBatch.from_csr(at, row_ptr, col, dist, inv, graph_ptr=gp_host, device=device, validate=False,
-                                    row_of=row_of)
-    b.positions, b.scale = pos, float(scale)
-    if pr is not None:
-        b.box, b.box_kind, b.box_kind_host = box, kind, kind_host
-    return b
+    return batch_from_positions(at, pos, Layout.ragged(gp_host, _graph_ptr_dev(gp_host, device)), scale,
+                                Boundary.from_host(pr, device), K, cutoff)

@@ -188,8 +188,7 @@ def shift_restraint(model, atoms, positions, targets, weights=None, neighbor_num
         dedges = run.expand_edge_grad(dedges)
     forces = -batch.positions_grad(dedges)[0]
     if virial:
-        from .graph import _box_grad
-        return energy, forces, -_box_grad(batch._box_state(), dedges, want_dvec=False)[0][0]
+        return energy, forces, -batch.box_grad(dedges, want_dvec=False)[0][0]
     return energy, forces
 
 
@@ -390,6 +389,7 @@ class ShiftRestraint:
     def __init__(self, model, atoms, targets, weights=None, replicas=1, neighbor_number=16, box=None, virial=False,
                  replay=True, tolerance=None, replica_weights=None, independent=False, tau=None):
         import torch
+        from .geometry import OPEN_BOUNDARY, UNIFORM, Boundary, Layout
         R = int(replicas)
         if R < 1 or R != replicas:
             raise ValueError(f"ShiftRestraint: replicas must be a positive integer, got {replicas!r}")
@@ -417,10 +417,7 @@ class ShiftRestraint:
         self.tau, self._lam = tau, lam
         # the forms go through ng_restraint_loss_ex; with none of them set the chain keeps ng_restraint_loss, launch for launch
         self._ex = tol is not None or c is not None or self.independent or tau is not None
-        self._tric = None
-        vecs = None
-        if box is not None:
-            vecs, self._tric = _restraint_box(box, R)
+        vecs, self._tric = (None, None) if box is None else _restraint_box(box, R)
         # ---- device side
         if model.engine is None:
             model.build(int(a_shape[1]))
@@ -434,10 +431,11 @@ class ShiftRestraint:
         self.s_w = torch.from_numpy(w).to(dev)
         self.s_pos = torch.zeros(R, n, 3, dtype=torch.float32, device=dev)
         self.s_box = None if vecs is None else torch.from_numpy(vecs).to(dev)
+        self._boundary = OPEN_BOUNDARY if vecs is None else Boundary(UNIFORM, self.s_box, bool(self._tric))
+        self._layout = Layout.frames(R, n)
         self._nlist = torch.empty(R * n, K, dtype=torch.int32, device=dev)
         self._edges = torch.empty(R * n, K, dtype=torch.float32, device=dev)
         self._inv = torch.empty(R * n, dtype=torch.float32, device=dev)
-        self._graph_ptr = np.arange(R + 1, dtype=np.int64) * n
         G = R if self.independent else 1
         self._e64 = torch.zeros(G, dtype=torch.float64, device=dev)
         self.energies = self._e64
@@ -466,23 +464,15 @@ class ShiftRestraint:
         import ctypes as C
         import torch
         from ._lib import ptr
-        from .graph import GraphBatch, _box_grad
+        from .graph import batch_from_positions
         eng = self.eng
         lib, h = eng.lib, eng.ctx.handle
         st = C.c_void_p(torch.cuda.current_stream(eng.device).cuda_stream)
-        R, n, K = self.R, self.n, self.K
-        if self.s_box is None:
-            eng._ck(lib.ng_knn_graph(h, st, R, n, K, 0.1, ptr(self.s_pos), ptr(self._nlist), ptr(self._edges), ptr(self._inv)),
-                    "ng_knn_graph")
-        else:
-            eng._ck(lib.ng_knn_graph_pbc(h, st, R, n, K, 0.1, ptr(self.s_pos), ptr(self.s_box), int(self._tric), ptr(self._nlist),
-                                         ptr(self._edges), ptr(self._inv)), "ng_knn_graph_pbc")
-        b = GraphBatch(self.s_atoms, self._nlist, self._edges, self._inv, graph_ptr=self._graph_ptr, device=eng.device,
-                       validate=False, nlist_c=self._nlist if n > K else None)
-        b.positions, b.scale = self.s_pos, 0.1
-        if self.s_box is not None:
-            b.box, b.box_triclinic = self.s_box, bool(self._tric)
-        self._batch = b         # the captured chain reads buffers the batch owns
+        R, n = self.R, self.n
+        # the builders' own path on the static buffers, no allocation, copy or host read of its own; the captured chain reads
+        # buffers the batch owns
+        self._batch = b = batch_from_positions(self.s_atoms, self.s_pos, self._layout, 0.1, self._boundary, self.K,
+                                               out=(self._nlist, self._edges, self._inv))
         keep = eng.edge_table
         if self._no_table:
             eng.edge_table = False
@@ -503,7 +493,7 @@ class ShiftRestraint:
         eng.backward(dpeaks, edge_grad=dedges, param_grad=False)
         torch.neg(b.positions_grad(dedges), out=self.forces)
         if self.virial:
-            torch.neg(_box_grad(b._box_state(), dedges, want_dvec=False)[0], out=self.virial_out)
+            torch.neg(b.box_grad(dedges, want_dvec=False)[0], out=self.virial_out)
 
     def _capture(self):
         import torch
