@@ -748,6 +748,26 @@ int ng_loss_name(ng_ctx*, void* stream, int64_t N, int G, const int32_t* graph_p
 int ng_name_metrics(ng_ctx*, void* stream, int64_t N, const float* y, const float* w, const int32_t* names, const float* pred,
                     int n_names, const uint32_t* member, int K, int accumulate, double* moments);
 
+/* Dense per-class moments for an evaluation report (nmrgnn/main.py:93-189, eval-tfrecords; csrc/class_moments.hip): the seven
+ * sums of ng_name_metrics, in its order, for 1 <= K <= 1024 classes and 1 <= M <= 4 groupings of the name ids in one pass over
+ * the atoms.  class_of [M][n_ids] int32 on the device: class_of[m][id] is the class of name id `id` under grouping m, a ROW
+ * index in [0, K) or -1 for "in no class"; the caller lays the groupings out in one row space (name classes in rows [0, Kn),
+ * element classes in [Kn, Kn + Ke), ...).  A value outside [-1, K) counts as -1 and is never used as an index.
+ *   An atom i counts iff w[i] > 0 (false for 0, -0.0, negative values and NaN) and 0 <= names[i] < n_ids; it then counts with
+ *   weight 1, not w[i] (the reference selects rows by `wi > 0` and is unweighted afterwards).  For every grouping m with
+ *   c = class_of[m][names[i]] in [0, K) it adds to
+ *   moments[c][7] = {S0 = count, Sd2 = sum (y - p)^2, Sy, Sp, Syy, Spp, Syp},  float64, y and p converted before any product
+ *   (an id that two groupings map to the same row adds twice).
+ * accumulate = 0: moments are overwritten; 1: the sums are added to them.  N = 0 writes zeros / adds nothing.  Two launches on
+ * `stream` (per-workgroup partials in the context's scratch, min(ceil(N / 256), 512) workgroups whatever the device, then a
+ * fixed-order sum): asynchronous, never reads the device on the host, no atomics; the same call on the same inputs writes the
+ * same bits.  Capturable once the scratch holds min(ceil(N / 256), 512) * K * 7 doubles.
+ * Refused (NG_ERR_INVALID, before any launch): NULL context; moments NULL; with N > 0 a NULL y, w, names or pred; class_of NULL
+ * with n_ids > 0; M outside [1, 4]; K outside [1, 1024]; n_ids outside [0, 2^24]; N < 0 or N >= 2^31 - 256; accumulate other
+ * than 0 or 1. */
+int ng_class_moments(ng_ctx*, void* stream, int64_t N, const float* y, const float* w, const int32_t* names, const float* pred,
+                     int n_ids, int M, const int32_t* class_of, int K, int accumulate, double* moments);
+
 /* Mini-batch collation from a device-resident record store (nmrgnn_amd/dataset.py: ShiftDataset.batch; csrc/collate.hip).
  * The store holds R records back to back, record r in the rows [rec_ptr[r], rec_ptr[r+1]) of
  *   s_atoms [Ntot,C] f32, s_nlist [Ntot,K] i32 (record-LOCAL indices), s_edges [Ntot,K] f32, s_inv_degree [Ntot] f32,

@@ -9,8 +9,10 @@ are built on the GPU (ng_knn_graph); the reference evaluates frame by frame with
 ``train RECORDS... NAME [EPOCHS]`` is the reference's training command on ``dataset.ShiftDataset`` files (``.npz``, written by
 ``ShiftDataset.save``; the package reads no TFRecords): ``GNNModel.fit`` with the reference's callbacks, the model saved to
 NAME and the history pickled beside it.  ``make-records OUT.npz --pair STRUCT SHIFTS ...`` writes such a file from structures
-and CSV tables of assigned shifts (``ShiftDataset.from_structures``).  Out of scope: ``--tensorboard``, ``hyper`` (the hyper-parameter search) and
-``eval-tfrecords`` (its table needs nmrdata's residue-name list, which the package does not ship)."""
+and CSV tables of assigned shifts (``ShiftDataset.from_structures``).  ``eval-records RECORDS... --embeddings
+FILE`` is the reference's ``eval-tfrecords`` (nmrgnn/main.py:93-189) on such files: the CSV of every labelled atom and the
+markdown table of r and squared error per element and atom name (``GNNModel.evaluate_report``).  Out of
+scope: ``--tensorboard`` and ``hyper`` (the hyper-parameter search)."""
 from __future__ import annotations
 
 import csv
@@ -450,6 +452,67 @@ def make_records_cmd(out, pairs, frames, neighbor_number, embeddings, embeddings
     try:
         make_records(out, pairs, frames=frames, neighbor_number=neighbor_number, embeddings=embeddings,
                      embeddings_out=embeddings_out, pbc=pbc, keep_going=keep_going, device=device, echo=click.echo)
+    except ValueError as e:
+        raise click.ClickException(str(e))
+
+
+def eval_records(records, model_file=None, embeddings=None, validation=0.0, data_name='', merge=None, batch_graphs=64,
+                 device=None, square_root=False, write_csv=True, out_dir=None, echo=print):
+    """The reference's ``eval-tfrecords`` (nmrgnn/main.py:93-189) on ``ShiftDataset`` files: per element and per atom name
+    the count, the Pearson r and the squared error of the model's shifts on the labelled atoms (``GNNModel.evaluate_report``:
+    the sums are taken on the device, one pass per batch).  Writes ``{model_name}.csv`` (``element,y,yhat,class,name``, unless
+    ``write_csv`` is off) and ``{model_name}.md`` into ``out_dir`` (default: the working directory), or the table into the
+    ``merge`` file with that file's rows appended; ``model_name`` is the base name of ``model_file`` (``baseline`` without one).
+    ``embeddings``: the file ``train --embeddings`` reads; its ``'name'`` table says which key a name id of the records stands
+    for.  ``validation`` > 0: only the validation share of ``ShiftDataset.split`` is evaluated.  The rows keyed ``-rmsd`` hold
+    the MEAN SQUARED ERROR, as the reference's do; ``square_root`` writes the root instead.  Returns the ``EvalReport``."""
+    from .dataset import ShiftDataset
+    from .library import load_model
+    if len(records) == 0:
+        raise ValueError('Must give input record files')
+    if embeddings is None:
+        raise ValueError('eval-records needs --embeddings: the record files carry name ids, the table their keys')
+    name_table = _load_embeddings(embeddings)['name']
+    model = load_model(model_file, device=device)
+    model_name = 'baseline' if model_file is None else os.path.basename(os.path.normpath(model_file))
+    data = ShiftDataset.load(list(records), device=device)
+    train_data, validation_data = data.split(validation)
+    data = validation_data if validation > 0 else train_data
+    echo('Computing...')
+    report = model.evaluate_report(data, name_table, data_name=data_name, batch_graphs=batch_graphs, rows=write_csv)
+    echo(f'done: {len(data)} records, {report.labelled} labelled atoms' + (f', {report.unnamed} of them unnamed' if report.unnamed else ''))
+    out_dir = '.' if out_dir is None else out_dir
+    if write_csv:
+        report.to_csv(os.path.join(out_dir, f'{model_name}.csv'))
+    target = os.path.join(out_dir, f'{model_name}.md') if merge is None else merge
+    report.to_markdown(target, model_name, merge=merge, square_root=square_root)
+    echo(f'You can now find your result in {target}')
+    return report
+
+
+@main.command(name='eval-records')
+@click.argument('records', nargs=-1, type=click.Path(exists=True))
+@click.option('--model-file', type=click.Path(exists=True), default=None,
+              help='Model file. If not provided, baseline will be used.')
+@click.option('--validation', default=0.0, help='relative size of validation. If non-zero, only validation will be saved')
+@click.option('--data-name', default='', help='Short name for data on table output')
+@click.option('--merge', default=None, help='Merge results with another markdown table')
+@click.option('--embeddings', required=True, type=click.Path(exists=True),
+              help='JSON or pickle file with the embeddings dict whose name table gives the key of every name id')
+@click.option('--batch-graphs', default=64, help='Records per device batch')
+@click.option('--device', default=None, help='Device, e.g. cuda:0')
+@click.option('--sqrt', 'square_root', is_flag=True,
+              help='Write the root of the mean squared error in the -rmsd rows; by default they hold the MEAN SQUARED ERROR, '
+                   'as the reference writes it under that key')
+@click.option('--no-csv', is_flag=True, help='Write the table only, not the CSV of every labelled atom')
+def eval_records_cmd(records, model_file, validation, data_name, merge, embeddings, batch_graphs, device, square_root, no_csv):
+    '''Evaluate a model on ShiftDataset record files (.npz): r and squared error per element and atom name'''
+    if len(records) == 0:
+        raise click.UsageError('Must give input record files')
+    try:
+        eval_records(records, model_file=model_file, embeddings=embeddings, validation=validation, data_name=data_name,
+                     merge=merge, batch_graphs=batch_graphs, device=device, square_root=square_root, write_csv=not no_csv,
+                     echo=click.echo)
     except ValueError as e:
         raise click.ClickException(str(e))
 

@@ -251,6 +251,57 @@ class GNNModel:
             out.update(nm.results())
         return out
 
+    def evaluate_report(self, data, name_table, data_name='', batch_graphs=64, rows=True):
+        """The table of nmrgnn/main.py:93-189 (``eval-tfrecords``) over ``data``, a ``dataset.ShiftDataset`` or a view of one:
+        count, Pearson r, squared error and bias per atom name, per residue and per element of ``name_table`` (the
+        ``{'RES-NAME': id}`` table the records' name ids come from: ``ShiftDataset.name_table`` or ``embeddings['name']``).
+        Inference forwards over ``data.eval_batches(batch_graphs)``; after each, ONE ``ng_class_moments`` call adds the batch's
+        sums to the device accumulator (``report.ClassMoments``), weighting by the mask column of ``y_true`` exactly as
+        ``evaluate`` does.  The device is read once at the end; with ``rows=True`` the labelled atoms' predictions are read too
+        and the ``report.EvalReport`` returned holds them in store order.  A class's terms are added in the order the batches lay
+        the atoms out, so the last bits of the float64 moments depend on ``batch_graphs``."""
+        from .dataset import ShiftDataset
+        from .metrics import _split_y_true
+        from .report import ClassMoments, EvalReport, class_maps
+        if not isinstance(data, ShiftDataset):
+            raise TypeError("evaluate_report: data is a dataset.ShiftDataset or a view of one")
+        class_of, labels = class_maps(name_table)
+        if len(labels.text) == 0:
+            raise ValueError("evaluate_report: the name table has no 'RES-NAME' key, so there is no class to report")
+        self.build(data.C)
+        eng = self.engine
+        if data.device != eng.device:
+            raise ValueError(f"evaluate_report: the data lives on {data.device}, the model on {eng.device}")
+        cm = ClassMoments(class_of, len(labels.text), eng.device)
+        labelled = torch.zeros((), dtype=torch.float64, device=eng.device)
+        kept, record0 = [], 0
+        for batch, y_true in (data.eval_batches(batch_graphs) if len(data) else ()):
+            peaks = eng.forward(batch, training=False).reshape(-1)
+            y, w, names = _split_y_true(y_true, eng.device)
+            cm.update(peaks, y, w, names)
+            on = w > 0
+            labelled += on.sum()
+            if rows:
+                gp = batch.graph_ptr_host.astype(np.int64)
+                kept.append((record0, gp, on, y, names, peaks))
+            record0 += batch.G
+        out = torch.cat([cm.moments_dev.reshape(-1), labelled.reshape(1)]).cpu().numpy()     # the one read of the sums
+        moments, n_labelled = out[:-1].reshape(-1, 7), int(out[-1])
+        row_arrays = None
+        if rows:
+            if kept:
+                on = torch.cat([k[2] for k in kept])
+                vals = torch.stack([torch.cat([k[3] for k in kept])[on], torch.cat([k[5] for k in kept])[on]]).cpu().numpy()
+                ids = torch.cat([k[4] for k in kept])[on].cpu().numpy()
+                on = on.cpu().numpy()
+                record = np.concatenate([np.repeat(np.arange(len(gp) - 1) + r0, np.diff(gp)) for r0, gp, *_ in kept])[on]
+                atom = np.concatenate([np.arange(gp[-1]) - np.repeat(gp[:-1], np.diff(gp)) for _, gp, *_ in kept])[on]
+            else:
+                vals, ids = np.zeros((2, 0), np.float32), np.zeros(0, np.int32)
+                record = atom = np.zeros(0, np.int64)
+            row_arrays = {'record': record, 'atom': atom, 'id': ids, 'y': vals[0], 'yhat': vals[1]}
+        return EvalReport(moments, labels, class_of=class_of, data_name=data_name, rows=row_arrays, labelled=n_labelled)
+
     def fit(self, train, epochs=1, validation_data=None, batch_graphs=1, callbacks=(), shuffle=True, seed=0,
             initial_epoch=0, verbose=1):
         """Train on a ``dataset.ShiftDataset`` (keras ``model.fit`` as nmrgnn/main.py:79-80 calls it).  Runs ``epochs``
