@@ -768,6 +768,41 @@ int ng_name_metrics(ng_ctx*, void* stream, int64_t N, const float* y, const floa
 int ng_class_moments(ng_ctx*, void* stream, int64_t N, const float* y, const float* w, const int32_t* names, const float* pred,
                      int n_ids, int M, const int32_t* class_of, int K, int accumulate, double* moments);
 
+/* Maximum-entropy reweighting of a trajectory against measured shifts (nmrgnn_amd/reweight.py; csrc/reweight.hip; DESIGN.md
+ * §7.22).  S [T][M] float32 row-major (frame t, observable m), y [M] float32 targets, lambda [M] double multipliers, logw0 [T]
+ * double log prior weights (NULL: uniform, -log T; -inf: a frame of weight zero), all on the device.  In float64, S and y
+ * converted before their first use:
+ *   d_tm = S_tm - y_m,   a_t = logw0_t - sum_m lambda_m d_tm,   logZ = log sum_t exp(a_t),   p_t = exp(a_t - logZ),
+ *   out [1 + M] = {logZ, mean_0 .. mean_{M-1}},   mean_m = sum_t p_t d_tm.
+ * One pass over S for M <= 2048 (a wave owns a contiguous span of frames and keeps a running maximum, rescaling its sums only
+ * when the maximum rises); two passes for 2048 < M <= 16384 (the logits go to scratch, then the sums by blocks of 256 columns).
+ * Per-workgroup partials (max, sum, acc[M]) in the context's scratch are merged by a last launch in workgroup order by the
+ * log-sum-exp rule.  The grid is a function of (T, M) alone — min(ceil(T / 32), 1024) workgroups of four waves (256 in the
+ * two-pass form), frames [g s, (g + 1) s) for wave g with s = ceil(T / waves) — so the same call writes the same bits on any
+ * device; no atomics.  Asynchronous on `stream`, never reads the device on the host; capturable once the scratch holds
+ * workgroups * (2 + M) (+ T + workgroups in the two-pass form) doubles.  A span, a workgroup or a call whose frames all have
+ * a_t = -inf gives (-inf, 0, 0): the call then writes logZ = -inf and mean = 0.  NaN in S, y, lambda or logw0 propagates into
+ * logZ and the means: it is not handled.  S aligned to 16 bytes with M % 4 == 0 is read by 16-byte loads.
+ * Refused (NG_ERR_INVALID, before any launch): NULL context; T < 1 or T >= 2^31; M < 1 or M > 16384; NULL S, y, lambda or out. */
+int ng_reweight_eval(ng_ctx*, void* stream, int64_t T, int M, const float* S, const float* y, const double* logw0,
+                     const double* lambda, double* out);
+/* The weights of ng_reweight_eval's formulas at a given logZ (a device double, as out[0] of that call): p [T] double,
+ * p_t = exp(a_t - logZ), 0 where a_t = -inf; stats [2] = {sum_t p_t log(p_t / w0_t), sum_t p_t^2} with log(p_t / w0_t) =
+ * -sum_m lambda_m d_tm - logZ and a frame with p_t = 0 adding 0 to the first.  One read of S (any M <= 16384: the columns are
+ * strided over the lanes, lambda and y come from the cache); the sums run over the frames of a wave in order, the four waves
+ * of a workgroup in order, then a fixed tree over the workgroups in a second launch: no atomics, the same bits on every call.
+ * Grid and refusals as ng_reweight_eval, plus NULL logZ, p or stats. */
+int ng_reweight_weights(ng_ctx*, void* stream, int64_t T, int M, const float* S, const float* y, const double* logw0,
+                        const double* lambda, const double* logZ, double* p, double* stats);
+/* Weighted moments over the T frames of one structure, the weighted counterpart of ng_ensemble_moments: mu [T][N] float32
+ * shifts, p [T] double weights (assumed to sum to 1; zeros allowed).  With e_t = mu_t - mu_0 (exact in float64)
+ *   mean[i] = mu_0 + sum_t p_t e_t,   var[i] = max(0, sum_t p_t e_t^2 - (sum_t p_t e_t)^2)        (the population form)
+ * A workgroup owns 64 atoms, its sixteen waves the frame chunks [w c, (w + 1) c), c = ceil(T / 16): frames in order inside a
+ * chunk, chunks added in wave order — the order depends on (T, N) alone.  Float64 sums, each result rounded to float32 once; a
+ * column of equal values gives var exactly 0.  One launch, no atomics, no scratch, capturable.  N = 0 returns NG_OK.
+ * Refused: NULL context; T < 1 or T >= 2^31; N < 0 or N >= 2^31; NULL mu, p, mean or var. */
+int ng_weighted_moments(ng_ctx*, void* stream, int64_t T, int64_t N, const float* mu, const double* p, float* mean, float* var);
+
 /* Mini-batch collation from a device-resident record store (nmrgnn_amd/dataset.py: ShiftDataset.batch; csrc/collate.hip).
  * The store holds R records back to back, record r in the rows [rec_ptr[r], rec_ptr[r+1]) of
  *   s_atoms [Ntot,C] f32, s_nlist [Ntot,K] i32 (record-LOCAL indices), s_edges [Ntot,K] f32, s_inv_degree [Ntot] f32,

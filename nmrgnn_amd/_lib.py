@@ -153,6 +153,9 @@ SIGNATURES = {
     "ng_loss_name": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
     "ng_name_metrics": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp, _int, _int, _vp]),
     "ng_class_moments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _int, _vp, _int, _int, _vp]),
+    "ng_reweight_eval": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
+    "ng_reweight_weights": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ng_weighted_moments": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "ng_collate_batch": (_int, [_vp, _vp, _i64, _i64] + [_vp] * 9 + [_i64, _int, _int, _int] + [_vp] * 8),
     "ng_store_from_batch": (_int, [_vp, _vp, _i64, _int, _int, _int] + [_vp] * 6 + [_i64, _i64] + [_vp] * 7),
     "ng_label_moments": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp]),

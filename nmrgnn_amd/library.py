@@ -275,6 +275,63 @@ def shift_uncertainty(model, atoms, positions, samples=32, position_sigma=None, 
     return mean, torch.sqrt(var_model), torch.sqrt(var_in)
 
 
+def reweight_trajectory(model, atoms, frames, targets, sigma, theta, prior=None, neighbor_number=16, box=None,
+                        frames_per_batch=32, prune=False, **fit_args):
+    """Maximum-entropy reweighting of the frames of a trajectory against measured shifts (nmrgnn_amd.reweight):
+    ``(result, shifts)`` — a ``ReweightResult`` whose ``weights`` [T] make the ensemble agree with ``targets`` within
+    ``sigma`` as far as ``theta`` allows, and the predicted shifts of every frame, float32 on the device.
+
+    ``atoms`` [n, C] one-hot, ``frames`` [T, n, 3] in Angstrom, ``targets`` [n] in ppm with NaN where an atom has no label,
+    ``sigma`` a scalar or [n] (read on the labelled atoms only), ``theta`` > 0, ``prior`` [T] frame weights or None.  The
+    frozen model runs over the frames ``frames_per_batch`` at a time, as ``eval-struct`` does (``box``: [6] for every frame or
+    [T, 6]); the [T, n] shifts stay on the device, the labelled columns are gathered there, and ``ShiftReweighter.fit(theta,
+    **fit_args)`` does the rest.  ``prune=True``: the model runs on the receptive field of the labelled atoms alone
+    (``GNNModel.predict_selected``) and ``shifts`` is [T, M], the labelled atoms in ascending index.
+
+    ``ValueError``: no labelled atom, or a labelled atom whose ``sigma`` is not finite and > 0."""
+    import torch
+    from .graph import frames_to_batch
+    from .reweight import ShiftReweighter
+    atoms_np = atoms.detach().cpu().numpy() if isinstance(atoms, torch.Tensor) else np.asarray(atoms)
+    n = int(atoms_np.shape[0])
+    y = _host64(targets).reshape(-1)
+    if y.shape != (n,):
+        raise ValueError(f"reweight_trajectory: targets need {n} entries, got {y.shape}")
+    labelled = np.isfinite(y)
+    if not labelled.any():
+        raise ValueError("reweight_trajectory: no atom is labelled (targets are NaN everywhere)")
+    sg = _host64(sigma)
+    sg = np.full(n, float(sg)) if sg.ndim == 0 else sg.reshape(-1)
+    if sg.shape != (n,):
+        raise ValueError(f"reweight_trajectory: sigma must be a scalar or [{n}], got {sg.shape}")
+    bad = labelled & ~(np.isfinite(sg) & (sg > 0))
+    if bad.any():
+        raise ValueError(f"reweight_trajectory: atom {int(np.nonzero(bad)[0][0])} is labelled but its sigma is not finite and > 0")
+    shape = tuple(frames.shape)
+    if len(shape) != 3 or shape[1] != n or shape[2] != 3 or shape[0] < 1:
+        raise ValueError(f"reweight_trajectory: frames must be [T, {n}, 3] with T >= 1, got {shape}")
+    T = shape[0]
+    if model.engine is None:
+        model.build(int(atoms_np.shape[-1]))
+    model.freeze()
+    dev = model.engine.device
+    per_frame_box = box is not None and len(np.shape(box)) == 2
+    step = max(1, int(frames_per_batch))
+    kept = []
+    for b0 in range(0, T, step):
+        chunk = frames[b0:b0 + step]
+        G = int(chunk.shape[0])
+        batch = frames_to_batch(atoms_np, chunk.detach() if isinstance(chunk, torch.Tensor) else chunk, neighbor_number,
+                                device=dev, box=box[b0:b0 + step] if per_frame_box else box)
+        peaks = model.predict_selected(batch, np.tile(labelled, G)) if prune else model(batch)
+        kept.append(peaks.detach().reshape(G, -1))
+    shifts = torch.cat(kept)
+    idx = torch.from_numpy(np.nonzero(labelled)[0]).to(dev)
+    S = shifts if prune else shifts.index_select(1, idx).contiguous()
+    rw = ShiftReweighter(S, y[labelled], sg[labelled], prior=prior, device=dev)
+    return rw.fit(theta, **fit_args), shifts
+
+
 def _restraint_positions(positions, R, n):
     """host check of a call's positions: [R, n, 3] (or [n, 3] when R == 1); returns the torch view [R, n, 3] (not yet on the
     device) and whether the caller gave [n, 3]"""

@@ -44,7 +44,7 @@ def _open_structure(struct_files):
 
 def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16, stride=1,
                    frames_per_batch=32, keep_going=False, device=None, echo=print, pbc=False, separate=False, boxes=False,
-                   uncertainty=0, position_sigma=None, average=False, atom_names=None):
+                   uncertainty=0, position_sigma=None, average=False, atom_names=None, reweight=None, theta=None, sigma=None):
     """Predict shifts for every ``stride``-th frame and write the reference's CSV.  Returns the timing
     buckets in seconds.  ``pbc``: neighbour lists under the minimum-image convention in each frame's box (its CRYST1
     record); a frame without one is an error.  ``separate``: every file is a structure of its own (see
@@ -61,7 +61,28 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
 
     ``atom_names``: a sequence of PDB atom names (exact match) — rows for these atoms only, with their original ``index``;
     the model runs on their receptive field alone (GNNModel.predict_selected) and ``check_peaks`` on them.  Names that match
-    no atom raise AtomNamesError."""
+    no atom raise AtomNamesError.
+
+    ``reweight``: a CSV of assigned shifts (``structure.read_shift_table``; an optional ``error`` column in ppm) — maximum-
+    entropy reweighting of the frames read against it (nmrgnn_amd.reweight) at the strength ``theta``, with
+    the errors ``sigma`` (a number, ``'H=0.3,C=1.1'`` or what ``reweight.parse_sigma`` returns; a finite ``error`` of the
+    table wins for its row).  ONE row per atom: ``index, residues, resids, names, peaks`` (the weighted mean), ``peaks_std``
+    (the weighted standard deviation; both from ng_weighted_moments), ``confident`` (of the weighted mean), ``frames``,
+    ``peaks_prior`` (the unweighted mean, that of ``average``), ``target``, ``sigma`` (blank without a label); the frame
+    weights go to ``<output stem>.weights.csv`` (``frame, weight``).  With ``atom_names`` the observables are the labelled
+    atoms among the selected ones.  ReweightUsageError: no ``theta``, a labelled atom without a sigma, no labelled atom left,
+    or a combination with ``separate``, ``uncertainty`` or ``average``."""
+    if reweight is not None:
+        if separate or uncertainty or average:
+            raise ReweightUsageError('--reweight cannot be combined with --separate, --uncertainty or --average')
+        if theta is None:
+            raise ReweightUsageError('--reweight needs --theta X (the regularisation strength, > 0)')
+        if not (float(theta) > 0 and np.isfinite(float(theta))):
+            raise ReweightUsageError(f'--theta must be finite and > 0, got {theta}')
+        if sigma is None:
+            raise ReweightUsageError('--reweight needs --sigma SPEC: there is no default error')
+    elif theta is not None or sigma is not None:
+        raise ReweightUsageError('--theta and --sigma go with --reweight TABLE')
     if len(struct_files) == 0:
         raise ValueError('Must pass at least on structure file')
     uncertainty = int(uncertainty or 0)
@@ -104,6 +125,9 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         atoms_all, atoms, n = atoms, atoms[idx], len(idx)      # what follows the model call sees the selected atoms only
     else:
         atoms_all = atoms
+    rw_target = rw_sigma = None
+    if reweight is not None:
+        rw_target, rw_sigma = _reweight_labels(u, reweight, sigma, select)
     model.build(atoms.shape[1])
     model.freeze()          # inference only: the engine keeps its packed weight images across the per-frame calls
     timing = {'Structure': 0.0, 'Model Inference (MI355X)': 0.0, 'Parsing': 0.0}
@@ -120,7 +144,7 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         timing['Structure'] += time.perf_counter() - t
         t = time.perf_counter()
         peaks = model(batch) if select is None else model.predict_selected(batch, np.tile(select, len(chunk)))
-        if average:
+        if average or reweight is not None:
             kept.append(peaks.reshape(len(chunk), n))
             timing['Model Inference (MI355X)'] += time.perf_counter() - t
             echo('|'.join(f'{k}:{v:5.2f}s' for k, v in timing.items()))
@@ -172,6 +196,36 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
                 for j, i in enumerate(idx)]
         header = ['index', 'residues', 'resids', 'names', 'peaks', 'peaks_std', 'confident', 'frames']
         timing['Parsing'] += time.perf_counter() - t
+    if reweight is not None:
+        from .reweight import ShiftReweighter, weighted_moments, write_reweight_csv, write_weights_csv
+        t = time.perf_counter()
+        shifts = torch.cat(kept)                            # [frames, n] on the device
+        cols = np.nonzero(np.isfinite(rw_target[idx]))[0]   # the labelled atoms among the rows
+        S = shifts.index_select(1, torch.from_numpy(cols).to(shifts.device)).contiguous()
+        res = ShiftReweighter(S, rw_target[idx][cols], rw_sigma[idx][cols]).fit(float(theta))
+        mean, var = weighted_moments(shifts, res.weights)
+        prior_mean = model.engine.ensemble_moments(shifts)[0]
+        timing['Model Inference (MI355X)'] += time.perf_counter() - t
+        t = time.perf_counter()
+        mean = mean.cpu().numpy()
+        try:
+            conf = check_peaks(atoms, mean)
+        except Warning as w:
+            if not keep_going:
+                raise
+            echo(f'weighted mean over {len(frame_ids)} frames: {w}')
+            conf = np.zeros(n, dtype=bool)
+        write_reweight_csv(output_csv, idx, [u.resnames[i] for i in idx], [u.resids[i] for i in idx], [u.names[i] for i in idx],
+                           mean, torch.sqrt(var).cpu().numpy(), conf, len(frame_ids), prior_mean.cpu().numpy(),
+                           rw_target[idx], rw_sigma[idx])
+        weights_csv = os.path.splitext(output_csv)[0] + '.weights.csv'
+        write_weights_csv(weights_csv, res.weights)
+        timing['Parsing'] += time.perf_counter() - t
+        echo(f'reweighted {len(frame_ids)} frames on {len(cols)} shifts: theta {float(theta):g}, phi_eff {res.phi_eff:.4f}, '
+             f'chi2 {res.chi2_prior:.4f} -> {res.chi2_post:.4f}, {res.evaluations} evaluations, '
+             f"{'converged' if res.converged else 'NOT converged'}")
+        echo(f'You can now find your result in {output_csv} and the frame weights in {weights_csv}')
+        return timing
     os.makedirs(os.path.dirname(os.path.abspath(output_csv)), exist_ok=True)
     with open(output_csv, 'w', newline='') as f:
         wr = csv.writer(f)
@@ -179,6 +233,39 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         wr.writerows(rows)
     echo(f'You can now find your result in {output_csv}')
     return timing
+
+
+class ReweightUsageError(ValueError):
+    """--reweight used wrongly: the command line reports it as a usage error"""
+
+
+def _reweight_labels(u, table_file, sigma, select):
+    """``(target, sigma)`` float64 [n] of ``eval-struct --reweight``: the table's shifts laid on the atoms of ``u`` (NaN: no
+    label; with ``select`` the labels outside it are dropped) and the error of every labelled atom — the table's ``error``
+    where finite, else ``sigma`` (a number, a SPEC string or a parsed dict).  ReweightUsageError where no labelled atom is
+    left or one has no error."""
+    from .reweight import atom_sigma, parse_sigma, read_shift_errors
+    from .structure import join_shifts, read_shift_table
+    table = read_shift_table(table_file)
+    target = join_shifts(u, table, label=str(table_file))[0].astype(np.float64)
+    errors = read_shift_errors(table_file)
+    err_atoms = join_shifts(u, dict(table, shift=errors.astype(np.float32)), strict=False)[0].astype(np.float64)
+    if select is not None:
+        target[~select] = np.nan
+    labelled = np.isfinite(target)
+    if not labelled.any():
+        raise ReweightUsageError(f'--reweight {table_file}: no labelled atom' + (' among the selected atoms' if select is not None else ''))
+    try:
+        spec = parse_sigma(sigma) if isinstance(sigma, str) else sigma
+    except ValueError as e:
+        raise ReweightUsageError(str(e)) from None
+    sig = atom_sigma(u.elements, labelled, spec, err_atoms)
+    missing = np.nonzero(labelled & ~np.isfinite(sig))[0]
+    if len(missing):
+        i = int(missing[0])
+        raise ReweightUsageError(f'--sigma: the labelled atom {u.resnames[i]} {int(u.resids[i])} {u.names[i]} (element '
+                                 f'{u.elements[i]}) has no sigma; give one number, or a value for every labelled element')
+    return target, sig
 
 
 class AtomNamesError(ValueError):
@@ -290,8 +377,18 @@ def _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride
 @click.option('--atom-names', default=None, metavar='A,B,...',
               help='Only the atoms with one of these PDB names (exact match, comma separated, e.g. H,N,CA,CB,C): the model runs '
                    'on the atoms that can reach them; rows keep their original index')
+@click.option('--reweight', default=None, type=click.Path(exists=True), metavar='TABLE',
+              help='Maximum-entropy reweighting of the frames against the assigned shifts of TABLE (CSV: resid,name,shift'
+                   '[,resname][,error]): one row per atom with the weighted mean and spread, and <output stem>.weights.csv '
+                   'with the weight of every frame; needs --theta and --sigma')
+@click.option('--theta', default=None, type=float, metavar='X',
+              help='With --reweight: the regularisation strength (> 0); large keeps the ensemble, small fits the shifts')
+@click.option('--sigma', default=None, metavar='SPEC',
+              help='With --reweight: the error of a measured-minus-predicted shift in ppm, one number or per element as '
+                   'H=0.3,C=1.1,N=2.5; an error column of TABLE overrides it for its row.  No default: the honest values are '
+                   'the per-element RMSDs of an eval-records report of the model')
 def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going, pbc, separate,
-                boxes, uncertainty, position_sigma, average, atom_names):
+                boxes, uncertainty, position_sigma, average, atom_names, reweight, theta, sigma):
     '''Predict NMR chemical shifts with specific file'''
     if separate and (uncertainty or average):
         raise click.UsageError('--separate cannot be combined with --uncertainty or --average: the files are different '
@@ -307,6 +404,15 @@ def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, f
                                'structure')
     if boxes and not separate:
         raise click.UsageError('--boxes goes with --separate; use --pbc for frames of one topology')
+    if reweight is not None:
+        if separate or uncertainty or average:
+            raise click.UsageError('--reweight cannot be combined with --separate, --uncertainty or --average')
+        if theta is None:
+            raise click.UsageError('--reweight needs --theta X (the regularisation strength, > 0)')
+        if sigma is None:
+            raise click.UsageError('--reweight needs --sigma SPEC: there is no default error')
+    elif theta is not None or sigma is not None:
+        raise click.UsageError('--theta and --sigma go with --reweight TABLE')
     names = None
     if atom_names is not None:
         names = [a.strip() for a in atom_names.split(',') if a.strip()]
@@ -315,7 +421,10 @@ def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, f
     try:
         eval_structure(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch,
                        keep_going, echo=click.echo, pbc=pbc, separate=separate, boxes=boxes, uncertainty=uncertainty,
-                       position_sigma=position_sigma, average=average, atom_names=names)
+                       position_sigma=position_sigma, average=average, atom_names=names, reweight=reweight, theta=theta,
+                       sigma=sigma)
+    except ReweightUsageError as e:
+        raise click.UsageError(str(e))
     except AtomNamesError as e:
         raise click.ClickException(str(e))
 
