@@ -866,6 +866,34 @@ int ng_label_moments(ng_ctx*, void* stream, int64_t R, int64_t Ntot, int C, cons
 int ng_adam_step(ng_ctx*, void* stream, int64_t n, float* p, const float* g, float* m, float* v,
                  float lr, float beta1, float beta2, float eps, int64_t step, float grad_scale);
 
+/* Fine-tuning (csrc/optim.hip): Adam over parameter GROUPS of the flat buffer, and the clip factor of their gradient.
+ * The groups are n_seg <= NG_ADAM_MAX_SEGMENTS half-open element ranges [seg_begin[s], seg_end[s]) of [0, n) with a rate
+ * scale each — HOST arrays, sorted by begin, not overlapping (empty ranges are allowed), every scale finite and >= 0.
+ * The table travels in the kernel arguments by value: no device table, no copy, the launch can be captured.
+ *
+ * ng_adam_step_groups: lr_t is computed exactly as ng_adam_step does; segment s is updated with the rate
+ *   lr_t * seg_scale[s] (one float32 product) by the expressions of ng_adam_step.  An element of a segment of scale 0, or
+ *   of no segment, keeps the bits of p, m and v, and its g is NOT READ (it may be stale, NaN or never written).  All scales 1
+ *   over [0, n): the bits of ng_adam_step; a power-of-two scale: the bits of ng_adam_step called with lr * scale.
+ *   clip (device pointer or NULL): every gradient is multiplied by (float)clip[0] after grad_scale; clip[0] == 1 gives the
+ *   bits of clip == NULL.  The weight version is bumped and every registered image in [p, p + n) rebuilt as ng_adam_step
+ *   does (also those fed by frozen segments only).  n_seg == 0 and n == 0 launch no update.
+ *   Refused: an armed replay context (NG_ERR_UNSUPPORTED: a replayed step trains everything); step < 1, n_seg outside
+ *   [0, 64], a range outside [0, n) or with end < begin, ranges unsorted or overlapping, a negative or non-finite scale
+ *   (NG_ERR_INVALID) — before anything is launched or bumped.
+ * ng_grad_clip_factor: norm = sqrt(sum over the elements of segments with scale > 0 of ((double)(g[i] * grad_scale))^2),
+ *   the product rounded to float32 as Adam forms it, the squares and the sum in float64; two launches (per-workgroup partials
+ *   in the context's scratch, then a fixed-order sum), no atomics: the same bits on every run.
+ *   out2[0] = min(1, clipnorm / norm), and 1 where norm is 0 or not finite (a NaN gradient then reaches the weights as it
+ *   would unclipped, through its own element only); out2[1] = norm.  out2 (device, 2 doubles) is what `clip` points to.
+ *   Refused (NG_ERR_INVALID): the segment rules above; clipnorm not > 0 or not finite; out2 NULL; g NULL with n > 0. */
+#define NG_ADAM_MAX_SEGMENTS 64
+int ng_adam_step_groups(ng_ctx*, void* stream, int64_t n, float* p, const float* g, float* m, float* v, float lr, float beta1,
+                        float beta2, float eps, int64_t step, float grad_scale, int n_seg, const int64_t* seg_begin,
+                        const int64_t* seg_end, const float* seg_scale, const double* clip);
+int ng_grad_clip_factor(ng_ctx*, void* stream, int64_t n, const float* g, float grad_scale, int n_seg, const int64_t* seg_begin,
+                        const int64_t* seg_end, const float* seg_scale, double clipnorm, double* out2);
+
 /* Gradient exchange for a caller without torch.distributed (SURVEY §8(b) suggested export, §8(e): graph-parallel data
  * parallelism needs ONE all-reduce(sum, fp32) over the flat gradient bucket per step; the reference, nmrgnn/main.py:74-80,
  * is single-device).  RCCL is bound at first use (dlopen of librccl.so): NG_ERR_UNSUPPORTED where it is absent.

@@ -160,6 +160,9 @@ SIGNATURES = {
     "ng_store_from_batch": (_int, [_vp, _vp, _i64, _int, _int, _int] + [_vp] * 6 + [_i64, _i64] + [_vp] * 7),
     "ng_label_moments": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ng_adam_step": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64, _f]),
+    "ng_adam_step_groups": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _i64, _f, _int, C.POINTER(_i64),
+                                   C.POINTER(_i64), _c_float_p, _vp]),
+    "ng_grad_clip_factor": (_int, [_vp, _vp, _i64, _vp, _f, _int, C.POINTER(_i64), C.POINTER(_i64), _c_float_p, C.c_double, _vp]),
     "ng_comm_unique_id": (_int, [_vp]),
     "ng_comm_init": (_int, [_vp, _int, _int, _vp]),
     "ng_comm_destroy": (_int, [_vp]),

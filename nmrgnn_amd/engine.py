@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, finetune
 from ._lib import ptr, ptr_array
 from .graph import GraphBatch
 from .params import ParamStore
@@ -102,6 +102,11 @@ class Engine:
         self.adam_m = torch.zeros_like(self.params.flat)
         self.adam_v = torch.zeros_like(self.params.flat)
         self.adam_t = 0
+        # fine-tuning: the launch plan of a backward that trains everything; the segment tables of
+        # adam_step(groups=) by their key; the device words (factor, norm) of the last adam_step(clipnorm=)
+        self._full_plan = finetune.full_plan(self.L)
+        self._seg_tables = {}
+        self._clip = None
         self.tape = None
         self._rng_calls = 0
         self._frozen = False
@@ -554,7 +559,7 @@ class Engine:
         return bool(g[0]), float(g[4:6].view(np.float32)[0]), float(g[4:6].view(np.float32)[1])
 
     # ------------------------------------------------------------------ backward
-    def backward(self, dpeaks, on_node_grads=None, edge_grad=None, param_grad=True):
+    def backward(self, dpeaks, on_node_grads=None, edge_grad=None, param_grad=True, trainable=None):
         """fills params.grad (overwrite) from the upstream gradient dpeaks[N] (None: the gradient of the loss
         taken inside ``forward(loss=...)``).
         ``on_node_grads`` is called once every non-edge gradient has been enqueued (the data-parallel
@@ -567,7 +572,26 @@ class Engine:
         ``param_grad=False`` (needs ``edge_grad``): input gradients only — the head, FC-block and MPLayer backward get NULL
         weight-gradient outputs (include/nmrgnn_hip.h: no weight-gradient products, partials or queued sums are formed), and
         nothing whose only output is a parameter gradient is launched (no edge-MLP / table backward, no ng_embed_bwd, no
-        reduction flush).  ``params.grad`` is left untouched; ``edge_grad`` is bit for bit that of ``param_grad=True``."""
+        reduction flush).  ``params.grad`` is left untouched; ``edge_grad`` is bit for bit that of ``param_grad=True``.
+        ``trainable`` (fine-tuning; None: everything, today's launches exactly): a set of parameter tensor names
+        (``params.shapes``).  The backward stops at the lowest stage a trainable tensor needs (``finetune.launch_plan``): the
+        walk is out -> fc -> mp[L-1..0] -> embed, then the edge MLP from the summed de.  A group (out, fc, mp/l, embed,
+        edge_fc) is computed when any of its tensors is trainable; frozen groups the walk passes through get NULL
+        weight-gradient outputs.  AFTER SUCH A CALL ``params.grad`` IS DEFINED ONLY ON THE COMPUTED GROUPS
+        (``finetune.computed_groups``) — there bit for bit what the full backward writes — and holds stale or unwritten values
+        elsewhere: hand it to ``adam_step(groups=...)`` with the same tensors, never to the plain ``adam_step()``.
+        ``param_grad=False`` with ``trainable`` is refused, and so is ``edge_grad`` when the walk stops above MP layer 0: the
+        input gradient needs the full de.  Not to be confused with ``freeze_weights`` (constant weights, inference)."""
+        plan = None
+        if trainable is not None:
+            if not param_grad:
+                raise ValueError("backward(trainable=...) forms parameter gradients; param_grad=False forms none")
+            names = finetune.check_names(trainable, self.params.shapes)
+            plan = finetune.launch_plan(self.L, finetune.group_names(n for n in self.params.shapes if n in names))
+            if edge_grad is not None and plan.mp_stop > 0:
+                raise ValueError("backward(edge_grad=...) needs the full de, summed over every MP layer; this trainable set "
+                                 f"stops the backward above MP layer {plan.mp_stop - 1} (train embed, edge_fc or mp/0, or "
+                                 "drop trainable=)")
         if not param_grad:
             if edge_grad is None:
                 raise ValueError("backward(param_grad=False) needs edge_grad: without parameter gradients it is the only output")
@@ -595,17 +619,22 @@ class Engine:
         if self.cache_images:
             self._own_images()
         try:
-            self._backward(tp, dpeaks, on_node_grads, lib, h, st, edge_grad, bool(param_grad))
+            self._backward(tp, dpeaks, on_node_grads, lib, h, st, edge_grad, bool(param_grad), plan)
         finally:
             if self.cache_images:
                 lib.ng_weights_frozen(h, 0)
             self._ck(lib.ng_defer_reductions(h, st, 0), "ng_defer_reductions")
 
-    def _backward(self, tp, dpeaks, on_node_grads, lib, h, st, edge_grad=None, param_grad=True):
+    def _backward(self, tp, dpeaks, on_node_grads, lib, h, st, edge_grad=None, param_grad=True, plan=None):
         P = self.params
         # the weight-gradient outputs: views of params.grad, or NULL (param_grad=False)
         wg = P.g if param_grad else (lambda name: None)
         warr = ptr_array if param_grad else (lambda ts: None)
+        # plan (backward(trainable=)): where the walk stops and which stages on the way keep their weight-gradient outputs
+        if plan is None:
+            plan = self._full_plan
+        null = lambda name: None
+        wg_fc, warr_fc = (wg, warr) if plan.fc_dw else (null, null)
         b = tp.batch
         N, K, F, E = b.N, b.K, self.F, self.E
         Fh = F // 2
@@ -631,32 +660,36 @@ class Engine:
                                      ptr(P["out/kernel"]), ptr(b.atoms), ptr(self.peak_std),
                                      ptr(dpeaks), ptr(dg), ptr(wg("out/kernel")), ptr(wg("out/bias"))),
                      "ng_head_bwd")
-        dx = self._new(N, F)
-        Wfc = [P[f"fc/{t}/kernel"] for t in range(self.Lf)]
-        ns = int(lib.ng_fc_block_scratch_floats(N, F, self.Lf))
-        scratch = self._new(ns) if ns else None
-        self._ck(lib.ng_fc_block_bwd(h, st, N, F, self.Lf, self.fc_act, ptr_array(tp.fx), ptr(tp.g),
-                                     ptr_array(Wfc), ptr(dg), ptr(dx),
-                                     warr([wg(f"fc/{t}/kernel") for t in range(self.Lf)]),
-                                     warr([wg(f"fc/{t}/bias") for t in range(self.Lf)]),
-                                     ptr(scratch)), "ng_fc_block_bwd")
-        csc_ptr, csc_edge = b.csc()
-        de = self._new(ne, E)
-        # incoming-edge records (source atom + edge features in CSC order): shared by all MP layers
-        rec = None
-        if E <= 3 and not b.is_csr:
-            rec = self._new(ne, 4)
-            self._ck(lib.ng_mp_edge_records(h, st, N, K, E, ptr(csc_ptr), ptr(csc_edge), ptr(tp.e), ptr(rec)),
-                     "ng_mp_edge_records")
+        dx = None
+        if plan.fc_run:
+            dx = self._new(N, F)
+            Wfc = [P[f"fc/{t}/kernel"] for t in range(self.Lf)]
+            ns = int(lib.ng_fc_block_scratch_floats(N, F, self.Lf))
+            scratch = self._new(ns) if ns else None
+            self._ck(lib.ng_fc_block_bwd(h, st, N, F, self.Lf, self.fc_act, ptr_array(tp.fx), ptr(tp.g),
+                                         ptr_array(Wfc), ptr(dg), ptr(dx),
+                                         warr_fc([wg_fc(f"fc/{t}/kernel") for t in range(self.Lf)]),
+                                         warr_fc([wg_fc(f"fc/{t}/bias") for t in range(self.Lf)]),
+                                         ptr(scratch)), "ng_fc_block_bwd")
+        csc_ptr = csc_edge = de = rec = None
+        if plan.mp_stop < self.L:
+            csc_ptr, csc_edge = b.csc()
+            de = self._new(ne, E)
+            # incoming-edge records (source atom + edge features in CSC order): shared by all MP layers
+            if E <= 3 and not b.is_csr:
+                rec = self._new(ne, 4)
+                self._ck(lib.ng_mp_edge_records(h, st, N, K, E, ptr(csc_ptr), ptr(csc_edge), ptr(tp.e), ptr(rec)),
+                         "ng_mp_edge_records")
         dh = dx
-        for l in reversed(range(self.L)):
+        for l in reversed(range(plan.mp_stop, self.L)):
             dhn = self._new(N, F)
+            wg_mp = wg if plan.mp_dw[l] else null
             if b.is_csr:
                 self._ck(lib.ng_mp_layer_bwd_csr(h, st, N, ne, F, E, self.mp_act, ptr(tp.h[l]), ptr(b.row_ptr),
                                                  ptr(b.nlist), ptr(b.row_of), ptr(tp.e), ptr(b.inv_degree),
                                                  ptr(P[f"mp/{l}/w"]), ptr(tp.A[l]), ptr(tp.S[l]), ptr(csc_ptr),
                                                  ptr(csc_edge), ptr(dh), ptr(dhn), ptr(de),
-                                                 0 if l == self.L - 1 else 1, ptr(wg(f"mp/{l}/w"))),
+                                                 0 if l == self.L - 1 else 1, ptr(wg_mp(f"mp/{l}/w"))),
                          "ng_mp_layer_bwd_csr")
                 dh = dhn
                 continue
@@ -664,18 +697,21 @@ class Engine:
                                          ptr(tp.e), ptr(b.inv_degree), ptr(P[f"mp/{l}/w"]),
                                          ptr(tp.A[l]), ptr(tp.S[l]), ptr(csc_ptr), ptr(csc_edge),
                                          ptr(dh), ptr(dhn), ptr(de), 0 if l == self.L - 1 else 1,
-                                         ptr(wg(f"mp/{l}/w")), ptr(rec)), "ng_mp_layer_bwd")
+                                         ptr(wg_mp(f"mp/{l}/w")), ptr(rec)), "ng_mp_layer_bwd")
             dh = dhn
         if not param_grad:      # the embedding, the reductions and the edge MLP's weights: parameter gradients only
             self._edge_dinput(tp, de, edge_grad)
             self.tape = None
             return
-        self._ck(lib.ng_embed_bwd(h, st, N, self.C, F, ptr(b.atoms), ptr(dh),
-                                  ptr(P.g("embed/kernel"))), "ng_embed_bwd")
+        if plan.embed:
+            self._ck(lib.ng_embed_bwd(h, st, N, self.C, F, ptr(b.atoms), ptr(dh),
+                                      ptr(P.g("embed/kernel"))), "ng_embed_bwd")
         self._ck(lib.ng_flush_reductions(h, st), "ng_flush_reductions")
         if on_node_grads is not None:
             on_node_grads()
-        if tp.edge_path == "slots":
+        if not plan.edge_fc:        # the edge MLP is frozen: its gradient is not formed
+            pass
+        elif tp.edge_path == "slots":
             self._edge_mlp_bwd(ne, b.edges, tp.d_eff, tp.z_save, tp.z_layout, de, self._edge_grads())
         elif tp.edge_path == "live":
             perm, _, d_c, n_live = tp.live
@@ -799,18 +835,60 @@ class Engine:
                                        ptr(loss), ptr(dpred)), "ng_loss_name")
         return loss, dpred
 
-    def adam_step(self, lr=None, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-7):
+    def _segment_table(self, groups):
+        """(n_seg, begin, end, scale) host arrays of ng_adam_step_groups for ``groups`` = {tensor: scale}
+        (``finetune.segments``); kept per distinct ``groups``"""
+        key = tuple(sorted((str(k), float(v)) for k, v in groups.items()))
+        tab = self._seg_tables.get(key)
+        if tab is None:
+            P = self.params
+            segs = finetune.segments(dict(key), {n: int(np.prod(s)) for n, s in P.shapes.items()}, P.offsets)
+            n = len(segs)
+            tab = (n, (C.c_int64 * max(n, 1))(*[s[0] for s in segs]), (C.c_int64 * max(n, 1))(*[s[1] for s in segs]),
+                   (C.c_float * max(n, 1))(*[s[2] for s in segs]))
+            self._seg_tables[key] = tab
+        return tab
+
+    def last_grad_norm(self):
+        """the gradient norm the last ``adam_step(clipnorm=)`` measured, over the trained tensors and after ``grad_scale``
+        (one device-to-host read; None before the first such step)"""
+        return None if self._clip is None else float(self._clip[1].item())
+
+    def adam_step(self, lr=None, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-7, groups=None, clipnorm=None):
+        """One Adam update of the flat buffer from ``params.grad``.  Fine-tuning: ``groups`` = {tensor name:
+        rate scale} updates the listed tensors only, each at ``lr * scale`` — a tensor not listed, or of scale 0, keeps the
+        bits of its weights and moments and its gradient is not read (what a ``backward(trainable=)`` leaves undefined).
+        ``clipnorm``: the gradient of the updated tensors is scaled to that norm where it exceeds it, by one
+        ``ng_grad_clip_factor`` launch in front (``last_grad_norm()`` reads the norm); without ``groups`` it clips over
+        everything.  Neither given: ``ng_adam_step`` as ever."""
         if lr is None:
             lr = float(self.hp.get('learning_rate'))
+        if clipnorm is not None and not (0.0 < float(clipnorm) < float("inf")):
+            raise ValueError(f"adam_step: clipnorm must be positive and finite, got {clipnorm}")
+        if groups is None and clipnorm is not None:
+            groups = {n: 1.0 for n in self.params.shapes}
+        tab = None if groups is None else self._segment_table(groups)
+        if clipnorm is not None and self._clip is None:
+            self._clip = torch.zeros(2, dtype=torch.float64, device=self.device)
         self.adam_t += 1
         self._wgen += 1
         P = self.params
         if self.cache_images:       # the update is followed by ONE launch that rebuilds this engine's packed weight images
             self._own_images()
         try:
-            self._ck(self.lib.ng_adam_step(self.ctx.handle, self._st(), P.numel, ptr(P.flat), ptr(P.grad),
-                                           ptr(self.adam_m), ptr(self.adam_v), lr, beta1, beta2, eps,
-                                           self.adam_t, grad_scale), "ng_adam_step")
+            if tab is None:
+                self._ck(self.lib.ng_adam_step(self.ctx.handle, self._st(), P.numel, ptr(P.flat), ptr(P.grad),
+                                               ptr(self.adam_m), ptr(self.adam_v), lr, beta1, beta2, eps,
+                                               self.adam_t, grad_scale), "ng_adam_step")
+            else:
+                clip = None
+                if clipnorm is not None:
+                    clip = ptr(self._clip)
+                    self._ck(self.lib.ng_grad_clip_factor(self.ctx.handle, self._st(), P.numel, ptr(P.grad), grad_scale, *tab,
+                                                          float(clipnorm), clip), "ng_grad_clip_factor")
+                self._ck(self.lib.ng_adam_step_groups(self.ctx.handle, self._st(), P.numel, ptr(P.flat), ptr(P.grad),
+                                                      ptr(self.adam_m), ptr(self.adam_v), lr, beta1, beta2, eps,
+                                                      self.adam_t, grad_scale, *tab, clip), "ng_adam_step_groups")
             if self.cache_images:   # every registered image of this engine is that of the new weights
                 self._images_gen = self._announced
         finally:

@@ -444,13 +444,54 @@ def _load_embeddings(path):
     return emb
 
 
+def _parse_lr_scale(text):
+    """'mp/*=0.1,fc=0.5' -> {'mp/*': 0.1, 'fc': 0.5}, in the order given"""
+    out = {}
+    for item in text.split(','):
+        pat, eq, val = item.strip().partition('=')
+        try:
+            out[pat.strip()] = float(val)
+        except ValueError:
+            eq = ''
+        if not eq or not pat.strip():
+            raise ValueError(f"--lr-scale: {item!r} is not PATTERN=SCALE")
+    return out
+
+
+def _finetune_args(freeze, lr_scale, clipnorm):
+    """(trainable tensor names or None, lr_scale dict or None) of ``train``'s fine-tuning options, checked against the
+    model's parameter tensors: ``freeze`` names what KEEPS its values, so the trainable set is its complement.  ValueError on
+    a pattern that selects nothing, a malformed or negative scale, a freeze that leaves nothing, a clipnorm not > 0."""
+    from .finetune import resolve, scales
+    from .hypers import HyperParameters, declare_gnn_space
+    from .params import param_shapes
+    names = [n for n, _ in param_shapes(declare_gnn_space(HyperParameters()), 1)]      # what build_GNNModel builds
+    trainable = None
+    if freeze:
+        frozen = set(resolve(freeze, names))
+        trainable = [n for n in names if n not in frozen]
+        if not trainable:
+            raise ValueError(f"--freeze {freeze!r} leaves no tensor to train")
+    if isinstance(lr_scale, str):
+        lr_scale = _parse_lr_scale(lr_scale)
+    if lr_scale:
+        scales(names, trainable, lr_scale)
+    if clipnorm is not None and not 0.0 < float(clipnorm) < float('inf'):
+        raise ValueError(f"--clipnorm must be positive and finite, got {clipnorm}")
+    return trainable, (lr_scale or None)
+
+
 def train_model(records, name, epochs=3, checkpoint_path='/tmp/checkpoint', embeddings=None, validation=0.1, load=False,
-                loss_balance=1.0, batch_graphs=1, seed=0, device=None, echo=print, standards='default'):
+                loss_balance=1.0, batch_graphs=1, seed=0, device=None, echo=print, standards='default', freeze=None,
+                lr_scale=None, clipnorm=None):
     """The reference's ``train`` (nmrgnn/main.py:36-90) on ``ShiftDataset`` files: build the model, optionally load the
     checkpoint, fit with ReduceLROnPlateau(val_loss, 0.99, patience 4, min_lr 1e-4) and a checkpoint every epoch, save the
     model to ``name`` and pickle the history to the first free ``name-history-<i>.pb``.  Returns ``(model, history)``.
     ``standards``: ``'default'`` (the bundled ``standards.load_standards()``) or ``'data'`` (``standards()`` of the train
-    view: the per-element mean and spread of the labels the model is trained on)."""
+    view: the per-element mean and spread of the labels the model is trained on).
+    Fine-tuning (with ``load``): ``freeze``: patterns (``GNNModel.trainable_names``) of the tensors that KEEP their values —
+    everything else trains; ``lr_scale``: ``'pattern=scale,...'`` or a dict, the first match wins; ``clipnorm``: clip the
+    gradient of the trained tensors to this norm.  A pattern that matches nothing raises ValueError before any work."""
     import pickle
     from .callbacks import ModelCheckpoint, ReduceLROnPlateau, history_path
     from .dataset import ShiftDataset
@@ -460,10 +501,15 @@ def train_model(records, name, epochs=3, checkpoint_path='/tmp/checkpoint', embe
     if standards not in ('default', 'data'):
         raise ValueError(f"standards is 'default' or 'data', got {standards!r}")
     emb = _load_embeddings(embeddings) if embeddings is not None else None
+    trainable, lr_scale = _finetune_args(freeze, lr_scale, clipnorm)
     data = ShiftDataset.load(list(records), device=device)
     train_data, validation_data = data.split(validation)
     model = build_GNNModel(loss_balance=loss_balance, device=device, embeddings=emb,
                            peak_standards=train_data.standards() if standards == 'data' else None)
+    if trainable is not None:
+        from .params import param_shapes
+        sizes = {n: int(np.prod(sh)) for n, sh in param_shapes(model.hypers, train_data.C)}
+        echo(f"Training {sum(sizes[n] for n in trainable)} of {sum(sizes.values())} parameters: {', '.join(trainable)}")
     if load:
         model.load_weights(checkpoint_path)
     callbacks = []
@@ -471,7 +517,8 @@ def train_model(records, name, epochs=3, checkpoint_path='/tmp/checkpoint', embe
         callbacks.append(ReduceLROnPlateau(monitor='val_loss', factor=0.99, patience=4, min_lr=1e-4, verbose=1))
     callbacks.append(ModelCheckpoint(checkpoint_path))
     results = model.fit(train_data, epochs=epochs, callbacks=callbacks, batch_graphs=batch_graphs, seed=seed,
-                        validation_data=validation_data if len(validation_data) else None, verbose=0)
+                        validation_data=validation_data if len(validation_data) else None, verbose=0, trainable=trainable,
+                        lr_scale=lr_scale, clipnorm=clipnorm)
     for e, i in enumerate(results.epoch):
         echo(f"Epoch {i + 1}: " + " - ".join(f"{k}: {v[e]:.6g}" for k, v in results.history.items()))
     model.save(name)
@@ -497,14 +544,23 @@ def train_model(records, name, epochs=3, checkpoint_path='/tmp/checkpoint', embe
 @click.option('--device', default=None, help='Device, e.g. cuda:0')
 @click.option('--standards', default='default', type=click.Choice(['default', 'data']),
               help='Peak standards of the model: the bundled ones, or the per-element mean and spread of the training labels')
+@click.option('--freeze', default=None,
+              help="Fine-tuning: comma-separated tensors, groups or patterns that keep their values, e.g. "
+                   "'embed/*,edge_fc/*,mp/0/*'; everything else trains")
+@click.option('--lr-scale', default=None, help="Rate scales 'PATTERN=SCALE,...', e.g. 'mp/*=0.1'; the first match wins")
+@click.option('--clipnorm', default=None, type=float, help='Clip the gradient of the trained tensors to this norm')
 def train(records, name, epochs, checkpoint_path, embeddings, validation, load, loss_balance, batch_graphs, seed, device,
-          standards):
+          standards, freeze, lr_scale, clipnorm):
     '''Train the model on ShiftDataset record files (.npz)'''
     if len(records) == 0:
         raise click.UsageError('Must give input record files')
+    try:        # a pattern that selects nothing is a usage error, found before any data is read
+        _finetune_args(freeze, lr_scale, clipnorm)
+    except ValueError as e:
+        raise click.UsageError(str(e))
     train_model(records, name, epochs, checkpoint_path=checkpoint_path, embeddings=embeddings, validation=validation,
                 load=load, loss_balance=loss_balance, batch_graphs=batch_graphs, seed=seed, device=device, echo=click.echo,
-                standards=standards)
+                standards=standards, freeze=freeze, lr_scale=lr_scale, clipnorm=clipnorm)
 
 
 def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None, embeddings_out=None, pbc=False,

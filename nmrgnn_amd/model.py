@@ -303,7 +303,7 @@ class GNNModel:
         return EvalReport(moments, labels, class_of=class_of, data_name=data_name, rows=row_arrays, labelled=n_labelled)
 
     def fit(self, train, epochs=1, validation_data=None, batch_graphs=1, callbacks=(), shuffle=True, seed=0,
-            initial_epoch=0, verbose=1):
+            initial_epoch=0, verbose=1, trainable=None, lr_scale=None, clipnorm=None):
         """Train on a ``dataset.ShiftDataset`` (keras ``model.fit`` as nmrgnn/main.py:79-80 calls it).  Runs ``epochs``
         epochs, numbered ``initial_epoch, initial_epoch + 1, ...`` (the number seeds the shuffle and is what callbacks see;
         unlike keras, ``epochs`` counts the epochs RUN, so ``fit(epochs=1, initial_epoch=1)`` after ``load_weights`` is the
@@ -324,7 +324,11 @@ class GNNModel:
         ``Trainer.metric_results``).  ``val_*`` come from ``self.evaluate(validation_data.eval_batches(...))``: metrics
         accumulated over the whole set, and ``val_loss`` the L2 loss whatever ``loss_balance`` is.  ``lr`` is the rate the
         epoch ran with (callbacks change it afterwards).  Noise and dropout draws are keyed on the optimiser step, which
-        checkpoints carry, so a resumed run continues the sequence."""
+        checkpoints carry, so a resumed run continues the sequence.
+
+        Fine-tuning: ``trainable`` (patterns as ``trainable_names``), ``lr_scale`` ({pattern: scale}, first match wins) and
+        ``clipnorm`` go to the ``Trainer``: only the selected tensors are updated, the others keep their bits, and the
+        backward stops at the lowest stage a trainable tensor needs."""
         from .dataset import ShiftDataset
         from .losses import NameLoss
         from .train import Trainer
@@ -345,7 +349,9 @@ class GNNModel:
         opt = getattr(self, 'optimizer', None) or {}
         metrics = getattr(self, 'metrics', None) or None
         trainer = Trainer(eng, lr=float(opt.get('learning_rate', self.hypers.get('learning_rate'))),
-                          loss_balance=float(getattr(loss_fn, 's', 1.0)), metrics=metrics)
+                          loss_balance=float(getattr(loss_fn, 's', 1.0)), metrics=metrics,
+                          trainable=None if trainable is None else self.trainable_names(trainable), lr_scale=lr_scale,
+                          clipnorm=clipnorm)
         history = History()
         self.stop_training = False
         try:
@@ -407,10 +413,24 @@ class GNNModel:
         return self
 
     def freeze(self, on=True):
-        """declare the weights constant (inference): packed weight images are cached across calls"""
+        """declare ALL weights constant (inference): packed weight images are cached across calls.  Training part of the
+        model while the rest keeps its values is ``fit(trainable=...)`` / ``trainable_names``, not this."""
         self._need_engine()
         self.engine.freeze_weights(on)
         return self
+
+    def parameter_names(self):
+        """the parameter tensors in buffer order (they depend on the hyper-parameters alone: no engine needed)"""
+        from .params import param_shapes
+        return [n for n, _ in param_shapes(self.hypers, 1)]
+
+    def trainable_names(self, patterns):
+        """The parameter tensors ``patterns`` select, for ``fit(trainable=...)`` / ``Trainer(trainable=...)``: tensor names
+        ("fc/0/bias"), group names ("mp/2", "fc", "edge_fc", "out", "embed") or fnmatch patterns ("mp/*"), as a list or one
+        comma-separated string; a pattern that matches nothing raises ValueError.  (``freeze()`` is something else: all
+        weights constant, for inference.)"""
+        from .finetune import resolve
+        return resolve(patterns, self.parameter_names())
 
     # -- weights
     def get_weights(self):

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import torch
 
+from . import finetune
 from .engine import Engine
 from .graph import GraphBatch
 from .parallel import GradBuckets, shard_grad_weight
@@ -24,9 +25,18 @@ class Trainer:
     ``metrics``: a list of ``NameRMSD`` / ``NameCorr`` / ``NameCount`` (``model.metrics``) or a ``NameMetrics``.  A step
     given ``names`` (int32 name ids [N], the int32 of y_true[:, 1]) queues ONE ``ng_name_metrics`` launch on the step's
     training-mode peaks (what keras reports its training metrics on), with ``w`` as the weight column;
-    ``metric_results()`` reads them.  A step without ``names`` launches nothing more."""
+    ``metric_results()`` reads them.  A step without ``names`` launches nothing more.
 
-    def __init__(self, engine: Engine, lr=None, loss_balance=1.0, cache_images=True, metrics=None):
+    Fine-tuning.  ``trainable``: the tensors that train — names of ``engine.params.shapes``, group names
+    ("mp/2", "fc", "edge_fc") or fnmatch patterns ("mp/*"), see ``finetune.resolve``; everything else keeps its bits,
+    moments included, and the backward stops at the lowest stage a trainable tensor needs.  ``lr_scale``: {pattern: scale} on
+    the rate of the tensors a pattern selects, the first match winning.  ``clipnorm``: the gradient of the trained tensors is
+    clipped to that norm (``last_grad_norm()``).  All three None: the plain step.  In a data-parallel run EVERY RANK MUST BE
+    GIVEN THE SAME SET: the all-reduce still moves the whole gradient buffer, whose frozen ranges carry undefined values
+    that nothing reads."""
+
+    def __init__(self, engine: Engine, lr=None, loss_balance=1.0, cache_images=True, metrics=None, trainable=None,
+                 lr_scale=None, clipnorm=None):
         from .metrics import NameMetrics
         self.engine = engine
         self.metrics = None if not metrics else (metrics if isinstance(metrics, NameMetrics) else NameMetrics(metrics))
@@ -40,6 +50,13 @@ class Trainer:
         first_node = next(k for k in P.offsets if not k.startswith("edge_fc/"))
         self.buckets = GradBuckets(P.grad, P.offsets[first_node])
         self.step_count = 0
+        # fine-tuning: the trainable tensors (None: all, the plain backward) and {tensor: rate scale} (None: the plain Adam)
+        names = list(P.shapes)
+        self.trainable = None if trainable is None else frozenset(finetune.resolve(trainable, names))
+        self.clipnorm = None if clipnorm is None else float(clipnorm)
+        self.groups = None
+        if trainable is not None or lr_scale or clipnorm is not None:
+            self.groups = finetune.scales(names, self.trainable, lr_scale)
         # measure_comm = True: two events per step around the wait for the gradient all-reduces on the compute stream
         # (the time the collectives are EXPOSED, i.e. not hidden under the edge-MLP backward); comm_exposed_ms() reads them
         self.measure_comm = False
@@ -70,7 +87,7 @@ class Trainer:
                 dpred.mul_(wgt)
         if names is not None and self.metrics is not None:
             self.metrics.update(eng.tape.peaks, y, w, names)
-        eng.backward(dpred, on_node_grads=self.buckets.launch_node)
+        eng.backward(dpred, on_node_grads=self.buckets.launch_node, trainable=self.trainable)
         self.buckets.launch_edge()
         if self.measure_comm:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -80,9 +97,21 @@ class Trainer:
             self._comm_events.append((e0, e1))
         else:
             self.buckets.wait()
-        eng.adam_step(lr=self.lr, grad_scale=self.buckets.grad_scale())
+        eng.adam_step(lr=self.lr, grad_scale=self.buckets.grad_scale(), groups=self.groups, clipnorm=self.clipnorm)
         self.step_count += 1
         return loss
+
+    def last_grad_norm(self):
+        """the gradient norm of the last step, over the trained tensors (needs ``clipnorm``; one device-to-host read)"""
+        if self.clipnorm is None:
+            raise ValueError("Trainer was built without clipnorm: no norm is measured")
+        return self.engine.last_grad_norm()
+
+    def trainable_count(self):
+        """number of parameters the steps update"""
+        P = self.engine.params
+        names = P.shapes if self.groups is None else [n for n, sc in self.groups.items() if sc > 0]
+        return sum(int(torch.Size(P.shapes[n]).numel()) for n in names)
 
     def metric_results(self):
         """{metric name: value} of the last step that was given ``names`` (one device-to-host copy)"""
