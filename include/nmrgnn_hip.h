@@ -80,15 +80,28 @@ int ng_flush_reductions(ng_ctx* ctx, void* stream);
  * span <= 288.  Every kernel checks per tile that its window really holds the tile's sources and reads the others from
  * memory: results do not depend on the hint, a wrong hint only costs time. */
 int ng_ctx_set_graph_span(ng_ctx* ctx, int64_t max_graph_atoms);
-/* pre-size the scratch workspace (so that later calls never hipMalloc, e.g. under graph capture) */
+/* Pre-size the MAIN scratch workspace to at least `bytes` and allocate the fixed-size small scratch (range-guard word, gradient
+ * scales, replay block).  What it guarantees: a later call whose main-workspace need is <= `bytes` neither grows nor moves that
+ * block.  What it does not cover: the second ("aux") workspace of leaf kernels, the deferred-reduction arena and the cached
+ * weight images and their job tables — those are sized only by a warm-up call of the same shape, in the same state (deferral,
+ * frozen weights, armed), as the calls that follow. */
 int ng_ctx_reserve(ng_ctx* ctx, uint64_t bytes);
+/* Read-only view of the context's scratch (additive: NG_ABI_VERSION stays 9); launches nothing, synchronises nothing.  Writes
+ * min(cap, 10) 64-bit words and returns how many:
+ *   0 main workspace bytes   1 aux workspace bytes   2 small scratch bytes (0 until allocated)   3 chunks of the deferred-
+ *   reduction arena   4 arena bytes   5 bytes of cached weight images and their job tables   6 device allocations made by the
+ *   context's scratch management since ng_ctx_create   7 host synchronisations made by it (device / stream synchronise before a
+ *   block is freed, the synchronous upload of a private job table)   8 deferred reductions queued since ng_ctx_create
+ *   9 times a full queue (24 jobs) was run ahead of its flush. */
+int ng_ctx_scratch_info(ng_ctx* ctx, uint64_t* out, int cap);
 
 /* ---- graph replay of small calls (ABI 7; ng_replay_token / ng_replay_commit: ABI 8) -----------------------------------------------------------------------------
  * The reference trains on ONE graph per step (nmrgnn/library.py:88-89, nmrgnn/main.py:74-80) and predicts one structure per
  * call (main.py:236-245): ~33 / ~8 launches of a few microseconds each, bound by the host's launch rate.  Every entry point of
- * this library is asynchronous on the stream it is given and allocates nothing once its scratch is sized (a warm-up call, or
- * ng_ctx_reserve), so a chain of calls can be CAPTURED on that stream (hipStreamBeginCapture, torch.cuda.CUDAGraph) and
- * replayed as one graph launch per shape.  Three launch arguments of a training step change from step to step and would be
+ * this library is asynchronous on the stream it is given and allocates nothing once its scratch is sized: ALL of it by a warm-up
+ * call of the same shape and state, the main workspace and the small scratch alone by ng_ctx_reserve (which leaves the aux
+ * workspace, the reduction arena and the cached images to a warm-up call).  So a chain of calls can be CAPTURED on that
+ * stream (hipStreamBeginCapture, torch.cuda.CUDAGraph) and replayed as one graph launch per shape.  Three launch arguments of a training step change from step to step and would be
  * frozen into the captured nodes: the seed of ng_add_noise(_live) and ng_head_fwd_dropout, and ng_adam_step's bias-corrected
  * rate.  While a context is ARMED those launches ignore these arguments and read the values ng_replay_stage last wrote to
  * a device block of the context:

@@ -31,6 +31,7 @@ SIGNATURES = {
     "ng_ctx_destroy": (None, [_vp]),
     "ng_last_error": (C.c_char_p, [_vp]),
     "ng_ctx_reserve": (_int, [_vp, _u64]),
+    "ng_ctx_scratch_info": (_int, [_vp, C.POINTER(_u64), _int]),
     "ng_replay_arm": (_int, [_vp, _int]),
     "ng_replay_stage": (_int, [_vp, _vp, _u64, _f, _f, _f, _i64, _int, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),
     "ng_replay_token": (_int, [_vp, C.POINTER(_u64)]),
@@ -236,6 +237,17 @@ class Context:
             self.close()
         except Exception:
             pass
+
+    SCRATCH_WORDS = ("ws_bytes", "aux_bytes", "small_bytes", "chunks", "arena_bytes", "image_bytes", "allocs", "syncs", "jobs",
+                     "early_runs")
+
+    def scratch_info(self):
+        """ng_ctx_scratch_info as a dict (read-only: launches and synchronises nothing)"""
+        out = (_u64 * len(self.SCRATCH_WORDS))()
+        n = self.lib.ng_ctx_scratch_info(self.handle, out, len(self.SCRATCH_WORDS))
+        if n != len(self.SCRATCH_WORDS):
+            self.check(n if n < 0 else -1, "ng_ctx_scratch_info")
+        return {k: int(out[i]) for i, k in enumerate(self.SCRATCH_WORDS)}
 
     # --- profiling ------------------------------------------------------------------
     def prof_enable(self, on=True):

@@ -71,6 +71,7 @@ void* workspace(ng_ctx* ctx, size_t bytes) {
   size_t want = bytes + bytes / 2;
   if (ctx->ws) {
     (void)hipDeviceSynchronize();
+    ctx->n_syncs++;
     (void)hipFree(ctx->ws);
     ctx->ws = nullptr;
     ctx->ws_bytes = 0;
@@ -83,6 +84,7 @@ void* workspace(ng_ctx* ctx, size_t bytes) {
   }
   ctx->ws = p;
   ctx->ws_bytes = want;
+  ctx->n_allocs++;
   return p;
 }
 
@@ -92,6 +94,7 @@ void* aux_workspace(ng_ctx* ctx, size_t bytes) {
   const size_t want = bytes + bytes / 2;
   if (ctx->aux) {
     (void)hipDeviceSynchronize();
+    ctx->n_syncs++;
     (void)hipFree(ctx->aux);
     ctx->aux = nullptr;
     ctx->aux_bytes = 0;
@@ -104,6 +107,7 @@ void* aux_workspace(ng_ctx* ctx, size_t bytes) {
   }
   ctx->aux = p;
   ctx->aux_bytes = want;
+  ctx->n_allocs++;
   return p;
 }
 
@@ -118,6 +122,7 @@ void* small_scratch(ng_ctx* ctx) {
   }
   (void)hipMemset(p, 0, NG_SMALL_BYTES);      // the range-guard word must not start out equal to an epoch
   ctx->small = p;
+  ctx->n_allocs++;
   return p;
 }
 
@@ -168,6 +173,7 @@ float* deferred_partials(ng_ctx* ctx, size_t floats) {
   void* p = nullptr;
   if (hipMalloc(&p, want) != hipSuccess) return nullptr;      // the caller falls back to its own scratch + eager reduction
   q->chunks.push_back({(char*)p, want, bytes});
+  ctx->n_allocs++;
   return (float*)p;
 }
 
@@ -192,10 +198,11 @@ int flush_reductions(ng_ctx* ctx, hipStream_t st) {
     DeviceGuard dg(ctx->device);
     size_t total = 0;
     (void)hipDeviceSynchronize();
+    ctx->n_syncs++;
     for (auto& c : q->chunks) { total += c.bytes; (void)hipFree(c.p); }
     q->chunks.clear();
     void* p = nullptr;
-    if (hipMalloc(&p, total) == hipSuccess) q->chunks.push_back({(char*)p, total, 0});
+    if (hipMalloc(&p, total) == hipSuccess) { q->chunks.push_back({(char*)p, total, 0}); ctx->n_allocs++; }
   } else if (!q->chunks.empty()) {
     q->chunks[0].used = 0;
   }
@@ -215,10 +222,12 @@ static int queue_job(ng_ctx* ctx, hipStream_t st, const ReduceJob& j) {
   ReduceQueue* q = rqueue(ctx);
   if (q->batch.njobs == RB_MAX_JOBS) {
     // queue full: run what is queued (the arena keeps its contents: only the job list is emptied here)
+    ctx->n_queue_early++;
     const int rc = run_queue(ctx, st, q);
     if (rc) return rc;
   }
   ReduceBatch& b = q->batch;
+  ctx->n_jobs++;
   const int k = b.njobs++;
   if (k == 0) b.block0[0] = 0;
   b.job[k] = j;
@@ -305,7 +314,8 @@ extern "C" int ng_flush_reductions(ng_ctx* ctx, void* stream) {
 // ---- graph replay of small training steps (round 5) --------------------------------------------------------------------
 // One 256-atom graph per step is ~33 launches of a few microseconds: the step is bound by the host's launch rate.  The chain
 // can be captured once per shape (torch.cuda.CUDAGraph on the stream the caller passes, or hipStreamBeginCapture) and replayed
-// — if (a) nothing inside allocates or synchronises (scratch is sized by a warm-up step, ng_ctx_reserve) and (b) no kernel
+// — if (a) nothing inside allocates or synchronises (every block of scratch is sized by a warm-up step of the same chain;
+// ng_ctx_reserve covers the main workspace and the small scratch only) and (b) no kernel
 // argument changes from step to step.  Three do: the seed of GaussianNoise and Dropout and Adam's bias-corrected rate.  While
 // a context is armed those launches read them from a device block that ONE eager launch per step (ng_replay_stage) fills —
 // together with the step's inputs, copied into the static buffers the captured chain reads, and the range-guard word reset.
@@ -414,7 +424,22 @@ extern "C" const char* ng_last_error(ng_ctx* ctx) { return ctx ? ctx->err.c_str(
 
 extern "C" int ng_ctx_reserve(ng_ctx* ctx, uint64_t bytes) {
   if (!ctx) return NG_ERR_INVALID;
+  if (!ng::small_scratch(ctx)) return NG_ERR_NOMEM;      // fixed size: it need not wait for the first call that uses it
   return ng::workspace(ctx, (size_t)bytes) ? NG_OK : NG_ERR_NOMEM;
+}
+
+extern "C" int ng_ctx_scratch_info(ng_ctx* ctx, uint64_t* out, int cap) {
+  if (!ctx || !out || cap < 0) return NG_ERR_INVALID;
+  uint64_t chunks = 0, arena = 0;
+  if (const ng::ReduceQueue* q = (const ng::ReduceQueue*)ctx->rq) {
+    chunks = q->chunks.size();
+    for (auto& c : q->chunks) arena += c.bytes;
+  }
+  const uint64_t w[10] = {ctx->ws_bytes, ctx->aux_bytes, ctx->small ? (uint64_t)ng::NG_SMALL_BYTES : 0, chunks, arena,
+                          ng::image_cache_bytes(ctx), ctx->n_allocs, ctx->n_syncs, ctx->n_jobs, ctx->n_queue_early};
+  const int n = cap < 10 ? cap : 10;
+  for (int i = 0; i < n; ++i) out[i] = w[i];
+  return n;
 }
 
 extern "C" int ng_prof_enable(ng_ctx* ctx, int on) {

@@ -136,12 +136,18 @@ struct ng_ctx {
   // job tables of repack launches recorded while armed: one per job set, never rewritten or freed before ng_ctx_destroy — a
   // captured launch reads its table at every replay, whatever other engines of the device have registered since
   std::map<uint64_t, void*> wjobs_private;
+  size_t wjobs_private_bytes = 0;
   // the images each private table rebuilds (map nodes of wimg: stable addresses) and the table of the last armed repack launch:
   // ng_replay_token / ng_replay_commit re-stamp exactly these after a replayed step (round-5 advisor finding: a replay changes
   // the weights but runs no host bookkeeping, so every OTHER cached image kept reading as valid with weights of N steps ago)
   std::map<uint64_t, std::vector<WImage*>> wjobs_private_sel;
   uint64_t replay_token = 0;
   uint32_t replay_serial = 0;      // stagings so far (ng_replay_stage): behind the per-step image version of armed repack launches
+  // scratch management since ng_ctx_create (ng_ctx_scratch_info): device allocations made, and host-side synchronisations
+  // (device / stream synchronise, synchronous copies) — counted where they happen, in capi.hip and repack.hip
+  uint64_t n_allocs = 0, n_syncs = 0;
+  // deferred reductions queued since ng_ctx_create, and how often a full queue (RB_MAX_JOBS) was run before its flush
+  uint64_t n_jobs = 0, n_queue_early = 0;
 };
 
 namespace ng {
@@ -243,6 +249,8 @@ void weights_bump(ng_ctx* ctx);
 int repack_all(ng_ctx* ctx, hipStream_t st, const void* lo, const void* hi);
 // ng_ctx_destroy: the images and the job tables
 void image_cache_free(ng_ctx* ctx);
+// bytes held by the cached images and the job tables (ng_ctx_scratch_info)
+uint64_t image_cache_bytes(const ng_ctx* ctx);
 
 // RAII-less profiling bracket: call begin before the launch(es), end after.
 struct ProfScope {

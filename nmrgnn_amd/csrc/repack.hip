@@ -55,8 +55,9 @@ static ng_ctx::WImage* cached_image(ng_ctx* ctx, const void* src, int kind, size
   ng_ctx::WImage& w = ctx->wimg[std::make_pair(src, kind)];
   if (w.bytes < bytes) {
     DeviceGuard dg(ctx->device);
-    if (w.buf) { (void)hipDeviceSynchronize(); (void)hipFree(w.buf); w.buf = nullptr; w.bytes = 0; }
+    if (w.buf) { (void)hipDeviceSynchronize(); ctx->n_syncs++; (void)hipFree(w.buf); w.buf = nullptr; w.bytes = 0; }
     if (hipMalloc(&w.buf, bytes) != hipSuccess) { w.buf = nullptr; return nullptr; }
+    ctx->n_allocs++;
     (void)hipMemset(w.buf, 0, bytes);      // (flag words inside an image start out equal to no version)
     w.bytes = bytes;
     w.ver = 0;
@@ -87,6 +88,12 @@ int image_pack(ng_ctx* ctx, hipStream_t st, const ImageSlot& slot, const PackJob
 }
 
 void weights_bump(ng_ctx* ctx) { ctx->wver++; }
+
+uint64_t image_cache_bytes(const ng_ctx* ctx) {
+  uint64_t n = ctx->wjobs_cap + ctx->wjobs_private_bytes;
+  for (auto& kv : ctx->wimg) n += kv.second.bytes;
+  return n;
+}
 
 void image_cache_free(ng_ctx* ctx) {
   for (auto& kv : ctx->wimg)
@@ -150,6 +157,9 @@ int repack_all(ng_ctx* ctx, hipStream_t st, const void* lo, const void* hi) {
     if (it == ctx->wjobs_private.end()) {
       void* p = nullptr;
       if (hipMalloc(&p, need) != hipSuccess) return fail(ctx, NG_ERR_NOMEM, "repack_all: private job table");
+      ctx->n_allocs++;
+      ctx->wjobs_private_bytes += need;
+      ctx->n_syncs++;
       NG_HIP(ctx, hipMemcpy(p, host.data(), need, hipMemcpyHostToDevice));      // synchronous: `host` is a local
       it = ctx->wjobs_private.emplace(hash, p).first;
     }
@@ -160,8 +170,9 @@ int repack_all(ng_ctx* ctx, hipStream_t st, const void* lo, const void* hi) {
   } else {
   if (ctx->wjobs_dirty || ctx->wjobs_n != n || ctx->wjobs_hash != hash || ctx->wjobs_cap < need) {
     if (ctx->wjobs_cap < need) {
-      if (ctx->wjobs_dev) { (void)hipStreamSynchronize(st); (void)hipFree(ctx->wjobs_dev); ctx->wjobs_dev = nullptr; ctx->wjobs_cap = 0; }
+      if (ctx->wjobs_dev) { (void)hipStreamSynchronize(st); ctx->n_syncs++; (void)hipFree(ctx->wjobs_dev); ctx->wjobs_dev = nullptr; ctx->wjobs_cap = 0; }
       if (hipMalloc(&ctx->wjobs_dev, need * 2) != hipSuccess) return fail(ctx, NG_ERR_NOMEM, "repack_all: job table");
+      ctx->n_allocs++;
       ctx->wjobs_cap = need * 2;
     }
     unsigned blocks = 0;

@@ -39,7 +39,8 @@ def edge_path(edge_table, use_live_edges, live_kernels, E, n_edges, min_edges, i
     "table_host" the same table, its guard read on the host (edge shapes without the fused kernels);
     "live"       the per-edge MLP over the compacted live slots;
     "slots"      the per-edge MLP over every slot.
-    ``live_kernels``: ng_edge_live_supported of the edge shape; ``capturing``: a stream capture is in progress.
+    ``live_kernels``: ng_edge_live_supported of the edge shape; ``capturing``: a stream capture is in progress,
+    or the eager warm-up of one (``Engine.capture_warmup``).
     The caller still falls back to "slots" where the batch has no live view ("table", "live") or the host-read guard
     is up ("table_host")."""
     # the live kernels and the table index e with 32 bits (check_live in edge_fwd_h2.hip)
@@ -147,6 +148,10 @@ class Engine:
         self._jgate = None                    # the gate words of the last backward's J check (edge_grad_table_report)
         self._wgen = 0                        # bumped whenever the weights change: a table kept over calls (frozen weights)
         self._table_cache = None
+        # set by replay.py around the eager warm-up calls of a chain that is about to be captured: they must take the path
+        # the captured call will take (edge_path: capturing), or they size the scratch of another one
+        self.capture_warmup = False
+        self.last_edge_path = None
         # announced weight changes (load_state_dict, weights_changed()): they leave every packed image invalid, and a captured
         # chain — recorded while the images were valid — holds no pack launch.  ``_images_gen`` is the value of ``_announced``
         # at the last adam_step that rebuilt the images (cache_images): replay.py refuses a chain in between
@@ -293,7 +298,7 @@ class Engine:
         d_eff = d_src
         live_kernels = bool(lib.ng_edge_live_supported(H, E, self.Le, self.fc_act))
         path = edge_path(self.edge_table, self.use_live_edges, live_kernels, E, ne, self.edge_table_min_edges, batch.is_csr,
-                         torch.cuda.is_current_stream_capturing())
+                         self.capture_warmup or torch.cuda.is_current_stream_capturing())
         # live-edge view: the fused edge kernels walk the compacted live slots only (same e bit for bit); the device-guarded
         # table needs one even where no slot is dead
         live = batch.live_edges(force=path == "table") if path in ("table", "live") else None
@@ -322,6 +327,7 @@ class Engine:
             path = "slots"
         if path == "table":
             rows = table["gate"][1:]
+        self.last_edge_path = path      # the path this call runs (replay.py compares its warm-up with its capture)
         e = self._new(ne, E)
         z_save, z_layout = None, 0
         if path != "table_host":

@@ -7,7 +7,10 @@ is captured ONCE per shape as a HIP graph (``torch.cuda.CUDAGraph`` on the strea
 replayed with one graph launch per step.
 
 What makes the chain capturable (include/nmrgnn_hip.h, "graph replay of small calls"): every entry point is asynchronous
-and allocates nothing once the context's scratch is sized — a warm-up step before the capture sizes it; the tensors the
+and allocates nothing once the context's scratch is sized.  ``ng_ctx_reserve`` sizes only the main workspace and the small
+scratch; the aux workspace, the reduction arena and the cached weight images are sized by a warm-up call alone, so the
+warm-up steps before the capture run the very chain that is captured (``_warmup``: the engine picks its paths as if a
+capture were in progress) and ``capture_allocs`` records that the capture itself allocated nothing.  The tensors the
 engine allocates per call come from the graph's private pool of the caching allocator.  What changes from step to step
 are three launch arguments (noise seed, dropout seed, Adam's bias-corrected rate) and the inputs: ``ng_replay_stage``, ONE
 eager launch per step, writes the former into a device block the armed context's kernels read, and copies the latter into
@@ -18,6 +21,7 @@ a validation batch, a step of another shape — see the weights of NOW.
 Results are the bits of the eager chain (tests/test_gpu_replay.py: parameter trajectories and peaks ``torch.equal``)."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -38,6 +42,21 @@ def _stage(eng, seed, lr, step, pairs, beta1=0.9, beta2=0.999):
     nb = (C.c_uint64 * max(n, 1))(*[p[1].numel() * p[1].element_size() for p in pairs])
     eng._ck(eng.lib.ng_replay_stage(eng.ctx.handle, eng._st(), C.c_uint64(seed & ((1 << 64) - 1)), float(lr), beta1, beta2,
                                     int(step), n, src, dst, nb), "ng_replay_stage")
+
+
+@contextlib.contextmanager
+def _warmup(eng):
+    """eager calls that run the chain a capture will record: ``Engine`` chooses as under ``is_current_stream_capturing``"""
+    prev = eng.capture_warmup
+    eng.capture_warmup = True
+    try:
+        yield
+    finally:
+        eng.capture_warmup = prev
+
+
+def _allocs(eng):
+    return eng.ctx.scratch_info()["allocs"]
 
 
 def _like(dst, x):
@@ -140,12 +159,20 @@ class TrainStepReplay:
         with torch.cuda.stream(self._stream):
             eng._ck(eng.lib.ng_replay_arm(eng.ctx.handle, 1), "ng_replay_arm")
             try:
-                for _ in range(2):
-                    _stage(eng, 1, 0.0, 1, [])
-                    self._one_step()
+                self.warmup_edge_paths = []
+                with _warmup(eng):
+                    for _ in range(2):
+                        _stage(eng, 1, 0.0, 1, [])
+                        self._one_step()
+                        self.warmup_edge_paths.append(eng.last_edge_path)
                 torch.cuda.synchronize(eng.device)
+                before = _allocs(eng)
                 with torch.cuda.graph(self._graph, stream=self._stream):
                     self.loss = self._one_step()
+                self.captured_edge_path = eng.last_edge_path
+                # device allocations the library made between the end of the warm-up and the end of the capture: 0, or the
+                # warm-up ran another chain than the captured one (tests/test_gpu_cold_context.py)
+                self.capture_allocs = _allocs(eng) - before
                 tok = C.c_uint64(0)
                 eng._ck(eng.lib.ng_replay_token(eng.ctx.handle, C.byref(tok)), "ng_replay_token")
                 self._token = int(tok.value)
@@ -171,7 +198,8 @@ class TrainStepReplay:
         eng._ck(eng.lib.ng_replay_arm(eng.ctx.handle, 1), "ng_replay_arm")
         try:
             _stage(eng, 1, 0.0, 1, [])
-            self._one_step()
+            with _warmup(eng):      # the images of the CAPTURED chain's path
+                self._one_step()
         finally:
             eng.lib.ng_replay_arm(eng.ctx.handle, 0)
             self._gb = gb
@@ -236,11 +264,17 @@ class ForwardReplay:
         cur = torch.cuda.current_stream(dev)
         self._stream.wait_stream(cur)
         with torch.cuda.stream(self._stream):
-            for _ in range(2):
-                self._one()
+            self.warmup_edge_paths = []
+            with _warmup(engine):
+                for _ in range(2):
+                    self._one()
+                    self.warmup_edge_paths.append(engine.last_edge_path)
             torch.cuda.synchronize(dev)
+            before = _allocs(engine)
             with torch.cuda.graph(self._graph, stream=self._stream):
                 self.peaks = self._one()
+            self.captured_edge_path = engine.last_edge_path
+            self.capture_allocs = _allocs(engine) - before      # (TrainStepReplay._capture)
         cur.wait_stream(self._stream)
         self._wgen = engine._wgen
 
