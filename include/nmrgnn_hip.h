@@ -749,6 +749,33 @@ int ng_restraint_loss_ex(ng_ctx*, void* stream, int R, int64_t n, int mode, cons
 int ng_loss_name(ng_ctx*, void* stream, int64_t N, int G, const int32_t* graph_ptr, const float* y,
                  const float* w, const float* pred, float s, float* loss_out, float* dpred);
 
+/* Ensemble-averaged NameLoss (Engine.loss_groups; csrc/group_loss.hip): the loss of the MEAN prediction over
+ * the frames of a structure.  A batch of G graphs with graph_ptr [G+1] is partitioned into Q groups by group_ptr [Q+1] (int32
+ * graph indices, group_ptr[0] = 0, group_ptr[Q] = G, strictly increasing).  Group q has R_q = group_ptr[q+1] - group_ptr[q]
+ * members of the same atom count n_q; member r's atom i sits at row graph_ptr[group_ptr[q]] + r * n_q + i.  mean_ptr [Q+1] is the
+ * prefix sum of n_q, M = mean_ptr[Q]; flat mean index j = mean_ptr[q] + i.  All three on the device.
+ *   ng_group_mean:   c == NULL:  mean_out[j] = (sum_r pred_r) / R_q, float32, summed in member order (R_q = 1: the bits of pred)
+ *                    c [G]:      (..((c_0 p_0) + c_1 p_1) + ..), c_r = c[group_ptr[q] + r] as given (the caller normalises it per
+ *                                group); each product and sum rounded on its own, no fused multiply-add: the order of
+ *                                ng_restraint_loss_ex
+ *                    y_out[j], w_out[j], names_out[j] = the rows of the group's FIRST member (names and names_out may be NULL
+ *                    together)
+ *   ng_group_spread: dpred[row of (r, i)] = (dmean[j] / R_q) * scale   (c == NULL)
+ *                                         = (dmean[j] * c_r) * scale   (c given);  every row of dpred is written, scale = 1
+ *                    multiplies by one exactly.
+ * The loss between the two is ng_loss_l2 / ng_loss_name called with N := M, G := Q, graph_ptr := mean_ptr.
+ * One launch each of one thread per flat mean index (M is known to the device only: the grid covers N >= M indices), no
+ * atomics, no scratch, no host synchronisation: bitwise deterministic, asynchronous, capturable.  The device does not verify
+ * that the members of a group have equal sizes (the caller does); a group whose members would reach outside the batch is
+ * skipped, never read or written out of bounds.
+ * Refused (NG_ERR_INVALID, before any launch): NULL context; Q < 1; Q > G; N >= 2^31; N < G; a NULL graph_ptr, group_ptr,
+ * mean_ptr, pred, y, w, dmean or output; names NULL without names_out NULL or the reverse. */
+int ng_group_mean(ng_ctx*, void* stream, int64_t N, int G, int Q, const int32_t* graph_ptr, const int32_t* group_ptr,
+                  const int32_t* mean_ptr, const float* pred, const float* c, const float* y, const float* w,
+                  const int32_t* names, float* mean_out, float* y_out, float* w_out, int32_t* names_out);
+int ng_group_spread(ng_ctx*, void* stream, int64_t N, int G, int Q, const int32_t* graph_ptr, const int32_t* group_ptr,
+                    const int32_t* mean_ptr, const float* dmean, const float* c, float scale, float* dpred);
+
 /* Per-name shift metrics, nmrgnn/metrics.py:22-116 (NameRMSD 36-43, NameCount 64-70, NameCorr 91-116), for K <= 32 classes
  * in one pass over the atoms.  Per class k the seven float64 sums
  *   moments[K][7] = {S0 = sum m, Sd2 = sum m (y - p)^2, Sy = sum m y, Sp = sum m p, Syy = sum m y^2, Spp = sum m p^2,

@@ -152,6 +152,8 @@ SIGNATURES = {
     "ng_amp_attend_bwd": (_int, [_vp, _vp, _i64, _int, _int, _int] + [_vp] * 13),
     "ng_loss_l2": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ng_loss_name": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "ng_group_mean": (_int, [_vp, _vp, _i64, _int, _int] + [_vp] * 12),
+    "ng_group_spread": (_int, [_vp, _vp, _i64, _int, _int] + [_vp] * 5 + [_f, _vp]),
     "ng_name_metrics": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp, _int, _int, _vp]),
     "ng_class_moments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _int, _vp, _int, _int, _vp]),
     "ng_reweight_eval": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),

@@ -16,6 +16,11 @@ checks nothing and never reads the device.
 
 On a CPU device ``batch`` does the same with torch indexing (host tests, shard bookkeeping).
 
+Ensemble groups: ``group_ptr`` [S + 1] (host int64 over the view's records) makes consecutive records of
+one structure — its frames, with equal sizes and labels — one group; training and evaluation then take the loss on the mean
+prediction of a group.  A grouped store splits, permutes and cuts by groups and yields the batch's ``group_ptr`` beside each
+batch; an ungrouped one (every record its own group) behaves as it always did.
+
 ``from_structures`` fills a store from structures and shift tables, the lists built on the GPU and written into the store by
 ``ng_store_from_batch`` (csrc/records.hip); ``standards()`` gives the per-element label statistics of a view
 (``ng_label_moments``) for ``build_GNNModel(peak_standards=)``."""
@@ -126,10 +131,11 @@ class ShiftDataset:
     name_table = None      # {'RES-NAME': id} of a store built by from_structures
     join_report = None     # its label-join counts (structure.JOIN_COUNTS, 'rows', 'labelled', 'structures')
 
-    def __init__(self, arrays, rec_ptr, file_ptr, device=None, _ids=None, _parent=None):
+    def __init__(self, arrays, rec_ptr, file_ptr, device=None, _ids=None, _parent=None, group_ptr=None):
         if _parent is not None:                       # a view: shares every array
             self.__dict__.update(_parent.__dict__)
             self.record_ids = np.asarray(_ids, np.int64)
+            self.group_ptr = self._view_groups(self.record_ids)
             return
         self.device = _norm_device(device)
         self.rec_ptr_host = np.ascontiguousarray(rec_ptr, dtype=np.int64)
@@ -151,6 +157,116 @@ class ShiftDataset:
         self._sizes = np.diff(self.rec_ptr_host)
         self._side = {}                               # the prefetcher's stream and context (made at the first epoch)
         self.record_ids = np.arange(self.R, dtype=np.int64)
+        # ensemble groups.  Per STORE record: the first record and the size of its group; per view:
+        # group_ptr [S + 1] over the view's records.  Ungrouped: every record a group of its own.
+        self.grouped = False
+        self._group_first = np.arange(self.R, dtype=np.int64)
+        self._group_size = np.ones(self.R, np.int64)
+        self.group_ptr = np.arange(self.R + 1, dtype=np.int64)
+        if group_ptr is not None:
+            self._set_groups(group_ptr)
+
+    # ------------------------------------------------------------------ ensemble groups
+    def _set_groups(self, group_ptr):
+        """make the view's records the groups ``group_ptr`` [S + 1]; ``ValueError`` naming the group whose members are not
+        consecutive store records of one size"""
+        gp = np.asarray(group_ptr)
+        n = len(self.record_ids)
+        if gp.ndim != 1 or len(gp) < 1 or not np.issubdtype(gp.dtype, np.integer):
+            raise ValueError("group_ptr must be a 1-D integer array")
+        gp = gp.astype(np.int64)
+        if gp[0] != 0 or gp[-1] != n or (np.diff(gp) < 1).any():
+            raise ValueError(f"group_ptr must rise strictly from 0 to the {n} records")
+        if self.grouped:
+            raise ValueError("the store is grouped already")
+        counts = np.diff(gp)
+        ids = self.record_ids
+        first = np.repeat(ids[gp[:-1]], counts)
+        offs = np.arange(n) - np.repeat(gp[:-1], counts)
+        group_of = np.repeat(np.arange(len(counts)), counts)
+        bad = np.flatnonzero(ids != first + offs)
+        if len(bad):
+            raise ValueError(f"group {int(group_of[bad[0]])}: its members are not consecutive records of the store")
+        bad = np.flatnonzero(self._sizes[ids] != self._sizes[first])
+        if len(bad):
+            raise ValueError(f"group {int(group_of[bad[0]])}: record {int(bad[0])} has {int(self._sizes[ids[bad[0]]])} atoms, "
+                             f"the group's first member {int(self._sizes[first[bad[0]]])}")
+        self._group_first, self._group_size = self._group_first.copy(), self._group_size.copy()
+        self._group_first[ids] = first
+        self._group_size[ids] = np.repeat(counts, counts)
+        self.group_ptr = gp
+        self.grouped = True
+
+    def _view_groups(self, ids):
+        """group_ptr of a view of the records ``ids`` (store ids); ``ValueError`` when the view breaks a group: every group
+        it touches must be there whole, its members in their order"""
+        n = len(ids)
+        if not self.grouped:
+            return np.arange(n + 1, dtype=np.int64)
+        first = self._group_first[ids]
+        head = np.flatnonzero(ids == first)                     # view positions that hold a group's first member
+        gp = np.concatenate([head, [n]]).astype(np.int64)
+        counts = np.diff(gp)
+        ok = n == 0 or (len(head) > 0 and head[0] == 0 and np.array_equal(counts, self._group_size[ids[head]]) and
+                        np.array_equal(ids, np.repeat(ids[head], counts) + np.arange(n) - np.repeat(head, counts)))
+        if not ok:
+            raise ValueError("the records of a view of a grouped store must be whole groups, their members in order")
+        return gp
+
+    def _label_mismatch(self, gp):
+        """index of the first group of ``gp`` (over the view's records) whose members differ from its first member in a ``y``,
+        ``w`` or ``atoms`` row, or -1: one comparison on the store's device, one read"""
+        counts = np.diff(gp)
+        multi = np.flatnonzero(counts > 1)
+        if len(multi) == 0:
+            return -1
+        ids = self.record_ids
+        a_parts, b_parts, g_parts = [], [], []
+        for q in multi:                                         # rows of the members r >= 1 against the first member's
+            r0 = int(self.rec_ptr_host[ids[gp[q]]])
+            n = int(self._sizes[ids[gp[q]]])
+            extra = (int(counts[q]) - 1) * n
+            a_parts.append(r0 + n + np.arange(extra))
+            b_parts.append(r0 + np.arange(extra) % n)
+            g_parts.append(np.full(extra, q, np.int64))
+        a = torch.from_numpy(np.concatenate(a_parts)).to(self.device)
+        b = torch.from_numpy(np.concatenate(b_parts)).to(self.device)
+        bits = lambda t: t.view(torch.int32)                    # bit patterns: equal labels, NaN included
+        neq = (bits(self.y)[a] != bits(self.y)[b]).any(dim=1) | (bits(self.w)[a] != bits(self.w)[b]) \
+            | (bits(self.atoms)[a] != bits(self.atoms)[b]).any(dim=1)
+        hit, where = (int(v) for v in torch.stack([neq.any().to(torch.int64), torch.argmax(neq.to(torch.int8))]).cpu())
+        return int(np.concatenate(g_parts)[where]) if hit else -1
+
+    def with_groups(self, group_ptr):
+        """A grouped store over the same arrays: the view's records ``[group_ptr[q], group_ptr[q+1])`` are the frames of one
+        structure (``group_ptr`` host integers [S + 1], from 0 to ``len(self)``, strictly increasing).  Checked here, once:
+        the members of a group are consecutive records of the store with equal sizes (host) and equal ``y``, ``w`` and
+        ``atoms`` rows (one device comparison, one host read); ``ValueError`` naming the group otherwise.  No data is
+        copied."""
+        new = ShiftDataset(None, None, None, _ids=self.record_ids, _parent=self)
+        new._set_groups(group_ptr)
+        q = new._label_mismatch(new.group_ptr)
+        if q >= 0:
+            raise ValueError(f"group {q}: its members differ in their y, w or atoms rows; the frames of one structure carry "
+                             "the same labels")
+        return new
+
+    def group_sizes(self):
+        """members of every group of the view (host)"""
+        return np.diff(self.group_ptr)
+
+    def _batch_groups(self, ids):
+        """int32 group_ptr [Q + 1] of the batch of the view's records ``ids``; ``ValueError`` when they are not whole groups"""
+        ids = np.asarray(ids, np.int64).reshape(-1)
+        if len(ids) == 0 or ids.min() < 0 or ids.max() >= len(self.record_ids):
+            raise ValueError(f"batch: record ids must lie in [0, {len(self.record_ids)})")
+        return self._view_groups(self.record_ids[ids]).astype(np.int32)
+
+    def _group_lists(self, order, batch_graphs):
+        """record-id lists of batches of ``batch_graphs`` GROUPS in the group order ``order``"""
+        gp = self.group_ptr
+        return [np.concatenate([np.arange(gp[q], gp[q + 1]) for q in order[i:i + batch_graphs]]).astype(np.int64)
+                for i in range(0, len(order), batch_graphs)]
 
     # ------------------------------------------------------------------ building, files
     @classmethod
@@ -171,10 +287,11 @@ class ShiftDataset:
 
     @classmethod
     def from_structures(cls, structures, shifts, neighbor_number=16, frames='first', names=None, boxes=False, strict=True,
-                        chunk_atoms=1 << 20, device=None):
+                        chunk_atoms=1 << 20, device=None, ensembles=False):
         """The store of structures with assigned shifts: one record per structure (``frames='first'``) or
         per frame of it (``frames='all'``, every frame with the structure's labels), kNN lists of ``neighbor_number``
-        neighbours, one source (``file_ptr = [0, R]``).
+        neighbours, one source (``file_ptr = [0, R]``).  ``ensembles=True`` (with ``frames='all'``): the frames of every
+        structure are one ensemble group (``group_ptr``), so that training fits their MEAN to the labels.
 
         ``structures``: ``structure.Structure`` objects or PDB paths.  ``shifts``: per structure a table (the dict of
         ``structure.read_shift_table``), a path to one, or ``None`` (no labels).  Labels are joined on the host by ``(resid,
@@ -196,6 +313,8 @@ class ShiftDataset:
                                 name_table, read_pdb, read_shift_table)
         if frames not in ('first', 'all'):
             raise ValueError(f"from_structures: frames is 'first' or 'all', got {frames!r}")
+        if ensembles and frames != 'all':
+            raise ValueError("from_structures: ensembles=True groups the frames of a structure and needs frames='all'")
         structures = list(structures)
         shifts = list(shifts) if shifts is not None else [None] * len(structures)
         if not structures:
@@ -287,6 +406,8 @@ class ShiftDataset:
                 raise ValueError(f"from_structures: {bad} neighbour-list slot(s) point outside their structure")
             ds = cls(arrays, rec_ptr, [0, len(items)], device=device)
             report["labelled"] = labelled
+        if ensembles:                                 # same atoms and labels by construction: no comparison needed
+            ds._set_groups(np.concatenate([[0], np.cumsum([len(s) for s in structs])]).astype(np.int64))
         ds.name_table = table
         ds.join_report = report
         return ds
@@ -336,10 +457,13 @@ class ShiftDataset:
 
     def save(self, path):
         """one ``.npz``: the six arrays, ``rec_ptr``, ``file_ptr`` and ``format_version``.  A view saves its own records,
-        in its order, as one source."""
+        in its order, as one source.  A grouped store adds ``group_ptr`` (same format version: a reader that does not know
+        the array sees an ungrouped store)."""
         whole = len(self.record_ids) == self.R and np.array_equal(self.record_ids, np.arange(self.R))
         arrays, rec_ptr = self._host_arrays()
         file_ptr = self.file_ptr if whole else np.asarray([0, len(self.record_ids)], np.int64)
+        if self.grouped:
+            arrays["group_ptr"] = self.group_ptr.astype(np.int64)
         with open(path, "wb") as f:
             np.savez(f, rec_ptr=rec_ptr.astype(np.int64), file_ptr=file_ptr, format_version=np.asarray(FORMAT_VERSION, np.int64),
                      **arrays)
@@ -352,12 +476,21 @@ class ShiftDataset:
         if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
             paths = [paths]
         parts, rec_ptrs, file_ptrs, base_r, base_n = [], [np.zeros(1, np.int64)], [np.zeros(1, np.int64)], 0, 0
+        group_ptrs, grouped = [np.zeros(1, np.int64)], False
         for p in paths:
             with np.load(p) as z:
                 if "format_version" not in z.files or int(z["format_version"]) != FORMAT_VERSION:
                     raise ValueError(f"{p}: not a ShiftDataset file of format version {FORMAT_VERSION}")
                 arrs = {k: z[k] for k in _ARRAYS}
                 rp, fp = z["rec_ptr"].astype(np.int64), z["file_ptr"].astype(np.int64)
+                gq = z["group_ptr"].astype(np.int64) if "group_ptr" in z.files else None
+            if gq is None:                            # a file without groups: every record a group of its own
+                gq = np.arange(len(rp), dtype=np.int64)
+            else:
+                grouped = True
+                if gq.ndim != 1 or len(gq) < 1 or gq[0] != 0 or gq[-1] != len(rp) - 1 or (np.diff(gq) < 1).any():
+                    raise ValueError(f"{p}: inconsistent group_ptr")
+            group_ptrs.append(gq[1:] + base_r)
             if parts and (arrs["atoms"].shape[1] != parts[0]["atoms"].shape[1]
                           or arrs["nlist"].shape[1] != parts[0]["nlist"].shape[1]):
                 raise ValueError(f"{p}: C or K differ from those of {paths[0]}")
@@ -371,7 +504,8 @@ class ShiftDataset:
         if not parts:
             raise ValueError("load: no files")
         arrays = {k: np.concatenate([a[k] for a in parts]) for k in _ARRAYS}
-        return cls(arrays, np.concatenate(rec_ptrs), np.concatenate(file_ptrs), device=device)
+        return cls(arrays, np.concatenate(rec_ptrs), np.concatenate(file_ptrs), device=device,
+                   group_ptr=np.concatenate(group_ptrs) if grouped else None)
 
     def __len__(self):
         return len(self.record_ids)
@@ -386,10 +520,21 @@ class ShiftDataset:
     def split(self, validation):
         """``(train, val)`` views: of every source's records (within this view, in its order) the first
         ``int(validation * count)`` go to validation, the rest to train (nmrgnn/library.py:60-70 takes the same share of
-        every file).  No data is copied."""
+        every file).  No data is copied.  A grouped store splits by GROUPS: of every source's groups (a group belongs to the
+        source of its first member) the first ``int(validation * groups)`` go to validation, whole."""
         validation = float(validation)
         if not 0.0 <= validation <= 1.0:
             raise ValueError(f"split: validation must lie in [0, 1], got {validation}")
+        if self.grouped:
+            gp = self.group_ptr
+            gsrc = np.searchsorted(self.file_ptr, self.record_ids[gp[:-1]], side="right") - 1
+            train, val = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+            for s in range(len(self.file_ptr) - 1):
+                mine = np.flatnonzero(gsrc == s)
+                k = int(validation * len(mine))
+                val += [self.record_ids[gp[q]:gp[q + 1]] for q in mine[:k]]
+                train += [self.record_ids[gp[q]:gp[q + 1]] for q in mine[k:]]
+            return self._view(np.concatenate(train)), self._view(np.concatenate(val))
         src = np.searchsorted(self.file_ptr, self.record_ids, side="right") - 1
         train, val = [], []
         for s in range(len(self.file_ptr) - 1):
@@ -454,17 +599,22 @@ class ShiftDataset:
         return self._collate(ids, False)[:4]
 
     def _epoch_order(self, shuffle, seed, epoch):
-        n = len(self.record_ids)
+        n = len(self.group_ptr) - 1 if self.grouped else len(self.record_ids)
         if not shuffle:
             return np.arange(n, dtype=np.int64)
         return np.random.default_rng([int(seed), int(epoch)]).permutation(n).astype(np.int64)
 
     def epoch_ids(self, batch_graphs, shuffle=True, seed=0, epoch=0, drop_remainder=False):
-        """the id lists of an epoch's batches (what ``batches`` collates)"""
+        """the id lists of an epoch's batches (what ``batches`` collates).  On a grouped store the permutation runs over the
+        GROUPS and ``batch_graphs`` counts groups: a list holds the records of whole groups, members in order."""
         batch_graphs = int(batch_graphs)
         if batch_graphs < 1:
             raise ValueError(f"batch_graphs must be >= 1, got {batch_graphs}")
         order = self._epoch_order(shuffle, seed, epoch)
+        if self.grouped:
+            if drop_remainder:
+                order = order[:len(order) - len(order) % batch_graphs]
+            return self._group_lists(order, batch_graphs)
         out = [order[i:i + batch_graphs] for i in range(0, len(order), batch_graphs)]
         if drop_remainder and out and len(out[-1]) < batch_graphs:
             out.pop()
@@ -475,11 +625,21 @@ class ShiftDataset:
         ``np.random.default_rng([seed, epoch]).permutation(len(self))`` — a FULL permutation, where the reference shuffles
         through a 500-record buffer (nmrgnn/library.py:73); store order with ``shuffle=False``.  The last, shorter batch is
         kept unless ``drop_remainder``.  On the GPU batch t + 1 is collated on a side stream with its own library context
-        while the caller's step t runs (``graph.BatchPrefetcher``); the bits are those of ``batch(ids)``."""
-        return iter(_StorePrefetcher(self, self.epoch_ids(batch_graphs, shuffle, seed, epoch, drop_remainder)))
+        while the caller's step t runs (``graph.BatchPrefetcher``); the bits are those of ``batch(ids)``.  A grouped store
+        yields ``(GraphBatch, y, w, names, group_ptr)``: batches of ``batch_graphs`` groups and the batch's ``group_ptr``
+        (int32 host array [Q + 1] over its graphs, what ``Trainer.step(groups=)`` takes)."""
+        lists = self.epoch_ids(batch_graphs, shuffle, seed, epoch, drop_remainder)
+        if self.grouped:
+            gps = [self._batch_groups(ids) for ids in lists]
+            return (out + (gp,) for out, gp in zip(_StorePrefetcher(self, lists), gps))
+        return iter(_StorePrefetcher(self, lists))
 
     def eval_batches(self, batch_graphs):
-        """``(GraphBatch, y_true[N, 3])`` in store order: what ``GNNModel.evaluate`` takes"""
+        """``(GraphBatch, y_true[N, 3])`` in store order: what ``GNNModel.evaluate`` takes.  A grouped store yields
+        ``(GraphBatch, y_true, group_ptr)``, batches of ``batch_graphs`` groups."""
         for ids in self.epoch_ids(batch_graphs, shuffle=False):
             out = self._collate(ids, True)
-            yield out[0], out[4]
+            if self.grouped:
+                yield out[0], out[4], self._batch_groups(ids)
+            else:
+                yield out[0], out[4]

@@ -62,6 +62,12 @@ class Tape:
                  "peaks", "edge_path", "live", "table", "loss", "dpeaks", "dg", "head_partial", "inputs_only")
 
 
+class GroupMeans:
+    """what ``Engine.group_means`` returns: the member means of a batch's ensemble groups with the groups' labels, shaped
+    like a batch of Q graphs for the loss calls (``N`` = M means, ``G`` = Q, ``graph_ptr`` = mean_ptr on the device)"""
+    __slots__ = ("N", "G", "graph_ptr", "graph_ptr_host", "group_ptr", "member_weights", "means", "y", "w", "names")
+
+
 class Engine:
     _ids = 0
 
@@ -840,6 +846,78 @@ class Engine:
                                        ptr(batch.graph_ptr), ptr(y), ptr(w), ptr(peaks), float(s),
                                        ptr(loss), ptr(dpred)), "ng_loss_name")
         return loss, dpred
+
+    @staticmethod
+    def group_layout(graph_ptr, group_ptr, member_weights=None):
+        """``(group_ptr int32 [Q+1], mean_ptr int32 [Q+1])`` of the ensemble groups ``group_ptr`` over the graphs of
+        ``graph_ptr`` (host arrays), checked: ``group_ptr`` runs from 0 to G strictly increasing, the members of a group have
+        the same atom count, ``member_weights`` (if given) has one entry per graph.  ``ValueError`` otherwise."""
+        gp = np.asarray(graph_ptr, dtype=np.int64).reshape(-1)
+        G = len(gp) - 1
+        raw = np.asarray(group_ptr)
+        if raw.ndim != 1 or len(raw) < 2 or not np.issubdtype(raw.dtype, np.integer):
+            raise ValueError("loss_groups: group_ptr must be a 1-D integer array of at least two entries")
+        qp = raw.astype(np.int64)
+        if qp[0] != 0 or qp[-1] != G or (np.diff(qp) < 1).any():
+            raise ValueError(f"loss_groups: group_ptr must rise strictly from 0 to the batch's {G} graphs")
+        sizes = np.diff(gp)
+        first = sizes[qp[:-1]]
+        bad = np.flatnonzero(sizes != np.repeat(first, np.diff(qp)))
+        if len(bad):
+            q = int(np.searchsorted(qp, bad[0], side="right") - 1)
+            raise ValueError(f"loss_groups: group {q}: graph {int(bad[0])} has {int(sizes[bad[0]])} atoms, the group's first "
+                             f"member {int(first[q])}")
+        if member_weights is not None and int(np.prod(member_weights.shape)) != G:
+            raise ValueError(f"loss_groups: member_weights has {int(np.prod(member_weights.shape))} entries, the batch {G} "
+                             "graphs")
+        mp = np.zeros(len(qp), np.int64)
+        np.cumsum(first, out=mp[1:])
+        return qp.astype(np.int32), mp.astype(np.int32)
+
+    def group_means(self, batch, y, w, peaks, group_ptr, member_weights=None, names=None):
+        """The member means of the ensemble groups ``group_ptr`` (host integers [Q+1] over the batch's graphs) and the groups'
+        labels, by one ``ng_group_mean`` launch: a ``GroupMeans`` with ``means``, ``y``, ``w`` [M] (``names`` [M] int32 when
+        given) that stands for a batch of Q graphs of the means in ``loss_l2`` / ``loss_name`` (``N`` = M, ``G`` = Q,
+        ``graph_ptr`` = ``mean_ptr``).  ``ValueError`` before the launch as ``loss_groups``."""
+        c = None
+        if member_weights is not None:
+            c = member_weights if isinstance(member_weights, torch.Tensor) else torch.as_tensor(np.asarray(member_weights))
+        qp, mp = self.group_layout(batch.graph_ptr_host, group_ptr, c)
+        if c is not None:
+            c = c.to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        Q, M = len(qp) - 1, int(mp[-1])
+        meta = torch.from_numpy(np.concatenate([qp, mp])).to(self.device)      # one small copy
+        gm = GroupMeans()
+        gm.G, gm.N, gm.group_ptr, gm.graph_ptr, gm.graph_ptr_host, gm.member_weights = Q, M, meta[:Q + 1], meta[Q + 1:], mp, c
+        gm.means, gm.y, gm.w = self._new(M), self._new(M), self._new(M)
+        gm.names = None if names is None else torch.empty(M, dtype=torch.int32, device=self.device)
+        self._ck(self.lib.ng_group_mean(self.ctx.handle, self._st(), batch.N, batch.G, Q, ptr(batch.graph_ptr),
+                                        ptr(gm.group_ptr), ptr(gm.graph_ptr), ptr(peaks), ptr(c), ptr(y), ptr(w), ptr(names),
+                                        ptr(gm.means), ptr(gm.y), ptr(gm.w), ptr(gm.names)), "ng_group_mean")
+        return gm
+
+    def loss_groups(self, batch, y, w, peaks, group_ptr, s=1.0, member_weights=None, grad_weight=1.0, names=None):
+        """Ensemble-averaged NameLoss: the graphs ``[group_ptr[q], group_ptr[q+1])`` of the batch are the
+        frames of one structure, and the loss is the mean over GROUPS of the NameLoss of the group's mean prediction against
+        the labels of its first member.  ``group_ptr``: host integers [Q+1].  ``member_weights`` [G] (optional, device or
+        host): the weight of every member in its group's mean, normalised per group by the caller (the ``p`` of a
+        ``ShiftReweighter``); None: the plain mean.  ``grad_weight`` scales ``dpred`` (``parallel.shard_grad_weight``).
+        Three launches: ``ng_group_mean``, ``ng_loss_l2`` (s == 1) or ``ng_loss_name`` on the means, ``ng_group_spread``.
+        Returns ``(loss[1], dpred[N], means[M], (y_g[M], w_g[M]))``; with ``names`` (int32 [N]) the last is
+        ``(y_g, w_g, names_g)``.  ``ValueError`` before any launch for members of different sizes, a malformed ``group_ptr``
+        or ``member_weights`` of the wrong length."""
+        if not 0.0 <= float(s) <= 1.0:
+            raise ValueError("NameLoss balance s must lie in [0, 1]")
+        gm = self.group_means(batch, y, w, peaks, group_ptr, member_weights, names)
+        if float(s) == 1.0:
+            loss, dmean = self.loss_l2(gm, gm.y, gm.w, gm.means)
+        else:
+            loss, dmean = self.loss_name(gm, gm.y, gm.w, gm.means, s)
+        dpred = self._new(batch.N)
+        self._ck(self.lib.ng_group_spread(self.ctx.handle, self._st(), batch.N, batch.G, gm.G, ptr(batch.graph_ptr),
+                                          ptr(gm.group_ptr), ptr(gm.graph_ptr), ptr(dmean), ptr(gm.member_weights),
+                                          float(grad_weight), ptr(dpred)), "ng_group_spread")
+        return loss, dpred, gm.means, ((gm.y, gm.w) if names is None else (gm.y, gm.w, gm.names))
 
     def _segment_table(self, groups):
         """(n_seg, begin, end, scale) host arrays of ng_adam_step_groups for ``groups`` = {tensor: scale}

@@ -504,6 +504,9 @@ def train_model(records, name, epochs=3, checkpoint_path='/tmp/checkpoint', embe
     trainable, lr_scale = _finetune_args(freeze, lr_scale, clipnorm)
     data = ShiftDataset.load(list(records), device=device)
     train_data, validation_data = data.split(validation)
+    if train_data.grouped:
+        echo(f"Ensemble-averaged training: {len(train_data.group_ptr) - 1} groups of {len(train_data)} frames; the loss is "
+             "taken on the mean prediction of every group")
     model = build_GNNModel(loss_balance=loss_balance, device=device, embeddings=emb,
                            peak_standards=train_data.standards() if standards == 'data' else None)
     if trainable is not None:
@@ -564,12 +567,14 @@ def train(records, name, epochs, checkpoint_path, embeddings, validation, load, 
 
 
 def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None, embeddings_out=None, pbc=False,
-                 keep_going=False, device=None, echo=print):
+                 keep_going=False, device=None, echo=print, ensembles=False):
     """``make-records``: structures with assigned shifts -> one ``ShiftDataset`` file.  ``pairs``: ``(structure file, shift
     table CSV)`` per structure.  ``embeddings``: take the name ids from this file's ``'name'`` table (keys it lacks get id 0);
     otherwise the table is ``structure.name_table`` of the structures, and ``embeddings_out`` writes it as the JSON
     ``{'atom': ..., 'name': ...}`` that ``train --embeddings`` reads.  ``pbc``: minimum-image lists in every frame's CRYST1
-    box.  ``keep_going``: drop and count shift-table rows that do not join instead of stopping.  Returns the store."""
+    box.  ``keep_going``: drop and count shift-table rows that do not join instead of stopping.  ``ensembles`` (with
+    ``frames='all'``): the frames of every structure become one ensemble group, and ``train`` fits their mean.  Returns the
+    store."""
     import json
     from .dataset import ShiftDataset
     from .standards import load_embeddings
@@ -579,11 +584,14 @@ def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None
         raise ValueError('--embeddings and --embeddings-out cannot be combined')
     names = _load_embeddings(embeddings)['name'] if embeddings is not None else None
     ds = ShiftDataset.from_structures([p[0] for p in pairs], [p[1] for p in pairs], neighbor_number=neighbor_number,
-                                      frames=frames, names=names, boxes=pbc, strict=not keep_going, device=device)
+                                      frames=frames, names=names, boxes=pbc, strict=not keep_going, device=device,
+                                      ensembles=ensembles)
     ds.save(out)
     rep = ds.join_report
     echo(f"{ds.R} records, {ds.Ntot} atoms, {rep['labelled']} labelled rows from {rep['rows']} table rows of "
          f"{rep['structures']} structures written to {out}")
+    if ensembles:
+        echo(f"{len(ds.group_ptr) - 1} ensemble groups: the frames of a structure are trained on their mean")
     dropped = {k: v for k, v in rep.items() if k not in ('rows', 'labelled', 'structures') and v}
     if dropped:
         echo('table rows dropped: ' + ', '.join(f'{k}: {v}' for k, v in dropped.items()))
@@ -600,6 +608,8 @@ def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None
               help='A structure file (PDB) and the CSV of its assigned shifts (resid,name,shift[,resname]); repeat per structure')
 @click.option('--frames', default='first', type=click.Choice(['first', 'all']),
               help='One record per structure, or one per frame (MODEL) with the same labels')
+@click.option('--ensembles', is_flag=True,
+              help='With --frames all: the frames of a structure are one ensemble group; train then fits their MEAN to the shifts')
 @click.option('--neighbor-number', default=16, help='The model specific size of neighbor lists')
 @click.option('--embeddings', default=None, type=click.Path(exists=True),
               help='JSON or pickle file with an embeddings dict: name ids come from its name table')
@@ -608,15 +618,18 @@ def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None
 @click.option('--pbc', is_flag=True, help='Minimum-image neighbour lists in each frame\'s periodic box (CRYST1)')
 @click.option('--keep-going', is_flag=True, help='Drop and count shift-table rows that match no atom instead of stopping')
 @click.option('--device', default=None, help='Device, e.g. cuda:0')
-def make_records_cmd(out, pairs, frames, neighbor_number, embeddings, embeddings_out, pbc, keep_going, device):
+def make_records_cmd(out, pairs, frames, ensembles, neighbor_number, embeddings, embeddings_out, pbc, keep_going, device):
     '''Build a ShiftDataset record file (.npz) from structures and shift tables'''
     if len(pairs) == 0:
         raise click.UsageError('Must give at least one --pair STRUCT SHIFTS')
     if embeddings is not None and embeddings_out is not None:
         raise click.UsageError('--embeddings and --embeddings-out cannot be combined')
+    if ensembles and frames != 'all':
+        raise click.UsageError('--ensembles groups the frames of a structure and needs --frames all')
     try:
         make_records(out, pairs, frames=frames, neighbor_number=neighbor_number, embeddings=embeddings,
-                     embeddings_out=embeddings_out, pbc=pbc, keep_going=keep_going, device=device, echo=click.echo)
+                     embeddings_out=embeddings_out, pbc=pbc, keep_going=keep_going, device=device, echo=click.echo,
+                     ensembles=ensembles)
     except ValueError as e:
         raise click.ClickException(str(e))
 

@@ -208,7 +208,12 @@ class GNNModel:
         Returns ``{'loss': mean over ALL graphs of the per-graph L2 NameLoss, <metric name>: value}`` for ``metrics``
         (default ``self.metrics``).  The metrics are ACCUMULATED over the whole set (``NameMetrics(accumulate=True)``):
         the reference's metrics keep only the last batch (``assign``), which says nothing about a validation set.
-        With one graph per batch the loss equals keras's mean over batches."""
+        With one graph per batch the loss equals keras's mean over batches.
+
+        Ensemble groups: an item ``(GraphBatch, y_true, group_ptr)`` — what a grouped store's
+        ``eval_batches`` yields; a GraphBatch carries its own ``graph_ptr``, so the third element is the batch's ensemble
+        ``group_ptr`` — is judged on the MEAN prediction of every group against the group's labels: the loss is the mean
+        over all GROUPS, and the metrics take one row per atom of a group."""
         from .losses import NameLoss
         from .metrics import NameMetrics, _split_y_true
         metrics = getattr(self, 'metrics', []) if metrics is None else metrics
@@ -223,8 +228,9 @@ class GNNModel:
         for item in data:
             inputs, y_true = item[0], item[1]
             graph_ptr = item[2] if len(item) > 2 else None
+            groups = None
             if isinstance(inputs, GraphBatch):
-                batch = inputs
+                batch, groups = inputs, graph_ptr
             else:
                 atoms, nlist, edges, inv_degree = inputs
                 self.build(int(atoms.shape[-1]))
@@ -236,6 +242,9 @@ class GNNModel:
             y, w, names = _split_y_true(y_true, eng.device)
             if y.shape[0] != batch.N:
                 raise ValueError(f"evaluate: y_true has {y.shape[0]} rows for {batch.N} atoms")
+            if groups is not None:      # the groups' means and labels stand for the batch from here on
+                batch = eng.group_means(batch, y, w, peaks, groups, names=names)
+                peaks, y, w, names = batch.means, batch.y, batch.w, batch.names
             lw = w
             if label_idx is not None:
                 ln = torch.as_tensor(np.atleast_1d(np.asarray(label_idx, np.int32)), device=eng.device)
@@ -259,7 +268,9 @@ class GNNModel:
         sums to the device accumulator (``report.ClassMoments``), weighting by the mask column of ``y_true`` exactly as
         ``evaluate`` does.  The device is read once at the end; with ``rows=True`` the labelled atoms' predictions are read too
         and the ``report.EvalReport`` returned holds them in store order.  A class's terms are added in the order the batches lay
-        the atoms out, so the last bits of the float64 moments depend on ``batch_graphs``."""
+        the atoms out, so the last bits of the float64 moments depend on ``batch_graphs``.  On a grouped
+        store the moments take the MEAN prediction of every ensemble group against the group's labels: one
+        row per labelled atom of a structure, not one per frame, ``record`` being the group's first record."""
         from .dataset import ShiftDataset
         from .metrics import _split_y_true
         from .report import ClassMoments, EvalReport, class_maps
@@ -275,15 +286,22 @@ class GNNModel:
         cm = ClassMoments(class_of, len(labels.text), eng.device)
         labelled = torch.zeros((), dtype=torch.float64, device=eng.device)
         kept, record0 = [], 0
-        for batch, y_true in (data.eval_batches(batch_graphs) if len(data) else ()):
+        for item in (data.eval_batches(batch_graphs) if len(data) else ()):
+            batch, y_true = item[0], item[1]
             peaks = eng.forward(batch, training=False).reshape(-1)
             y, w, names = _split_y_true(y_true, eng.device)
+            first = None
+            if data.grouped:            # one row per atom of a GROUP: its mean prediction against its labels
+                first = record0 + np.asarray(item[2][:-1], np.int64)
+                means = eng.group_means(batch, y, w, peaks, item[2], names=names)
+                peaks, y, w, names = means.means, means.y, means.w, means.names
             cm.update(peaks, y, w, names)
             on = w > 0
             labelled += on.sum()
             if rows:
-                gp = batch.graph_ptr_host.astype(np.int64)
-                kept.append((record0, gp, on, y, names, peaks))
+                gp = (batch if first is None else means).graph_ptr_host.astype(np.int64)
+                # (the record of a row: its graph's, or the FIRST member's of its group)
+                kept.append((record0 + np.arange(batch.G) if first is None else first, gp, on, y, names, peaks))
             record0 += batch.G
         out = torch.cat([cm.moments_dev.reshape(-1), labelled.reshape(1)]).cpu().numpy()     # the one read of the sums
         moments, n_labelled = out[:-1].reshape(-1, 7), int(out[-1])
@@ -294,7 +312,7 @@ class GNNModel:
                 vals = torch.stack([torch.cat([k[3] for k in kept])[on], torch.cat([k[5] for k in kept])[on]]).cpu().numpy()
                 ids = torch.cat([k[4] for k in kept])[on].cpu().numpy()
                 on = on.cpu().numpy()
-                record = np.concatenate([np.repeat(np.arange(len(gp) - 1) + r0, np.diff(gp)) for r0, gp, *_ in kept])[on]
+                record = np.concatenate([np.repeat(rec, np.diff(gp)) for rec, gp, *_ in kept])[on]
                 atom = np.concatenate([np.arange(gp[-1]) - np.repeat(gp[:-1], np.diff(gp)) for _, gp, *_ in kept])[on]
             else:
                 vals, ids = np.zeros((2, 0), np.float32), np.zeros(0, np.int32)
@@ -325,6 +343,10 @@ class GNNModel:
         accumulated over the whole set, and ``val_loss`` the L2 loss whatever ``loss_balance`` is.  ``lr`` is the rate the
         epoch ran with (callbacks change it afterwards).  Noise and dropout draws are keyed on the optimiser step, which
         checkpoints carry, so a resumed run continues the sequence.
+
+        Ensemble-averaged training: on a grouped ``train`` store (``from_structures(ensembles=True)``,
+        ``with_groups``) ``batch_graphs`` counts GROUPS and every step is ``Trainer.step(groups=)`` — the loss of the mean
+        prediction over a structure's frames; a grouped ``validation_data`` is judged on the means as well.
 
         Fine-tuning: ``trainable`` (patterns as ``trainable_names``), ``lr_scale`` ({pattern: scale}, first match wins) and
         ``clipnorm`` go to the ``Trainer``: only the selected tensors are updated, the others keep their bits, and the
@@ -361,9 +383,10 @@ class GNNModel:
             for epoch in range(initial_epoch, initial_epoch + epochs):
                 total = torch.zeros((), dtype=torch.float64, device=eng.device)
                 steps = 0
-                for batch, y, w, names in train.batches(batch_graphs, shuffle=shuffle, seed=seed, epoch=epoch):
+                for batch, y, w, names, *groups in train.batches(batch_graphs, shuffle=shuffle, seed=seed, epoch=epoch):
                     lw = w if ln is None else w * torch.isin(names, ln).to(torch.float32)
-                    loss = trainer.step(batch, y, lw, names=names if metrics else None)
+                    # a grouped store yields the batch's ensemble group_ptr too: the step then fits the groups' means
+                    loss = trainer.step(batch, y, lw, names=names if metrics else None, groups=groups[0] if groups else None)
                     total += loss.reshape(()).to(torch.float64)
                     steps += 1
                 logs = {'loss': float(total.item()) / steps}

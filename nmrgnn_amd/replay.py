@@ -68,6 +68,10 @@ def _like(dst, x):
     return x.contiguous()
 
 
+_NO_GROUPS = ("TrainStepReplay: ensemble groups (Trainer.step(groups=), DESIGN.md 7.25) are not replayed: the captured chain is "
+              "the plain step's; run grouped steps eagerly")
+
+
 class TrainStepReplay:
     """``Trainer.step`` for batches of ONE fixed shape (N atoms, K neighbour slots, the graph partition ``graph_ptr``),
     replayed as a HIP graph.  ``step(tuple, y, w)`` = ``trainer.step(GraphBatch(*tuple, graph_ptr=...), y, w)`` bit for
@@ -90,8 +94,10 @@ class TrainStepReplay:
     ``names`` (int32 name ids [N]) captures the trainer's metric launch into the step (``Trainer(..., metrics=...)``);
     the ids become one more staged buffer, and a ``step`` without ``names`` keeps the previous step's ids."""
 
-    def __init__(self, trainer, example, y, w, graph_ptr=None, names=None):
+    def __init__(self, trainer, example, y, w, graph_ptr=None, names=None, groups=None):
         eng = trainer.engine
+        if groups is not None:
+            raise ValueError(_NO_GROUPS)
         if trainer.buckets.world() != 1:
             raise ValueError("TrainStepReplay: single-process training only")
         if getattr(trainer, "measure_comm", False):
@@ -207,8 +213,10 @@ class TrainStepReplay:
         eng._wgen = wgen            # the weights did not move: what is kept per weight generation stays valid
         self._switches_seen = eng.ctx.owner_switches
 
-    def step(self, graph_tuple, y, w, names=None):
+    def step(self, graph_tuple, y, w, names=None, groups=None):
         eng, tr = self.eng, self.trainer
+        if groups is not None:
+            raise ValueError(_NO_GROUPS)
         if eng.cache_images and eng._images_gen != eng._announced:
             raise ValueError("TrainStepReplay.step: the weights were changed by a load or weights_changed() and no step has "
                              "rebuilt their packed images since; the captured chain holds no pack launch and would read the "

@@ -41,6 +41,23 @@ def inv_degree(nlist):
     return out
 
 
+def make_ensemble_records(n_atoms, frames, K=16, num_elem=10, p_pad=0.05, rng=None, n_names=8, labelled=0.8):
+    """``frames`` records ``((atoms, nlist, edges, inv_degree), y, w)`` of ONE synthetic structure: every frame a graph of its
+    own (``make_graph``) over the same atoms with the same labels ``y = (shift ~ N(0, 1), name id, mask)`` and weights — the
+    members of one ensemble group of ``dataset.ShiftDataset.with_groups``."""
+    rng = np.random.default_rng(0) if rng is None else rng
+    atoms = make_graph(n_atoms, K, num_elem, p_pad, rng)[0]
+    mask = (rng.random(n_atoms) < labelled).astype(np.float32)
+    mask[0] = 1.0
+    y = np.stack([rng.standard_normal(n_atoms), rng.integers(0, n_names, size=n_atoms), mask], axis=1).astype(np.float32)
+    w = (mask * rng.choice([1.0, 0.5], size=n_atoms)).astype(np.float32)
+    recs = []
+    for _ in range(frames):
+        _, nl, d = make_graph(n_atoms, K, num_elem, p_pad, rng)
+        recs.append(((atoms, nl.astype(np.int32), d, inv_degree(nl)), y, w))
+    return recs
+
+
 def make_batch(n_graphs=512, n_atoms=256, K=16, num_elem=10, p_pad=0.05, seed=42):
     """Returns dict with the concatenated tuple (global neighbour indices), graph_ptr and labels."""
     rng = np.random.default_rng(seed)

@@ -62,12 +62,24 @@ class Trainer:
         self.measure_comm = False
         self._comm_events = []
 
-    def step(self, batch: GraphBatch, y: torch.Tensor, w: torch.Tensor, seed=None, total_graphs=None, names=None):
+    def step(self, batch: GraphBatch, y: torch.Tensor, w: torch.Tensor, seed=None, total_graphs=None, names=None, groups=None,
+             member_weights=None):
         """One optimiser step.  ``total_graphs``: number of graphs over ALL ranks this step (every rank can
         compute it from ``parallel.shard_range``); needed only when the shards are uneven — the loss is a mean
         over graphs, so a rank holding G_local of G_total graphs must weigh its gradient G_local/G_total, not
-        1/world.  Default: equal shards."""
+        1/world.  Default: equal shards.
+
+        ``groups``: the batch's ensemble ``group_ptr`` (host integers [Q + 1] over its graphs, the fifth
+        element of a grouped store's ``batches``).  The loss is then the NameLoss of every group's MEAN prediction
+        (``Engine.loss_groups`` with ``loss_balance`` as ``s``; ``member_weights`` [G]: the members' weights in the mean,
+        normalised per group), ``total_graphs`` counts groups, and the name metrics are taken on the means with the groups'
+        labels.  ``groups=None`` is the plain step."""
         eng = self.engine
+        if groups is None and member_weights is not None:
+            raise ValueError("Trainer.step: member_weights go with groups")
+        if groups is not None and (eng.capture_warmup or torch.cuda.is_current_stream_capturing()):
+            raise ValueError("Trainer.step(groups=): ensemble steps are not replayed (replay.TrainStepReplay captures the plain "
+                             "step only)")
         world, rank = self.buckets.world(), self.buckets.rank()
         if seed is None:
             # different noise / dropout draws on every rank and every step
@@ -75,8 +87,16 @@ class Trainer:
             # sequence of draws instead of replaying it
             seed = 0x9E3779B97F4A7C15 ^ (eng.adam_t * 1000003) ^ (rank * 0x5851F42D4C957F2D)
         seed &= (1 << 63) - 1
-        wgt = shard_grad_weight(batch.G, world, total_graphs)
-        if self.loss_balance == 1.0:
+        wgt = shard_grad_weight(batch.G if groups is None else len(groups) - 1, world, total_graphs)
+        if groups is not None:
+            # ensemble groups: the loss of the groups' mean predictions (the spread launch applies wgt), the metrics on the means
+            peaks = eng.forward(batch, training=True, seed=seed)
+            loss, dpred, means, labels = eng.loss_groups(batch, y, w, peaks, groups, s=self.loss_balance,
+                                                         member_weights=member_weights, grad_weight=wgt,
+                                                         names=names if self.metrics is not None else None)
+            if len(labels) == 3:
+                self.metrics.update(means, *labels)
+        elif self.loss_balance == 1.0:
             # the L2 loss is taken inside the forward: head, loss and the head's backward are one launch where the shape allows
             eng.forward(batch, training=True, seed=seed, loss=(y, w, wgt))
             loss, dpred = eng.tape.loss, None
@@ -85,7 +105,7 @@ class Trainer:
             loss, dpred = eng.loss_name(batch, y, w, peaks, self.loss_balance)
             if wgt != 1.0:
                 dpred.mul_(wgt)
-        if names is not None and self.metrics is not None:
+        if groups is None and names is not None and self.metrics is not None:
             self.metrics.update(eng.tape.peaks, y, w, names)
         eng.backward(dpred, on_node_grads=self.buckets.launch_node, trainable=self.trainable)
         self.buckets.launch_edge()
