@@ -843,6 +843,23 @@ int ng_reweight_weights(ng_ctx*, void* stream, int64_t T, int M, const float* S,
  * Refused: NULL context; T < 1 or T >= 2^31; N < 0 or N >= 2^31; NULL mu, p, mean or var. */
 int ng_weighted_moments(ng_ctx*, void* stream, int64_t T, int64_t N, const float* mu, const double* p, float* mean, float* var);
 
+/* Frames of a binary trajectory (DCD, Amber NetCDF-3; nmrgnn_amd/trajectory.py, csrc/traj.hip): raw [raw_bytes] is a chunk of
+ * file bytes on the device holding G frames frame_stride bytes apart; out [G][n_out][3] float32 receives the positions.
+ * Component c of source atom a of frame g is the 32-bit word at  g * frame_stride + off_c + a * elem_stride  (planar DCD:
+ * elem_stride 4, offsets one record apart; interleaved NetCDF: elem_stride 12, offsets 4 apart).  swap = 1 reverses the bytes
+ * of every word.  sel: int32 [n_out] source atoms in [0, n_src) (any order, repeats allowed), or NULL for the identity with
+ * n_out == n_src; the caller validates sel (an entry outside the range reads nothing, gives a NaN and is counted).  Words move
+ * as bits: NaN payloads, -0.0 and subnormals are kept.  *bad (a device int32 the caller zeroes) is increased by the number of
+ * output values that are not finite, by integer atomics: an exact count.  One launch of G * ceil(n_out / 256) workgroups, output
+ * rows staged through LDS and stored as consecutive words; 64-bit addressing, no scratch, capturable.  G == 0 or n_out == 0
+ * returns NG_OK without a launch.  Refused (NG_ERR_INVALID, before any launch): NULL context, raw, out or bad; a negative G,
+ * n_src or n_out; raw_bytes outside [0, 2^31); an offset or stride that is negative or no multiple of 4, or raw not aligned to
+ * 4 bytes; swap outside {0, 1}; sel == NULL with n_out != n_src; a layout whose last word ends beyond raw_bytes:
+ * (G - 1) * frame_stride + max(off) + (n_src - 1) * elem_stride + 4 > raw_bytes. */
+int ng_frames_decode(ng_ctx*, void* stream, const void* raw, int64_t raw_bytes, int64_t G, int64_t frame_stride, int64_t off_x,
+                     int64_t off_y, int64_t off_z, int64_t elem_stride, int swap, int64_t n_src, const int32_t* sel,
+                     int64_t n_out, float* out, int* bad);
+
 /* Mini-batch collation from a device-resident record store (nmrgnn_amd/dataset.py: ShiftDataset.batch; csrc/collate.hip).
  * The store holds R records back to back, record r in the rows [rec_ptr[r], rec_ptr[r+1]) of
  *   s_atoms [Ntot,C] f32, s_nlist [Ntot,K] i32 (record-LOCAL indices), s_edges [Ntot,K] f32, s_inv_degree [Ntot] f32,

@@ -159,6 +159,7 @@ SIGNATURES = {
     "ng_reweight_eval": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp]),
     "ng_reweight_weights": (_int, [_vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ng_weighted_moments": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "ng_frames_decode": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _i64, _vp, _i64, _vp, _vp]),
     "ng_collate_batch": (_int, [_vp, _vp, _i64, _i64] + [_vp] * 9 + [_i64, _int, _int, _int] + [_vp] * 8),
     "ng_store_from_batch": (_int, [_vp, _vp, _i64, _int, _int, _int] + [_vp] * 6 + [_i64, _i64] + [_vp] * 7),
     "ng_label_moments": (_int, [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp]),

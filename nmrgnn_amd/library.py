@@ -275,13 +275,69 @@ def shift_uncertainty(model, atoms, positions, samples=32, position_sigma=None, 
     return mean, torch.sqrt(var_model), torch.sqrt(var_in)
 
 
+def _is_trajectory(x):
+    """a binary trajectory in one of the forms the consumers take: a path, a reader or a stream"""
+    from .trajectory import TrajectoryStream, _Trajectory
+    return isinstance(x, (str, os.PathLike, _Trajectory, TrajectoryStream))
+
+
+def _trajectory_stream(x, chunk_frames, device):
+    """the stream of a path or reader in chunks of ``chunk_frames`` on ``device``; a stream is taken as it is"""
+    from .trajectory import TrajectoryStream
+    return x if isinstance(x, TrajectoryStream) else TrajectoryStream(x, chunk_frames=chunk_frames, device=device)
+
+
+def predict_trajectory(model, atoms, traj_or_stream, neighbor_number=16, pbc=False, select=None, frames_per_batch=32):
+    """The predicted shifts of every frame of a binary trajectory, float32 [T, n] on the device.
+
+    ``atoms`` [n, C] one-hot; ``traj_or_stream``: a path, a reader (``trajectory.open_trajectory``) or a
+    ``trajectory.TrajectoryStream`` (its frames, stride and chunk size then hold; it must deliver all n atoms).  The frozen
+    model runs over the chunks of the stream (``frames_per_batch`` frames each): one ``frames_to_batch`` and one model call per
+    chunk, the positions decoded on the device (``ng_frames_decode``).  ``pbc``: minimum-image lists in every frame's box, from
+    the file's cell data; a frame without one raises ValueError.  ``select``: a mask [n] or an index array — the model runs on
+    the receptive field of these atoms alone (``GNNModel.predict_selected``) and the result is [T, n_sel], the selected atoms
+    in ascending index."""
+    import torch
+    from .graph import frames_to_batch
+    atoms_np = atoms.detach().cpu().numpy() if isinstance(atoms, torch.Tensor) else np.asarray(atoms)
+    n = int(atoms_np.shape[0])
+    mask = None
+    if select is not None:
+        s = np.asarray(select)
+        mask = s.astype(bool) if s.dtype == bool else np.isin(np.arange(n), s.astype(np.int64))
+        if mask.shape != (n,) or not mask.any():
+            raise ValueError(f"predict_trajectory: select must name atoms in [0, {n})")
+    if model.engine is None:
+        model.build(int(atoms_np.shape[-1]))
+    model.freeze()
+    dev = model.engine.device
+    stream = _trajectory_stream(traj_or_stream, max(1, int(frames_per_batch)), dev)
+    if stream.n_out != n:
+        raise ValueError(f"predict_trajectory: atoms has {n} rows but the trajectory delivers {stream.n_out} atoms")
+    kept = []
+    for ids, pos, dims in stream:
+        box = None
+        if pbc:
+            if dims is None or np.isnan(dims).any():
+                k = 0 if dims is None else int(np.argmax(np.isnan(dims).any(axis=1)))
+                raise ValueError(f"predict_trajectory: pbc, but frame {int(ids[k])} has no box (no cell data, or zero lengths)")
+            box = dims
+        batch = frames_to_batch(atoms_np, pos, neighbor_number, device=dev, box=box)
+        peaks = model(batch) if mask is None else model.predict_selected(batch, np.tile(mask, len(ids)))
+        kept.append(peaks.detach().reshape(len(ids), -1))
+    if not kept:
+        return torch.empty((0, n if mask is None else int(mask.sum())), dtype=torch.float32, device=dev)
+    return torch.cat(kept)
+
+
 def reweight_trajectory(model, atoms, frames, targets, sigma, theta, prior=None, neighbor_number=16, box=None,
                         frames_per_batch=32, prune=False, **fit_args):
     """Maximum-entropy reweighting of the frames of a trajectory against measured shifts (nmrgnn_amd.reweight):
     ``(result, shifts)`` — a ``ReweightResult`` whose ``weights`` [T] make the ensemble agree with ``targets`` within
     ``sigma`` as far as ``theta`` allows, and the predicted shifts of every frame, float32 on the device.
 
-    ``atoms`` [n, C] one-hot, ``frames`` [T, n, 3] in Angstrom, ``targets`` [n] in ppm with NaN where an atom has no label,
+    ``atoms`` [n, C] one-hot, ``frames`` [T, n, 3] in Angstrom — or a binary trajectory (a path, a reader of
+    ``trajectory.open_trajectory`` or a ``trajectory.TrajectoryStream``: the same chunks, decoded on the device) —, ``targets`` [n] in ppm with NaN where an atom has no label,
     ``sigma`` a scalar or [n] (read on the labelled atoms only), ``theta`` > 0, ``prior`` [T] frame weights or None.  The
     frozen model runs over the frames ``frames_per_batch`` at a time, as ``eval-struct`` does (``box``: [6] for every frame or
     [T, 6]); the [T, n] shifts stay on the device, the labelled columns are gathered there, and ``ShiftReweighter.fit(theta,
@@ -307,19 +363,29 @@ def reweight_trajectory(model, atoms, frames, targets, sigma, theta, prior=None,
     bad = labelled & ~(np.isfinite(sg) & (sg > 0))
     if bad.any():
         raise ValueError(f"reweight_trajectory: atom {int(np.nonzero(bad)[0][0])} is labelled but its sigma is not finite and > 0")
-    shape = tuple(frames.shape)
-    if len(shape) != 3 or shape[1] != n or shape[2] != 3 or shape[0] < 1:
-        raise ValueError(f"reweight_trajectory: frames must be [T, {n}, 3] with T >= 1, got {shape}")
-    T = shape[0]
+    step = max(1, int(frames_per_batch))
+    binary = _is_trajectory(frames)
+    if not binary:
+        shape = tuple(frames.shape)
+        if len(shape) != 3 or shape[1] != n or shape[2] != 3 or shape[0] < 1:
+            raise ValueError(f"reweight_trajectory: frames must be [T, {n}, 3] with T >= 1, got {shape}")
     if model.engine is None:
         model.build(int(atoms_np.shape[-1]))
     model.freeze()
     dev = model.engine.device
+    if binary:                      # a binary trajectory: the same chunks, decoded on the device
+        stream = _trajectory_stream(frames, step, dev)
+        if stream.n_out != n or len(stream.frame_ids) < 1:
+            raise ValueError(f"reweight_trajectory: the trajectory must hold frames of {n} atoms, got {len(stream.frame_ids)} "
+                             f"frames of {stream.n_out}")
+        chunks = (pos for _, pos, _ in stream)
+    else:
+        chunks = (frames[b0:b0 + step] for b0 in range(0, shape[0], step))
     per_frame_box = box is not None and len(np.shape(box)) == 2
-    step = max(1, int(frames_per_batch))
     kept = []
-    for b0 in range(0, T, step):
-        chunk = frames[b0:b0 + step]
+    b0 = -step
+    for chunk in chunks:
+        b0 += step
         G = int(chunk.shape[0])
         batch = frames_to_batch(atoms_np, chunk.detach() if isinstance(chunk, torch.Tensor) else chunk, neighbor_number,
                                 device=dev, box=box[b0:b0 + step] if per_frame_box else box)

@@ -5,6 +5,9 @@ of a trajectory are independent graphs, so they are concatenated ``--frames-per-
 one device batch (one launch sequence per batch instead of one per frame) and their neighbour lists
 are built on the GPU (ng_knn_graph); the reference evaluates frame by frame with a CPU neighbour search.  With
 ``--separate`` every file is a structure of its own, batched as a ragged batch (graph.structures_to_batch).
+The first file is a PDB; the files behind it are further PDB pieces, or binary trajectories (``.dcd``, ``.nc``, ``.ncdf``:
+nmrgnn_amd.trajectory) — then, as with ``md.Universe(topology, *trajectory)``, the PDB gives the names only and
+the frames are those of the trajectory files in order, decoded on the device.
 
 ``train RECORDS... NAME [EPOCHS]`` is the reference's training command on ``dataset.ShiftDataset`` files (``.npz``, written by
 ``ShiftDataset.save``; the package reads no TFRecords): ``GNNModel.fit`` with the reference's callbacks, the model saved to
@@ -31,7 +34,18 @@ def main():
 
 def _open_structure(struct_files):
     from .structure import Structure, read_pdb
+    from .trajectory import TrajectoryUniverse, is_trajectory_file
+    if is_trajectory_file(struct_files[0]):
+        raise ValueError(f"{struct_files[0]}: the first file is the topology and must be a PDB; trajectory files follow it")
     first = read_pdb(struct_files[0])
+    binary = [f for f in struct_files[1:] if is_trajectory_file(f)]
+    if binary:
+        # md.Universe(topology, *trajectory files): the topology gives the names, the trajectory files every frame
+        if len(binary) != len(struct_files) - 1:
+            other = [f for f in struct_files[1:] if not is_trajectory_file(f)]
+            raise ValueError(f"PDB and binary trajectory files cannot be mixed behind the topology {struct_files[0]}: "
+                             f"{other[0]} is no .dcd, .nc or .ncdf file, {binary[0]} is one")
+        return TrajectoryUniverse(first, binary, label=struct_files[0])
     frames, dims = list(first.frames), list(first.dimensions)
     for extra in struct_files[1:]:                  # md.Universe(topology, *trajectory pieces)
         s = read_pdb(extra)
@@ -50,6 +64,12 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     record); a frame without one is an error.  ``separate``: every file is a structure of its own (see
     :func:`_eval_separate`); with ``boxes`` every (file, frame) structure uses its own CRYST1 box when it has one and open
     boundaries otherwise.
+
+    ``struct_files``: a PDB, then more PDB pieces of the same atoms or binary trajectory files (DCD, Amber NetCDF-3; not both
+    kinds).  With binary files the PDB contributes the atoms only, the frames are the trajectory files' in order, every file
+    must have the PDB's atom count, ``pbc`` takes the boxes from the cell records, and ``separate`` is refused.  The frames
+    reach the loop below through one frame source either way (``trajectory.frame_source``), ``frames_per_batch`` at a time, so
+    a binary trajectory gives the batches, and the CSV, of the same frames as a PDB.
 
     ``uncertainty`` = S > 0: two more columns behind ``frame``, ``std_model`` and ``std_input`` in ppm, rounded like
     ``peaks``: the error bar of every shift from S replicas of its frame (library.shift_uncertainty, seeded with the frame
@@ -101,20 +121,27 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     if boxes and not separate:
         raise ValueError('--boxes goes with --separate (one box, or none, per structure); use --pbc for frames of one topology')
     if separate:
+        from .trajectory import is_trajectory_file
+        if any(is_trajectory_file(f) for f in struct_files):
+            raise ValueError('--separate takes PDB files, each a structure of its own; a binary trajectory (.dcd, .nc, .ncdf) '
+                             'holds frames of the topology in front of it: run it without --separate')
         return _eval_separate(struct_files, output_csv, model_file, neighbor_number, stride, frames_per_batch, keep_going,
                               device, echo, boxes, atom_names)
     import torch
     from .graph import frames_to_batch
     from .library import check_peaks, load_model, shift_uncertainty
     from .structure import atoms_onehot
+    from .trajectory import frame_source
 
     model = load_model(model_file, device=device)
     u = _open_structure(struct_files)
+    source = frame_source(u)        # host frames of a PDB, or binary trajectory files decoded on the device
     frame_ids = list(range(0, len(u), stride))
     if pbc:
-        missing = [fr for fr in frame_ids if u.dimensions[fr] is None]
+        missing = [fr for fr, box in zip(frame_ids, source.boxes(frame_ids)) if box is None]
         if missing:
-            raise ValueError(f"--pbc: frame {missing[0]} has no box (no CRYST1 record, or the 1 Angstrom placeholder)")
+            raise ValueError(f"--pbc: frame {missing[0]} has no box (no CRYST1 record, or the 1 Angstrom placeholder; in a "
+                             "binary trajectory: no cell record, or one with zero lengths)")
     atoms = atoms_onehot(u.elements)
     n = atoms.shape[0]
     select = _name_mask(u.names, atom_names)        # None: every atom
@@ -133,13 +160,18 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
     timing = {'Structure': 0.0, 'Model Inference (MI355X)': 0.0, 'Parsing': 0.0}
     rows = []
     kept = []               # --average: the [frames, n] peaks stay on the device
-    for b0 in range(0, len(frame_ids), max(1, frames_per_batch)):
-        chunk = frame_ids[b0:b0 + max(1, frames_per_batch)]
+    step = max(1, frames_per_batch)
+    chunks = source.chunks([frame_ids[b0:b0 + step] for b0 in range(0, len(frame_ids), step)], device=model.engine.device)
+    while True:
         t = time.perf_counter()
+        taken = next(chunks, None)          # (frame numbers, positions [G, n, 3] on the host or the device, boxes)
+        if taken is None:
+            break
+        chunk, positions, chunk_boxes = taken
         model.build(atoms.shape[1])
         dev = model.engine.device
-        box = np.stack([u.dimensions[fr] for fr in chunk]) if pbc else None
-        batch = frames_to_batch(atoms_all, np.stack([u.frames[fr] for fr in chunk]), neighbor_number, device=dev, box=box)
+        box = np.stack(chunk_boxes) if pbc else None
+        batch = frames_to_batch(atoms_all, positions, neighbor_number, device=dev, box=box)
         torch.cuda.synchronize(dev)
         timing['Structure'] += time.perf_counter() - t
         t = time.perf_counter()
@@ -152,9 +184,9 @@ def eval_structure(struct_files, output_csv, model_file=None, neighbor_number=16
         peaks = peaks.cpu().numpy()
         peaks = peaks.reshape(len(chunk), n)
         stds = []
-        for fr in (chunk if uncertainty else ()):
-            _, sm, si = shift_uncertainty(model, atoms_all, u.frames[fr], samples=uncertainty, position_sigma=position_sigma,
-                                          neighbor_number=neighbor_number, box=u.dimensions[fr] if pbc else None, seed=fr,
+        for k, fr in (enumerate(chunk) if uncertainty else ()):
+            _, sm, si = shift_uncertainty(model, atoms_all, positions[k], samples=uncertainty, position_sigma=position_sigma,
+                                          neighbor_number=neighbor_number, box=chunk_boxes[k] if pbc else None, seed=fr,
                                           select=select)
             if select is not None:
                 sm, si = sm[idx], si[idx]
@@ -404,6 +436,9 @@ def eval_struct(struct_files, output_csv, model_file, neighbor_number, stride, f
                                'structure')
     if boxes and not separate:
         raise click.UsageError('--boxes goes with --separate; use --pbc for frames of one topology')
+    if separate and any(f.lower().endswith(('.dcd', '.nc', '.ncdf')) for f in struct_files):
+        raise click.UsageError('--separate takes PDB files, each a structure of its own; a binary trajectory (.dcd, .nc, '
+                               '.ncdf) holds frames of the topology in front of it: run it without --separate')
     if reweight is not None:
         if separate or uncertainty or average:
             raise click.UsageError('--reweight cannot be combined with --separate, --uncertainty or --average')
@@ -566,6 +601,19 @@ def train(records, name, epochs, checkpoint_path, embeddings, validation, load, 
                 standards=standards, freeze=freeze, lr_scale=lr_scale, clipnorm=clipnorm)
 
 
+def _pair_structure(field):
+    """the structure field of ``make-records --pair``: a PDB path, or ``top.pdb,traj.dcd[,more]`` — the atoms of the PDB with
+    the frames of the binary trajectory files (``trajectory.load_structure``)"""
+    from .trajectory import is_trajectory_file, load_structure
+    parts = [p for p in str(field).split(',') if p]
+    if not os.path.exists(str(field)) and len(parts) > 1 and all(is_trajectory_file(p) for p in parts[1:]):
+        missing = [p for p in parts if not os.path.exists(p)]
+        if missing:
+            raise ValueError(f"--pair {field}: {missing[0]} does not exist")
+        return load_structure(parts[0], *parts[1:])
+    return field
+
+
 def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None, embeddings_out=None, pbc=False,
                  keep_going=False, device=None, echo=print, ensembles=False):
     """``make-records``: structures with assigned shifts -> one ``ShiftDataset`` file.  ``pairs``: ``(structure file, shift
@@ -583,7 +631,7 @@ def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None
     if embeddings is not None and embeddings_out is not None:
         raise ValueError('--embeddings and --embeddings-out cannot be combined')
     names = _load_embeddings(embeddings)['name'] if embeddings is not None else None
-    ds = ShiftDataset.from_structures([p[0] for p in pairs], [p[1] for p in pairs], neighbor_number=neighbor_number,
+    ds = ShiftDataset.from_structures([_pair_structure(p[0]) for p in pairs], [p[1] for p in pairs], neighbor_number=neighbor_number,
                                       frames=frames, names=names, boxes=pbc, strict=not keep_going, device=device,
                                       ensembles=ensembles)
     ds.save(out)
@@ -604,8 +652,9 @@ def make_records(out, pairs, frames='first', neighbor_number=16, embeddings=None
 
 @main.command(name='make-records')
 @click.argument('out', type=click.Path())
-@click.option('--pair', 'pairs', nargs=2, multiple=True, type=click.Path(exists=True), metavar='STRUCT SHIFTS',
-              help='A structure file (PDB) and the CSV of its assigned shifts (resid,name,shift[,resname]); repeat per structure')
+@click.option('--pair', 'pairs', nargs=2, multiple=True, type=click.Path(), metavar='STRUCT SHIFTS',
+              help='A structure file (PDB, or top.pdb,traj.dcd[,more.nc]: the frames of binary trajectory files on the atoms of '
+                   'the PDB) and the CSV of its assigned shifts (resid,name,shift[,resname]); repeat per structure')
 @click.option('--frames', default='first', type=click.Choice(['first', 'all']),
               help='One record per structure, or one per frame (MODEL) with the same labels')
 @click.option('--ensembles', is_flag=True,
@@ -626,6 +675,10 @@ def make_records_cmd(out, pairs, frames, ensembles, neighbor_number, embeddings,
         raise click.UsageError('--embeddings and --embeddings-out cannot be combined')
     if ensembles and frames != 'all':
         raise click.UsageError('--ensembles groups the frames of a structure and needs --frames all')
+    for struct, table in pairs:
+        for p in ([struct] if os.path.exists(struct) else [q for q in struct.split(',') if q]) + [table]:
+            if not os.path.exists(p):
+                raise click.BadParameter(f"Path '{p}' does not exist.", param_hint="'--pair'")
     try:
         make_records(out, pairs, frames=frames, neighbor_number=neighbor_number, embeddings=embeddings,
                      embeddings_out=embeddings_out, pbc=pbc, keep_going=keep_going, device=device, echo=click.echo,
